@@ -5,19 +5,23 @@ columns resident in HBM (BASELINE.json metric; SURVEY.md §8d cfg-dense: ts=i, v
 One "step" = one full Rolling.Aggregate(WindowStart(time), ArithmeticMean(value)) over the rank's
 rows through the C ABI (bitmap init + bucketing/reduction kernel + status readback + null counts).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): `value` (rows/s over the timed steps),
+`ms_per_step` and the roofline fraction from the kernel time of those same steps.  `--dump-outputs DIR` then also writes what the
+last timed step computed (rank 0's outputs) as DIR/<name>.npy - see dump_outputs().  Everything else is behind `--full`:
+`parity_check` (the outputs of the timed call compared, outside the timed region, with the oracle on the first and the last 2e6
+rows of rank 0's rows bit for bit, plus the WindowStart progression of every window - a mismatch is a non-zero exit), the in-run
+roofline probes, the PCIe-inclusive `host_pinned` legs, the CPU baselines and, for N > 1, the exchange figures.
 
 N > 1: rows are range-partitioned (rank r owns rows [r*R, (r+1)*R): weak scaling); the only exchange of a step is ONE
 all_gather of a fixed-size record per rank (first / last timestamp + the running state of the rank's last window) over RCCL,
 started BEFORE the rank's pass is enqueued and collected after (bowgpu_shard_begin / _pass_begin / _finish: the exchange is off
-the critical path; `exchange_ms` = one exchange alone, `exchange_hidden_ms` = what the overlap saves per step against the serial
-order, both measured after the timed region); the ownership rules live behind the C ABI.  Without a launcher (no WORLD_SIZE in
-the environment) `--gpus N` starts its own N rank processes.  A preflight (device count, one exchange under a watchdog) turns a
-rendezvous that cannot complete into a non-zero exit with a message instead of a hang.
-Rank 0 prints ONE JSON line; it carries `parity_check`: the outputs of the timed call compared, outside the timed region, with
-the oracle on the first and the last 2e6 rows of rank 0's rows bit for bit, plus the WindowStart progression of every window -
-a mismatch is a non-zero exit.
+the critical path; with --full, `exchange_ms` = one exchange alone, `exchange_hidden_ms` = what the overlap saves per step against
+the serial order, both measured after the timed region); the ownership rules live behind the C ABI.  Without a launcher (no
+WORLD_SIZE in the environment) `--gpus N` starts its own N rank processes.  A preflight (device count, one exchange under a
+watchdog) turns a rendezvous that cannot complete into a non-zero exit with a message instead of a hang.
 """
 import argparse
 import json
@@ -255,6 +259,39 @@ def parity_check(capi, outs, rows, row0, interval, offset, owned, first_slot, s0
     return res
 
 
+DUMP_SAMPLE = 1_000_000   # windows written per output by --dump-outputs: 5 files, 32 MB in all
+DUMP_SEED = 2024
+
+
+def dump_outputs(capi, outs, owned, directory):
+    """--dump-outputs: what a caller of the timed call receives (rank 0's outputs: WindowStart and ArithmeticMean, values and
+    validity), written after the timed region as float64 / float32 .npy files.  Up to DUMP_SAMPLE windows all of them are written;
+    beyond that a fixed sample: one window drawn (seeded) out of each of DUMP_SAMPLE equal strides, so two builds run with the same
+    arguments write the same windows.  window_index.npy holds the output slots written (float64, exact below 2^53)."""
+    import numpy as np
+    if owned <= DUMP_SAMPLE:
+        idx = np.arange(owned, dtype=np.int64)
+    else:
+        stride = owned // DUMP_SAMPLE
+        idx = np.arange(DUMP_SAMPLE, dtype=np.int64) * stride + np.random.default_rng(DUMP_SEED).integers(0, stride, DUMP_SAMPLE)
+    arrays = {"window_index": idx.astype(np.float64)}
+    CH = 1 << 24
+    for name, o in zip(("window_start", "mean"), outs):
+        vals = np.empty(len(idx), np.float64)
+        for k0 in range(0, owned, CH):
+            m = min(CH, owned - k0)
+            lo, hi = np.searchsorted(idx, [k0, k0 + m])
+            if hi > lo:
+                chunk = o.values.to_numpy(np.int64 if o.type == capi.INT64 else np.float64, m, first=k0)
+                vals[lo:hi] = chunk[idx[lo:hi] - k0]
+        bm = o.validity.to_numpy(np.uint8, (owned + 7) // 8)
+        arrays[name] = vals
+        arrays[name + "_valid"] = ((bm[idx >> 3] >> (idx & 7)) & 1).astype(np.float32)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def preflight(dist, torch, world, rank, backend, seconds=120):
     """N > 1, before anything is timed: every rank must see its device, and ONE exchange of the record-sized buffer must complete.
     A rendezvous that cannot (a rank on the wrong device, a transport that never connects) ends the run with a message and a
@@ -351,12 +388,20 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rows", type=_count, default=1_000_000_000, help="rows per GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's outputs) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: parity_check, roofline probes, host_pinned, CPU baselines, "
+                         "the exchange figures of N > 1")
     ap.add_argument("--cpu-sample", type=_count, default=100_000_000)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the parity_check of the timed outputs against the oracle")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity_check of the timed outputs against the oracle")
     ap.add_argument("--no-pinned", action="store_true",
-                    help="skip the host_pinned aside (profiling: it launches the same kernel over PCIe, which would pollute per-kernel averages)")
+                    help="with --full: skip the host_pinned aside (profiling: it launches the same kernel over PCIe, which would pollute "
+                         "per-kernel averages)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around us: be the launcher (before anything touches the GPU in this process)
@@ -436,8 +481,14 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        # before anything below runs the kernels again or probes into the output buffers
+        if world == 1:
+            dump_outputs(capi, outs, W, args.dump_outputs)
+        else:
+            dump_outputs(capi, runner.provider.outs, runner.decision.windows_owned, args.dump_outputs)
     exch = None
-    if world > 1:
+    if world > 1 and args.full:
         # after the timed region: the same steps in the SERIAL order (begin -> exchange -> pass) and the exchange alone
         g = runner.gather
         exch = {"window_ms": g.ms / max(g.calls, 1), "host_wait_ms": g.wait_ms / max(g.calls, 1), "per_step": g.calls / args.steps}
@@ -464,7 +515,7 @@ def main():
         barrier()
 
     parity = None
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         # BEFORE the probes below (the read + write probe stores into the output buffers)
         if world == 1:
             parity = parity_check(capi, outs, rows, 0, INTERVAL, 0, W, 0, s0)
@@ -506,7 +557,7 @@ def main():
         line["roofline"]["traffic"] = measured_traffic(rows, kernel_instance)
         if line["roofline"]["traffic"] is not None:
             line["roofline"]["traffic_source"] = "profiles/" + os.path.basename(newest_traffic_file()) + " (2 x FETCH_SIZE + WRITE_SIZE, same kernel_sha)"
-        if world > 1:
+        if exch is not None:
             # THE exchange of a step (upload + all_gather of one 2424-byte record per rank + download, pinned buffers allocated once):
             # alone it takes exchange_ms; in the timed steps it is in flight while the pass runs, and the step is exchange_hidden_ms
             # shorter than the same step in the serial order
@@ -517,7 +568,7 @@ def main():
                                 "window_ms_per_step": exch["window_ms"], "exchanges_per_step": exch["per_step"],
                                 "record_bytes": runner.gather.n, "buffers": "pinned host + device, allocated once"}
             line["exchanges_per_step"] = exch["per_step"]
-        if world == 1:
+        if world == 1 and args.full:
             # the achievable line: a trivial streaming sum over the same two columns, measured in this run
             try:
                 ceil = capi.stream_read_ceiling(cols[0].values, cols[1].values, rows * 8)
@@ -534,7 +585,7 @@ def main():
                                                                "the reads - not a bound (the product kernel is usually a little faster)"}
             except Exception as e:
                 line["roofline"]["stream_rw_probe"] = {"error": repr(e)}
-        if world == 1 and not args.no_pinned:
+        if world == 1 and args.full and not args.no_pinned:
             # PCIe-inclusive aside (never `value`): the same call on HOST-resident columns of a 1e8-row sample - registered buffers
             # read in place by the kernels (BOWGPU_HOST_PINNED, zero-copy), outputs by DMA into registered buffers
             try:
@@ -542,7 +593,7 @@ def main():
                 line["host_pinned_multi"] = line["host_pinned"].pop("multi", None)
             except Exception as e:
                 line["host_pinned"] = {"error": repr(e)}
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             try:
                 line["cpu_baseline"] = cpu_baseline(capi, min(args.cpu_sample, rows))
                 # the Go reference itself would be the baseline of choice; it needs a Go toolchain plus the module's

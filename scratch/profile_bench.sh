@@ -18,6 +18,6 @@ python3 scratch/profile_collect.py $OUT $TAG > $OUT/collect.log 2>&1
 # 5. the bench line itself (un-profiled), LAST: the counter file of THIS collection is in profiles/ by now, so the line carries
 #    roofline.traffic the way the driver's run of the committed tree will (bench.py quotes it when the kernel's sha matches)
 cp $OUT/${TAG}_pmc_hbm_traffic_bench_1e9.csv profiles/
-timeout -s KILL 400 python3 bench.py --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
+timeout -s KILL 400 python3 bench.py --steps 20 --warmup 3 --full > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/collect.log
 echo "== $OUT/bench.json"; cat $OUT/bench.json

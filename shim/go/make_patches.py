@@ -109,6 +109,10 @@ def error_strings():
     src = open(os.path.join(REF, "rolling", "aggregation.go")).read()
     m = re.search(r'"(must keep interval column \'%s\')"', src)
     out["rolling/aggregation.go keep interval"] = m.group(1)
+    src = open(os.path.join(REF, "rolling", "interpolation.go")).read()
+    for fn in ("intervalRolling.interpolateWindows", "newIntervalRolling"):
+        m = re.search(r'fmt\.Errorf\("(%s: %%w)", err\)' % re.escape(fn), src)
+        out["rolling/interpolation.go wraps %s" % fn] = m.group(1)
     return out
 
 

@@ -54,8 +54,12 @@ def test_launcher_dead_rank_fails_the_run(tmp_path):
 
 def test_bench_without_gpu_fails_loudly_for_n2():
     """No GPU in this container: both ranks must refuse (no CPU fallback), and the launcher must report it."""
-    import torch
-    if torch.cuda.is_available():
+    from bow_amd import capi
+    try:
+        n = capi.device_count()   # (not torch in this process: once libbowgpu is loaded, torch's own HIP runtime copy sees no device)
+    except capi.BowGpuError:
+        n = 0
+    if n > 0:
         pytest.skip("GPU box: covered by test_bench_two_ranks_on_one_gpu")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "1e5", "--steps", "1",
@@ -71,7 +75,7 @@ def test_bench_two_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(BOW_BENCH_SINGLE_DEVICE="1", BOW_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "1e7", "--steps", "3",
-                        "--warmup", "1", "--no-cpu"], env=env, capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--no-cpu", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout
@@ -85,12 +89,12 @@ def test_bench_two_ranks_on_one_gpu():
 
 @pytest.mark.gpu
 def test_bench_line_contract_single_gpu():
-    """`python bench.py` at N = 1 (a reduced row count, everything else as the default run): ONE JSON line on stdout with the keys of
+    """`python bench.py --full` at N = 1 (a reduced row count, everything else as the default run): ONE JSON line on stdout with the keys of
     the bench contract - the metric of BASELINE.json, the roofline object (live kernel time on the library's stream, the in-run
     ceilings) and the cpu_baseline object - and values that hang together."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "2e7", "--steps", "4", "--warmup", "1",
-                        "--cpu-sample", "2e6"], env=env, capture_output=True, text=True, timeout=900)
+                        "--cpu-sample", "2e6", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout
@@ -113,3 +117,45 @@ def test_bench_line_contract_single_gpu():
     assert rec["host_pinned"]["value"] > 0 and rec["host_pinned"]["pageable_rows_per_s"] > 0
     par = rec["parity_check"]
     assert par["ok"] is True and par["progression_checked"] == 2_000_000 and par["checked_against_oracle"] >= 2_000_000 // 10 * 2 - 2
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_the_timed_outputs(tmp_path):
+    """`python bench.py` without --full: the headline keys and none of what --full adds.  --dump-outputs DIR writes what the last timed
+    step computed: a fixed sample of windows as float32 / float64 .npy files, at most 64 MB, equal to the oracle's outputs bit for bit
+    and the same in a second run with the same arguments."""
+    import numpy as np
+    import bench
+    from oracle import pyoracle as orc
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    rows, windows = 20_000_000, 2_000_000
+
+    def run(d):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "2e7", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout
+        return json.loads(lines[0]), {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+    rec, got = run(tmp_path / "a")
+    assert rec["metric"] == "rows/sec rolling-mean on 1B-row float64" and rec["unit"] == "rows/s" and rec["higher_is_better"] is True
+    assert rec["dtype"] == "f64" and rec["steps"] == 3 and rec["warmup"] == 1
+    assert abs(rec["value"] - rows / (rec["ms_per_step"] * 1e-3)) / rec["value"] < 1e-6
+    assert rec["parity_check"] is None
+    assert not {"cpu_baseline", "cpu_baseline_all_cores", "host_pinned", "host_pinned_multi"} & set(rec)
+    assert not {"stream_read_ceiling", "stream_rw_probe"} & set(rec["roofline"])
+    assert sorted(got) == ["mean", "mean_valid", "window_index", "window_start", "window_start_valid"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(os.path.getsize(tmp_path / "a" / (k + ".npy")) for k in got) <= 64 * 2 ** 20
+    idx = got["window_index"].astype(np.int64)
+    assert len(idx) == bench.DUMP_SAMPLE and idx[0] >= 0 and idx[-1] < windows and (np.diff(idx) > 0).all()
+    ts, val = orc.gen_dense(0, rows, seed=42)
+    want, _ = orc.aggregate([orc.Column(ts, None, orc.INT64), orc.Column(val, None, orc.FLOAT64)], 0, bench.INTERVAL,
+                            [("WindowStart", 0), ("ArithmeticMean", 1)])
+    assert want[0].length == windows
+    for name, w in (("window_start", want[0]), ("mean", want[1])):
+        assert np.array_equal(got[name], w.values[:windows][idx].astype(np.float64)), name
+        assert np.array_equal(got[name + "_valid"], w.valid_mask()[idx].astype(np.float32)), name
+    _, again = run(tmp_path / "b")
+    assert all(np.array_equal(got[k].view(np.uint8), again[k].view(np.uint8)) for k in got)

@@ -177,8 +177,9 @@ def test_every_identifier_the_shim_uses_on_a_reference_type_exists_there():
     # the lazy Rolling implements the whole Rolling interface (rolling.go:14-29) and nothing else the reference does not know
     assert sorted(set(re.findall(r"^func \(l \*lazyInterpolation\) (\w+)\(", lazy, flags=re.M)) - {"materialised"}) == SHAPES["rolling.Rolling"]["methods"]
     assert "rCopy.lazyInterpolationGPU(interps, newIntervalCol); lazy != nil" in _added_by_patches("rolling/interpolation.go")
-    for text in ('fmt.Errorf("intervalRolling.interpolateWindows: %w", err)', 'fmt.Errorf("newIntervalRolling: %w", err)'):
-        assert text in lazy and text in open(os.path.join(REF, "rolling", "interpolation.go")).read() if os.path.isdir(REF) else text in lazy
+    for fn in ("intervalRolling.interpolateWindows", "newIntervalRolling"):
+        want = SHAPES["error_strings"]["rolling/interpolation.go wraps %s" % fn]     # the reference's own wording of the wrap
+        assert want == fn + ": %w" and 'fmt.Errorf("%s", err)' % want in lazy
     for name in set(re.findall(r"\br\.(\w+)", cgo)):
         assert name in R["fields"] or name in R["methods"] or name in shim_methods, ("intervalRolling", name)
     for name in set(re.findall(r"\br\.options\.(\w+)", cgo)):

@@ -843,7 +843,7 @@ def test_interpolate_count_to_fill_reuse_is_dropped_when_the_column_changes():
     rc, outs = fill(max(m_a, want_b[0].length) + 8)
     assert rc == 0 and outs[0].length == orc.interpolate([orc.Column(ts_b, None, orc.INT64), orc.Column(v_a, bm_a, orc.FLOAT64)], 0, 10, ip)[0].length
     # 2. ... behind the library's back (a raw hipMemcpy): the fill's own row count does not add up -> BOWGPU_ERR_ARG
-    hip = C.CDLL("libamdhip64.so")
+    hip = capi.lib()     # hipMemcpy of the HIP runtime the library is linked to (torch may have loaded a second copy in this process)
     assert count() == outs[0].length
     assert hip.hipMemcpy(C.c_void_p(cols[0].values.ptr), ts_a.ctypes.data_as(C.c_void_p), C.c_size_t(ts_a.nbytes), 1) == 0
     rc, _ = fill(max(m_a, want_b[0].length) + 8)

@@ -18,6 +18,12 @@ import numpy as np
 from bow_amd import capi, sharded
 L = capi.lib()
 assert capi.LIB_PATH.endswith("libbowgpu_host_asan.so")
+try:   # the sweep asserts the no-GPU answers; with a device visible a valid call would reach the stubs, which abort
+    ndev = capi.device_count()
+except capi.BowGpuError:
+    ndev = 0
+if ndev:
+    raise SystemExit("the sanitized sweep sees %d device(s); it runs with none visible (HIP_VISIBLE_DEVICES=-1)" % ndev)
 rng = np.random.default_rng(11)
 
 # ---- plans / ctor errors on host columns (newIntervalRolling, enforceIntervalAndOffset, countWindows)
@@ -173,6 +179,7 @@ def _env():
     env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=1:halt_on_error=1:protect_shadow_gap=0"   # (python itself leaks by design)
     env["UBSAN_OPTIONS"] = "halt_on_error=1:print_stacktrace=1"
     env["BOWGPU_LIB"] = ASAN_LIB
+    env["HIP_VISIBLE_DEVICES"] = "-1"   # no device on a GPU box either: the sweep drives the entry points that work without one
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
     return env
 
