@@ -26,7 +26,7 @@ INTERP = {"WindowStart": 0, "Linear": 1, "StepPrevious": 2, "None": 3, "Const": 
 
 MAX_FACTORS = 4
 CARRY_MAX_AGGS = 16
-ABI_VERSION = 6   # include/bowgpu.h BOWGPU_ABI_VERSION (asserted when the library is loaded)
+ABI_VERSION = 7   # include/bowgpu.h BOWGPU_ABI_VERSION (asserted when the library is loaded)
 
 ERR_NAMES = {
     -1: "INTERVAL", -2: "TS_TYPE", -3: "FIRST_TS_NULL", -4: "NO_AGG", -5: "KEEP_INTERVAL", -6: "BAD_COL",
@@ -97,12 +97,6 @@ class NextRow(C.Structure):
     _fields_ = [("present", C.c_int32), ("_pad", C.c_int32), ("ts", C.c_int64), ("bits", C.c_uint64 * 16), ("valid", C.c_int32 * 16)]
 
 
-class ShardCarry(C.Structure):
-    _fields_ = [("first_window_id", C.c_int64), ("last_window_id", C.c_int64), ("first_ts", C.c_int64),
-                ("last_ts", C.c_int64), ("nrows", C.c_int64), ("naggs", C.c_int32), ("_pad", C.c_int32),
-                ("last", CarryState * CARRY_MAX_AGGS)]
-
-
 class Plan(C.Structure):
     """bowgpu_plan: what newIntervalRolling computes once per Rolling"""
     _fields_ = [("s0", C.c_int64), ("num_windows", C.c_int64), ("first_ts", C.c_int64), ("last_ts", C.c_int64),
@@ -132,7 +126,7 @@ SYMBOLS = [
     "bowgpu_rolling_aggregate", "bowgpu_plan_windows_ex", "bowgpu_rolling_aggregate_planned", "bowgpu_window_bounds", "bowgpu_aggregate_whole",
     "bowgpu_rolling_interpolate_count", "bowgpu_rolling_interpolate_fill", "bowgpu_shard_interp_points",
     "bowgpu_shard_interpolate_count", "bowgpu_shard_interpolate_fill", "bowgpu_fill_linear", "bowgpu_fill_linear_sorted", "bowgpu_fill",
-    "bowgpu_is_col_sorted", "bowgpu_shard_span", "bowgpu_shard_aggregate", "bowgpu_shard_carry_only", "bowgpu_shard_first_row", "bowgpu_shard_fix_first", "bowgpu_carry_merge",
+    "bowgpu_is_col_sorted", "bowgpu_carry_merge",
     "bowgpu_shard_begin", "bowgpu_shard_pass_begin", "bowgpu_shard_plan", "bowgpu_shard_finish", "bowgpu_gen_dense",
     "bowgpu_gen_sparse", "bowgpu_stream_read_ceiling", "bowgpu_stream_rw_probe", "bowgpu_debug_status", "bowgpu_debug_host_copy", "bowgpu_checksum64", "bowgpu_parquet_open", "bowgpu_parquet_close",
     "bowgpu_parquet_info", "bowgpu_parquet_column", "bowgpu_parquet_read_column",

@@ -2291,181 +2291,17 @@ int bowgpu_rolling_aggregate_planned(const bowgpu_col *cols, int32_t ncols, int3
 // fill_linear, is_col_sorted, shard_* ----
 
 
-// ---- row-range sharding -------------------------------------------------------------------
+// ---- row-range sharding: the shard protocol, begin -> one exchange -> finish ---------------------------------------------
 
 static bool strict_wanted(const bowgpu_options *o) { return (o && o->strict_order) || (route_mask() & BOWGPU_ROUTE_STRICT_ORDER); }
 struct StrictScope { bool was; explicit StrictScope(bool on) : was(g_strict_order) { g_strict_order = on; } ~StrictScope() { g_strict_order = was; } };
-// allow_strict: the record protocol (bowgpu_shard_begin / _pass_begin / _finish) serves bowgpu_options.strict_order since round 5 - a
-// rank's own windows by the unsharded forms, a window shared by TWO ranks by the right rank's re-walk of its rows seeded with the left
-// rank's running state (row order across the boundary); a window spread over three or more ranks merges partial sums and is declined
-// by _finish.  The building blocks of round 1 (bowgpu_shard_aggregate, _carry_only) still decline it.
-static int shard_check(const bowgpu_col *cols, int32_t ncols, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs,
-                       const bowgpu_options *o, bool allow_strict = false) {
-    if (!allow_strict && strict_wanted(o)) return fail(BOWGPU_ERR_UNSUPPORTED, "sharded aggregate: strict_order is offered by the record protocol only (bowgpu_shard_begin / _pass_begin / _finish)");
-    // (allow_strict: the record protocol.  It also takes HOST-resident columns and outputs since round 5 - staged through HBM per call the way
-    // the unsharded entry points stage them: the pass put in flight by _pass_begin keeps its staged copies until _finish collects it)
-    for (int i = 0; i < naggs; i++) {
-        // a window cut by a shard boundary needs all its rows in one place: Mode has no constant-size partial state
-        if (aggs[i].kind == BOWGPU_AGG_MODE) return fail(BOWGPU_ERR_UNSUPPORTED, "sharded aggregate: Mode is not a mergeable reducer");
-        if (!allow_strict && outs[i].residency != BOWGPU_DEVICE) return fail(BOWGPU_ERR_UNSUPPORTED, "sharded aggregate: outputs must be device-resident");
-    }
-    for (int i = 0; i < ncols; i++)
-        if (!allow_strict && cols[i].residency != BOWGPU_DEVICE) return fail(BOWGPU_ERR_UNSUPPORTED, "sharded aggregate: columns must be device-resident");
-    if (naggs > BOWGPU_CARRY_MAX_AGGS) return fail(BOWGPU_ERR_UNSUPPORTED, "sharded aggregate: too many aggregations");
-    return 0;
-}
-
-// the plan of a shard: global s0, local first/last ts -> local window range
-static int shard_plan(Ctx *c, const bowgpu_col *ts, int64_t interval, int64_t raw_offset, int64_t global_s0, Plan *p,
-                      int64_t *wid_first, int64_t *wid_last) {
-    BG_TRY(plan_make(c, ts, interval, raw_offset, p));  // validates type / interval / first ts; local s0, W are replaced below
-    p->s0 = global_s0;
-    *wid_first = -1;
-    *wid_last = -1;
-    p->W = 0;
-    if (ts->length == 0) return 0;
-    if (p->last_ts < global_s0) return 0;
-    const int64_t f = p->first_ts < global_s0 ? global_s0 : p->first_ts;
-    *wid_first = (int64_t)(((uint64_t)f - (uint64_t)global_s0) / (uint64_t)interval);
-    *wid_last = (int64_t)(((uint64_t)p->last_ts - (uint64_t)global_s0) / (uint64_t)interval);
-    p->W = *wid_last - *wid_first + 1;
-    return 0;
-}
-
-int bowgpu_shard_aggregate(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, int64_t interval,
-                           const bowgpu_options *opts, int64_t global_s0, int32_t holds_global_row0,
-                           int64_t lead, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs,
-                           bowgpu_shard_carry *carry, const bowgpu_next_row *next_row, int32_t finish_last) {
-    if (!cols || ncols <= 0 || !carry || !outs) return fail(BOWGPU_ERR_ARG, "null argument");
-    if (ts_col < 0 || ts_col >= ncols) return fail(BOWGPU_ERR_BAD_COL, "no interval column with index %d", ts_col);
-    bowgpu_options o = {0, 0, 0};
-    if (opts) o = *opts;
-    int inclusive = 0, nic = -1;
-    BG_TRY(validate_aggs(cols, ncols, ts_col, aggs, naggs, &inclusive, &nic));
-    BG_TRY(shard_check(cols, ncols, aggs, naggs, outs, &o));
-    Ctx *c;
-    BG_TRY(ctx_get(&c));
-    Plan plan;
-    int64_t wf, wl;
-    BG_TRY(shard_plan(c, &cols[ts_col], interval, o.offset, global_s0, &plan, &wf, &wl));
-    memset(carry, 0, sizeof *carry);
-    carry->first_window_id = wf;
-    carry->last_window_id = wl;
-    carry->first_ts = plan.first_ts;
-    carry->last_ts = plan.last_ts;
-    carry->nrows = cols[ts_col].length;
-    carry->naggs = naggs;
-    AggJob job;
-    if (lead < 0 || (wf < 0 && lead != 0) || (wf >= 0 && lead > wf)) return fail(BOWGPU_ERR_ARG, "bad lead_empty_windows %lld", (long long)lead);
-    const int64_t Wtot = plan.W + lead;
-    BG_TRY(job_build(c, cols, ncols, ts_col, plan, inclusive, aggs, naggs, outs, wf < 0 ? 0 : wf - lead, Wtot, holds_global_row0 != 0, &job));
-    BG_TRY(job_run(c, &job, aggs, naggs, nullptr, nullptr, false, &plan));
-    if (lead > 0) BG_TRY(launch_fill_empty(c, job.P, 0, lead));
-    if (plan.W > 0) {
-        // running state of the last window over this shard's rows; when the shard owns that window and the windows are
-        // inclusive, its outputs are rewritten with the next shard's first row folded in where it is the inclusive row
-        void *pool;
-        BG_TRY(ctx_pool(c, kPoolShard, 16384, &pool));
-        bowgpu_carry_state *dst = reinterpret_cast<bowgpu_carry_state *>(pool);
-        bowgpu_next_row *dnext = nullptr;
-        const bool finish = inclusive && finish_last && next_row && next_row->present;
-        if (finish) {
-            dnext = reinterpret_cast<bowgpu_next_row *>(reinterpret_cast<char *>(pool) + 8192);
-            BG_HIP(hipMemcpyAsync(dnext, next_row, sizeof *next_row, hipMemcpyHostToDevice, c->stream));
-        }
-        BG_TRY(launch_range_state(c, job.P, finish ? 2 : 0, (uint64_t)wl, nullptr, dst, dnext, 0));
-        BG_HIP(hipMemcpyAsync(carry->last, dst, sizeof(bowgpu_carry_state) * naggs, hipMemcpyDeviceToHost, c->stream));
-        BG_HIP(hipStreamSynchronize(c->stream));
-    }
-    BG_TRY(job_finish(c, &job, aggs, naggs));
-    return 0;
-}
-
-int bowgpu_shard_carry_only(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, int64_t interval, const bowgpu_options *opts,
-                            int64_t global_s0, int32_t holds_global_row0, const bowgpu_agg *aggs, int32_t naggs,
-                            bowgpu_shard_carry *carry) {
-    if (!cols || ncols <= 0 || !carry) return fail(BOWGPU_ERR_ARG, "null argument");
-    if (ts_col < 0 || ts_col >= ncols) return fail(BOWGPU_ERR_BAD_COL, "no interval column with index %d", ts_col);
-    bowgpu_options o = {0, 0, 0};
-    if (opts) o = *opts;
-    int inclusive = 0, nic = -1;
-    BG_TRY(validate_aggs(cols, ncols, ts_col, aggs, naggs, &inclusive, &nic));
-    if (inclusive) return fail(BOWGPU_ERR_UNSUPPORTED, "bowgpu_shard_carry_only: inclusive windows take their carry from bowgpu_shard_aggregate");
-    if (naggs > BOWGPU_CARRY_MAX_AGGS) return fail(BOWGPU_ERR_UNSUPPORTED, "sharded aggregate: too many aggregations");
+// what a window cut by a shard boundary needs on top of validate_aggs: a constant-size running state per reducer (Mode has none)
+// and room for it in the record.  Columns and outputs of any residency: host-resident ones are staged through HBM per call the way
+// the unsharded entry points stage them (the pass put in flight by _pass_begin keeps its staged copies until _finish collects it)
+static int shard_check(const bowgpu_agg *aggs, int32_t naggs) {
     for (int i = 0; i < naggs; i++)
         if (aggs[i].kind == BOWGPU_AGG_MODE) return fail(BOWGPU_ERR_UNSUPPORTED, "sharded aggregate: Mode is not a mergeable reducer");
-    for (int i = 0; i < ncols; i++)
-        if (cols[i].residency != BOWGPU_DEVICE) return fail(BOWGPU_ERR_UNSUPPORTED, "sharded aggregate: columns must be device-resident");
-    Ctx *c;
-    BG_TRY(ctx_get(&c));
-    Plan plan;
-    int64_t wf, wl;
-    BG_TRY(shard_plan(c, &cols[ts_col], interval, o.offset, global_s0, &plan, &wf, &wl));
-    memset(carry, 0, sizeof *carry);
-    carry->first_window_id = wf;
-    carry->last_window_id = wl;
-    carry->first_ts = plan.first_ts;
-    carry->last_ts = plan.last_ts;
-    carry->nrows = cols[ts_col].length;
-    carry->naggs = naggs;
-    if (plan.W <= 0) return 0;
-    // the descriptor block of the shard's call, with output columns nobody writes (range_state mode 0 only reads rows)
-    std::vector<bowgpu_out> no_outs(naggs);
-    void *dummy;
-    BG_TRY(ctx_pool(c, kPoolShard, 16384, &dummy));
-    for (int i = 0; i < naggs; i++) {
-        memset(&no_outs[i], 0, sizeof(bowgpu_out));
-        no_outs[i].values = dummy; no_outs[i].validity = reinterpret_cast<uint8_t *>(dummy);
-        no_outs[i].length = 0; no_outs[i].residency = BOWGPU_DEVICE;
-    }
-    AggJob job;
-    BG_TRY(job_build(c, cols, ncols, ts_col, plan, 0, aggs, naggs, no_outs.data(), wf, 0, holds_global_row0 != 0, &job));
-    bowgpu_carry_state *dst = reinterpret_cast<bowgpu_carry_state *>(dummy);
-    BG_TRY(launch_range_state(c, job.P, 0, (uint64_t)wl, nullptr, dst, nullptr));
-    BG_HIP(hipMemcpyAsync(carry->last, dst, sizeof(bowgpu_carry_state) * naggs, hipMemcpyDeviceToHost, c->stream));
-    BG_HIP(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int bowgpu_shard_fix_first(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, int64_t interval,
-                           const bowgpu_options *opts, int64_t global_s0, int64_t lead, const bowgpu_agg *aggs,
-                           int32_t naggs, bowgpu_out *outs, int64_t first_window_id, const bowgpu_carry_state *seeds,
-                           bowgpu_carry_state *merged_out, const bowgpu_next_row *next_row) {
-    if (!cols || ncols <= 0 || !seeds || !outs) return fail(BOWGPU_ERR_ARG, "null argument");
-    bowgpu_options o = {0, 0, 0};
-    if (opts) o = *opts;
-    int inclusive = 0, nic = -1;
-    BG_TRY(validate_aggs(cols, ncols, ts_col, aggs, naggs, &inclusive, &nic));
-    BG_TRY(shard_check(cols, ncols, aggs, naggs, outs, &o));
-    Ctx *c;
-    BG_TRY(ctx_get(&c));
-    Plan plan;
-    int64_t wf, wl;
-    BG_TRY(shard_plan(c, &cols[ts_col], interval, o.offset, global_s0, &plan, &wf, &wl));
-    if (wf != first_window_id) return fail(BOWGPU_ERR_ARG, "first_window_id %lld does not match the shard (%lld)", (long long)first_window_id, (long long)wf);
-    AggJob job;
-    if (lead < 0 || lead > wf) return fail(BOWGPU_ERR_ARG, "bad lead_empty_windows %lld", (long long)lead);
-    const int64_t Wtot = plan.W + lead;
-    BG_TRY(job_build(c, cols, ncols, ts_col, plan, inclusive, aggs, naggs, outs, wf - lead, Wtot, false, &job));
-    // the caller's validity bytes are the truth for this second phase: bring them into the word-aligned working copy
-    for (int i = 0; i < naggs; i++)
-        BG_HIP(hipMemcpyAsync(job.douts[i].validity, outs[i].validity, (size_t)((Wtot + 7) >> 3), hipMemcpyDeviceToDevice, c->stream));
-    void *pool;
-    BG_TRY(ctx_pool(c, kPoolShard, 16384, &pool));
-    bowgpu_carry_state *dseed = reinterpret_cast<bowgpu_carry_state *>(pool);
-    bowgpu_carry_state *dout = reinterpret_cast<bowgpu_carry_state *>(reinterpret_cast<char *>(pool) + 4096);
-    bowgpu_next_row *dnext = nullptr;
-    if (inclusive && next_row && next_row->present) {
-        dnext = reinterpret_cast<bowgpu_next_row *>(reinterpret_cast<char *>(pool) + 8192);
-        BG_HIP(hipMemcpyAsync(dnext, next_row, sizeof *next_row, hipMemcpyHostToDevice, c->stream));
-    }
-    BG_HIP(hipMemcpyAsync(dseed, seeds, sizeof(bowgpu_carry_state) * naggs, hipMemcpyHostToDevice, c->stream));
-    BG_TRY(launch_range_state(c, job.P, 1, (uint64_t)wf, dseed, dout, dnext));
-    if (merged_out) {
-        BG_HIP(hipMemcpyAsync(merged_out, dout, sizeof(bowgpu_carry_state) * naggs, hipMemcpyDeviceToHost, c->stream));
-        BG_HIP(hipStreamSynchronize(c->stream));
-    }
-    BG_TRY(job_finish(c, &job, aggs, naggs));
+    if (naggs > BOWGPU_CARRY_MAX_AGGS) return fail(BOWGPU_ERR_UNSUPPORTED, "sharded aggregate: too many aggregations");
     return 0;
 }
 
@@ -2509,22 +2345,8 @@ int bowgpu_carry_merge(const bowgpu_carry_state *L, const bowgpu_carry_state *R,
     return 0;
 }
 
-int bowgpu_shard_span(const bowgpu_col *ts, int64_t *first_ts, int64_t *last_ts, int64_t *nrows) {
-    if (!ts || !first_ts || !last_ts || !nrows) return fail(BOWGPU_ERR_ARG, "null argument");
-    *first_ts = 0; *last_ts = 0; *nrows = ts->length;
-    if (ts->length == 0) return 0;
-    Plan p;
-    BG_TRY(plan_make(nullptr, ts, 1, 0, &p));  // (interval 1: only the two scalars matter; one synchronisation)
-    *first_ts = p.first_ts;
-    *last_ts = p.last_ts;
-    return 0;
-}
-
-int bowgpu_shard_first_row(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, const bowgpu_agg *aggs, int32_t naggs,
-                           bowgpu_next_row *out) {
-    if (!cols || !aggs || !out || ncols <= 0) return fail(BOWGPU_ERR_ARG, "null argument");
-    if (ts_col < 0 || ts_col >= ncols) return fail(BOWGPU_ERR_BAD_COL, "no interval column with index %d", ts_col);
-    if (naggs > BOWGPU_CARRY_MAX_AGGS) return fail(BOWGPU_ERR_UNSUPPORTED, "sharded aggregate: too many aggregations");
+// the rank's first row as the rank to its left needs it for an inclusive window (bowgpu_shard_record.first_row)
+static int shard_first_row(const bowgpu_col *cols, int32_t ts_col, const bowgpu_agg *aggs, int32_t naggs, bowgpu_next_row *out) {
     memset(out, 0, sizeof *out);
     if (cols[ts_col].length == 0) return 0;
     Ctx *c;
@@ -2548,17 +2370,12 @@ int bowgpu_shard_first_row(const bowgpu_col *cols, int32_t ncols, int32_t ts_col
     uint64_t tsb = 0;
     int32_t tv = 0;
     BG_TRY(fetch(cols[ts_col], &tsb, &tv));
-    for (int i = 0; i < naggs; i++) {
-        if (aggs[i].col < 0 || aggs[i].col >= ncols) return fail(BOWGPU_ERR_BAD_COL, "aggregation %d: no column with index %d", i, aggs[i].col);
-        BG_TRY(fetch(cols[aggs[i].col], &out->bits[i], &out->valid[i]));
-    }
+    for (int i = 0; i < naggs; i++) BG_TRY(fetch(cols[aggs[i].col], &out->bits[i], &out->valid[i]));   // (validate_aggs checked aggs[i].col)
     BG_HIP(hipStreamSynchronize(c->stream));
     out->ts = (int64_t)tsb;
     out->present = 1;
     return 0;
 }
-
-// ---- the shard protocol: begin -> one exchange -> finish --------------------------------------------------------------
 
 // largest point of the window grid {offset + k * interval} that is <= t; false when it is not an int64
 static bool grid_floor(int64_t t, int64_t interval, int64_t offset_norm, int64_t *out) {
@@ -2570,14 +2387,6 @@ static bool grid_floor(int64_t t, int64_t interval, int64_t offset_norm, int64_t
     return true;
 }
 
-static int shard_cols_check(const bowgpu_col *cols, int32_t ncols, const bowgpu_agg *aggs, int32_t naggs) {
-    (void)cols; (void)ncols;   // (any residency: bowgpu_shard_begin stages host-resident columns like every other entry point)
-    for (int i = 0; i < naggs; i++)
-        if (aggs[i].kind == BOWGPU_AGG_MODE) return fail(BOWGPU_ERR_UNSUPPORTED, "sharded aggregate: Mode is not a mergeable reducer");
-    if (naggs > BOWGPU_CARRY_MAX_AGGS) return fail(BOWGPU_ERR_UNSUPPORTED, "sharded aggregate: too many aggregations");
-    return 0;
-}
-
 int bowgpu_shard_begin(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, int64_t interval, const bowgpu_options *opts,
                        const bowgpu_agg *aggs, int32_t naggs, const int64_t *global_s0, bowgpu_shard_record *rec) {
     if (!cols || ncols <= 0 || !rec || !aggs) return fail(BOWGPU_ERR_ARG, "null argument");
@@ -2586,7 +2395,7 @@ int bowgpu_shard_begin(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, in
     if (opts) o = *opts;
     int inclusive = o.inclusive ? 1 : 0, nic = -1;
     BG_TRY(validate_aggs(cols, ncols, ts_col, aggs, naggs, &inclusive, &nic));
-    BG_TRY(shard_cols_check(cols, ncols, aggs, naggs));
+    BG_TRY(shard_check(aggs, naggs));
     memset(rec, 0, sizeof *rec);
     rec->naggs = naggs;
     rec->flags = global_s0 ? 1 : 0;
@@ -2609,7 +2418,7 @@ int bowgpu_shard_begin(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, in
     // (window 0 of the real grid also takes the rows below s0: range_state_kernel starts at row 0 for it)
     rec->carry_from_ts = wl == 0 ? INT64_MIN : (int64_t)((uint64_t)base + (uint64_t)wl * (uint64_t)interval);
     if (inclusive)
-        BG_TRY(bowgpu_shard_first_row(cols, ncols, ts_col, aggs, naggs, &rec->first_row));
+        BG_TRY(shard_first_row(cols, ts_col, aggs, naggs, &rec->first_row));
     std::vector<bowgpu_out> no_outs(naggs);
     void *dummy;
     BG_TRY(ctx_pool(c, kPoolShard, 16384, &dummy));
@@ -2645,7 +2454,7 @@ int bowgpu_shard_pass_begin(const bowgpu_col *cols, int32_t ncols, int32_t ts_co
     if (opts) o = *opts;
     int inclusive = o.inclusive ? 1 : 0, nic = -1;
     BG_TRY(validate_aggs(cols, ncols, ts_col, aggs, naggs, &inclusive, &nic));
-    BG_TRY(shard_check(cols, ncols, aggs, naggs, outs, &o, true));
+    BG_TRY(shard_check(aggs, naggs));
     if (cols[ts_col].type != BOWGPU_INT64) return fail(BOWGPU_ERR_TS_TYPE, "impossible to create a new intervalRolling on column of type float64");
     if (me->nrows != cols[ts_col].length) return fail(BOWGPU_ERR_ARG, "the record says %lld rows, the interval column has %lld",
                                                       (long long)me->nrows, (long long)cols[ts_col].length);
@@ -2756,7 +2565,7 @@ int bowgpu_shard_finish(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, i
     if (opts) o = *opts;
     int inclusive = o.inclusive ? 1 : 0, nic = -1;
     BG_TRY(validate_aggs(cols, ncols, ts_col, aggs, naggs, &inclusive, &nic));
-    BG_TRY(shard_check(cols, ncols, aggs, naggs, outs, &o, true));
+    BG_TRY(shard_check(aggs, naggs));
     const bool strict = strict_wanted(&o);
     StrictScope strict_scope(strict);
     bowgpu_shard_decision d;

@@ -395,7 +395,7 @@ int launch_and_bits(Ctx *c, const uint32_t *a, int64_t abit0, const uint32_t *b,
 
 // shard.hip
 int launch_range_state(Ctx *c, const AggParams &p, int mode, uint64_t wid, const bowgpu_carry_state *d_seeds,
-                       bowgpu_carry_state *d_states_out, const bowgpu_next_row *d_next = nullptr, int seed_alive = 1, int strict = 0);
+                       bowgpu_carry_state *d_states_out, const bowgpu_next_row *d_next, int seed_alive, int strict);
 
 int launch_fill_empty(Ctx *c, const AggParams &p, int64_t slot0, int64_t slot1);
 
@@ -416,7 +416,7 @@ size_t stats_size();
 constexpr int kNbrBlockBits = 4096;
 constexpr int kPoolMode = 17;    // aggregation.Mode: its output's validity working copy
 constexpr int kPoolColOrder = 18; // IsColSorted: one (first valid, last valid) record per 512-row trip
-constexpr int kPoolShard = 19;   // shard stitch: seed / merged states and the next shard's first row
+constexpr int kPoolShard = 19;   // shard stitch: the record's states, the seeds and the next shard's first row
 constexpr int kPoolGaps = 32;    // window_first_rows: queued runs of empty windows
 constexpr int kPoolWhole = 33;        // bowgpu_aggregate_whole: partial states, the reducers' values and validity bytes
 constexpr int kPoolInterpEdge = 31;   // Interpolate: the trips' edge words (interp_wave3_kernel)

@@ -1,11 +1,13 @@
 // shard.hip — the boundary-window stitch of the row-range sharded Rolling.Aggregate.
 //
 // A rank reduces its own rows with the ordinary tile kernels.  Only the window that straddles a
-// shard boundary needs more: the left rank exports the RUNNING STATE of its last window
-// (range_state_kernel, mode 0), the ranks exchange those fixed-size records (one RCCL all_gather of
-// bytes, done by the caller), and the right rank re-walks its own rows of that window seeded with
-// the left state (mode 1) - i.e. the straddling window is folded in the reference's row order
-// (sum.go:16-22, arithmeticmean.go:17-24, minmax.go:16-28), bit-exact, with no collective on the data.
+// shard boundary needs more: bowgpu_shard_begin puts the RUNNING STATE of the rank's last window
+// in its record (range_state_kernel, mode 0), the ranks exchange those fixed-size records (one RCCL
+// all_gather of bytes, done by the caller), and bowgpu_shard_finish on the right rank re-walks its
+// own rows of that window seeded with the left state (mode 1) - i.e. the straddling window is folded
+// in the reference's row order (sum.go:16-22, arithmeticmean.go:17-24, minmax.go:16-28), bit-exact,
+// with no collective on the data.  _finish also closes the rank's last window with the next rank's
+// first row when that row is the window's inclusive row (mode 2).
 #include "agg_device.h"
 
 namespace bowgpu {
@@ -32,10 +34,11 @@ constexpr int kSeqLimit = 8192;  // longer ranges are merged from 256 contiguous
 
 }  // namespace
 
-// mode 0: state of window `wid` over rows [lower_bound(ts, start(wid)), n)        -> states_out
-// mode 1: seeds + rows [0, lower_bound(ts, start(wid+1))) of window `wid` -> outputs slot + states_out
-// mode 2: like mode 0, and the outputs of slot `wid` are (re)written: the shard owns its last window and only now learns
-//         whether the next shard's first row is that window's inclusive row
+// mode 0 (bowgpu_shard_begin): state of window `wid` over rows [lower_bound(ts, start(wid)), n)          -> states_out
+// mode 1 (bowgpu_shard_finish): seeds + rows [0, lower_bound(ts, start(wid+1))) of window `wid`          -> outputs of slot `wid`
+// mode 2 (bowgpu_shard_finish): rows as in mode 0, no seeds; the shard owns its last window and only now learns whether the next
+//         shard's first row is that window's inclusive row                                                 -> outputs of slot `wid`
+// Modes 1 and 2 write no states (states_out: nullptr); mode 0 writes no outputs.
 // next: the first row of the next non-empty shard to the right (nullable).  The window's inclusive row (rolling.go:201-209) is
 // the local row right after its rows when that row sits exactly on the window's end, else `next` when ITS timestamp does.
 // seed_alive: some row behind the seeds has ts >= s0.  Window 0 also spans the rows BELOW s0 (negative timestamps), but it is an
@@ -129,8 +132,8 @@ __global__ __launch_bounds__(256) void range_state_kernel(const AggParams p, con
         }
         if (tid == 0) {
             int64_t nrows = seed_rows + len;
-            if (states_out) stats_to_carry(acc, nrows, states_out[a]);
-            if (mode != 0 && (uint64_t)oslot < (uint64_t)p.W) {
+            if (mode == 0) stats_to_carry(acc, nrows, states_out[a]);
+            else if ((uint64_t)oslot < (uint64_t)p.W) {
                 if (wid == 0 && !incl_src && !seed_alive && !(len > 0 && p.ts[r1 - 1] >= p.s0)) {   // dead window 0: an empty slice
                     stats_init(acc);
                     nrows = 0;

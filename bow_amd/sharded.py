@@ -224,7 +224,6 @@ class GpuProvider:
         s0 = C.byref(C.c_int64(global_s0)) if global_s0 is not None else None
         capi.check(capi.lib().bowgpu_shard_begin(self._carr, len(self.cols), self.ts_col, C.c_int64(self.interval),
                                                  C.byref(self._opts), self._aarr, len(self.aggs), s0, C.byref(rec)))
-        self._f, self._l = rec.first_ts, rec.last_ts
         return bytes(rec)
 
     def pass_begin(self, record):
@@ -269,43 +268,6 @@ class GpuProvider:
             oarr[i] = o.c()
             oarr[i].length = o.slots
         return oarr
-
-    # ---- the building blocks the protocol is made of (kept in the ABI; tests compare them with the fused path)
-    def first_last_nrows(self):
-        capi = self.capi
-        if self.n == 0:
-            return 0, 0, 0
-        f, l, n = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        c = self.cols[self.ts_col].c()
-        capi.check(capi.lib().bowgpu_shard_span(C.byref(c), C.byref(f), C.byref(l), C.byref(n)))
-        self._f, self._l = f.value, l.value
-        return self._f, self._l, self.n
-
-    def shard_aggregate(self, s0, holds_row0, lead, next_row=None, finish_last=False):
-        capi = self.capi
-        if self.outs is None:
-            self.first_last_nrows()
-            need = (self._l - max(self._f, s0)) // self.interval + 2 + lead if self.n else 1
-            self._ensure_outs(need)
-        oarr = self._ensure_outs(1)
-        carry = capi.ShardCarry()
-        nr = capi.NextRow.from_buffer_copy(next_row) if next_row is not None else None
-        capi.check(capi.lib().bowgpu_shard_aggregate(self._carr, len(self.cols), self.ts_col, C.c_int64(self.interval),
-                                                     C.byref(self._opts), C.c_int64(s0), int(holds_row0), C.c_int64(lead),
-                                                     self._aarr, len(self.aggs), oarr, C.byref(carry),
-                                                     C.byref(nr) if nr is not None else None, int(bool(finish_last))))
-        for i, o in enumerate(self.outs):
-            o.absorb(oarr[i])
-        return bytes(carry)
-
-    def shard_carry_only(self, s0, holds_row0):
-        """the carry shard_aggregate will return, from the rows of the last window alone"""
-        capi = self.capi
-        carry = capi.ShardCarry()
-        capi.check(capi.lib().bowgpu_shard_carry_only(self._carr, len(self.cols), self.ts_col, C.c_int64(self.interval),
-                                                      C.byref(self._opts), C.c_int64(s0), int(holds_row0),
-                                                      self._aarr, len(self.aggs), C.byref(carry)))
-        return bytes(carry)
 
 
 class ShardedRolling:

@@ -29,7 +29,9 @@ extern "C" {
  * arguments; bowgpu_agg_info gained nothing (same layout). */
 /* 6 (round 6): bowgpu_set_devices / bowgpu_get_devices / bowgpu_set_fanout_min_rows added (one call over several devices); no struct
  * changed. */
-#define BOWGPU_ABI_VERSION 6
+/* 7: the one-call-per-phase shard entry points bowgpu_shard_{span, aggregate, carry_only, fix_first, first_row} and the
+ * bowgpu_shard_carry struct removed (the shard record protocol is the one sharded Aggregate); no remaining struct changed. */
+#define BOWGPU_ABI_VERSION 7
 
 /* bow.Type (reference bowtypes.go:17-32) */
 enum {
@@ -145,8 +147,8 @@ typedef struct bowgpu_options {
                                    the shard record protocol - bowgpu_shard_begin / _pass_begin / _finish: a window shared by TWO ranks
                                    is re-walked by the right rank seeded with the left rank's running state, i.e. in row order across
                                    the boundary; a window spread over three or more ranks, or a boundary window of more than 2^20
-                                   rows, is BOWGPU_ERR_UNSUPPORTED.  The round-1 building blocks (bowgpu_shard_aggregate,
-                                   _carry_only) decline it.  0: see bowgpu_agg_info.long_windows for the bound that applies */
+                                   rows, is BOWGPU_ERR_UNSUPPORTED.  0: see bowgpu_agg_info.long_windows for the bound that
+                                   applies */
 } bowgpu_options;
 
 /* Diagnostics of one aggregate call */
@@ -472,7 +474,7 @@ int bowgpu_parquet_column(const bowgpu_parquet *handle, int32_t i, char *name, i
 /* out: num_rows slots (HOST or DEVICE residency); values, validity, null_count and type are filled in */
 int bowgpu_parquet_read_column(bowgpu_parquet *handle, int32_t i, bowgpu_out *out);
 
-/* ---- row-range sharding across GPUs ----------------------------------- */
+/* ---- row-range sharded Rolling.Aggregate across GPUs: the records the ranks exchange ------------------ */
 
 /* Running state of one reducer over the rows a rank holds of a window that straddles a shard
  * boundary: what the reference's loops carry from one row to the next (sum.go:15-22,
@@ -496,8 +498,8 @@ typedef struct bowgpu_carry_state {
 } bowgpu_carry_state;
 
 /* The first row of the next non-empty shard to the right, per aggregator: what an INCLUSIVE window that ends exactly where
- * this shard's rows end needs from its successor (rolling.go:201-209).  Fixed size: it rides in the same all_gather as
- * (first_ts, last_ts, nrows). */
+ * this shard's rows end needs from its successor (rolling.go:201-209).  Fixed size: it rides in the rank's record
+ * (bowgpu_shard_record.first_row). */
 typedef struct bowgpu_next_row {
     int32_t present;                  /* 0: there is no row to the right */
     int32_t _pad;
@@ -507,64 +509,11 @@ typedef struct bowgpu_next_row {
 } bowgpu_next_row;
 
 #define BOWGPU_CARRY_MAX_AGGS 16
-typedef struct bowgpu_shard_carry {
-    int64_t first_window_id;   /* global id of the FIRST window with a row in this shard; -1: empty shard */
-    int64_t last_window_id;    /* global id of the LAST one */
-    int64_t first_ts, last_ts;
-    int64_t nrows;
-    int32_t naggs;
-    int32_t _pad;
-    bowgpu_carry_state last[BOWGPU_CARRY_MAX_AGGS];  /* per aggregator: state of the LAST window over this shard's rows */
-} bowgpu_shard_carry;
-
-/* first / last timestamp and row count of a shard's interval column: what the ranks exchange first (one round trip to the device) */
-int bowgpu_shard_span(const bowgpu_col *ts, int64_t *first_ts, int64_t *last_ts, int64_t *nrows);
-
-/* Sharded Rolling.Aggregate, phase 1.  This rank holds rows [row0, row0+len) of every column
- * (device-resident; outs device-resident).  global_s0 comes from bowgpu_plan_windows on the rank
- * that holds global row 0.  Reduces every window that has a row in the shard - output slot k is
- * global window first_window_id + k - treating the shard's first row as a window start, and
- * exports in *carry the running state of its last window.  All reducers; when some reducer needs inclusive windows
- * (IntegralTrapezoid, WeightedAverageLinear) pass next_row = the first row of the next non-empty shard to the right
- * (bowgpu_shard_first_row there), and finish_last = 1 when this shard owns its last window and that window is not
- * also its first one shared with ranks to the left (then bowgpu_shard_fix_first folds the row in).
- * lead_empty_windows: number of EMPTY windows between the left neighbour's last window and this
- * shard's first one that this rank also outputs (known after the ranks exchanged first/last ts):
- * output slot k is then global window first_window_id - lead_empty_windows + k. */
-int bowgpu_shard_aggregate(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, int64_t interval,
-                           const bowgpu_options *opts, int64_t global_s0, int32_t holds_global_row0,
-                           int64_t lead_empty_windows,
-                           const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs,
-                           bowgpu_shard_carry *carry,
-                           const bowgpu_next_row *next_row /* nullable */, int32_t finish_last);
-
-/* The carry bowgpu_shard_aggregate would export, WITHOUT reducing the shard: only the rows of the shard's last window are read.
- * Lets a caller put the carry exchange in flight before the shard's main pass (the exchange is latency, the pass is milliseconds).
- * For calls without inclusive reducers (with them the last window's state depends on the neighbour's first row: use the carry
- * bowgpu_shard_aggregate returns). */
-int bowgpu_shard_carry_only(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, int64_t interval,
-                            const bowgpu_options *opts, int64_t global_s0, int32_t holds_global_row0,
-                            const bowgpu_agg *aggs, int32_t naggs, bowgpu_shard_carry *carry);
-
-/* This shard's first row in the layout bowgpu_shard_aggregate / _fix_first of the LEFT neighbour expect. */
-int bowgpu_shard_first_row(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, const bowgpu_agg *aggs, int32_t naggs,
-                           bowgpu_next_row *out);
-
-/* Phase 2, after the ranks exchanged their carries.  seeds[i] is the state of this shard's first
- * window accumulated over the rows the LEFT ranks hold (one rank: its carry as is; several:
- * bowgpu_carry_merge in rank order).  Re-walks the shard's rows of that window seeded with it - so
- * the straddling window is reduced in the reference's row order - and rewrites output slot 0. */
-int bowgpu_shard_fix_first(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, int64_t interval,
-                           const bowgpu_options *opts, int64_t global_s0,
-                           int64_t lead_empty_windows,
-                           const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs,
-                           int64_t first_window_id, const bowgpu_carry_state *seeds,
-                           bowgpu_carry_state *merged_out /* nullable: state after this shard's rows */,
-                           const bowgpu_next_row *next_row /* nullable: used when the window is also the shard's last */);
 
 /* left (earlier rows) then right: the state of the concatenation.  Pure bookkeeping on two
- * records (no column data); Sum is left.sum + right.sum, i.e. NOT the row-order association -
- * only used when one window spans three or more ranks. */
+ * states (no column data); Sum is left.sum + right.sum, i.e. NOT the row-order association.
+ * bowgpu_shard_finish applies it to the records of the ranks to the left when one window spans
+ * three or more ranks (the seed of the right rank's re-walk). */
 int bowgpu_carry_merge(const bowgpu_carry_state *left, const bowgpu_carry_state *right,
                        bowgpu_carry_state *out);
 
@@ -613,8 +562,7 @@ typedef struct bowgpu_shard_decision {
 
 /* Columns and outputs of the three calls below: any residency since ABI 5.  Host-resident ones are staged through HBM per call
  * the way bowgpu_rolling_aggregate stages them (so begin + pass_begin move each column over PCIe twice, once for the record and
- * once for the pass; a pass put in flight keeps its staged copies until bowgpu_shard_finish collects it).  The one-call-per-phase
- * building blocks above (bowgpu_shard_aggregate, _fix_first, _shard_span) keep taking device memory only.
+ * once for the pass; a pass put in flight keeps its staged copies until bowgpu_shard_finish collects it).
  * global_s0: NULL on the first attempt. */
 int bowgpu_shard_begin(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, int64_t interval,
                        const bowgpu_options *opts, const bowgpu_agg *aggs, int32_t naggs,

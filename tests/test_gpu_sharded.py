@@ -1,13 +1,15 @@
 """Row-range sharding on ONE GPU: K simulated ranks each hold a row range in HBM and
 run the real protocol behind the C ABI (bowgpu_shard_begin -> the gathered records -> bowgpu_shard_finish; bow_amd/sharded.py
 is the transport) with the HIP provider; the stitched windows must equal the oracle on the whole frame."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
 from bow_amd import capi, sharded
 from test_gpu_callers import both_interp_kernels
 from oracle import pyoracle as orc
-from tolerance import assert_within, order_free_bounds
+from tolerance import U, assert_within, order_free_bounds
 
 pytestmark = pytest.mark.gpu
 
@@ -333,10 +335,63 @@ def test_sharded_window_0_of_rows_below_s0_only(tw):
                 assert np.array_equal(gv[gm], wv[wm]), label
 
 
-def test_carry_only_equals_the_carry_of_the_pass():
-    """bowgpu_shard_carry_only (what the bench's ranks exchange while their main pass runs) against the carry that
-    bowgpu_shard_aggregate returns, over random splits - empty shards, one-row shards, last windows of thousands of rows,
-    rows below s0 on the first shard"""
+CARRY_FIELDS = [f for f, _ in capi.CarryState._fields_]
+SEQ_LIMIT = 8192   # shard.hip kSeqLimit: a longer range is merged from 256 partials unless strict_order
+INTEGRAL = {"IntegralStep", "IntegralTrapezoid", "WeightedAverageStep", "WeightedAverageLinear"}   # (agg_device.h kind_is_integral)
+
+
+def row_order_state(ts, vals, valid, integral):
+    """bowgpu_carry_state of one reducer over the given rows, folded in row order (agg_device.h stats_value<true> / stats_point, the
+    fields as shard.hip stats_to_carry maps them; valid all False: a reducer that reads no column), and per order-free field the sum
+    of |terms| that its bound in tests/tolerance.py is made of"""
+    s = {f: 0.0 if t is C.c_double else 0 for f, t in capi.CarryState._fields_}
+    s["nrows"] = len(ts)
+    mags = {"sum": 0.0, "integ_step": 0.0, "integ_trap": 0.0}
+    for t, x, ok in zip(ts.tolist(), vals.tolist(), valid.tolist()):
+        if not ok:
+            continue
+        raw = int(np.float64(x).view(np.uint64))
+        s["sum"] += x
+        mags["sum"] += abs(x)
+        s["count"] += 1
+        if s["has_value"]:
+            if x < s["vmin"]:
+                s["vmin"] = x
+            if x > s["vmax"]:
+                s["vmax"] = x
+        else:
+            s["vmin"] = s["vmax"] = x
+            s["first_bits"] = raw
+            s["has_value"] = 1
+        s["last_bits"] = raw
+        if x == x:
+            if not s["has_nn"]:
+                s["nn_min"] = s["nn_max"] = x
+                s["has_nn"] = 1
+            else:
+                s["nn_min"] = x if x < s["nn_min"] else s["nn_min"]
+                s["nn_max"] = x if x > s["nn_max"] else s["nn_max"]
+        if integral:
+            t = float(t)
+            if s["has_point"]:
+                trap = (s["pv"] + x) / 2 * (t - s["pt"])
+                step = s["pv"] * (t - s["pt"])
+                s["integ_trap"] += trap
+                s["integ_step"] += step
+                mags["integ_trap"] += abs(trap)
+                mags["integ_step"] += abs(step)
+                s["has_pair"] = 1
+            else:
+                s["first_pt"], s["first_pv"], s["has_point"] = t, x, 1
+            s["pt"], s["pv"] = t, x
+    return s, mags
+
+
+def test_record_states_are_the_row_order_states_of_the_last_window():
+    """the running states bowgpu_shard_begin puts in a rank's record (computed on the offset-aligned grid, before any rank knows
+    s0) against the rank's last window folded in row order on the host, over random splits - empty shards, one-row shards, last
+    windows of thousands of rows, rows below s0 on the first shard, plain and time-weighted sets, nulls.  Bit for bit, except the
+    float sums of a range longer than SEQ_LIMIT rows without strict_order (merged from partials): those within the order-free bound"""
     rng = np.random.default_rng(77)
     for case in range(40):
         n = int(rng.integers(1, 30_000))
@@ -348,23 +403,32 @@ def test_carry_only_equals_the_carry_of_the_pass():
         K = int(rng.integers(2, 6))
         cuts = np.sort(rng.integers(0, n + 1, K - 1))
         bounds = list(zip([0] + list(cuts), list(cuts) + [n]))
-        first_nonempty = next(a for a, b in bounds if b > a)
-        s0 = sharded.first_window_start(int(ts[first_nonempty]), interval, offset)
         aggs = TW_AGGS[:3] + AGGS[1:5] if case % 2 else AGGS
-        aggs = [a for a in aggs if a[0] not in ("IntegralTrapezoid", "WeightedAverageLinear")]
         for r, (a, b) in enumerate(bounds):
             if b == a:
                 continue
+            first, last = int(ts[a]), int(ts[b - 1])
+            start = last - (last - offset) % interval          # the grid window {offset + k * interval} that holds the last row
+            keep = ts[a:b] >= start
+            rows = int(keep.sum())
+            want = {(reads, tw): row_order_state(ts[a:b][keep], vals[a:b][keep], valid[a:b][keep] & reads, tw)
+                    for reads in (False, True) for tw in (False, True)}
             cols = [capi.Column(ts[a:b].copy(), None, capi.INT64).to_device(),
                     capi.Column(vals[a:b].copy(), np.packbits(valid[a:b], bitorder="little"), capi.FLOAT64, 0, b - a, -1).to_device()]
-            prov = sharded.GpuProvider(cols, 0, interval, aggs, offset=offset)
-            prov.first_last_nrows()
-            early = prov.shard_carry_only(s0, a == 0)
-            full = prov.shard_aggregate(s0, a == 0, 0)
-            assert early == full, (case, r, n, interval, offset)
-            # ... and the states bowgpu_shard_begin puts in the rank's record (computed on the offset-aligned grid, before any
-            # rank knows s0) are those same states whenever the record covers the rank's whole last window
-            rec = capi.ShardRecord.from_buffer_copy(prov.begin())
-            car = capi.ShardCarry.from_buffer_copy(full)
-            if s0 <= int(ts[a]):
-                assert bytes(rec.last) == bytes(car.last), (case, r, n, interval, offset)
+            for strict in (False, True):
+                rec = capi.ShardRecord.from_buffer_copy(sharded.GpuProvider(cols, 0, interval, aggs, offset=offset, strict_order=strict).begin())
+                label = (case, r, n, interval, offset, strict)
+                assert (rec.nrows, rec.first_ts, rec.last_ts, rec.naggs) == (b - a, first, last, len(aggs)), label
+                assert rec.carry_from_ts == (-2 ** 63 if start <= first else start), label
+                for i, (kind, _) in enumerate(aggs):
+                    exp, mags = want[(kind not in ("WindowStart", "NumRows"), kind in INTEGRAL)]
+                    for f in CARRY_FIELDS:
+                        got = getattr(rec.last[i], f)
+                        if f in mags and rows > SEQ_LIMIT and not strict:
+                            bound = (2.0 if f == "sum" else 4.0) * (rows + 2.0) * U * mags[f]
+                            assert_within(label + (kind, f), [got], [exp[f]], [bound])
+                        elif isinstance(exp[f], float):
+                            assert np.float64(got).view(np.uint64) == np.float64(exp[f]).view(np.uint64), label + (kind, f, got, exp[f])
+                        else:
+                            assert got == exp[f], label + (kind, f, got, exp[f])
+                assert not any(any(bytes(st)) for st in rec.last[len(aggs):]), label
