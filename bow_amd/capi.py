@@ -26,7 +26,7 @@ INTERP = {"WindowStart": 0, "Linear": 1, "StepPrevious": 2, "None": 3, "Const": 
 
 MAX_FACTORS = 4
 CARRY_MAX_AGGS = 16
-ABI_VERSION = 7   # include/bowgpu.h BOWGPU_ABI_VERSION (asserted when the library is loaded)
+ABI_VERSION = 8   # include/bowgpu.h BOWGPU_ABI_VERSION (asserted when the library is loaded)
 
 ERR_NAMES = {
     -1: "INTERVAL", -2: "TS_TYPE", -3: "FIRST_TS_NULL", -4: "NO_AGG", -5: "KEEP_INTERVAL", -6: "BAD_COL",
@@ -132,6 +132,7 @@ SYMBOLS = [
     "bowgpu_parquet_info", "bowgpu_parquet_column", "bowgpu_parquet_read_column",
     "bowgpu_debug_set_route", "bowgpu_debug_get_route", "bowgpu_checksum64_at",
     "bowgpu_set_devices", "bowgpu_get_devices", "bowgpu_set_fanout_min_rows", "bowgpu_last_call_ranks", "bowgpu_fanout_counts",
+    "bowgpu_rolling_aggregate_sharded",
 ]
 
 _lib = None
@@ -577,6 +578,58 @@ def rolling_aggregate(cols, ts_col, interval, aggs, offset=0, inclusive=False, o
     for i, o in enumerate(outs):
         o.absorb(oarr[i])
     return outs, info
+
+
+def _sharded_args(cols_by_rank, device_ids, aggs):
+    world = len(cols_by_rank)
+    if len(device_ids) != world:
+        raise ValueError("one device id per rank: %d ranks, %d ids" % (world, len(device_ids)))
+    ncols = len(cols_by_rank[0]) if world else 0
+    carrs = [_cols(cols) for cols in cols_by_rank]
+    cptrs = (C.POINTER(Col) * max(world, 1))(*[C.cast(a, C.POINTER(Col)) for a in carrs])
+    ids = (C.c_int32 * max(world, 1))(*device_ids)
+    return world, ncols, carrs, cptrs, ids, _aggs(aggs)
+
+
+def _sharded_call(cols_by_rank, ts_col, interval, aggs, device_ids, offset, inclusive, strict_order, oarrs):
+    world, ncols, carrs, cptrs, ids, aarr = _sharded_args(cols_by_rank, device_ids, aggs)
+    optrs = None
+    if oarrs is not None:
+        optrs = (C.POINTER(Out) * max(world, 1))(*[C.cast(a, C.POINTER(Out)) for a in oarrs])
+    decisions = (ShardDecision * max(world, 1))()
+    info = AggInfo()
+    opts = Options(offset, int(bool(inclusive)), int(bool(strict_order)))
+    check(lib().bowgpu_rolling_aggregate_sharded(cptrs, ids, world, ncols, ts_col, C.c_int64(interval), C.byref(opts), aarr, len(aggs),
+                                                 optrs, decisions, C.byref(info)))
+    return [decisions[r] for r in range(world)], info
+
+
+def sharded_layout(cols_by_rank, ts_col, interval, aggs, device_ids, offset=0, inclusive=False, strict_order=False):
+    """bowgpu_rolling_aggregate_sharded's layout query: every rank's ShardDecision (first_slot_window_id, windows_local, windows_owned,
+    ...) from the ranks' row counts and first / last timestamps, no pass run"""
+    return _sharded_call(cols_by_rank, ts_col, interval, aggs, device_ids, offset, inclusive, strict_order, None)[0]
+
+
+def rolling_aggregate_sharded(cols_by_rank, ts_col, interval, aggs, device_ids, offset=0, inclusive=False, strict_order=False,
+                              out_residency=DEVICE, outs_by_rank=None):
+    """ONE Rolling.Aggregate over a frame held as row-range shards (cols_by_rank[r]: rank r's columns, on device_ids[r]) -
+    bowgpu_rolling_aggregate_sharded.  Returns (outs_by_rank, decisions, info): outs_by_rank[r][i] holds the windows_owned slots of
+    output i that rank r owns, slot k = global window decisions[r].first_slot_window_id + k.  Without outs_by_rank the outputs are
+    allocated from the layout query (capacity windows_local each)."""
+    if outs_by_rank is None:
+        ds = sharded_layout(cols_by_rank, ts_col, interval, aggs, device_ids, offset, inclusive, strict_order)
+        outs_by_rank = [[OutColumn(max(d.windows_local, 0), out_residency) for _ in aggs] for d in ds]
+    oarrs = []
+    for outs in outs_by_rank:
+        oarr = (Out * max(len(aggs), 1))()
+        for i, o in enumerate(outs):
+            oarr[i] = o.c()
+        oarrs.append(oarr)
+    decisions, info = _sharded_call(cols_by_rank, ts_col, interval, aggs, device_ids, offset, inclusive, strict_order, oarrs)
+    for outs, oarr in zip(outs_by_rank, oarrs):
+        for i, o in enumerate(outs):
+            o.absorb(oarr[i])
+    return outs_by_rank, decisions, info
 
 
 def window_bounds(ts, interval, offset=0, inclusive=False):

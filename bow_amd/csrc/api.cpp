@@ -2305,6 +2305,36 @@ static int shard_check(const bowgpu_agg *aggs, int32_t naggs) {
     return 0;
 }
 
+}  // extern "C"
+
+namespace bowgpu {
+int sharded_validate(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, int64_t interval, const bowgpu_agg *aggs, int32_t naggs) {
+    // plan_make's order (newIntervalRolling first), then validateAggregation's, then the protocol's own limits
+    const int t = cols[ts_col].type;
+    if (t != BOWGPU_INT64)
+        return fail(BOWGPU_ERR_TS_TYPE, "impossible to create a new intervalRolling on column of type %s",
+                    t == BOWGPU_FLOAT64 ? "float64" : t == BOWGPU_BOOLEAN ? "bool" : t == BOWGPU_STRING ? "utf8" : "undefined");
+    int64_t off;
+    BG_TRY(enforce_interval_and_offset(interval, 0, &off));
+    int inclusive = 0, nic = -1;
+    BG_TRY(validate_aggs(cols, ncols, ts_col, aggs, naggs, &inclusive, &nic));
+    return shard_check(aggs, naggs);
+}
+
+int ts_null_rows(Ctx *c, const bowgpu_col *ts, int64_t *nulls) {
+    *nulls = 0;
+    if (!ts->validity || ts->null_count == 0 || ts->length == 0) return 0;
+    if (ts->null_count > 0) { *nulls = ts->null_count; return 0; }
+    DevCol probe;
+    BG_TRY(devcol_prepare(c, ts, &probe, false, true));
+    *nulls = probe.null_count;
+    BG_HIP(hipStreamSynchronize(c->stream));   // (before the probe's blocks go back to the cache)
+    return 0;
+}
+}  // namespace bowgpu
+
+extern "C" {
+
 int bowgpu_carry_merge(const bowgpu_carry_state *L, const bowgpu_carry_state *R, bowgpu_carry_state *out) {
     // concatenation of two row ranges of one window, left then right (same rules as the device stats_merge)
     if (!L || !R || !out) return fail(BOWGPU_ERR_ARG, "null argument");

@@ -174,6 +174,22 @@ int multi_interpolate_aggregate(const bowgpu_col *cols, int32_t ncols, int32_t t
                                 const bowgpu_interp *interps, int32_t ninterps, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs,
                                 bowgpu_agg_info *info, bool *done);
 
+// api.cpp, for bowgpu_rolling_aggregate_sharded (multi.cpp): the checks of bowgpu_rolling_aggregate that need no column data
+// (interval column type, interval, aggregators) plus the shard protocol's own (Mode, at most 16 aggregators) - host only
+int sharded_validate(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, int64_t interval, const bowgpu_agg *aggs, int32_t naggs);
+// nulls of an interval column (counted on the calling thread's device when the caller said -1)
+int ts_null_rows(Ctx *c, const bowgpu_col *ts, int64_t *nulls);
+
+// shard.hip: the tail of a rank of bowgpu_rolling_aggregate_sharded that does not own its last output slot (one lane per output)
+struct ShardTailArgs {
+    uint64_t *values[BOWGPU_CARRY_MAX_AGGS];
+    uint8_t *validity[BOWGPU_CARRY_MAX_AGGS];
+    uint8_t *report;     // host-mapped block: byte i = whether output i's slot was valid
+    int64_t slot;
+    int32_t n;
+};
+int launch_shard_tail(Ctx *c, const ShardTailArgs &a);
+
 // ---------------------------------------------------------------- kernels (rolling_agg.hip)
 constexpr int kMaxCols = 8;    // value columns reduced per launch
 constexpr int kMaxAggs = 16;   // output columns per launch

@@ -15,6 +15,11 @@
 // thread's device (how a one-GPU box exercises the path: the same id listed N times).  Everything the record protocol declines
 // (Mode, more than 16 aggregators, interval columns with nulls, strict_order windows over three ranks) is served by the one-device
 // path as before.  No CPU implementation of anything here: the ranks run the HIP kernels.
+//
+// bowgpu_rolling_aggregate_sharded (below the fan-out, with a worker pool of its own) serves the frame the CALLER already holds as row
+// ranges, one per device: each rank runs its whole part inside ONE dispatch - record, pass in flight, record published, a barrier among
+// the workers, finish straight into the caller's buffers of that rank, the tail of a window it does not own (shard.hip
+// shard_tail_kernel) - and the calling thread joins once.  No device temporaries for the outputs, no bitmaps through the host.
 #include <stdlib.h>
 #include <string.h>
 
@@ -413,6 +418,234 @@ void rank_cleanup(Worker *w, Call *call, int r) {
 
 bool is_decline(int rc) { return rc == BOWGPU_ERR_UNSUPPORTED || rc == BOWGPU_ERR_TS_NULLS; }
 
+// ---------------------------------------------------------------- bowgpu_rolling_aggregate_sharded: the caller's shards, one dispatch, one join
+// A barrier among the workers of one call.  Sticky abort: once a rank has failed, every wait - now or later - returns false, so no
+// worker is left waiting for a rank that will not come.
+struct Barrier {
+    std::mutex mu;
+    std::condition_variable cv;
+    int n = 0, arrived = 0;
+    uint64_t gen = 0;
+    bool aborted = false;
+    bool wait() {
+        std::unique_lock<std::mutex> lk(mu);
+        if (aborted) return false;
+        const uint64_t g = gen;
+        if (++arrived == n) { arrived = 0; gen++; cv.notify_all(); return true; }
+        cv.wait(lk, [&] { return gen != g || aborted; });
+        return gen != g;
+    }
+    void abort() {
+        std::lock_guard<std::mutex> g(mu);
+        aborted = true;
+        cv.notify_all();
+    }
+};
+
+struct ShardedCall {
+    const bowgpu_col *const *cols_by_rank;
+    const int32_t *ids;
+    int world;
+    int32_t ncols, ts_col;
+    int64_t interval;
+    bowgpu_options opts;
+    const bowgpu_agg *aggs;
+    int32_t naggs;
+    bowgpu_out *const *outs_by_rank;
+    uint32_t route;
+    std::vector<Call> views;                       // rank r's columns as rank_stage sees them (a Call of one rank: rows [0, length))
+    std::vector<Rank> ranks;                       // ... and its staged copies
+    std::vector<bowgpu_shard_record> records[2];   // the exchange: first round, second round (rows below s0 split across ranks)
+    std::vector<bowgpu_shard_decision> decisions;
+    std::vector<bowgpu_agg_info> infos;
+    Barrier barrier;
+    std::mutex err_mu;
+    int rc = 0;
+    std::string err;
+    void fail_rank(int code) {   // on the failing worker: its thread-local message
+        {
+            std::lock_guard<std::mutex> g(err_mu);
+            if (rc == 0) { rc = code; err = bowgpu_last_error(); }
+        }
+        barrier.abort();
+    }
+};
+
+Fanout *g_sharded = nullptr;   // the workers of bowgpu_rolling_aggregate_sharded (not the fan-out's); never destroyed, like g_fan
+
+Fanout *sharded_pool() {
+    std::lock_guard<std::mutex> g(g_cfg_mu);
+    if (!g_sharded) g_sharded = new Fanout();
+    return g_sharded;
+}
+
+void sharded_grow_locked(Fanout *f, int world) {
+    while ((int)f->workers.size() < world) {
+        Worker *w = new Worker();
+        w->device = -1;
+        w->th = std::thread(worker_main, w);
+        f->workers.push_back(w);
+    }
+}
+
+int sharded_enter(Worker *w, int device, uint32_t route, Ctx **c) {
+    if (!w->device_set || w->device != device) {
+        BG_TRY(bowgpu_set_device(device));
+        w->device = device;
+        w->device_set = true;
+    }
+    BG_TRY(bowgpu_debug_set_route(route));
+    return ctx_get(c);
+}
+
+// a rank that wrote a window it does not own (drops_last): the slot out of its outputs.  Device-resident outputs: shard_tail_kernel and
+// the one synchronisation of the rank's stream it needs anyway; host-resident ones are on the host already (the finish has synchronised)
+int sharded_tail(Ctx *c, ShardedCall *sc, int r, const bowgpu_shard_decision &d) {
+    bowgpu_out *outs = sc->outs_by_rank[r];
+    const int na = sc->naggs;
+    if (!d.drops_last || d.windows_local <= 0) return 0;
+    const int64_t s = d.windows_owned;   // = windows_local - 1: the last slot written
+    uint8_t was_valid[BOWGPU_CARRY_MAX_AGGS] = {};
+    ShardTailArgs a;
+    memset(&a, 0, sizeof a);
+    int dev[BOWGPU_CARRY_MAX_AGGS];
+    for (int i = 0; i < na; i++) {
+        if (outs[i].residency == BOWGPU_DEVICE) {
+            a.values[a.n] = reinterpret_cast<uint64_t *>(outs[i].values);
+            a.validity[a.n] = outs[i].validity;
+            dev[a.n++] = i;
+        } else {
+            uint8_t *bp = outs[i].validity + (s >> 3);
+            const int k = (int)(s & 7);
+            was_valid[i] = (uint8_t)((*bp >> k) & 1u);
+            *bp = (uint8_t)(*bp & ((1u << k) - 1u));
+            reinterpret_cast<uint64_t *>(outs[i].values)[s] = 0;
+        }
+    }
+    if (a.n > 0) {
+        char *hp;
+        BG_TRY(ctx_pinned(c, 16384, reinterpret_cast<void **>(&hp)));
+        a.report = reinterpret_cast<uint8_t *>(hp + 12288);   // (bytes 12288.. of the context's pinned block: free once the finish has returned)
+        a.slot = s;
+        BG_TRY(launch_shard_tail(c, a));
+        BG_HIP(hipStreamSynchronize(c->stream));
+        for (int k = 0; k < a.n; k++) was_valid[dev[k]] = a.report[k];
+    }
+    for (int i = 0; i < na; i++) {
+        outs[i].length = s;
+        if (!kind_never_nil(sc->aggs[i].kind) && !was_valid[i]) outs[i].null_count -= 1;
+    }
+    return 0;
+}
+
+// rank r's whole part of the call, inside ONE dispatch: begin + pass in flight -> record published -> barrier -> finish (-> the
+// second round of the rows-below-s0 corner: begin, barrier, finish) -> tail.  1: another rank failed (nothing of this rank's to report)
+int sharded_rank_impl(Worker *w, ShardedCall *sc, int r, Ctx **cp) {
+    BG_TRY(sharded_enter(w, sc->ids[r], sc->route, cp));
+    Ctx *c = *cp;
+    Call &view = sc->views[r];
+    Rank *rk = &sc->ranks[r];
+    const int32_t nc = sc->ncols, ts = sc->ts_col, na = sc->naggs;
+    bool pageable = false;
+    for (int i = 0; i < nc; i++) pageable |= view.cols[i].residency == BOWGPU_HOST;
+    if (pageable) {
+        BG_TRY(rank_stage(c, view, rk));
+    } else {   // (nothing to stage: the rank's columns as given, without rank_stage's synchronisation)
+        rk->cols.assign(view.cols, view.cols + nc);
+    }
+    int64_t nulls = 0;
+    BG_TRY(ts_null_rows(c, &rk->cols[ts], &nulls));
+    if (nulls > 0)
+        return fail(BOWGPU_ERR_TS_NULLS, "rank %d: interval column has %lld nulls: the sharded call does not serve them", r, (long long)nulls);
+    const bowgpu_col *cols = rk->cols.data();
+    bowgpu_out *outs = sc->outs_by_rank[r];
+    bowgpu_shard_record rec;
+    BG_TRY(bowgpu_shard_begin(cols, nc, ts, sc->interval, &sc->opts, sc->aggs, na, nullptr, &rec));
+    const int p = bowgpu_shard_pass_begin(cols, nc, ts, sc->interval, &sc->opts, sc->aggs, na, outs, &rec);
+    if (p < 0) return p;
+    sc->records[0][r] = rec;
+    if (!sc->barrier.wait()) return 1;
+    for (int round = 0; round < 2; round++) {
+        const bowgpu_shard_record *recs = sc->records[round].data();
+        bowgpu_shard_decision d;
+        BG_TRY(bowgpu_shard_plan(recs, sc->world, r, sc->interval, sc->opts.offset, &d));
+        if (!d.retry_with_s0)
+            for (int i = 0; i < na; i++)
+                if (outs[i].length < d.windows_local)
+                    return fail(BOWGPU_ERR_ARG, "rank %d: output %d has %lld slots, %lld needed", r, i, (long long)outs[i].length,
+                                (long long)d.windows_local);
+        bowgpu_agg_info info;
+        const int f = bowgpu_shard_finish(cols, nc, ts, sc->interval, &sc->opts, sc->aggs, na, outs, recs, sc->world, r, &d, &info);
+        if (f < 0) return f;
+        if (f == 0) {
+            // a first window spread over three or more ranks is stitched from the middle ranks' merged partial states
+            // (bowgpu_carry_merge: not the reference's row order) - an order-free window, and counted as one where this rank owns it
+            if (d.seed_first_rank >= 0 && d.lead_empty_windows < d.windows_owned) {
+                int with_rows = 0;
+                for (int q = d.seed_first_rank; q < r; q++) with_rows += recs[q].nrows > 0;
+                if (with_rows > 1) info.long_windows += 1;
+            }
+            sc->decisions[r] = d;
+            sc->infos[r] = info;
+            return sharded_tail(c, sc, r, d);
+        }
+        if (round == 1) return fail(BOWGPU_ERR_ARG, "internal: the shard protocol did not settle after the second exchange");
+        const int64_t s0 = d.s0;   // rows below the first window start split across ranks (rolling.go:96-99): once more, s0 known
+        BG_TRY(bowgpu_shard_begin(cols, nc, ts, sc->interval, &sc->opts, sc->aggs, na, &s0, &rec));
+        sc->records[1][r] = rec;
+        if (!sc->barrier.wait()) return 1;
+    }
+    return 0;
+}
+
+void sharded_rank(Worker *w, ShardedCall *sc, int r) {
+    Ctx *c = nullptr;
+    const int rc = sharded_rank_impl(w, sc, r, &c);
+    if (rc < 0) sc->fail_rank(rc);
+    if (c) {
+        // (ctx_get outside the protocol's own calls settles a pass still in flight; then nothing of this rank runs any more)
+        Ctx *cc;
+        if (ctx_get(&cc) == 0) (void)hipStreamSynchronize(cc->stream);
+    }
+    sc->ranks[r].release();
+}
+
+// the layout query of a device-resident interval column: its row count and first / last timestamp, read on the rank's device
+void sharded_layout_rank(Worker *w, ShardedCall *sc, int r) {
+    const bowgpu_col &t = sc->cols_by_rank[r][sc->ts_col];
+    bowgpu_shard_record &rec = sc->records[0][r];
+    Ctx *c;
+    int rc = sharded_enter(w, sc->ids[r], sc->route, &c);
+    int64_t nulls = 0;
+    if (rc == 0) rc = ts_null_rows(c, &t, &nulls);
+    if (rc == 0 && nulls > 0)
+        rc = fail(BOWGPU_ERR_TS_NULLS, "rank %d: interval column has %lld nulls: the sharded call does not serve them", r, (long long)nulls);
+    bowgpu_plan p;
+    if (rc == 0) rc = bowgpu_plan_windows_ex(&t, sc->interval, sc->opts.offset, &p);
+    if (rc == 0) { rec.first_ts = p.first_ts; rec.last_ts = p.last_ts; }
+    if (rc < 0) sc->fail_rank(rc);
+}
+
+int host_ts_nulls(const bowgpu_col &t, int64_t *nulls) {
+    *nulls = 0;
+    if (!t.validity || t.null_count == 0) return 0;
+    if (t.null_count > 0) { *nulls = t.null_count; return 0; }
+    for (int64_t i = 0; i < t.length; i++) {
+        const int64_t b = t.offset + i;
+        *nulls += !((t.validity[b >> 3] >> (b & 7)) & 1);
+    }
+    return 0;
+}
+
+int device_of(const void *p, int *dev) {
+    hipPointerAttribute_t a;
+    memset(&a, 0, sizeof a);
+    const hipError_t e = hipPointerGetAttributes(&a, p);
+    if (e != hipSuccess) { (void)hipGetLastError(); *dev = -1; return 0; }
+    *dev = a.device;
+    return 0;
+}
+
 }  // namespace
 
 // One fanned-out call.  *done = false (and 0 returned): the call is not one for the fan-out - the caller goes on with the one-device
@@ -670,6 +903,156 @@ int bowgpu_fanout_counts(int64_t *calls, int64_t *served) {
     if (!calls || !served) return fail(BOWGPU_ERR_ARG, "null argument");
     *calls = g_calls_listed.load(std::memory_order_relaxed);
     *served = g_calls_served.load(std::memory_order_relaxed);
+    return 0;
+}
+
+int bowgpu_rolling_aggregate_sharded(const bowgpu_col *const *cols_by_rank, const int32_t *device_ids, int32_t world, int32_t ncols,
+                                     int32_t ts_col, int64_t interval, const bowgpu_options *opts, const bowgpu_agg *aggs, int32_t naggs,
+                                     bowgpu_out *const *outs_by_rank, bowgpu_shard_decision *decisions, bowgpu_agg_info *info) {
+    if (!cols_by_rank || !device_ids || !decisions || !aggs) return fail(BOWGPU_ERR_ARG, "null argument");
+    if (world <= 0 || world > 64) return fail(BOWGPU_ERR_ARG, "world %d: 1 .. 64 ranks", world);
+    if (ncols <= 0) return fail(BOWGPU_ERR_ARG, "no columns");
+    for (int r = 0; r < world; r++) {
+        if (!cols_by_rank[r]) return fail(BOWGPU_ERR_ARG, "rank %d: null column array", r);
+        if (outs_by_rank && !outs_by_rank[r]) return fail(BOWGPU_ERR_ARG, "rank %d: null output array", r);
+    }
+    if (ts_col < 0 || ts_col >= ncols) return fail(BOWGPU_ERR_BAD_COL, "no interval column with index %d", ts_col);
+    // one schema: rank 0's types everywhere; within a rank, columns of one length
+    for (int r = 0; r < world; r++)
+        for (int i = 0; i < ncols; i++) {
+            if (cols_by_rank[r][i].type != cols_by_rank[0][i].type)
+                return fail(BOWGPU_ERR_ARG, "rank %d: column %d has type %d, rank 0's has type %d (every rank has the same schema)", r, i,
+                            cols_by_rank[r][i].type, cols_by_rank[0][i].type);
+            if (cols_by_rank[r][i].length != cols_by_rank[r][ts_col].length)
+                return fail(BOWGPU_ERR_ARG, "rank %d: column %d has %lld rows, interval column has %lld", r, i, (long long)cols_by_rank[r][i].length,
+                            (long long)cols_by_rank[r][ts_col].length);
+        }
+    BG_TRY(sharded_validate(cols_by_rank[0], ncols, ts_col, interval, aggs, naggs));
+    bowgpu_options o = {0, 0, 0};
+    if (opts) o = *opts;
+
+    ShardedCall sc;
+    sc.cols_by_rank = cols_by_rank; sc.ids = device_ids; sc.world = world; sc.ncols = ncols; sc.ts_col = ts_col; sc.interval = interval;
+    sc.opts = o; sc.aggs = aggs; sc.naggs = naggs; sc.outs_by_rank = outs_by_rank; sc.route = route_mask();
+    sc.records[0].assign(world, bowgpu_shard_record());
+    sc.records[1].assign(world, bowgpu_shard_record());
+    sc.decisions.assign(world, bowgpu_shard_decision());
+    sc.infos.assign(world, bowgpu_agg_info());
+    sc.barrier.n = world;
+
+    auto check_ids = [&](bool only_device_ts) -> int {
+        int count = 0;
+        if (bowgpu_device_count(&count) != 0 || count <= 0)
+            return fail(BOWGPU_ERR_NO_DEVICE, "no HIP device available; the bowgpu path has no CPU fallback");
+        for (int r = 0; r < world; r++) {
+            if (only_device_ts && !(cols_by_rank[r][ts_col].residency == BOWGPU_DEVICE && cols_by_rank[r][ts_col].length > 0)) continue;
+            if (device_ids[r] < 0 || device_ids[r] >= count)
+                return fail(BOWGPU_ERR_NO_DEVICE, "rank %d: device %d out of range (%d devices)", r, device_ids[r], count);
+        }
+        return 0;
+    };
+
+    if (!outs_by_rank) {
+        // ---- the layout query: each rank's row count and first / last timestamp, then the plan every rank of the full call makes
+        bool any_device = false;
+        for (int r = 0; r < world; r++) {
+            const bowgpu_col &t = cols_by_rank[r][ts_col];
+            bowgpu_shard_record &rec = sc.records[0][r];
+            rec.nrows = t.length;
+            rec.naggs = naggs;
+            rec.flags = 1;   // (decided with s0 known: what the full call's records say once the protocol has settled)
+            if (t.length <= 0) continue;
+            if (t.residency == BOWGPU_DEVICE) { any_device = true; continue; }
+            int64_t nulls = 0;
+            BG_TRY(host_ts_nulls(t, &nulls));
+            if (nulls > 0)
+                return fail(BOWGPU_ERR_TS_NULLS, "rank %d: interval column has %lld nulls: the sharded call does not serve them", r, (long long)nulls);
+            const int64_t *v = reinterpret_cast<const int64_t *>(t.values) + t.offset;
+            rec.first_ts = v[0];
+            rec.last_ts = v[t.length - 1];
+        }
+        if (any_device) {
+            BG_TRY(check_ids(true));
+            {   // (the workers read the interval columns on streams of their own: what the calling thread's stream has in flight first)
+                Ctx *c;
+                BG_TRY(ctx_get(&c));
+                BG_HIP(hipStreamSynchronize(c->stream));
+            }
+            Fanout *f = sharded_pool();
+            std::lock_guard<std::mutex> call_lock(f->call_mu);
+            sharded_grow_locked(f, world);
+            fan_run(f, world, [&](int r) {
+                const bowgpu_col &t = cols_by_rank[r][ts_col];
+                if (t.residency == BOWGPU_DEVICE && t.length > 0) sharded_layout_rank(f->workers[r], &sc, r);
+            });
+            if (sc.rc < 0) return fail(sc.rc, "%s", sc.err.c_str());
+        }
+        for (int r = 0; r < world; r++) BG_TRY(bowgpu_shard_plan(sc.records[0].data(), world, r, interval, o.offset, &decisions[r]));
+        return 0;
+    }
+
+    // ---- the full call
+    BG_TRY(check_ids(false));
+    // device-resident buffers of rank r live on device_ids[r]
+    for (int r = 0; r < world; r++) {
+        auto on_device = [&](const void *p, const char *what, int i) -> int {
+            if (!p) return 0;
+            int dev = -1;
+            BG_TRY(device_of(p, &dev));
+            if (dev != device_ids[r])
+                return fail(BOWGPU_ERR_ARG, "rank %d: a device-resident buffer of %s %d lives on device %d, not on device_ids[%d] = %d", r, what, i, dev,
+                            r, device_ids[r]);
+            return 0;
+        };
+        for (int i = 0; i < ncols; i++) {
+            const bowgpu_col &cl = cols_by_rank[r][i];
+            if (cl.residency != BOWGPU_DEVICE || cl.length <= 0) continue;
+            BG_TRY(on_device(cl.values, "column", i));
+            if (cl.null_count != 0) BG_TRY(on_device(cl.validity, "column", i));
+        }
+        for (int i = 0; i < naggs; i++) {
+            const bowgpu_out &u = outs_by_rank[r][i];
+            if (!u.values || !u.validity) return fail(BOWGPU_ERR_ARG, "rank %d: output %d lacks a values or validity buffer", r, i);
+            if (u.residency != BOWGPU_DEVICE) continue;
+            BG_TRY(on_device(u.values, "output", i));
+            BG_TRY(on_device(u.validity, "output", i));
+        }
+    }
+    {   // the ranks work on streams of their own: what the calling thread's stream still has in flight is done first
+        Ctx *c;
+        BG_TRY(ctx_get(&c));
+        BG_HIP(hipStreamSynchronize(c->stream));
+    }
+    sc.views.resize(world);
+    sc.ranks.resize(world);
+    for (int r = 0; r < world; r++) {
+        Call &v = sc.views[r];
+        v.cols = cols_by_rank[r]; v.ncols = ncols; v.ts_col = ts_col; v.interval = interval; v.opts = o;
+        v.aggs = aggs; v.naggs = naggs; v.outs = nullptr; v.route = sc.route; v.world = 1;
+        sc.ranks[r].row0 = 0;
+        sc.ranks[r].nrows = cols_by_rank[r][ts_col].length;
+    }
+    Fanout *f = sharded_pool();
+    {
+        std::lock_guard<std::mutex> call_lock(f->call_mu);
+        sharded_grow_locked(f, world);
+        fan_run(f, world, [&](int r) { sharded_rank(f->workers[r], &sc, r); });   // the one dispatch, the one join
+    }
+    if (sc.rc < 0) return fail(sc.rc, "%s", sc.err.c_str());
+    const int64_t W = sc.decisions[0].num_windows;
+    int64_t owned = 0;
+    for (int r = 0; r < world; r++) owned += std::max<int64_t>(sc.decisions[r].windows_owned, 0);
+    if (owned != W) return fail(BOWGPU_ERR_ARG, "internal: the ranks own %lld of %lld windows", (long long)owned, (long long)W);
+    for (int r = 0; r < world; r++) decisions[r] = sc.decisions[r];
+    if (info) {
+        const bowgpu_agg_info &i0 = sc.infos[0];
+        info->s0 = sc.decisions[0].s0; info->num_windows = W; info->new_interval_col = i0.new_interval_col; info->inclusive = i0.inclusive;
+        info->long_windows = 0; info->kernel_ms = 0;
+        for (int r = 0; r < world; r++) {
+            info->long_windows += sc.infos[r].long_windows;
+            info->kernel_ms = std::max(info->kernel_ms, sc.infos[r].kernel_ms);
+        }
+    }
     return 0;
 }
 

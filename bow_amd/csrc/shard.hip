@@ -7,7 +7,8 @@
 // own rows of that window seeded with the left state (mode 1) - i.e. the straddling window is folded
 // in the reference's row order (sum.go:16-22, arithmeticmean.go:17-24, minmax.go:16-28), bit-exact,
 // with no collective on the data.  _finish also closes the rank's last window with the next rank's
-// first row when that row is the window's inclusive row (mode 2).
+// first row when that row is the window's inclusive row (mode 2).  shard_tail_kernel clears the slot a rank of
+// bowgpu_rolling_aggregate_sharded wrote but does not own.
 #include "agg_device.h"
 
 namespace bowgpu {
@@ -195,6 +196,30 @@ int launch_fill_empty(Ctx *c, const AggParams &p, int64_t slot0, int64_t slot1) 
     int64_t grid = (slot1 - slot0 + 255) / 256;
     if (grid > 4096) grid = 4096;
     hipLaunchKernelGGL(fill_empty_kernel, dim3((unsigned)grid), dim3(256), 0, c->stream, p, slot0, slot1);
+    BG_HIP(hipGetLastError());
+    return 0;
+}
+
+// bowgpu_rolling_aggregate_sharded (multi.cpp): a rank whose last output slot holds a window that continues on the next non-empty rank
+// does not own it.  That slot is the last one the finish wrote, so its byte is the last validity byte written.  One lane per output:
+// the slot's value -> 0, its validity bit and every bit above it in that byte -> 0, whether the bit was set -> report[i] (a
+// host-mapped block the host reads after the rank's one synchronisation, to take the slot out of null_count)
+__global__ __launch_bounds__(64) void shard_tail_kernel(const ShardTailArgs a) {
+    const int i = threadIdx.x;
+    if (i >= a.n) return;
+    const int64_t s = a.slot;
+    uint8_t *bp = a.validity[i] + (s >> 3);
+    const uint32_t k = (uint32_t)(s & 7);
+    const uint32_t b = *bp;
+    a.report[i] = (uint8_t)((b >> k) & 1u);
+    *bp = (uint8_t)(b & ((1u << k) - 1u));
+    a.values[i][s] = 0;
+}
+
+int launch_shard_tail(Ctx *c, const ShardTailArgs &a) {
+    if (a.n <= 0) return 0;
+    if (a.n > BOWGPU_CARRY_MAX_AGGS) return fail(BOWGPU_ERR_ARG, "internal: %d outputs for the shard tail", a.n);
+    hipLaunchKernelGGL(shard_tail_kernel, dim3(1), dim3(64), 0, c->stream, a);
     BG_HIP(hipGetLastError());
     return 0;
 }

@@ -31,7 +31,9 @@ extern "C" {
  * changed. */
 /* 7: the one-call-per-phase shard entry points bowgpu_shard_{span, aggregate, carry_only, fix_first, first_row} and the
  * bowgpu_shard_carry struct removed (the shard record protocol is the one sharded Aggregate); no remaining struct changed. */
-#define BOWGPU_ABI_VERSION 7
+/* 8: bowgpu_rolling_aggregate_sharded added (one Rolling.Aggregate over row-range shards held on several devices); no struct
+ * changed. */
+#define BOWGPU_ABI_VERSION 8
 
 /* bow.Type (reference bowtypes.go:17-32) */
 enum {
@@ -587,6 +589,48 @@ int bowgpu_shard_finish(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, i
                         const bowgpu_options *opts, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs,
                         const bowgpu_shard_record *records, int32_t world, int32_t rank,
                         bowgpu_shard_decision *decision /* nullable */, bowgpu_agg_info *info /* nullable */);
+
+/* ---- ONE Rolling.Aggregate over a frame held as row-range shards on several devices --------------------------------
+ * The C ABI's one call (reference rolling/aggregation.go:123-145) for a frame too large for one GPU: the shard protocol above runs
+ * inside the library, on one persistent library thread per list entry, with its exchange in host memory.
+ *   THE FRAME.  cols_by_rank[r] holds ncols columns: rank r's rows.  Every rank has the same schema (types, ts_col); the shards
+ * concatenated in rank order are the frame.  Ranks may be empty (length 0), all of them too.  1 <= world <= 64.  device_ids[r]: the
+ * device rank r runs on (else BOWGPU_ERR_NO_DEVICE); an id may be listed several times - how a one-GPU box runs the path.
+ *   RESIDENCY.  Columns and outputs: any residency.  A BOWGPU_DEVICE buffer of rank r must live on device_ids[r] (checked with
+ * hipPointerGetAttributes: BOWGPU_ERR_ARG naming the rank).  Pageable (BOWGPU_HOST) columns are staged through HBM once per rank.
+ *   LAYOUT QUERY.  outs_by_rank == NULL: only `decisions` is filled, from each rank's row count and first / last timestamp; nothing
+ * else is read and no pass runs.  These are the decisions the full call takes (retry_with_s0 is 0).  Host-resident interval columns
+ * make it host arithmetic, with no GPU needed (as bowgpu_plan_windows); a device-resident one is read on device_ids[r].
+ *   OUTPUTS.  outs_by_rank[r][i] is output i of rank r, capacity (length on entry) >= decisions[r].windows_local, else BOWGPU_ERR_ARG
+ * naming the size.  On return: length = windows_owned, slot k holds global window first_slot_window_id + k, null_count counts the
+ * nulls of those slots only, type as bowgpu_rolling_aggregate resolves it.  A rank does not own a last window that continues on the
+ * next non-empty rank (that rank outputs it): where the pass wrote it, its value slot ends up 0 and its validity bit 0.  Every
+ * validity bit the call writes at or past length is 0.  Each rank's outputs are its own buffers: no byte is shared between ranks.
+ *   THE GUARANTEE: slots [0, windows_owned) of output i concatenated over the ranks in rank order are, bit for bit, what
+ * bowgpu_rolling_aggregate gives for the concatenated frame on one device - values, validity and null counts - except for the
+ * generated-NaN bits this header excludes everywhere (bowgpu_agg_info.long_windows); when info.long_windows != 0 the bound stated
+ * there applies instead.
+ *   INFO (nullable): s0, num_windows, new_interval_col and inclusive of the one-device call; long_windows: the ranks' sum, where a
+ * rank also counts the window it owns that is spread over three or more ranks (the middle ranks' running states are merged,
+ * bowgpu_carry_merge: an order-free form of its Sum / ArithmeticMean / Integral* / WeightedAverage*); kernel_ms: the slowest rank's.
+ *   DECLINES ARE ERRORS HERE: no single device holds the frame, so there is nothing to fall back to.  Mode or more than 16
+ * aggregators: BOWGPU_ERR_UNSUPPORTED; an interval column with nulls on any rank: BOWGPU_ERR_TS_NULLS; strict_order with a window
+ * spread over three or more ranks: BOWGPU_ERR_UNSUPPORTED; timestamps not ascending within a rank or across ranks:
+ * BOWGPU_ERR_TS_UNSORTED.  Validation errors (INTERVAL, TS_TYPE, NO_AGG, KEEP_INTERVAL, BAD_COL, and the type whitelist's
+ * UNSUPPORTED) are those bowgpu_rolling_aggregate returns for the same frame.  A rank whose columns differ from rank 0's in type, or
+ * whose columns differ in length, is BOWGPU_ERR_ARG.  On any error the outputs are undefined; the first error's code and message
+ * are the call's.
+ *   ORDERING.  Inputs must be complete when the call is made: it first synchronises the calling thread's stream (work on other streams
+ * is the caller's to finish) - the layout query too, when it reads a device-resident interval column.  On return every output is
+ * complete.
+ *   INDEPENDENT of bowgpu_set_devices: neither reads nor changes the device list or min_rows, does not count in bowgpu_fanout_counts,
+ * leaves bowgpu_last_call_ranks alone.  Calls of this entry point are serialised process-wide. */
+int bowgpu_rolling_aggregate_sharded(const bowgpu_col *const *cols_by_rank, const int32_t *device_ids, int32_t world,
+                                     int32_t ncols, int32_t ts_col, int64_t interval, const bowgpu_options *opts,
+                                     const bowgpu_agg *aggs, int32_t naggs,
+                                     bowgpu_out *const *outs_by_rank,   /* NULL: layout query only */
+                                     bowgpu_shard_decision *decisions,  /* world entries, always filled */
+                                     bowgpu_agg_info *info);            /* nullable */
 
 /* ---- synthetic inputs generated in HBM -------------------------------- */
 
