@@ -26,12 +26,12 @@ INTERP = {"WindowStart": 0, "Linear": 1, "StepPrevious": 2, "None": 3, "Const": 
 
 MAX_FACTORS = 4
 CARRY_MAX_AGGS = 16
-ABI_VERSION = 8   # include/bowgpu.h BOWGPU_ABI_VERSION (asserted when the library is loaded)
+ABI_VERSION = 9   # include/bowgpu.h BOWGPU_ABI_VERSION (asserted when the library is loaded)
 
 ERR_NAMES = {
     -1: "INTERVAL", -2: "TS_TYPE", -3: "FIRST_TS_NULL", -4: "NO_AGG", -5: "KEEP_INTERVAL", -6: "BAD_COL",
     -7: "TYPE", -8: "NOT_SORTED", -9: "UNSUPPORTED", -10: "ARG", -11: "NO_DEVICE", -12: "HIP",
-    -13: "TS_NULLS", -14: "TS_UNSORTED", -15: "OOM",
+    -13: "TS_NULLS", -14: "TS_UNSORTED", -15: "OOM", -16: "SORT_NULLS",
 }
 
 
@@ -133,6 +133,7 @@ SYMBOLS = [
     "bowgpu_debug_set_route", "bowgpu_debug_get_route", "bowgpu_checksum64_at",
     "bowgpu_set_devices", "bowgpu_get_devices", "bowgpu_set_fanout_min_rows", "bowgpu_last_call_ranks", "bowgpu_fanout_counts",
     "bowgpu_rolling_aggregate_sharded",
+    "bowgpu_argsort", "bowgpu_take", "bowgpu_sort_by_col",
 ]
 
 _lib = None
@@ -813,6 +814,67 @@ def is_col_sorted(col):
     s = C.c_int32(0)
     check(lib().bowgpu_is_col_sorted(C.byref(c), C.byref(s)))
     return bool(s.value)
+
+
+def argsort(col, out_residency=HOST):
+    """bowgpu_argsort -> (perm, sorted): the stable ascending permutation of one Int64 / Float64 column as a numpy int64 array
+    (out_residency HOST) or a DeviceBuffer of col.length int64 (DEVICE); perm is None when the column is already in order"""
+    n = col.length
+    c = col.c()
+    s = C.c_int32(0)
+    if out_residency == DEVICE:
+        buf = DeviceBuffer(max(n, 1) * 8)
+        ptr = C.c_void_p(buf.ptr)
+    else:
+        buf = np.full(max(n, 1), -1, dtype=np.int64)
+        ptr = buf.ctypes.data_as(C.c_void_p)
+    check(lib().bowgpu_argsort(C.byref(c), ptr, out_residency, C.byref(s)))
+    if s.value:
+        return None, True
+    return (buf if out_residency == DEVICE else buf[:n]), False
+
+
+def take(col, idx, n_idx=None, out_residency=HOST, out=None):
+    """bowgpu_take: out[j] = col[idx[j]] -> OutColumn.  idx: a numpy int64 array (HOST) or a DeviceBuffer of n_idx int64 (DEVICE)"""
+    if isinstance(idx, DeviceBuffer):
+        assert n_idx is not None
+        ptr, res = C.c_void_p(idx.ptr), DEVICE
+    else:
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        if n_idx is None:
+            n_idx = len(idx)
+        ptr, res = idx.ctypes.data_as(C.c_void_p), HOST
+    if out is None:
+        out = OutColumn(n_idx, out_residency)
+    o = out.c()
+    c = col.c()
+    check(lib().bowgpu_take(C.byref(c), ptr, C.c_int64(n_idx), res, C.byref(o)))
+    out.absorb(o)
+    return out
+
+
+def sort_by_col(cols, key_col, out_residency=HOST, outs=None):
+    """Bow.SortByCol (bowgpu_sort_by_col) -> (list[OutColumn], unchanged).  unchanged: the reference returns the receiver (already
+    sorted, or fewer than 2 rows) - the outputs were not written"""
+    if outs is None:
+        n = cols[key_col].length if 0 <= key_col < len(cols) else 0
+        outs = [OutColumn(n, out_residency) for _ in cols]
+    oarr = (Out * max(len(cols), 1))()
+    for i, o in enumerate(outs):
+        oarr[i] = o.c()
+    unchanged = C.c_int32(0)
+    check(lib().bowgpu_sort_by_col(_cols(cols), len(cols), key_col, oarr, C.byref(unchanged)))
+    if not unchanged.value:
+        for i, o in enumerate(outs):
+            o.absorb(oarr[i])
+    return outs, bool(unchanged.value)
+
+
+def out_as_column(out):
+    """an OutColumn (what a call produced) as an input Column of the same residency"""
+    if out.residency == DEVICE:
+        return Column(out.values, out.validity, out.type, 0, out.length, out.null_count)
+    return Column(out.values[:out.length].view(np.int64 if out.type == INT64 else np.float64), out.validity, out.type, 0, out.length, out.null_count)
 
 
 def gen_dense(row0, n, seed=42):

@@ -544,6 +544,30 @@ struct WholeFinishH {
 int whole_value_run(Ctx *c, const void *params_blob, int64_t nblocks);
 int whole_finish_run(Ctx *c, const void *partials, int64_t nblocks, const WholeFinishH &fin);
 
+// sort.hip: Bow.SortByCol - stable LSD radix argsort over (key image, 32-bit row index) pairs, and the gather (host side: sort_api.cpp)
+constexpr int kSortTileRows = 4096;   // rows per scatter tile: one 256-entry digit histogram each
+constexpr int kGatherCols = 4;        // columns moved per gather launch (the permutation is read once per group)
+struct GatherArgs {
+    int32_t ncols, _pad;
+    int64_t n_idx, length;                       // rows to produce; rows of the source columns
+    const uint64_t *values[kGatherCols];
+    const uint32_t *vbits[kGatherCols];          // nullptr: no nulls
+    int64_t vbit0[kGatherCols];
+    uint64_t *out_values[kGatherCols];
+    unsigned long long *out_valid[kGatherCols];  // 8-byte aligned, ceil(n_idx / 64) words: every word stored whole by its wave
+    unsigned long long *null_counts;             // [kGatherCols], zeroed by the host
+    uint32_t *bad;                               // |= 1: a caller's index outside [0, length)
+};
+// hist: [8][256] digit counts, flags: [0] not ascending, [1] NaN seen (both zeroed by the host); img_out: nullable
+int launch_sort_hist(Ctx *c, const uint64_t *key, int64_t n, int is_float, uint32_t *d_hist, uint32_t *d_flags, uint64_t *img_out);
+// one stable pass on digit `shift / 8`.  mode 0 / 1: src holds raw Int64 / Float64 keys, 2: images; src_idx == nullptr: row i carries index i.
+// tile_hist: 256 * ceil(n / kSortTileRows) words; sums: ceil(that / 4096) words
+int launch_sort_pass(Ctx *c, const uint64_t *src, int mode, const uint32_t *src_idx, int64_t n, int shift, uint32_t *tile_hist, uint32_t *sums,
+                     uint64_t *dst, uint32_t *dst_idx);
+int launch_sort_widen(Ctx *c, const uint32_t *idx, int64_t n, int64_t *out);
+// exactly one of idx32 (the library's own permutation: trusted) / idx64 (a caller's indices: range-checked) is given
+int launch_gather(Ctx *c, const GatherArgs &a, const uint32_t *idx32, const int64_t *idx64);
+
 // generate.hip
 int launch_gen_dense(Ctx *c, int64_t row0, int64_t n, uint64_t seed, int64_t *ts, double *val);
 int launch_gen_sparse(Ctx *c, int64_t row0, int64_t n, uint64_t seed, int64_t *ts, double *val, uint8_t *validity);

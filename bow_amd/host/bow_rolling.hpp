@@ -108,7 +108,7 @@ inline Series NewSeries(const std::string &name, Type typ, const std::vector<T> 
 class Bow;
 using BowPtr = std::shared_ptr<const Bow>;
 
-class Bow {
+class Bow : public std::enable_shared_from_this<Bow> {
   public:
     std::vector<Series> cols;
     // a slice shares nothing here (copies): slices are only made for the user's closures
@@ -214,6 +214,8 @@ class Bow {
     std::pair<BowPtr, Error> FillPrevious(std::vector<int> colIndices = {}) const { return fill(BOWGPU_FILL_PREVIOUS, colIndices); }
     std::pair<BowPtr, Error> FillNext(std::vector<int> colIndices = {}) const { return fill(BOWGPU_FILL_NEXT, colIndices); }
     std::pair<BowPtr, Error> FillMean(std::vector<int> colIndices = {}) const { return fill(BOWGPU_FILL_MEAN, colIndices); }
+    // SortByCol: bowsort.go:10-41 (device; stable); returns the receiver when the column is already sorted
+    std::pair<BowPtr, Error> SortByCol(int colIndex) const;
 
 private:
     std::pair<BowPtr, Error> fill(int method, const std::vector<int> &colIndices) const;
@@ -349,6 +351,27 @@ inline std::pair<BowPtr, Error> Bow::fill(int method, const std::vector<int> &co
         if (rc) return {nullptr, detail::AbiError(rc)};
         out->cols[ci] = st.ToSeries(cols[ci].Name, o);
     }
+    return {out, Error()};
+}
+
+inline std::pair<BowPtr, Error> Bow::SortByCol(int colIndex) const {
+    if (colIndex < 0 || colIndex > NumCols() - 1) return {nullptr, Errorf("no column '" + std::to_string(colIndex) + "'")};
+    if (cols[colIndex].NullN() != 0)   // bowsort.go:11-15
+        return {nullptr, Errorf("column to sort by has " + std::to_string(cols[colIndex].NullN()) + " nil values")};
+    std::vector<bowgpu_col> c;
+    for (int i = 0; i < NumCols(); i++) c.push_back(ArrowCol(i));
+    std::vector<detail::OutStore> st((size_t)NumCols());
+    std::vector<bowgpu_out> o;
+    for (int i = 0; i < NumCols(); i++) o.push_back(st[(size_t)i].Make(NumRows()));
+    int32_t unchanged = 0;
+    int rc = bowgpu_sort_by_col(c.data(), NumCols(), colIndex, o.data(), &unchanged);
+    if (rc) return {nullptr, detail::AbiError(rc)};
+    if (unchanged) {   // bowsort.go:19-21 returns b itself (a copy where the receiver is not held by a shared_ptr)
+        BowPtr self = weak_from_this().lock();
+        return {self ? self : std::make_shared<Bow>(*this), Error()};
+    }
+    auto out = std::make_shared<Bow>();
+    for (int i = 0; i < NumCols(); i++) out->cols.push_back(st[(size_t)i].ToSeries(cols[i].Name, o[(size_t)i]));
     return {out, Error()};
 }
 

@@ -33,7 +33,9 @@ extern "C" {
  * bowgpu_shard_carry struct removed (the shard record protocol is the one sharded Aggregate); no remaining struct changed. */
 /* 8: bowgpu_rolling_aggregate_sharded added (one Rolling.Aggregate over row-range shards held on several devices); no struct
  * changed. */
-#define BOWGPU_ABI_VERSION 8
+/* 9: bowgpu_argsort / bowgpu_take / bowgpu_sort_by_col added (Bow.SortByCol on the device) and BOWGPU_ERR_SORT_NULLS with them; no struct
+ * changed. */
+#define BOWGPU_ABI_VERSION 9
 
 /* bow.Type (reference bowtypes.go:17-32) */
 enum {
@@ -74,8 +76,10 @@ enum {
                                         windows: a row on a window start has null timestamps behind it and then an EQUAL timestamp, or sits on
                                         -1): the device path declines (caller keeps the reference path); Aggregate and Interpolate are served
                                         otherwise. */
-    BOWGPU_ERR_TS_UNSORTED = -14,    /* interval column not ascending: device path declines */
-    BOWGPU_ERR_OOM = -15
+    BOWGPU_ERR_TS_UNSORTED = -14,    /* interval column not ascending: device path declines.  The remedy on the device is bowgpu_sort_by_col
+                                        (Bow.SortByCol, what the reference's users run in front of a Rolling); no rolling call sorts on its own */
+    BOWGPU_ERR_OOM = -15,
+    BOWGPU_ERR_SORT_NULLS = -16      /* "column to sort by has %d nil values"            bowsort.go:11-15 */
 };
 
 /* One Arrow array as bow holds it.  Replaces per-element Bow.GetInt64/GetFloat64/GetValue
@@ -457,6 +461,53 @@ int bowgpu_fill(const bowgpu_col *col, int32_t method, bowgpu_out *out, int32_t 
 /* Bow.IsColSorted — reference bowassertion.go:15-81 (ascending OR descending, nulls skipped,
  * empty => false). */
 int bowgpu_is_col_sorted(const bowgpu_col *col, int32_t *sorted);
+
+/* ---- Bow.SortByCol ----------------------------------------------------------------- */
+
+/* Bow.SortByCol - reference bowsort.go:10-41 - as three calls: the permutation (bowgpu_argsort), its application to one column
+ * (bowgpu_take), and the whole frame in one call (bowgpu_sort_by_col).  ONE device, any residency, Int64 / Float64 columns:
+ * BOWGPU_HOST inputs are staged through HBM as bowgpu_rolling_aggregate stages them, BOWGPU_HOST_PINNED inputs are read where they lie,
+ * BOWGPU_DEVICE inputs are used where they lie; outputs may have any residency.  Per-thread contexts and streams as for every other
+ * call (callable from several OS threads at once).  bowgpu_set_devices does not apply.  A sort ACROSS row-range shards on several
+ * devices is a different algorithm (sample / merge exchange) and is not offered: sort each shard, or bring the key to one device.
+ *   THE KEY COLUMN: Int64 or Float64, else BOWGPU_ERR_TYPE.  A key with nulls (null_count as given; counted when -1) is
+ * BOWGPU_ERR_SORT_NULLS with the reference's message.  key_col out of range: BOWGPU_ERR_BAD_COL.  Columns of unequal length:
+ * BOWGPU_ERR_ARG.  For host-resident columns these are decided before the device is touched (as bowgpu_plan_windows does), so they
+ * are answered on a box without a GPU; a valid call of two or more rows without a GPU is BOWGPU_ERR_NO_DEVICE - no CPU fallback.
+ *   THE ORDER: ascending by the reference's Buffer.Less (bowbuffer.go:126-139), STABLE: rows with equal keys keep their input order.
+ * The reference uses sort.Sort, which promises nothing for equal keys; the stable order is one of the results it may give, the one
+ * its own test table expects (bowsort_test.go:133-157), and the only one that makes the result a function of the input.  On keys
+ * without duplicates the result is the reference's, bit for bit.  Float64: -0.0 and +0.0 are equal under Less and keep their input
+ * order (each output value keeps its own bits: values are gathered from the input).  A Float64 key holding a NaN is
+ * BOWGPU_ERR_UNSUPPORTED (Less is not an order there; the caller keeps the reference path).
+ *   ALREADY SORTED means what sort.IsSorted means: no row i with key[i] < key[i-1] (ties included).  It is found in the one read of the
+ * key that also builds the digit histograms; such a call costs that read and nothing else, and writes nothing.
+ *   VALUE COLUMNS: Int64 / Float64 with or without validity, any Arrow offset (bit offsets that are no multiple of 8 included), moved
+ * as raw 64-bit payloads - a NaN's payload and sign survive.  Other types: BOWGPU_ERR_UNSUPPORTED.  Outputs: value, validity bit and
+ * null_count; null slots hold 0 and the padding bits of the last validity byte are clear (what Buffer.SetOrDropStrict leaves,
+ * bowsort.go:33-36).
+ *   SIZE: fewer than 2^31 rows (row indices inside the sort are 32 bits wide); more is BOWGPU_ERR_UNSUPPORTED naming the limit.
+ * HBM WORKSPACE, taken from the calling thread's scratch cache like every other call's (exhaustion: BOWGPU_ERR_OOM): 24 bytes per row
+ * (a 64-bit key image and a 32-bit row index, double-buffered) + 1 KB per 4096 rows of digit counts; + 8 bytes per row for the
+ * widened permutation when bowgpu_argsort's perm is host-resident; + the staged copies of BOWGPU_HOST columns and the device
+ * temporaries of host-resident outputs, at most 4 columns at a time.  A key that is already sorted takes none of it.
+ *   THE METHOD (bow_amd/csrc/sort.hip): least-significant-digit radix sort over 8-bit digits of the key image (x ^ 2^63 for Int64; the
+ * sign-flip map for Float64 with -0 folded onto +0); a digit that is the same in every key costs no pass (timestamps rarely use all
+ * eight bytes).  The result does not depend on scheduling: the same call gives the same bytes. */
+
+/* perm[j] = row of `key` that comes j-th in ascending order; key->length entries, residency as given.
+ * *sorted = 1: the column is already in order (bowsort.go:19-21; 0 or 1 rows included) and perm is NOT written. */
+int bowgpu_argsort(const bowgpu_col *key, int64_t *perm, int32_t perm_residency, int32_t *sorted);
+
+/* out[j] = col[idx[j]] for j < n_idx: value, validity bit, null_count (out->length = n_idx; capacity on entry >= n_idx).  Indices may
+ * repeat and n_idx may differ from col->length.  An index outside [0, col->length) is BOWGPU_ERR_ARG (nothing is read through it; the
+ * output is then undefined). */
+int bowgpu_take(const bowgpu_col *col, const int64_t *idx, int64_t n_idx, int32_t idx_residency, bowgpu_out *out);
+
+/* Bow.SortByCol.  outs[ncols]: one output per column of the Bow, in column order, capacity >= rows.  *unchanged = 1 where the
+ * reference returns the receiver itself (already sorted, or fewer than 2 rows): the outputs are then not written - neither their
+ * buffers nor their length / null_count / type. */
+int bowgpu_sort_by_col(const bowgpu_col *cols, int32_t ncols, int32_t key_col, bowgpu_out *outs, int32_t *unchanged);
 
 /* ---- Parquet column chunk -> device column --------------------------- */
 
