@@ -25,8 +25,10 @@ AGG = {
 INTERP = {"WindowStart": 0, "Linear": 1, "StepPrevious": 2, "None": 3, "Const": 4}
 
 MAX_FACTORS = 4
+FILTER_MAX_VALUES = 32
+FILTER_MAX_PREDS = 8
 CARRY_MAX_AGGS = 16
-ABI_VERSION = 9   # include/bowgpu.h BOWGPU_ABI_VERSION (asserted when the library is loaded)
+ABI_VERSION = 10  # include/bowgpu.h BOWGPU_ABI_VERSION (asserted when the library is loaded)
 
 ERR_NAMES = {
     -1: "INTERVAL", -2: "TS_TYPE", -3: "FIRST_TS_NULL", -4: "NO_AGG", -5: "KEEP_INTERVAL", -6: "BAD_COL",
@@ -103,6 +105,11 @@ class Plan(C.Structure):
                 ("interval", C.c_int64), ("offset", C.c_int64), ("nrows", C.c_int64)]
 
 
+class FilterPred(C.Structure):
+    """bowgpu_filter_pred: one MakeFilterValues(col, values...) after Type.Convert"""
+    _fields_ = [("col", C.c_int32), ("n_values", C.c_int32), ("match_null", C.c_int32), ("_pad", C.c_int32), ("values", C.c_void_p)]
+
+
 class ShardRecord(C.Structure):
     """bowgpu_shard_record: what one rank contributes to the exchange of a sharded Aggregate"""
     _fields_ = [("nrows", C.c_int64), ("first_ts", C.c_int64), ("last_ts", C.c_int64), ("carry_from_ts", C.c_int64),
@@ -134,6 +141,7 @@ SYMBOLS = [
     "bowgpu_set_devices", "bowgpu_get_devices", "bowgpu_set_fanout_min_rows", "bowgpu_last_call_ranks", "bowgpu_fanout_counts",
     "bowgpu_rolling_aggregate_sharded",
     "bowgpu_argsort", "bowgpu_take", "bowgpu_sort_by_col",
+    "bowgpu_filter_mask", "bowgpu_compact", "bowgpu_filter",
 ]
 
 _lib = None
@@ -868,6 +876,96 @@ def sort_by_col(cols, key_col, out_residency=HOST, outs=None):
         for i, o in enumerate(outs):
             o.absorb(oarr[i])
     return outs, bool(unchanged.value)
+
+
+def _preds(cols, preds):
+    """preds: (col, values[, match_null]) tuples; values in the column's type (a numpy array is passed as it is).  Returns the
+    ctypes array and the value arrays it points into (to be kept alive over the call)"""
+    arr = (FilterPred * max(len(preds), 1))()
+    keep = []
+    for i, p in enumerate(preds):
+        col, values = p[0], p[1]
+        if isinstance(values, np.ndarray) and values.dtype in (np.int64, np.float64, np.uint64):
+            v = np.ascontiguousarray(values)
+        else:
+            typ = cols[col].type if 0 <= col < len(cols) else INT64
+            v = np.array(list(values), dtype=np.float64 if typ == FLOAT64 else np.int64)
+        keep.append(v)
+        arr[i].col, arr[i].n_values = col, len(v)
+        arr[i].match_null = int(bool(p[2])) if len(p) > 2 else 0
+        arr[i].values = v.ctypes.data if len(v) else None
+    return arr, keep
+
+
+def _mask_arg(mask, pinned=False):
+    """a row bitmap (numpy uint8 array, DeviceBuffer or None) as (pointer, residency, keep-alive); pinned: the numpy array is
+    registered (host_register) and is passed as HOST_PINNED"""
+    if mask is None:
+        return None, HOST, None
+    if isinstance(mask, DeviceBuffer):
+        return C.c_void_p(mask.ptr), DEVICE, mask
+    m = np.ascontiguousarray(mask, dtype=np.uint8)
+    return (m.ctypes.data_as(C.c_void_p) if m.size else None), (HOST_PINNED if pinned else HOST), m
+
+
+def filter_mask(cols, preds, and_mask=None, out_residency=HOST, mask_pinned=False):
+    """bowgpu_filter_mask -> (mask, selected, first, last): the row bitmap of the ANDed predicates (and and_mask) as a numpy uint8
+    array of ceil(rows / 8) bytes (HOST) or a DeviceBuffer (DEVICE)"""
+    n = cols[0].length if cols else 0
+    nb = (n + 7) // 8
+    parr, keep = _preds(cols, preds)
+    aptr, ares, akeep = _mask_arg(and_mask, mask_pinned)
+    if out_residency == DEVICE:
+        buf = DeviceBuffer(max(nb, 1))
+        ptr = C.c_void_p(buf.ptr)
+    else:
+        buf = np.full(max(nb, 1), 0xA5, dtype=np.uint8)
+        ptr = buf.ctypes.data_as(C.c_void_p)
+    sel, first, last = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    check(lib().bowgpu_filter_mask(_cols(cols), len(cols), parr, len(preds), aptr, ares, ptr, out_residency,
+                                   C.byref(sel), C.byref(first), C.byref(last)))
+    del keep, akeep
+    return (buf if out_residency == DEVICE else buf[:nb]), sel.value, first.value, last.value
+
+
+def _filter_outs(cols, out_residency, outs, capacity):
+    if outs is None:
+        n = cols[0].length if cols else 0
+        outs = [OutColumn(n if capacity is None else capacity, out_residency) for _ in cols]
+    oarr = (Out * max(len(cols), 1))()
+    for i, o in enumerate(outs):
+        oarr[i] = o.c()
+    return outs, oarr
+
+
+def compact(cols, mask, out_residency=HOST, outs=None, capacity=None, mask_pinned=False):
+    """bowgpu_compact -> (list[OutColumn], first, count, contiguous).  contiguous: the selected rows are consecutive (or there are
+    none) - rows [first, first + count) of the inputs are the result and the outputs were not written"""
+    outs, oarr = _filter_outs(cols, out_residency, outs, capacity)
+    mptr, mres, mkeep = _mask_arg(mask, mask_pinned)
+    first, count, contiguous = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    check(lib().bowgpu_compact(_cols(cols), len(cols), mptr, mres, oarr, C.byref(first), C.byref(count), C.byref(contiguous)))
+    del mkeep
+    if not contiguous.value:
+        for i, o in enumerate(outs):
+            o.absorb(oarr[i])
+    return outs, first.value, count.value, bool(contiguous.value)
+
+
+def filter(cols, preds, and_mask=None, out_residency=HOST, outs=None, capacity=None, mask_pinned=False):
+    """Bow.Filter (bowgpu_filter) -> (list[OutColumn], first, count, contiguous); preds as for filter_mask, and_mask: a row bitmap
+    ANDed in (user closures evaluated by the caller).  contiguous: as for compact"""
+    outs, oarr = _filter_outs(cols, out_residency, outs, capacity)
+    parr, keep = _preds(cols, preds)
+    aptr, ares, akeep = _mask_arg(and_mask, mask_pinned)
+    first, count, contiguous = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    check(lib().bowgpu_filter(_cols(cols), len(cols), parr, len(preds), aptr, ares, oarr, C.byref(first), C.byref(count),
+                              C.byref(contiguous)))
+    del keep, akeep
+    if not contiguous.value:
+        for i, o in enumerate(outs):
+            o.absorb(oarr[i])
+    return outs, first.value, count.value, bool(contiguous.value)
 
 
 def out_as_column(out):

@@ -568,6 +568,44 @@ int launch_sort_widen(Ctx *c, const uint32_t *idx, int64_t n, int64_t *out);
 // exactly one of idx32 (the library's own permutation: trusted) / idx64 (a caller's indices: range-checked) is given
 int launch_gather(Ctx *c, const GatherArgs &a, const uint32_t *idx32, const int64_t *idx64);
 
+// exclusive scan of m 32-bit counts in place (their total below 2^32); sums: ceil(m / 4096) words of scratch
+int launch_scan_u32(Ctx *c, uint32_t *v, int64_t m, uint32_t *sums);
+
+// filter.hip: Bow.Filter - value-set predicates into a row bitmap, ordered compaction of the selected rows (host side: filter_api.cpp)
+constexpr int kFilterTileRows = 4096;   // rows per tile: 64 mask words, one selected count
+constexpr int kFilterCols = 4;          // columns moved per scatter launch (the bitmap is read once per group)
+struct FilterPredDev {
+    const uint64_t *values;
+    const uint32_t *vbits;               // nullptr: no nulls
+    int64_t vbit0;
+    int32_t n_values, match_null, is_float, _pad;
+    uint64_t set[BOWGPU_FILTER_MAX_VALUES];   // raw 64-bit payloads of the column's type; compared with wave-uniform operands
+};
+struct FilterMaskArgs {
+    int64_t n;
+    int32_t npreds, _pad;
+    const uint8_t *and_mask;             // nullable: bit i (LSB first) of byte i / 8; any alignment
+    unsigned long long *mask;            // 64 * ceil(n / kFilterTileRows) words, every one stored (rows >= n: clear bits)
+    uint32_t *tile_counts;               // ceil(n / kFilterTileRows)
+    uint32_t *tile_spans;                // ... per tile: lowest | highest << 16 selected row of the tile (tile-relative)
+    uint32_t *stats;                     // 4 words zeroed by the host (filter_stats_kernel)
+    uint32_t *host_stats;                // registered host memory: receives [0] selected rows, [1] lowest, [2] highest selected row
+    FilterPredDev preds[BOWGPU_FILTER_MAX_PREDS];
+};
+struct FilterScatterArgs {
+    int32_t ncols, _pad;
+    int64_t n;
+    const unsigned long long *mask;      // as filter_mask_kernel left it
+    const uint32_t *tile_base;           // the scanned tile counts
+    const uint64_t *values[kFilterCols];
+    const uint32_t *vbits[kFilterCols];  // nullptr: no nulls
+    int64_t vbit0[kFilterCols];
+    uint64_t *out_values[kFilterCols];
+    unsigned long long *out_valid[kFilterCols];   // 8-byte aligned, ceil(selected / 64) words, zeroed by the host
+};
+int launch_filter_mask(Ctx *c, const FilterMaskArgs &a);
+int launch_filter_scatter(Ctx *c, const FilterScatterArgs &a);
+
 // generate.hip
 int launch_gen_dense(Ctx *c, int64_t row0, int64_t n, uint64_t seed, int64_t *ts, double *val);
 int launch_gen_sparse(Ctx *c, int64_t row0, int64_t n, uint64_t seed, int64_t *ts, double *val, uint8_t *validity);

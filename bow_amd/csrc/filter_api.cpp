@@ -1,0 +1,307 @@
+// filter_api.cpp — C-ABI entry points of Bow.Filter (reference bowsetters.go:58-132): bowgpu_filter_mask, bowgpu_compact, bowgpu_filter.
+// Host code validates, prepares residency and orchestrates the kernels of filter.hip; no value is compared and no row is moved on the
+// CPU.
+#include <stdio.h>
+#include <string.h>
+
+#include "common.h"
+
+using namespace bowgpu;
+
+namespace {
+
+constexpr int64_t kFilterMaxRows = (int64_t)1 << 31;   // rows and counts inside the kernels are 32 bits wide
+
+// the context's small scratch block as this file lays it out
+constexpr size_t kScrStats = 0;                        // filter_stats_kernel's four words
+constexpr size_t kScrNulls = 16;                       // kFilterCols counts of valid output rows
+constexpr size_t kScrBytes = 4096;                      // (what devcol_prepare's null count asks for: the block does not move under a call)
+static_assert(kScrNulls + 8 * kFilterCols <= kScrBytes, "scratch layout");
+
+bool residency_ok(int32_t r) { return r == BOWGPU_HOST || r == BOWGPU_DEVICE || r == BOWGPU_HOST_PINNED; }
+bool movable(int32_t t) { return t == BOWGPU_INT64 || t == BOWGPU_FLOAT64; }
+
+// everything that can be said about the frame and the predicates without reading a column; *n: rows of the frame
+int frame_checks(const bowgpu_col *cols, int32_t ncols, const bowgpu_filter_pred *preds, int32_t npreds, int64_t *n) {
+    if (ncols < 0 || npreds < 0) return fail(BOWGPU_ERR_ARG, "negative column or predicate count");
+    if ((ncols > 0 && !cols) || (npreds > 0 && !preds)) return fail(BOWGPU_ERR_ARG, "null argument");
+    if (npreds > BOWGPU_FILTER_MAX_PREDS)
+        return fail(BOWGPU_ERR_UNSUPPORTED, "%d comparators: the device filter serves at most BOWGPU_FILTER_MAX_PREDS = %d", npreds, BOWGPU_FILTER_MAX_PREDS);
+    *n = ncols > 0 ? cols[0].length : 0;
+    for (int i = 0; i < ncols; i++) {
+        if (cols[i].length < 0 || cols[i].offset < 0) return fail(BOWGPU_ERR_ARG, "negative column length/offset");
+        if (cols[i].length != *n) return fail(BOWGPU_ERR_ARG, "columns differ in length");
+        if (!movable(cols[i].type)) return fail(BOWGPU_ERR_UNSUPPORTED, "column %d is of unsupported type (Int64 / Float64 only)", i);
+        if (!residency_ok(cols[i].residency)) return fail(BOWGPU_ERR_ARG, "unknown residency %d", cols[i].residency);
+    }
+    for (int p = 0; p < npreds; p++) {
+        if (preds[p].col < 0 || preds[p].col > ncols - 1) return fail(BOWGPU_ERR_BAD_COL, "no column '%d'", preds[p].col);
+        if (preds[p].n_values < 0) return fail(BOWGPU_ERR_ARG, "negative value count");
+        if (preds[p].n_values > BOWGPU_FILTER_MAX_VALUES)
+            return fail(BOWGPU_ERR_UNSUPPORTED, "%d values in one comparator: the device filter serves at most BOWGPU_FILTER_MAX_VALUES = %d",
+                        preds[p].n_values, BOWGPU_FILTER_MAX_VALUES);
+        if (preds[p].n_values > 0 && !preds[p].values) return fail(BOWGPU_ERR_ARG, "null argument");
+    }
+    if (*n >= kFilterMaxRows)
+        return fail(BOWGPU_ERR_UNSUPPORTED, "the frame has %lld rows: the device filter serves fewer than 2^31 = 2147483648 rows", (long long)*n);
+    return 0;
+}
+
+// what can be said about the outputs before the selected count is known (the capacity comparison needs the count)
+int outs_checks(const bowgpu_out *outs, int32_t ncols) {
+    for (int i = 0; i < ncols; i++) {
+        if (!residency_ok(outs[i].residency)) return fail(BOWGPU_ERR_ARG, "unknown residency %d", outs[i].residency);
+        if (outs[i].length < 0) return fail(BOWGPU_ERR_ARG, "output column %d has a negative capacity", i);
+        if (outs[i].length > 0 && (!outs[i].values || !outs[i].validity)) return fail(BOWGPU_ERR_ARG, "output column lacks a values or validity buffer");
+    }
+    return 0;
+}
+
+// the bitmap of one call, its tile counts and the predicate columns (kept staged for the scatter that follows)
+struct MaskWork {
+    DevBuf mask, tiles, spans, sums, staged_mask;
+    DevCol pcol[BOWGPU_FILTER_MAX_PREDS];
+    int32_t pcol_of[BOWGPU_FILTER_MAX_PREDS];   // the frame column pcol[i] holds
+    int npcols = 0;
+    int64_t selected = 0, first = -1, last = -1;
+    const DevCol *staged(int32_t col) const {
+        for (int i = 0; i < npcols; i++) if (pcol_of[i] == col) return &pcol[i];
+        return nullptr;
+    }
+};
+
+// the predicate pass (bracketed by the context's events) and its three numbers; synchronises
+int mask_device(Ctx *c, const bowgpu_col *cols, const bowgpu_filter_pred *preds, int32_t npreds, const uint8_t *and_mask, int32_t and_residency,
+                int64_t n, MaskWork *w) {
+    const int64_t ntiles = (n + kFilterTileRows - 1) / kFilterTileRows;
+    FilterMaskArgs a;
+    memset(&a, 0, sizeof a);
+    a.n = n;
+    a.npreds = npreds;
+    if (and_mask) {
+        const size_t nb = (size_t)((n + 7) >> 3);
+        if (and_residency == BOWGPU_DEVICE) {
+            a.and_mask = and_mask;
+        } else if (and_residency == BOWGPU_HOST_PINNED) {
+            void *dp = nullptr;
+            if (hipHostGetDevicePointer(&dp, const_cast<uint8_t *>(and_mask), 0) != hipSuccess || !dp) {
+                (void)hipGetLastError();
+                return fail(BOWGPU_ERR_ARG, "BOWGPU_HOST_PINNED: the mask buffer is not registered (bowgpu_host_register)");
+            }
+            a.and_mask = reinterpret_cast<const uint8_t *>(dp);
+        } else {
+            BG_TRY(w->staged_mask.alloc(nb));
+            BG_TRY(copy_h2d(c, w->staged_mask.p, and_mask, nb));
+            a.and_mask = reinterpret_cast<const uint8_t *>(w->staged_mask.p);
+        }
+    }
+    for (int p = 0; p < npreds; p++) {
+        const int32_t col = preds[p].col;
+        const DevCol *dc = w->staged(col);
+        if (!dc) {
+            BG_TRY(devcol_prepare(c, &cols[col], &w->pcol[w->npcols], true, true));
+            w->pcol_of[w->npcols] = col;
+            dc = &w->pcol[w->npcols++];
+        }
+        FilterPredDev &P = a.preds[p];
+        P.values = reinterpret_cast<const uint64_t *>(dc->values);
+        P.vbits = dc->vbits;
+        P.vbit0 = dc->vbit0;
+        P.n_values = preds[p].n_values;
+        P.match_null = preds[p].match_null != 0;
+        P.is_float = cols[col].type == BOWGPU_FLOAT64;
+        if (P.n_values > 0) memcpy(P.set, preds[p].values, (size_t)P.n_values * 8);
+    }
+    void *scr;
+    BG_TRY(ctx_scratch(c, kScrBytes, &scr));
+    char *s = reinterpret_cast<char *>(scr);
+    BG_TRY(w->mask.alloc((size_t)ntiles * (kFilterTileRows / 8)));
+    BG_TRY(w->tiles.alloc((size_t)ntiles * 4));
+    BG_TRY(w->spans.alloc((size_t)ntiles * 4));
+    a.mask = reinterpret_cast<unsigned long long *>(w->mask.p);
+    a.tile_counts = reinterpret_cast<uint32_t *>(w->tiles.p);
+    a.tile_spans = reinterpret_cast<uint32_t *>(w->spans.p);
+    a.stats = reinterpret_cast<uint32_t *>(s + kScrStats);
+    volatile uint32_t *back;   // the context's registered block: filter_stats_kernel stores the three numbers there itself
+    BG_TRY(ctx_pinned(c, 16384, reinterpret_cast<void **>(const_cast<uint32_t **>(&back))));
+    a.host_stats = const_cast<uint32_t *>(back);
+    BG_HIP(hipMemsetAsync(s + kScrStats, 0, 16, c->stream));
+    BG_HIP(hipEventRecord(c->ev0, c->stream));
+    BG_TRY(launch_filter_mask(c, a));
+    BG_HIP(hipEventRecord(c->ev1, c->stream));
+    BG_HIP(hipStreamSynchronize(c->stream));
+    w->selected = back[0];
+    w->first = back[0] ? (int64_t)back[1] : -1;
+    w->last = back[0] ? (int64_t)back[2] : -1;
+    return 0;
+}
+
+// outs[i] = the selected rows of cols[i], for every column of the frame in groups of kFilterCols (the caller has checked the capacities)
+int scatter_device(Ctx *c, const bowgpu_col *cols, int32_t ncols, int64_t n, MaskWork *w, bowgpu_out *outs) {
+    const int64_t ntiles = (n + kFilterTileRows - 1) / kFilterTileRows, count = w->selected;
+    BG_TRY(w->sums.alloc((size_t)((ntiles + 4095) / 4096) * 4));
+    // the context's events: from the scan to the last scatter launch.  For a frame of up to kFilterCols device-resident columns that is
+    // the scan, the memsets and the scatter kernel; with more groups or host-resident columns their staging and copies fall inside
+    BG_HIP(hipEventRecord(c->ev0, c->stream));
+    BG_TRY(launch_scan_u32(c, reinterpret_cast<uint32_t *>(w->tiles.p), ntiles, reinterpret_cast<uint32_t *>(w->sums.p)));
+    for (int g0 = 0; g0 < ncols; g0 += kFilterCols) {
+        // (each group's staged inputs and output temporaries are released before the next group's are taken)
+        const int g = ncols - g0 < kFilterCols ? ncols - g0 : kFilterCols;
+        DevCol staged[kFilterCols];
+        DevOut douts[kFilterCols];
+        FilterScatterArgs a;
+        memset(&a, 0, sizeof a);
+        a.ncols = g;
+        a.n = n;
+        a.mask = reinterpret_cast<const unsigned long long *>(w->mask.p);
+        a.tile_base = reinterpret_cast<const uint32_t *>(w->tiles.p);
+        for (int i = 0; i < g; i++) {
+            const int col = g0 + i;
+            const DevCol *dc = w->staged(col);
+            if (!dc) {
+                BG_TRY(devcol_prepare(c, &cols[col], &staged[i], true, true));
+                dc = &staged[i];
+            }
+            BG_TRY(devout_prepare(c, &outs[col], count, &douts[i]));
+            a.values[i] = reinterpret_cast<const uint64_t *>(dc->values);
+            a.vbits[i] = dc->vbits;
+            a.vbit0[i] = dc->vbit0;
+            a.out_values[i] = reinterpret_cast<uint64_t *>(douts[i].values);
+            // (the working copy of devout_prepare, ((ceil(count/8)+3)&~3)+4 bytes, always holds ceil(count/64) whole words)
+            a.out_valid[i] = reinterpret_cast<unsigned long long *>(douts[i].validity);
+            BG_HIP(hipMemsetAsync(douts[i].validity, 0, (size_t)((count + 63) >> 6) * 8, c->stream));
+        }
+        void *scr;   // (taken after the columns are staged: counting a column's nulls may have replaced the block)
+        BG_TRY(ctx_scratch(c, kScrBytes, &scr));
+        char *s = reinterpret_cast<char *>(scr);
+        BG_TRY(launch_filter_scatter(c, a));
+        BG_HIP(hipEventRecord(c->ev1, c->stream));
+        // null_count = rows - set bits of the finished bitmap (an input column without nulls has none to count)
+        unsigned long long valid[kFilterCols] = {};
+        for (int i = 0; i < g; i++)
+            if (a.vbits[i]) BG_TRY(launch_popcount(c, reinterpret_cast<const uint32_t *>(douts[i].validity), 0, count, reinterpret_cast<uint64_t *>(s + kScrNulls) + i));
+        bool counted = false;
+        for (int i = 0; i < g; i++) counted |= a.vbits[i] != nullptr;
+        if (counted) BG_HIP(hipMemcpyAsync(valid, s + kScrNulls, sizeof valid, hipMemcpyDeviceToHost, c->stream));
+        // the copies of the finished columns are queued behind it: one synchronise for the group, the null counts filled in after it
+        for (int i = 0; i < g; i++) BG_TRY(devout_finish(c, &douts[i], count, cols[g0 + i].type, 0));
+        BG_HIP(hipStreamSynchronize(c->stream));
+        for (int i = 0; i < g; i++)
+            if (a.vbits[i]) outs[g0 + i].null_count = count - (int64_t)valid[i];
+    }
+    return 0;
+}
+
+void kernel_done(Ctx *c, const char *name) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) != hipSuccess) (void)hipGetLastError();
+    c->last_kernel_ms = ms;
+    c->last_kernel_name = name;
+}
+
+// bowgpu_filter and bowgpu_compact after their argument checks
+int filter_run(const bowgpu_col *cols, int32_t ncols, const bowgpu_filter_pred *preds, int32_t npreds, const uint8_t *and_mask,
+               int32_t and_residency, int64_t n, bowgpu_out *outs, int64_t *first, int64_t *count, int32_t *contiguous) {
+    Ctx *c;
+    BG_TRY(ctx_get(&c));
+    MaskWork w;
+    {
+        const int rc = mask_device(c, cols, preds, npreds, and_mask, and_residency, n, &w);
+        if (rc != 0) { (void)hipStreamSynchronize(c->stream); return rc; }
+    }
+    *count = w.selected;
+    *first = w.selected ? w.first : 0;
+    *contiguous = w.selected == 0 || w.selected == w.last - w.first + 1;
+    if (*contiguous) {   // bowsetters.go:74-82: the empty slice, or a slice of the receiver
+        kernel_done(c, "filter_mask_kernel");
+        return 0;
+    }
+    bool device_out = false;
+    for (int i = 0; i < ncols; i++) {
+        if (outs[i].length < w.selected)
+            return fail(BOWGPU_ERR_ARG, "output column %d has %lld slots, %lld needed", i, (long long)outs[i].length, (long long)w.selected);
+        device_out |= outs[i].residency == BOWGPU_DEVICE;
+    }
+    const int rc = scatter_device(c, cols, ncols, n, &w, outs);
+    if (rc != 0) { (void)hipStreamSynchronize(c->stream); return rc; }
+    BG_HIP(hipStreamSynchronize(c->stream));
+    if (device_out) device_write_epoch_bump();
+    kernel_done(c, "filter_scatter_kernel");
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bowgpu_filter_mask(const bowgpu_col *cols, int32_t ncols, const bowgpu_filter_pred *preds, int32_t npreds, const uint8_t *and_mask,
+                       int32_t and_mask_residency, uint8_t *mask_out, int32_t mask_residency, int64_t *selected, int64_t *first, int64_t *last) {
+    if (!selected || !first || !last) return fail(BOWGPU_ERR_ARG, "null argument");
+    int64_t n = 0;
+    BG_TRY(frame_checks(cols, ncols, preds, npreds, &n));
+    if (and_mask && !residency_ok(and_mask_residency)) return fail(BOWGPU_ERR_ARG, "unknown residency %d", and_mask_residency);
+    if (!residency_ok(mask_residency)) return fail(BOWGPU_ERR_ARG, "unknown residency %d", mask_residency);
+    *selected = 0;
+    *first = *last = -1;
+    if (n == 0) return 0;
+    if (!mask_out) return fail(BOWGPU_ERR_ARG, "null argument");
+    const size_t nb = (size_t)((n + 7) >> 3);
+    if (npreds == 0 && !and_mask && mask_residency != BOWGPU_DEVICE) {   // the empty filter into host memory: every row
+        memset(mask_out, 0xFF, nb);
+        if (n & 7) mask_out[nb - 1] = (uint8_t)((1u << (n & 7)) - 1u);
+        *selected = n;
+        *first = 0;
+        *last = n - 1;
+        return 0;
+    }
+    Ctx *c;
+    BG_TRY(ctx_get(&c));
+    MaskWork w;
+    {
+        const int rc = mask_device(c, cols, preds, npreds, and_mask, and_mask_residency, n, &w);
+        if (rc != 0) { (void)hipStreamSynchronize(c->stream); return rc; }
+    }
+    kernel_done(c, "filter_mask_kernel");
+    if (mask_residency == BOWGPU_DEVICE) {
+        BG_HIP(hipMemcpyAsync(mask_out, w.mask.p, nb, hipMemcpyDeviceToDevice, c->stream));
+        device_write_epoch_bump();
+    } else {
+        BG_TRY(copy_d2h(c, mask_out, w.mask.p, nb, mask_residency == BOWGPU_HOST_PINNED));
+    }
+    BG_HIP(hipStreamSynchronize(c->stream));
+    *selected = w.selected;
+    *first = w.first;
+    *last = w.last;
+    return 0;
+}
+
+int bowgpu_compact(const bowgpu_col *cols, int32_t ncols, const uint8_t *mask, int32_t mask_residency, bowgpu_out *outs, int64_t *first,
+                   int64_t *count, int32_t *contiguous) {
+    if (!first || !count || !contiguous || (ncols > 0 && !outs)) return fail(BOWGPU_ERR_ARG, "null argument");
+    int64_t n = 0;
+    BG_TRY(frame_checks(cols, ncols, nullptr, 0, &n));
+    if (!residency_ok(mask_residency)) return fail(BOWGPU_ERR_ARG, "unknown residency %d", mask_residency);
+    BG_TRY(outs_checks(outs, ncols));
+    *first = 0;
+    *count = 0;
+    *contiguous = 1;
+    if (n == 0) return 0;
+    if (!mask) return fail(BOWGPU_ERR_ARG, "null argument");
+    return filter_run(cols, ncols, nullptr, 0, mask, mask_residency, n, outs, first, count, contiguous);
+}
+
+int bowgpu_filter(const bowgpu_col *cols, int32_t ncols, const bowgpu_filter_pred *preds, int32_t npreds, const uint8_t *and_mask,
+                  int32_t and_mask_residency, bowgpu_out *outs, int64_t *first, int64_t *count, int32_t *contiguous) {
+    if (!first || !count || !contiguous || (ncols > 0 && !outs)) return fail(BOWGPU_ERR_ARG, "null argument");
+    int64_t n = 0;
+    BG_TRY(frame_checks(cols, ncols, preds, npreds, &n));
+    if (and_mask && !residency_ok(and_mask_residency)) return fail(BOWGPU_ERR_ARG, "unknown residency %d", and_mask_residency);
+    BG_TRY(outs_checks(outs, ncols));
+    *first = 0;
+    *count = n;
+    *contiguous = 1;
+    if (n == 0 || (npreds == 0 && !and_mask)) return 0;   // no rows; or the empty filter: the receiver itself
+    return filter_run(cols, ncols, preds, npreds, and_mask, and_mask_residency, n, outs, first, count, contiguous);
+}
+
+}  // extern "C"

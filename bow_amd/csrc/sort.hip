@@ -321,14 +321,22 @@ int launch_sort_hist(Ctx *c, const uint64_t *key, int64_t n, int is_float, uint3
     return 0;
 }
 
+// the three launches of the exclusive scan, for the radix passes and for filter.hip's tile counts
+int launch_scan_u32(Ctx *c, uint32_t *v, int64_t m, uint32_t *sums) {
+    const int64_t nb = (m + kScanBlock - 1) / kScanBlock;
+    hipLaunchKernelGGL(sort_scan_sums_kernel, dim3((unsigned)nb), dim3(kThreads), 0, c->stream, v, m, sums);
+    hipLaunchKernelGGL(sort_scan_top_kernel, dim3(1), dim3(kThreads), 0, c->stream, sums, nb);
+    hipLaunchKernelGGL(sort_scan_apply_kernel, dim3((unsigned)nb), dim3(kThreads), 0, c->stream, v, m, sums);
+    BG_HIP(hipGetLastError());
+    return 0;
+}
+
 int launch_sort_pass(Ctx *c, const uint64_t *src, int mode, const uint32_t *src_idx, int64_t n, int shift, uint32_t *tile_hist, uint32_t *sums,
                      uint64_t *dst, uint32_t *dst_idx) {
     const int64_t ntiles = (n + kTile - 1) / kTile;
-    const int64_t m = 256 * ntiles, nb = (m + kScanBlock - 1) / kScanBlock;
+    const int64_t m = 256 * ntiles;
     hipLaunchKernelGGL(sort_tile_hist_kernel, dim3((unsigned)ntiles), dim3(kThreads), 0, c->stream, src, mode, n, shift, tile_hist, ntiles);
-    hipLaunchKernelGGL(sort_scan_sums_kernel, dim3((unsigned)nb), dim3(kThreads), 0, c->stream, tile_hist, m, sums);
-    hipLaunchKernelGGL(sort_scan_top_kernel, dim3(1), dim3(kThreads), 0, c->stream, sums, nb);
-    hipLaunchKernelGGL(sort_scan_apply_kernel, dim3((unsigned)nb), dim3(kThreads), 0, c->stream, tile_hist, m, sums);
+    BG_TRY(launch_scan_u32(c, tile_hist, m, sums));
     hipLaunchKernelGGL(sort_scatter_kernel, dim3((unsigned)ntiles), dim3(kThreads), 0, c->stream, src, mode, src_idx, n, shift, tile_hist, ntiles,
                        dst, dst_idx);
     BG_HIP(hipGetLastError());

@@ -19,7 +19,11 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <errno.h>
+
+#include <cctype>
 #include <cmath>
+#include <cstdlib>
 #include <functional>
 #include <memory>
 #include <optional>
@@ -107,6 +111,46 @@ inline Series NewSeries(const std::string &name, Type typ, const std::vector<T> 
 
 class Bow;
 using BowPtr = std::shared_ptr<const Bow>;
+
+// one argument of MakeFilterValues (an interface{} there): nil, a number, a bool or a string
+struct FilterArg {
+    enum Kind { KNil, KInt, KFloat, KBool, KStr } kind = KNil;
+    int64_t i = 0;
+    double f = 0;
+    bool b = false;
+    std::string s;
+    FilterArg() = default;
+    FilterArg(int v) : kind(KInt), i(v) {}
+    FilterArg(long v) : kind(KInt), i(v) {}
+    FilterArg(long long v) : kind(KInt), i(v) {}
+    FilterArg(float v) : kind(KFloat), f(v) {}
+    FilterArg(double v) : kind(KFloat), f(v) {}
+    FilterArg(bool v) : kind(KBool), b(v) {}
+    FilterArg(const char *v) : kind(KStr), s(v) {}
+    FilterArg(std::string v) : kind(KStr), s(std::move(v)) {}
+    FilterArg(const Value &v) {
+        if (!v) return;
+        if (std::holds_alternative<int64_t>(*v)) { kind = KInt; i = std::get<int64_t>(*v); }
+        else if (std::holds_alternative<double>(*v)) { kind = KFloat; f = std::get<double>(*v); }
+        else { kind = KBool; b = std::get<bool>(*v); }
+    }
+};
+// Type.Convert for the numeric column types (bowtypes.go:64-81, bowconvert.go:11-73): numbers, bools and numeric strings; anything
+// else becomes nil
+Value Convert(Type t, const FilterArg &a);
+
+// RowCmp: bowsetters.go:58-61.  Either a user closure over (bow, row) or what MakeFilterValues prepares: a column, the converted
+// values and whether one of them became nil (the comparator then holds on null rows) - the form the device evaluates
+struct RowCmp {
+    std::function<bool(const Bow &, int)> fn;   // set: a user closure
+    int col = -1;
+    Type typ = Type::Unknown;
+    std::vector<uint64_t> values;               // 64-bit payloads of `typ`
+    bool match_null = false;
+    RowCmp() = default;
+    template <typename Fn, typename = decltype(std::declval<Fn &>()(std::declval<const Bow &>(), 0))>
+    RowCmp(Fn f) : fn(std::move(f)) {}
+};
 
 class Bow : public std::enable_shared_from_this<Bow> {
   public:
@@ -216,6 +260,14 @@ class Bow : public std::enable_shared_from_this<Bow> {
     std::pair<BowPtr, Error> FillMean(std::vector<int> colIndices = {}) const { return fill(BOWGPU_FILL_MEAN, colIndices); }
     // SortByCol: bowsort.go:10-41 (device; stable); returns the receiver when the column is already sorted
     std::pair<BowPtr, Error> SortByCol(int colIndex) const;
+    // MakeFilterValues: bowsetters.go:111-132 ; Filter: bowsetters.go:63-100 (device).  Built-in comparators are evaluated by
+    // bowgpu_filter; user closures are evaluated here into a row bitmap that the call ANDs in.  Consecutive selected rows come back as
+    // a slice of the receiver, none as the empty slice.  (The reference's Filter returns a Bow alone and panics; the Error carries
+    // what the device path can answer, e.g. no device.)
+    RowCmp MakeFilterValuesV(int colIndex, const std::vector<FilterArg> &values) const;
+    template <typename... V> RowCmp MakeFilterValues(int colIndex, V... values) const;
+    std::pair<BowPtr, Error> FilterV(const std::vector<RowCmp> &cmps) const;
+    template <typename... C> std::pair<BowPtr, Error> Filter(const C &...cmps) const;
 
 private:
     std::pair<BowPtr, Error> fill(int method, const std::vector<int> &colIndices) const;
@@ -373,6 +425,92 @@ inline std::pair<BowPtr, Error> Bow::SortByCol(int colIndex) const {
     auto out = std::make_shared<Bow>();
     for (int i = 0; i < NumCols(); i++) out->cols.push_back(st[(size_t)i].ToSeries(cols[i].Name, o[(size_t)i]));
     return {out, Error()};
+}
+
+inline Value Convert(Type t, const FilterArg &a) {
+    if (t != Type::Int64 && t != Type::Float64) return Nil();
+    const bool to_int = t == Type::Int64;
+    switch (a.kind) {
+    case FilterArg::KInt: return to_int ? Scalar(a.i) : Scalar((double)a.i);
+    case FilterArg::KFloat: return to_int ? Scalar(GoInt64(a.f)) : Scalar(a.f);
+    case FilterArg::KBool: return to_int ? Scalar((int64_t)(a.b ? 1 : 0)) : Scalar(a.b ? 1. : 0.);
+    case FilterArg::KStr: {   // strconv.ParseInt(s, 10, 64) / strconv.ParseFloat(s, 64): the whole string, no surrounding space
+        if (a.s.empty() || isspace((unsigned char)a.s[0])) return Nil();
+        char *end = nullptr;
+        errno = 0;
+        if (to_int) {
+            const long long v = strtoll(a.s.c_str(), &end, 10);
+            if (errno == ERANGE || *end != '\0') return Nil();
+            return Scalar((int64_t)v);
+        }
+        const double v = strtod(a.s.c_str(), &end);
+        if (*end != '\0' || (errno == ERANGE && std::isinf(v))) return Nil();
+        return Scalar(v);
+    }
+    default: return Nil();
+    }
+}
+
+inline RowCmp Bow::MakeFilterValuesV(int colIndex, const std::vector<FilterArg> &values) const {
+    RowCmp r;
+    r.col = colIndex;
+    r.typ = ColumnType(colIndex);
+    for (const FilterArg &a : values) {
+        const Value v = Convert(r.typ, a);
+        if (!v) { r.match_null = true; continue; }
+        uint64_t bits;
+        if (r.typ == Type::Int64) { const int64_t x = std::get<int64_t>(*v); memcpy(&bits, &x, 8); }
+        else { const double x = std::get<double>(*v); memcpy(&bits, &x, 8); }
+        r.values.push_back(bits);
+    }
+    return r;
+}
+template <typename... V> inline RowCmp Bow::MakeFilterValues(int colIndex, V... values) const {
+    return MakeFilterValuesV(colIndex, std::vector<FilterArg>{FilterArg(values)...});
+}
+
+inline std::pair<BowPtr, Error> Bow::FilterV(const std::vector<RowCmp> &cmps) const {
+    const int n = NumRows();
+    std::vector<bowgpu_filter_pred> preds;
+    std::vector<uint8_t> closure_rows;   // the user closures, ANDed: bit i of byte i / 8
+    for (const RowCmp &r : cmps) {
+        if (r.fn) {
+            if (closure_rows.empty() && n > 0) {
+                closure_rows.assign((size_t)((n + 7) / 8), 0xFF);
+                if (n & 7) closure_rows.back() = (uint8_t)((1u << (n & 7)) - 1u);
+            }
+            for (int i = 0; i < n; i++)
+                if (((closure_rows[(size_t)i >> 3] >> (i & 7)) & 1) && !r.fn(*this, i)) closure_rows[(size_t)i >> 3] &= (uint8_t)~(1u << (i & 7));
+            continue;
+        }
+        bowgpu_filter_pred p;
+        memset(&p, 0, sizeof p);
+        p.col = r.col;
+        p.match_null = r.match_null;
+        // (values boxed as another type than the column's never equal its values: only nil == nil is left of such a comparator)
+        if (r.col >= 0 && r.col < NumCols() && r.typ == ColumnType(r.col)) {
+            p.n_values = (int32_t)r.values.size();
+            p.values = r.values.empty() ? nullptr : r.values.data();
+        }
+        preds.push_back(p);
+    }
+    std::vector<bowgpu_col> c;
+    for (int i = 0; i < NumCols(); i++) c.push_back(ArrowCol(i));
+    std::vector<detail::OutStore> st((size_t)NumCols());
+    std::vector<bowgpu_out> o;
+    for (int i = 0; i < NumCols(); i++) o.push_back(st[(size_t)i].Make(n));
+    int64_t first = 0, count = 0;
+    int32_t contiguous = 0;
+    const int rc = bowgpu_filter(c.data(), NumCols(), preds.data(), (int32_t)preds.size(), closure_rows.empty() ? nullptr : closure_rows.data(),
+                                 BOWGPU_HOST, o.data(), &first, &count, &contiguous);
+    if (rc) return {nullptr, detail::AbiError(rc)};
+    if (contiguous) return {count == 0 ? NewEmptySlice() : NewSlice((int)first, (int)(first + count)), Error()};   // bowsetters.go:74-82
+    auto out = std::make_shared<Bow>();
+    for (int i = 0; i < NumCols(); i++) out->cols.push_back(st[(size_t)i].ToSeries(cols[i].Name, o[(size_t)i]));
+    return {out, Error()};
+}
+template <typename... C> inline std::pair<BowPtr, Error> Bow::Filter(const C &...cmps) const {
+    return FilterV(std::vector<RowCmp>{RowCmp(cmps)...});
 }
 
 inline bool Bow::IsColSorted(int colIndex) const {

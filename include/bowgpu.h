@@ -35,7 +35,9 @@ extern "C" {
  * changed. */
 /* 9: bowgpu_argsort / bowgpu_take / bowgpu_sort_by_col added (Bow.SortByCol on the device) and BOWGPU_ERR_SORT_NULLS with them; no struct
  * changed. */
-#define BOWGPU_ABI_VERSION 9
+/* 10: bowgpu_filter_mask / bowgpu_compact / bowgpu_filter and the bowgpu_filter_pred struct added (Bow.Filter on the device); no existing
+ * struct changed. */
+#define BOWGPU_ABI_VERSION 10
 
 /* bow.Type (reference bowtypes.go:17-32) */
 enum {
@@ -508,6 +510,71 @@ int bowgpu_take(const bowgpu_col *col, const int64_t *idx, int64_t n_idx, int32_
  * reference returns the receiver itself (already sorted, or fewer than 2 rows): the outputs are then not written - neither their
  * buffers nor their length / null_count / type. */
 int bowgpu_sort_by_col(const bowgpu_col *cols, int32_t ncols, int32_t key_col, bowgpu_out *outs, int32_t *unchanged);
+
+/* ---- Bow.Filter -------------------------------------------------------------------- */
+
+/* Bow.Filter - reference bowsetters.go:58-132 - as three calls: the predicates evaluated into a row bitmap (bowgpu_filter_mask), the
+ * rows of a bitmap moved together in row order (bowgpu_compact), and both in one call (bowgpu_filter).  The conventions are those of the
+ * sort entry points: ONE device, any residency for inputs and outputs (BOWGPU_HOST staged through HBM, BOWGPU_HOST_PINNED and
+ * BOWGPU_DEVICE read where they lie), per-thread contexts and streams; bowgpu_set_devices does not apply.  A filter ACROSS row-range
+ * shards on several devices is not offered: filter each shard.
+ *   PREDICATES.  One bowgpu_filter_pred is one MakeFilterValues(col, values...) (bowsetters.go:114-132) after the caller has run
+ * Type.Convert on the values: the row is kept when its value equals one of `values`.  Equality is Go's == on the boxed value: Int64
+ * exactly; Float64 by IEEE == (a NaN in the column or in the set matches nothing; -0.0 equals +0.0).  A null row matches only through
+ * match_null (a value Convert turned into nil: GetValue gives nil, nil == nil).  n_values == 0 with match_null == 0 selects nothing.
+ * Several predicates are ANDed (matchRowCmps), and so is the caller's bitmap and_mask (what a shim evaluates user closures
+ * into), bit i of byte i / 8, LSB first, no offset, any alignment; NULL: none.
+ *   NO SELECTOR: npreds == 0 without and_mask is the reference's "empty filter": every row is selected, which is
+ * contiguous; bowgpu_filter then needs no device.
+ *   COLUMNS: predicate and value columns are Int64 / Float64, with or without validity, at any Arrow offset (bit offsets that are no
+ * multiple of 8 included).  Boolean / String anywhere: BOWGPU_ERR_UNSUPPORTED.  More than BOWGPU_FILTER_MAX_VALUES values or
+ * BOWGPU_FILTER_MAX_PREDS predicates: BOWGPU_ERR_UNSUPPORTED naming the limit.  pred.col out of range: BOWGPU_ERR_BAD_COL.  Columns of
+ * unequal length: BOWGPU_ERR_ARG.  Fewer than 2^31 rows; more is BOWGPU_ERR_UNSUPPORTED naming the limit.  For host-resident
+ * arguments all of this is decided before the device is touched; a valid call that has rows to look at is BOWGPU_ERR_NO_DEVICE on a box
+ * without a GPU - no CPU fallback.
+ *   THE CONTIGUOUS CASE.  Where the reference returns a slice of the receiver or the empty slice (bowsetters.go:74-82) - the selected
+ * rows are consecutive, or there are none - *contiguous = 1, *first / *count say which rows (*first = 0 when there are none), and the
+ * outputs are NOT written: neither their buffers nor length / null_count / type.  It is known after the predicate pass, which is
+ * then the whole cost of the call.
+ *   OUTPUTS otherwise are what Buffer.SetOrDropStrict leaves and what bowgpu_take leaves: values moved as raw 64-bit payloads (a NaN's
+ * bits survive), validity bit and null_count set, null slots 0, padding bits of the last validity byte clear, length = *count.
+ * Nothing is written past slot *count - 1 or past validity byte ceil(*count / 8) - 1.  CAPACITY: bowgpu_out.length on entry; the
+ * number of rows always suffices; too small is BOWGPU_ERR_ARG naming the size needed, and nothing is written.  A caller who wants
+ * exact buffers calls bowgpu_filter_mask first (*selected) and then bowgpu_compact.
+ *   HBM WORKSPACE, from the calling thread's scratch cache (exhaustion: BOWGPU_ERR_OOM): 1/8 byte per row (the bitmap) + 8 bytes
+ * per 4096 rows (tile records, + 4 per 4096 of those for the scan of the counts); + the staged copy of a BOWGPU_HOST and_mask / mask, the staged
+ * copies of BOWGPU_HOST columns and the device temporaries of host-resident outputs - the predicate columns for the whole call, the
+ * others at most 4 columns at a time.
+ *   THE METHOD (bow_amd/csrc/filter.hip): a predicate pass that reads only the predicate columns and stores one 64-bit word per 64
+ * rows; an exclusive scan of the per-tile counts; a scatter pass in which lanes load only the rows they keep and a tile that keeps
+ * nothing reads nothing but its 64 mask words.  No workgroup waits on another; the same call gives the same bytes. */
+#define BOWGPU_FILTER_MAX_VALUES 32
+#define BOWGPU_FILTER_MAX_PREDS  8
+typedef struct bowgpu_filter_pred {
+    int32_t col;
+    int32_t n_values;
+    int32_t match_null;   /* a value Convert turned into nil: the predicate then holds on null rows */
+    int32_t _pad;
+    const void *values;   /* HOST memory, n_values items of the column's type; may be NULL when n_values == 0 */
+} bowgpu_filter_pred;
+
+/* mask_out bit i (LSB first, no offset) = all preds hold on row i AND (and_mask == NULL or its bit i); ceil(rows / 8) bytes, the padding
+ * bits of the last byte clear.  *selected = set bits; *first / *last = lowest / highest selected row (-1 / -1 when none).  cols may
+ * hold the whole frame: only the predicate columns are read (with no predicate, cols[0] gives the number of rows). */
+int bowgpu_filter_mask(const bowgpu_col *cols, int32_t ncols, const bowgpu_filter_pred *preds, int32_t npreds,
+                       const uint8_t *and_mask, int32_t and_mask_residency, uint8_t *mask_out, int32_t mask_residency,
+                       int64_t *selected, int64_t *first, int64_t *last);
+
+/* outs[c] = the rows of cols[c] whose mask bit is set, in row order (mask: ceil(rows / 8) bytes as bowgpu_filter_mask writes them; bits
+ * past the last row are ignored).  The contiguous case: see above. */
+int bowgpu_compact(const bowgpu_col *cols, int32_t ncols, const uint8_t *mask, int32_t mask_residency,
+                   bowgpu_out *outs, int64_t *first, int64_t *count, int32_t *contiguous);
+
+/* Bow.Filter in one call: the predicates, an optional caller mask ANDed in (NULL: none), the compaction.  The bitmap stays in the
+ * workspace between the two passes (1/8 byte per row written and read, against 8 or more per row to evaluate the predicates twice). */
+int bowgpu_filter(const bowgpu_col *cols, int32_t ncols, const bowgpu_filter_pred *preds, int32_t npreds,
+                  const uint8_t *and_mask, int32_t and_mask_residency,
+                  bowgpu_out *outs, int64_t *first, int64_t *count, int32_t *contiguous);
 
 /* ---- Parquet column chunk -> device column --------------------------- */
 
