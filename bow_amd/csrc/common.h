@@ -144,6 +144,65 @@ int copy_h2d(Ctx *c, void *dst, const void *src, size_t bytes, bool registered =
 int devout_prepare(Ctx *c, bowgpu_out *out, int64_t slots, DevOut *d, int pool_slot = -1);
 int devout_finish(Ctx *c, DevOut *d, int64_t slots, int32_t type, int64_t null_count, bool copy_bitmap = true);
 
+// ---------------------------------------------------------------- frame_cols.cpp: what the frame-level operations share on the host
+// (Bow.SortByCol, Bow.Filter: once the key is sorted / the mask built, both move the rows of every column of a frame into the caller's
+// bowgpu_out columns, kMoveCols columns a launch)
+constexpr int kMoveCols = 4;          // columns moved per launch (the permutation / the bitmap is read once per group)
+struct MoveCols {                     // the columns of one launch, as gather_kernel and filter_scatter_kernel read them
+    int32_t ncols, _pad;
+    const uint64_t *values[kMoveCols];
+    const uint32_t *vbits[kMoveCols];            // nullptr: no nulls
+    int64_t vbit0[kMoveCols];
+    uint64_t *out_values[kMoveCols];
+    unsigned long long *out_valid[kMoveCols];    // 8-byte aligned, ceil(count / 64) words (the working copy of devout_prepare,
+                                                 // ((ceil(count/8)+3)&~3)+4 bytes, always holds them)
+};
+// the context's small scratch block as these operations lay it out
+constexpr size_t kScrHist = 0;                         // Sort: [8][256] digit counts
+constexpr size_t kScrFlags = 8 * 256 * 4;              // four words.  Sort: [0] not ascending, [1] NaN seen, [2] bad index (take); Filter: filter_stats_kernel's
+constexpr size_t kScrNulls = kScrFlags + 16;           // kMoveCols 64-bit counts: the outputs' nulls (gather) / valid rows (scatter)
+constexpr size_t kScrBytes = kScrNulls + 8 * kMoveCols;   // (more than devcol_prepare's null count asks for: the block does not move under a call)
+
+bool movable_type(int32_t t);         // Int64 / Float64
+bool residency_ok(int32_t r);
+// nulls of a column where that is known without the device (host-resident bitmaps are counted here); -1: ask the device
+int64_t host_count_nulls(const bowgpu_col *col);
+// the per-column checks of a frame of n rows, in the order the entry points report them.  Filter's form (residencies = true) reports a
+// negative length before a differing one and checks the residencies; Sort's leaves both to the key's checks and to devcol_prepare
+int frame_cols_checks(const bowgpu_col *cols, int32_t ncols, int64_t n, bool residencies);
+// output columns for `slots` rows each; slots < 0: the count is not known yet (Filter) - residency and capacity must make sense
+int outs_checks(const bowgpu_out *outs, int32_t ncols, int64_t slots);
+// a caller's side buffer (`what`: "index", "mask") on the device: as is, through its registration, or staged into *own
+int aux_in(Ctx *c, const void *p, size_t bytes, int32_t residency, const char *what, const void **dptr, DevBuf *own);
+// a result buffer handed to the caller: dst in device memory is src itself or gets a device-to-device copy (and the write epoch moves)
+int aux_out(Ctx *c, void *dst, const void *src, size_t bytes, int32_t residency);
+int synced(Ctx *c, int rc);            // rc - a failure only after the stream has drained: the call's kernels may still be running on its work buffers
+void kernel_done(Ctx *c, const char *name);   // last_kernel_ms = what ev0 .. ev1 bracket; name must outlive the call
+// columns a call has staged before it moves the frame (Sort: the key; Filter: the predicate columns), by frame column
+struct StagedCols {
+    DevCol dc[BOWGPU_FILTER_MAX_PREDS];
+    int32_t col[BOWGPU_FILTER_MAX_PREDS];
+    int n = 0;
+    DevCol *add(int32_t c) { col[n] = c; return &dc[n++]; }   // (to be filled in by devcol_prepare)
+    const DevCol *find(int32_t c) const {
+        for (int i = 0; i < n; i++) if (col[i] == c) return &dc[i];
+        return nullptr;
+    }
+};
+// One group of up to kMoveCols columns from frame column g0 on.  prepare: stages the inputs `have` lacks, prepares the outputs for
+// `count` slots, fills cols, and only then takes the scratch block (counting a column's nulls may have replaced it).  The caller
+// launches and reads its counts back.  finish: devout_finish of every output + the group's one synchronise.  Both report a failure
+// through synced().  A group's staged inputs and
+// output temporaries go back when the MoveGroup does: before the next group's are taken.
+struct MoveGroup {
+    MoveCols cols;
+    char *scratch = nullptr;
+    DevCol staged[kMoveCols];
+    DevOut douts[kMoveCols];
+};
+int move_group_prepare(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t g0, const StagedCols &have, bowgpu_out *outs, int64_t count, MoveGroup *g);
+int move_group_finish(Ctx *c, MoveGroup *g, const bowgpu_col *cols, int32_t g0, int64_t count, const int64_t *null_counts);
+
 // ---------------------------------------------------------------- division by the interval
 // Granlund–Montgomery round-up method (N = 64): exact floor(n / d) for every 0 <= n < 2^64.
 struct MagicDiv {
@@ -546,16 +605,10 @@ int whole_finish_run(Ctx *c, const void *partials, int64_t nblocks, const WholeF
 
 // sort.hip: Bow.SortByCol - stable LSD radix argsort over (key image, 32-bit row index) pairs, and the gather (host side: sort_api.cpp)
 constexpr int kSortTileRows = 4096;   // rows per scatter tile: one 256-entry digit histogram each
-constexpr int kGatherCols = 4;        // columns moved per gather launch (the permutation is read once per group)
 struct GatherArgs {
-    int32_t ncols, _pad;
+    MoveCols cols;                               // out_valid: ceil(n_idx / 64) words, every one stored whole by its wave
     int64_t n_idx, length;                       // rows to produce; rows of the source columns
-    const uint64_t *values[kGatherCols];
-    const uint32_t *vbits[kGatherCols];          // nullptr: no nulls
-    int64_t vbit0[kGatherCols];
-    uint64_t *out_values[kGatherCols];
-    unsigned long long *out_valid[kGatherCols];  // 8-byte aligned, ceil(n_idx / 64) words: every word stored whole by its wave
-    unsigned long long *null_counts;             // [kGatherCols], zeroed by the host
+    unsigned long long *null_counts;             // [kMoveCols], zeroed by the host
     uint32_t *bad;                               // |= 1: a caller's index outside [0, length)
 };
 // hist: [8][256] digit counts, flags: [0] not ascending, [1] NaN seen (both zeroed by the host); img_out: nullable
@@ -573,7 +626,6 @@ int launch_scan_u32(Ctx *c, uint32_t *v, int64_t m, uint32_t *sums);
 
 // filter.hip: Bow.Filter - value-set predicates into a row bitmap, ordered compaction of the selected rows (host side: filter_api.cpp)
 constexpr int kFilterTileRows = 4096;   // rows per tile: 64 mask words, one selected count
-constexpr int kFilterCols = 4;          // columns moved per scatter launch (the bitmap is read once per group)
 struct FilterPredDev {
     const uint64_t *values;
     const uint32_t *vbits;               // nullptr: no nulls
@@ -593,15 +645,10 @@ struct FilterMaskArgs {
     FilterPredDev preds[BOWGPU_FILTER_MAX_PREDS];
 };
 struct FilterScatterArgs {
-    int32_t ncols, _pad;
+    MoveCols cols;                       // out_valid: ceil(selected / 64) words, zeroed by the host
     int64_t n;
     const unsigned long long *mask;      // as filter_mask_kernel left it
     const uint32_t *tile_base;           // the scanned tile counts
-    const uint64_t *values[kFilterCols];
-    const uint32_t *vbits[kFilterCols];  // nullptr: no nulls
-    int64_t vbit0[kFilterCols];
-    uint64_t *out_values[kFilterCols];
-    unsigned long long *out_valid[kFilterCols];   // 8-byte aligned, ceil(selected / 64) words, zeroed by the host
 };
 int launch_filter_mask(Ctx *c, const FilterMaskArgs &a);
 int launch_filter_scatter(Ctx *c, const FilterScatterArgs &a);

@@ -173,7 +173,7 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, int lane) {
 // one address cost more than everything else in the kernel (measured); the host popcounts the finished bitmaps instead.
 constexpr int kHalfWords = kWaveWords / 2;
 __global__ __launch_bounds__(kThreads) void filter_scatter_kernel(FilterScatterArgs a) {
-    __shared__ uint8_t sok[kFilterCols][kTile];   // validity of the tile's kept rows, per column, in output order
+    __shared__ uint8_t sok[kMoveCols][kTile];   // validity of the tile's kept rows, per column, in output order
     __shared__ unsigned long long sword[kTileWords];
     __shared__ uint32_t sbase[kTileWords + 1];    // kept rows in the tile's earlier words; [kTileWords]: in the whole tile
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -194,15 +194,15 @@ __global__ __launch_bounds__(kThreads) void filter_scatter_kernel(FilterScatterA
     const unsigned long long below = (1ull << lane) - 1ull;
 #pragma unroll
     for (int h = 0; h < 2; h++) {
-        uint64_t v[kFilterCols][kHalfWords];
-        uint32_t okm[kFilterCols];
+        uint64_t v[kMoveCols][kHalfWords];
+        uint32_t okm[kMoveCols];
 #pragma unroll
-        for (int c = 0; c < kFilterCols; c++) {
+        for (int c = 0; c < kMoveCols; c++) {
             okm[c] = 0;
-            if (c < a.ncols) {
-                const uint64_t *vals = a.values[c];
-                const uint32_t *vb = a.vbits[c];
-                const int64_t vb0 = a.vbit0[c];
+            if (c < a.cols.ncols) {
+                const uint64_t *vals = a.cols.values[c];
+                const uint32_t *vb = a.cols.vbits[c];
+                const int64_t vb0 = a.cols.vbit0[c];
 #pragma unroll
                 for (int k = 0; k < kHalfWords; k++) {
                     const int wi = w * kWaveWords + h * kHalfWords + k;
@@ -225,9 +225,9 @@ __global__ __launch_bounds__(kThreads) void filter_scatter_kernel(FilterScatterA
             if ((word >> lane) & 1ull) {
                 const uint32_t slot = sbase[wi] + (uint32_t)__popcll(word & below);
 #pragma unroll
-                for (int c = 0; c < kFilterCols; c++) {
-                    if (c < a.ncols) {
-                        a.out_values[c][base + slot] = v[c][k];
+                for (int c = 0; c < kMoveCols; c++) {
+                    if (c < a.cols.ncols) {
+                        a.cols.out_values[c][base + slot] = v[c][k];
                         sok[c][slot] = (uint8_t)((okm[c] >> k) & 1u);
                     }
                 }
@@ -238,9 +238,9 @@ __global__ __launch_bounds__(kThreads) void filter_scatter_kernel(FilterScatterA
     // output validity, by the output's own 64-row words: one inside the tile's run is stored whole, the at most two shared with the
     // neighbouring tiles' runs are ORed into the zeroed bitmap
 #pragma unroll
-    for (int c = 0; c < kFilterCols; c++) {
-        if (c < a.ncols) {
-            unsigned long long *ob = a.out_valid[c];
+    for (int c = 0; c < kMoveCols; c++) {
+        if (c < a.cols.ncols) {
+            unsigned long long *ob = a.cols.out_valid[c];
             for (int64_t W = (base >> 6) + w; W <= ((end - 1) >> 6); W += kWaves) {
                 const int64_t o = W * 64 + lane;
                 const bool in = o >= base && o < end;

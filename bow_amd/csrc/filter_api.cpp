@@ -12,15 +12,6 @@ namespace {
 
 constexpr int64_t kFilterMaxRows = (int64_t)1 << 31;   // rows and counts inside the kernels are 32 bits wide
 
-// the context's small scratch block as this file lays it out
-constexpr size_t kScrStats = 0;                        // filter_stats_kernel's four words
-constexpr size_t kScrNulls = 16;                       // kFilterCols counts of valid output rows
-constexpr size_t kScrBytes = 4096;                      // (what devcol_prepare's null count asks for: the block does not move under a call)
-static_assert(kScrNulls + 8 * kFilterCols <= kScrBytes, "scratch layout");
-
-bool residency_ok(int32_t r) { return r == BOWGPU_HOST || r == BOWGPU_DEVICE || r == BOWGPU_HOST_PINNED; }
-bool movable(int32_t t) { return t == BOWGPU_INT64 || t == BOWGPU_FLOAT64; }
-
 // everything that can be said about the frame and the predicates without reading a column; *n: rows of the frame
 int frame_checks(const bowgpu_col *cols, int32_t ncols, const bowgpu_filter_pred *preds, int32_t npreds, int64_t *n) {
     if (ncols < 0 || npreds < 0) return fail(BOWGPU_ERR_ARG, "negative column or predicate count");
@@ -28,12 +19,7 @@ int frame_checks(const bowgpu_col *cols, int32_t ncols, const bowgpu_filter_pred
     if (npreds > BOWGPU_FILTER_MAX_PREDS)
         return fail(BOWGPU_ERR_UNSUPPORTED, "%d comparators: the device filter serves at most BOWGPU_FILTER_MAX_PREDS = %d", npreds, BOWGPU_FILTER_MAX_PREDS);
     *n = ncols > 0 ? cols[0].length : 0;
-    for (int i = 0; i < ncols; i++) {
-        if (cols[i].length < 0 || cols[i].offset < 0) return fail(BOWGPU_ERR_ARG, "negative column length/offset");
-        if (cols[i].length != *n) return fail(BOWGPU_ERR_ARG, "columns differ in length");
-        if (!movable(cols[i].type)) return fail(BOWGPU_ERR_UNSUPPORTED, "column %d is of unsupported type (Int64 / Float64 only)", i);
-        if (!residency_ok(cols[i].residency)) return fail(BOWGPU_ERR_ARG, "unknown residency %d", cols[i].residency);
-    }
+    BG_TRY(frame_cols_checks(cols, ncols, *n, true));
     for (int p = 0; p < npreds; p++) {
         if (preds[p].col < 0 || preds[p].col > ncols - 1) return fail(BOWGPU_ERR_BAD_COL, "no column '%d'", preds[p].col);
         if (preds[p].n_values < 0) return fail(BOWGPU_ERR_ARG, "negative value count");
@@ -47,27 +33,11 @@ int frame_checks(const bowgpu_col *cols, int32_t ncols, const bowgpu_filter_pred
     return 0;
 }
 
-// what can be said about the outputs before the selected count is known (the capacity comparison needs the count)
-int outs_checks(const bowgpu_out *outs, int32_t ncols) {
-    for (int i = 0; i < ncols; i++) {
-        if (!residency_ok(outs[i].residency)) return fail(BOWGPU_ERR_ARG, "unknown residency %d", outs[i].residency);
-        if (outs[i].length < 0) return fail(BOWGPU_ERR_ARG, "output column %d has a negative capacity", i);
-        if (outs[i].length > 0 && (!outs[i].values || !outs[i].validity)) return fail(BOWGPU_ERR_ARG, "output column lacks a values or validity buffer");
-    }
-    return 0;
-}
-
 // the bitmap of one call, its tile counts and the predicate columns (kept staged for the scatter that follows)
 struct MaskWork {
     DevBuf mask, tiles, spans, sums, staged_mask;
-    DevCol pcol[BOWGPU_FILTER_MAX_PREDS];
-    int32_t pcol_of[BOWGPU_FILTER_MAX_PREDS];   // the frame column pcol[i] holds
-    int npcols = 0;
+    StagedCols pcols;
     int64_t selected = 0, first = -1, last = -1;
-    const DevCol *staged(int32_t col) const {
-        for (int i = 0; i < npcols; i++) if (pcol_of[i] == col) return &pcol[i];
-        return nullptr;
-    }
 };
 
 // the predicate pass (bracketed by the context's events) and its three numbers; synchronises
@@ -79,29 +49,18 @@ int mask_device(Ctx *c, const bowgpu_col *cols, const bowgpu_filter_pred *preds,
     a.n = n;
     a.npreds = npreds;
     if (and_mask) {
-        const size_t nb = (size_t)((n + 7) >> 3);
-        if (and_residency == BOWGPU_DEVICE) {
-            a.and_mask = and_mask;
-        } else if (and_residency == BOWGPU_HOST_PINNED) {
-            void *dp = nullptr;
-            if (hipHostGetDevicePointer(&dp, const_cast<uint8_t *>(and_mask), 0) != hipSuccess || !dp) {
-                (void)hipGetLastError();
-                return fail(BOWGPU_ERR_ARG, "BOWGPU_HOST_PINNED: the mask buffer is not registered (bowgpu_host_register)");
-            }
-            a.and_mask = reinterpret_cast<const uint8_t *>(dp);
-        } else {
-            BG_TRY(w->staged_mask.alloc(nb));
-            BG_TRY(copy_h2d(c, w->staged_mask.p, and_mask, nb));
-            a.and_mask = reinterpret_cast<const uint8_t *>(w->staged_mask.p);
-        }
+        const void *dp;
+        BG_TRY(aux_in(c, and_mask, (size_t)((n + 7) >> 3), and_residency, "mask", &dp, &w->staged_mask));
+        a.and_mask = reinterpret_cast<const uint8_t *>(dp);
     }
     for (int p = 0; p < npreds; p++) {
         const int32_t col = preds[p].col;
-        const DevCol *dc = w->staged(col);
+        StagedCols &pc = w->pcols;
+        const DevCol *dc = pc.find(col);
         if (!dc) {
-            BG_TRY(devcol_prepare(c, &cols[col], &w->pcol[w->npcols], true, true));
-            w->pcol_of[w->npcols] = col;
-            dc = &w->pcol[w->npcols++];
+            DevCol *fresh = pc.add(col);
+            BG_TRY(devcol_prepare(c, &cols[col], fresh, true, true));
+            dc = fresh;
         }
         FilterPredDev &P = a.preds[p];
         P.values = reinterpret_cast<const uint64_t *>(dc->values);
@@ -121,11 +80,11 @@ int mask_device(Ctx *c, const bowgpu_col *cols, const bowgpu_filter_pred *preds,
     a.mask = reinterpret_cast<unsigned long long *>(w->mask.p);
     a.tile_counts = reinterpret_cast<uint32_t *>(w->tiles.p);
     a.tile_spans = reinterpret_cast<uint32_t *>(w->spans.p);
-    a.stats = reinterpret_cast<uint32_t *>(s + kScrStats);
+    a.stats = reinterpret_cast<uint32_t *>(s + kScrFlags);
     volatile uint32_t *back;   // the context's registered block: filter_stats_kernel stores the three numbers there itself
     BG_TRY(ctx_pinned(c, 16384, reinterpret_cast<void **>(const_cast<uint32_t **>(&back))));
     a.host_stats = const_cast<uint32_t *>(back);
-    BG_HIP(hipMemsetAsync(s + kScrStats, 0, 16, c->stream));
+    BG_HIP(hipMemsetAsync(s + kScrFlags, 0, 16, c->stream));
     BG_HIP(hipEventRecord(c->ev0, c->stream));
     BG_TRY(launch_filter_mask(c, a));
     BG_HIP(hipEventRecord(c->ev1, c->stream));
@@ -136,67 +95,49 @@ int mask_device(Ctx *c, const bowgpu_col *cols, const bowgpu_filter_pred *preds,
     return 0;
 }
 
-// outs[i] = the selected rows of cols[i], for every column of the frame in groups of kFilterCols (the caller has checked the capacities)
-int scatter_device(Ctx *c, const bowgpu_col *cols, int32_t ncols, int64_t n, MaskWork *w, bowgpu_out *outs) {
-    const int64_t ntiles = (n + kFilterTileRows - 1) / kFilterTileRows, count = w->selected;
-    BG_TRY(w->sums.alloc((size_t)((ntiles + 4095) / 4096) * 4));
-    // the context's events: from the scan to the last scatter launch.  For a frame of up to kFilterCols device-resident columns that is
-    // the scan, the memsets and the scatter kernel; with more groups or host-resident columns their staging and copies fall inside
-    BG_HIP(hipEventRecord(c->ev0, c->stream));
-    BG_TRY(launch_scan_u32(c, reinterpret_cast<uint32_t *>(w->tiles.p), ntiles, reinterpret_cast<uint32_t *>(w->sums.p)));
-    for (int g0 = 0; g0 < ncols; g0 += kFilterCols) {
-        // (each group's staged inputs and output temporaries are released before the next group's are taken)
-        const int g = ncols - g0 < kFilterCols ? ncols - g0 : kFilterCols;
-        DevCol staged[kFilterCols];
-        DevOut douts[kFilterCols];
-        FilterScatterArgs a;
-        memset(&a, 0, sizeof a);
-        a.ncols = g;
-        a.n = n;
-        a.mask = reinterpret_cast<const unsigned long long *>(w->mask.p);
-        a.tile_base = reinterpret_cast<const uint32_t *>(w->tiles.p);
-        for (int i = 0; i < g; i++) {
-            const int col = g0 + i;
-            const DevCol *dc = w->staged(col);
-            if (!dc) {
-                BG_TRY(devcol_prepare(c, &cols[col], &staged[i], true, true));
-                dc = &staged[i];
-            }
-            BG_TRY(devout_prepare(c, &outs[col], count, &douts[i]));
-            a.values[i] = reinterpret_cast<const uint64_t *>(dc->values);
-            a.vbits[i] = dc->vbits;
-            a.vbit0[i] = dc->vbit0;
-            a.out_values[i] = reinterpret_cast<uint64_t *>(douts[i].values);
-            // (the working copy of devout_prepare, ((ceil(count/8)+3)&~3)+4 bytes, always holds ceil(count/64) whole words)
-            a.out_valid[i] = reinterpret_cast<unsigned long long *>(douts[i].validity);
-            BG_HIP(hipMemsetAsync(douts[i].validity, 0, (size_t)((count + 63) >> 6) * 8, c->stream));
-        }
-        void *scr;   // (taken after the columns are staged: counting a column's nulls may have replaced the block)
-        BG_TRY(ctx_scratch(c, kScrBytes, &scr));
-        char *s = reinterpret_cast<char *>(scr);
-        BG_TRY(launch_filter_scatter(c, a));
-        BG_HIP(hipEventRecord(c->ev1, c->stream));
-        // null_count = rows - set bits of the finished bitmap (an input column without nulls has none to count)
-        unsigned long long valid[kFilterCols] = {};
-        for (int i = 0; i < g; i++)
-            if (a.vbits[i]) BG_TRY(launch_popcount(c, reinterpret_cast<const uint32_t *>(douts[i].validity), 0, count, reinterpret_cast<uint64_t *>(s + kScrNulls) + i));
-        bool counted = false;
-        for (int i = 0; i < g; i++) counted |= a.vbits[i] != nullptr;
-        if (counted) BG_HIP(hipMemcpyAsync(valid, s + kScrNulls, sizeof valid, hipMemcpyDeviceToHost, c->stream));
-        // the copies of the finished columns are queued behind it: one synchronise for the group, the null counts filled in after it
-        for (int i = 0; i < g; i++) BG_TRY(devout_finish(c, &douts[i], count, cols[g0 + i].type, 0));
-        BG_HIP(hipStreamSynchronize(c->stream));
-        for (int i = 0; i < g; i++)
-            if (a.vbits[i]) outs[g0 + i].null_count = count - (int64_t)valid[i];
+// one scatter launch over a prepared group, and the counts of valid rows of its nullable columns on their way to valid[] (no synchronise)
+int scatter_launch(Ctx *c, const MoveGroup &g, int64_t n, const MaskWork &w, unsigned long long *valid) {
+    const int64_t count = w.selected;
+    FilterScatterArgs a;
+    a.cols = g.cols;
+    a.n = n;
+    a.mask = reinterpret_cast<const unsigned long long *>(w.mask.p);
+    a.tile_base = reinterpret_cast<const uint32_t *>(w.tiles.p);
+    for (int i = 0; i < g.cols.ncols; i++) BG_HIP(hipMemsetAsync(g.cols.out_valid[i], 0, (size_t)((count + 63) >> 6) * 8, c->stream));
+    BG_TRY(launch_filter_scatter(c, a));
+    BG_HIP(hipEventRecord(c->ev1, c->stream));
+    // null_count = rows - set bits of the finished bitmap (an input column without nulls has none to count)
+    uint64_t *d_valid = reinterpret_cast<uint64_t *>(g.scratch + kScrNulls);
+    bool counted = false;
+    for (int i = 0; i < g.cols.ncols; i++) {
+        if (!g.cols.vbits[i]) continue;
+        BG_TRY(launch_popcount(c, reinterpret_cast<const uint32_t *>(g.cols.out_valid[i]), 0, count, d_valid + i));
+        counted = true;
     }
+    if (counted) BG_HIP(hipMemcpyAsync(valid, d_valid, 8 * kMoveCols, hipMemcpyDeviceToHost, c->stream));
     return 0;
 }
 
-void kernel_done(Ctx *c, const char *name) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) != hipSuccess) (void)hipGetLastError();
-    c->last_kernel_ms = ms;
-    c->last_kernel_name = name;
+// outs[i] = the selected rows of cols[i], for every column of the frame (the caller has checked the capacities)
+int scatter_device(Ctx *c, const bowgpu_col *cols, int32_t ncols, int64_t n, MaskWork *w, bowgpu_out *outs) {
+    const int64_t ntiles = (n + kFilterTileRows - 1) / kFilterTileRows, count = w->selected;
+    BG_TRY(w->sums.alloc((size_t)((ntiles + 4095) / 4096) * 4));
+    // the context's events: from the scan to the last scatter launch.  For a frame of up to kMoveCols device-resident columns that is
+    // the scan, the memsets and the scatter kernel; with more groups or host-resident columns their staging and copies fall inside
+    BG_HIP(hipEventRecord(c->ev0, c->stream));
+    BG_TRY(launch_scan_u32(c, reinterpret_cast<uint32_t *>(w->tiles.p), ntiles, reinterpret_cast<uint32_t *>(w->sums.p)));
+    for (int g0 = 0; g0 < ncols; g0 += kMoveCols) {
+        MoveGroup g;
+        BG_TRY(move_group_prepare(c, cols, ncols, g0, w->pcols, outs, count, &g));
+        unsigned long long valid[kMoveCols] = {};
+        BG_TRY(synced(c, scatter_launch(c, g, n, *w, valid)));
+        // the copies of the finished columns are queued behind the counts: one synchronise for the group, the null counts filled in after it
+        const int64_t none[kMoveCols] = {};
+        BG_TRY(move_group_finish(c, &g, cols, g0, count, none));
+        for (int i = 0; i < g.cols.ncols; i++)
+            if (g.cols.vbits[i]) outs[g0 + i].null_count = count - (int64_t)valid[i];
+    }
+    return 0;
 }
 
 // bowgpu_filter and bowgpu_compact after their argument checks
@@ -205,10 +146,7 @@ int filter_run(const bowgpu_col *cols, int32_t ncols, const bowgpu_filter_pred *
     Ctx *c;
     BG_TRY(ctx_get(&c));
     MaskWork w;
-    {
-        const int rc = mask_device(c, cols, preds, npreds, and_mask, and_residency, n, &w);
-        if (rc != 0) { (void)hipStreamSynchronize(c->stream); return rc; }
-    }
+    BG_TRY(synced(c, mask_device(c, cols, preds, npreds, and_mask, and_residency, n, &w)));
     *count = w.selected;
     *first = w.selected ? w.first : 0;
     *contiguous = w.selected == 0 || w.selected == w.last - w.first + 1;
@@ -222,8 +160,7 @@ int filter_run(const bowgpu_col *cols, int32_t ncols, const bowgpu_filter_pred *
             return fail(BOWGPU_ERR_ARG, "output column %d has %lld slots, %lld needed", i, (long long)outs[i].length, (long long)w.selected);
         device_out |= outs[i].residency == BOWGPU_DEVICE;
     }
-    const int rc = scatter_device(c, cols, ncols, n, &w, outs);
-    if (rc != 0) { (void)hipStreamSynchronize(c->stream); return rc; }
+    BG_TRY(synced(c, scatter_device(c, cols, ncols, n, &w, outs)));
     BG_HIP(hipStreamSynchronize(c->stream));
     if (device_out) device_write_epoch_bump();
     kernel_done(c, "filter_scatter_kernel");
@@ -257,17 +194,9 @@ int bowgpu_filter_mask(const bowgpu_col *cols, int32_t ncols, const bowgpu_filte
     Ctx *c;
     BG_TRY(ctx_get(&c));
     MaskWork w;
-    {
-        const int rc = mask_device(c, cols, preds, npreds, and_mask, and_mask_residency, n, &w);
-        if (rc != 0) { (void)hipStreamSynchronize(c->stream); return rc; }
-    }
+    BG_TRY(synced(c, mask_device(c, cols, preds, npreds, and_mask, and_mask_residency, n, &w)));
     kernel_done(c, "filter_mask_kernel");
-    if (mask_residency == BOWGPU_DEVICE) {
-        BG_HIP(hipMemcpyAsync(mask_out, w.mask.p, nb, hipMemcpyDeviceToDevice, c->stream));
-        device_write_epoch_bump();
-    } else {
-        BG_TRY(copy_d2h(c, mask_out, w.mask.p, nb, mask_residency == BOWGPU_HOST_PINNED));
-    }
+    BG_TRY(aux_out(c, mask_out, w.mask.p, nb, mask_residency));
     BG_HIP(hipStreamSynchronize(c->stream));
     *selected = w.selected;
     *first = w.first;
@@ -281,7 +210,7 @@ int bowgpu_compact(const bowgpu_col *cols, int32_t ncols, const uint8_t *mask, i
     int64_t n = 0;
     BG_TRY(frame_checks(cols, ncols, nullptr, 0, &n));
     if (!residency_ok(mask_residency)) return fail(BOWGPU_ERR_ARG, "unknown residency %d", mask_residency);
-    BG_TRY(outs_checks(outs, ncols));
+    BG_TRY(outs_checks(outs, ncols, -1));
     *first = 0;
     *count = 0;
     *contiguous = 1;
@@ -296,7 +225,7 @@ int bowgpu_filter(const bowgpu_col *cols, int32_t ncols, const bowgpu_filter_pre
     int64_t n = 0;
     BG_TRY(frame_checks(cols, ncols, preds, npreds, &n));
     if (and_mask && !residency_ok(and_mask_residency)) return fail(BOWGPU_ERR_ARG, "unknown residency %d", and_mask_residency);
-    BG_TRY(outs_checks(outs, ncols));
+    BG_TRY(outs_checks(outs, ncols, -1));
     *first = 0;
     *count = n;
     *contiguous = 1;

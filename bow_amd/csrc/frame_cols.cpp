@@ -1,0 +1,120 @@
+// frame_cols.cpp — the host layer under the frame-level operations (sort_api.cpp, filter_api.cpp): argument checks of a frame and its
+// output columns, a caller's side buffers in and out, and the staging of the columns of a frame, kMoveCols a launch, around the kernel
+// that moves their rows.  No kernel is launched here.
+#include "common.h"
+
+namespace bowgpu {
+
+bool movable_type(int32_t t) { return t == BOWGPU_INT64 || t == BOWGPU_FLOAT64; }
+bool residency_ok(int32_t r) { return r == BOWGPU_HOST || r == BOWGPU_DEVICE || r == BOWGPU_HOST_PINNED; }
+
+int64_t host_count_nulls(const bowgpu_col *col) {
+    if (!col->validity || col->null_count == 0 || col->length <= 0) return 0;
+    if (col->null_count > 0) return col->null_count;
+    if (col->residency == BOWGPU_DEVICE) return -1;
+    int64_t set = 0;
+    for (int64_t i = 0; i < col->length; i++) {
+        const int64_t bit = col->offset + i;
+        set += (col->validity[bit >> 3] >> (bit & 7)) & 1;
+    }
+    return col->length - set;
+}
+
+int frame_cols_checks(const bowgpu_col *cols, int32_t ncols, int64_t n, bool residencies) {
+    for (int i = 0; i < ncols; i++) {
+        if (residencies && (cols[i].length < 0 || cols[i].offset < 0)) return fail(BOWGPU_ERR_ARG, "negative column length/offset");
+        if (cols[i].length != n) return fail(BOWGPU_ERR_ARG, "columns differ in length");
+        if (cols[i].offset < 0) return fail(BOWGPU_ERR_ARG, "negative column length/offset");
+        if (!movable_type(cols[i].type)) return fail(BOWGPU_ERR_UNSUPPORTED, "column %d is of unsupported type (Int64 / Float64 only)", i);
+        if (residencies && !residency_ok(cols[i].residency)) return fail(BOWGPU_ERR_ARG, "unknown residency %d", cols[i].residency);
+    }
+    return 0;
+}
+
+int outs_checks(const bowgpu_out *outs, int32_t ncols, int64_t slots) {
+    for (int i = 0; i < ncols; i++) {
+        const bowgpu_out &o = outs[i];
+        if (slots < 0) {
+            if (!residency_ok(o.residency)) return fail(BOWGPU_ERR_ARG, "unknown residency %d", o.residency);
+            if (o.length < 0) return fail(BOWGPU_ERR_ARG, "output column %d has a negative capacity", i);
+        } else if (o.length < slots) {
+            return fail(BOWGPU_ERR_ARG, "output column has %lld slots, %lld needed", (long long)o.length, (long long)slots);
+        }
+        if ((slots < 0 ? o.length : slots) > 0 && (!o.values || !o.validity)) return fail(BOWGPU_ERR_ARG, "output column lacks a values or validity buffer");
+    }
+    return 0;
+}
+
+int aux_in(Ctx *c, const void *p, size_t bytes, int32_t residency, const char *what, const void **dptr, DevBuf *own) {
+    *dptr = p;
+    if (residency == BOWGPU_HOST_PINNED) {
+        void *dp = nullptr;
+        if (hipHostGetDevicePointer(&dp, const_cast<void *>(p), 0) != hipSuccess || !dp) {
+            (void)hipGetLastError();
+            return fail(BOWGPU_ERR_ARG, "BOWGPU_HOST_PINNED: the %s buffer is not registered (bowgpu_host_register)", what);
+        }
+        *dptr = dp;
+    } else if (residency == BOWGPU_HOST) {
+        BG_TRY(own->alloc(bytes));
+        BG_TRY(copy_h2d(c, own->p, p, bytes));
+        *dptr = own->p;
+    }
+    return 0;
+}
+
+int aux_out(Ctx *c, void *dst, const void *src, size_t bytes, int32_t residency) {
+    if (residency != BOWGPU_DEVICE) return copy_d2h(c, dst, src, bytes, residency == BOWGPU_HOST_PINNED);
+    if (dst != src) BG_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
+    device_write_epoch_bump();
+    return 0;
+}
+
+void kernel_done(Ctx *c, const char *name) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) != hipSuccess) (void)hipGetLastError();
+    c->last_kernel_ms = ms;
+    c->last_kernel_name = name;
+}
+
+int synced(Ctx *c, int rc) {
+    if (rc != 0) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+int move_group_prepare(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t g0, const StagedCols &have, bowgpu_out *outs, int64_t count, MoveGroup *g) {
+    MoveCols &m = g->cols;
+    m = MoveCols();
+    m.ncols = ncols - g0 < kMoveCols ? ncols - g0 : kMoveCols;
+    for (int i = 0; i < m.ncols; i++) {
+        const DevCol *dc = have.find(g0 + i);
+        if (!dc) {
+            const int rc = devcol_prepare(c, &cols[g0 + i], &g->staged[i], true, true);
+            if (rc != 0) return synced(c, rc);
+            dc = &g->staged[i];
+        }
+        m.values[i] = reinterpret_cast<const uint64_t *>(dc->values);
+        m.vbits[i] = dc->vbits;
+        m.vbit0[i] = dc->vbit0;
+    }
+    for (int i = 0; i < m.ncols; i++) {
+        const int rc = devout_prepare(c, &outs[g0 + i], count, &g->douts[i]);
+        if (rc != 0) return synced(c, rc);
+        m.out_values[i] = reinterpret_cast<uint64_t *>(g->douts[i].values);
+        m.out_valid[i] = reinterpret_cast<unsigned long long *>(g->douts[i].validity);
+    }
+    void *scr = nullptr;
+    const int rc = ctx_scratch(c, kScrBytes, &scr);
+    g->scratch = reinterpret_cast<char *>(scr);
+    return synced(c, rc);
+}
+
+int move_group_finish(Ctx *c, MoveGroup *g, const bowgpu_col *cols, int32_t g0, int64_t count, const int64_t *null_counts) {
+    for (int i = 0; i < g->cols.ncols; i++) {
+        const int rc = devout_finish(c, &g->douts[i], count, cols[g0 + i].type, null_counts[i]);
+        if (rc != 0) return synced(c, rc);
+    }
+    BG_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+}  // namespace bowgpu

@@ -626,17 +626,6 @@ void sharded_layout_rank(Worker *w, ShardedCall *sc, int r) {
     if (rc < 0) sc->fail_rank(rc);
 }
 
-int host_ts_nulls(const bowgpu_col &t, int64_t *nulls) {
-    *nulls = 0;
-    if (!t.validity || t.null_count == 0) return 0;
-    if (t.null_count > 0) { *nulls = t.null_count; return 0; }
-    for (int64_t i = 0; i < t.length; i++) {
-        const int64_t b = t.offset + i;
-        *nulls += !((t.validity[b >> 3] >> (b & 7)) & 1);
-    }
-    return 0;
-}
-
 int device_of(const void *p, int *dev) {
     hipPointerAttribute_t a;
     memset(&a, 0, sizeof a);
@@ -963,8 +952,7 @@ int bowgpu_rolling_aggregate_sharded(const bowgpu_col *const *cols_by_rank, cons
             rec.flags = 1;   // (decided with s0 known: what the full call's records say once the protocol has settled)
             if (t.length <= 0) continue;
             if (t.residency == BOWGPU_DEVICE) { any_device = true; continue; }
-            int64_t nulls = 0;
-            BG_TRY(host_ts_nulls(t, &nulls));
+            const int64_t nulls = host_count_nulls(&t);
             if (nulls > 0)
                 return fail(BOWGPU_ERR_TS_NULLS, "rank %d: interval column has %lld nulls: the sharded call does not serve them", r, (long long)nulls);
             const int64_t *v = reinterpret_cast<const int64_t *>(t.values) + t.offset;

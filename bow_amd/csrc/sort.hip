@@ -5,7 +5,7 @@
 //   per radix pass         sort_tile_hist_kernel (digit counts per 4096-row tile, digit-major) -> exclusive scan over (digit, tile)
 //                          -> sort_scatter_kernel (stable: ranks by ballot matching inside a wave, waves combined in wave order in LDS,
 //                          the tile staged in LDS in digit order so that global stores leave in runs per digit)
-//   gather_kernel          out[j] = in[idx[j]] for up to kGatherCols columns; a wave owns its 64-bit validity word
+//   gather_kernel          out[j] = in[idx[j]] for up to kMoveCols columns; a wave owns its 64-bit validity word
 //
 // Every count is an integer added in an order-free way (LDS / global atomics) or scanned in a fixed order; the position of a row
 // after a pass is a function of the keys alone, never of scheduling.
@@ -269,7 +269,7 @@ __global__ __launch_bounds__(kThreads) void gather_kernel(GatherArgs a, const Id
     const int lane = threadIdx.x & 63;
     const int64_t stride = (int64_t)gridDim.x * kThreads;
     const int64_t rounds = (a.n_idx + stride - 1) / stride;
-    uint32_t nulls[kGatherCols] = {};
+    uint32_t nulls[kMoveCols] = {};
     bool bad = false;
     int64_t j = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     for (int64_t r = 0; r < rounds; r++, j += stride) {
@@ -280,20 +280,20 @@ __global__ __launch_bounds__(kThreads) void gather_kernel(GatherArgs a, const Id
             if (p < 0 || p >= a.length) { bad = true; p = -1; }   // (the library's own permutation never trips this: it guards the reads all the same)
         }
 #pragma unroll
-        for (int c = 0; c < kGatherCols; c++) {
-            if (c < a.ncols) {
+        for (int c = 0; c < kMoveCols; c++) {
+            if (c < a.cols.ncols) {
                 bool valid = in && p >= 0;
                 uint64_t v = 0;
-                if (valid && a.vbits[c]) {
-                    const int64_t bit = a.vbit0[c] + p;
-                    valid = (a.vbits[c][bit >> 5] >> (bit & 31)) & 1u;
+                if (valid && a.cols.vbits[c]) {
+                    const int64_t bit = a.cols.vbit0[c] + p;
+                    valid = (a.cols.vbits[c][bit >> 5] >> (bit & 31)) & 1u;
                 }
-                if (valid) v = a.values[c][p];
-                if (in) a.out_values[c][j] = v;
+                if (valid) v = a.cols.values[c][p];
+                if (in) a.cols.out_values[c][j] = v;
                 const unsigned long long word = __ballot(valid);
                 const unsigned long long rows = __ballot(in);
                 if (lane == 0 && rows) {
-                    a.out_valid[c][j >> 6] = word;
+                    a.cols.out_valid[c][j >> 6] = word;
                     nulls[c] += (uint32_t)__popcll(rows & ~word);
                 }
             }
@@ -301,8 +301,8 @@ __global__ __launch_bounds__(kThreads) void gather_kernel(GatherArgs a, const Id
     }
     if (lane == 0) {
 #pragma unroll
-        for (int c = 0; c < kGatherCols; c++)
-            if (c < a.ncols && nulls[c]) atomicAdd(&a.null_counts[c], (unsigned long long)nulls[c]);
+        for (int c = 0; c < kMoveCols; c++)
+            if (c < a.cols.ncols && nulls[c]) atomicAdd(&a.null_counts[c], (unsigned long long)nulls[c]);
     }
     if (__any(bad) && lane == 0) atomicOr(a.bad, 1u);
 }

@@ -12,43 +12,16 @@ namespace {
 
 constexpr int64_t kSortMaxRows = (int64_t)1 << 31;   // row indices inside the sort are 32 bits wide
 
-// the context's small scratch block as this file lays it out
-constexpr size_t kScrHist = 0;                        // [8][256] digit counts
-constexpr size_t kScrFlags = 8 * 256 * 4;             // [0] not ascending, [1] NaN seen, [2] bad index (take)
-constexpr size_t kScrNulls = kScrFlags + 16;          // kGatherCols null counts
-constexpr size_t kScrBytes = kScrNulls + 8 * kGatherCols;
-
 thread_local char g_kernel_name[64];
 
-bool sortable(int32_t t) { return t == BOWGPU_INT64 || t == BOWGPU_FLOAT64; }
-
-// nulls of a key column where that is known without the device (host-resident bitmaps are counted here); -1: ask the device
-int64_t host_null_count(const bowgpu_col *k) {
-    if (!k->validity || k->null_count == 0 || k->length == 0) return 0;
-    if (k->null_count > 0) return k->null_count;
-    if (k->residency == BOWGPU_DEVICE) return -1;
-    int64_t set = 0;
-    for (int64_t i = 0; i < k->length; i++) {
-        const int64_t bit = k->offset + i;
-        set += (k->validity[bit >> 3] >> (bit & 7)) & 1;
-    }
-    return k->length - set;
-}
-
 int key_checks(const bowgpu_col *key) {
-    if (!sortable(key->type)) return fail(BOWGPU_ERR_TYPE, "column to sort by is of unsupported type (Int64 / Float64 only)");
+    if (!movable_type(key->type)) return fail(BOWGPU_ERR_TYPE, "column to sort by is of unsupported type (Int64 / Float64 only)");
     if (key->length < 0 || key->offset < 0) return fail(BOWGPU_ERR_ARG, "negative column length/offset");
-    const int64_t nulls = host_null_count(key);
+    const int64_t nulls = host_count_nulls(key);
     if (nulls > 0) return fail(BOWGPU_ERR_SORT_NULLS, "column to sort by has %d nil values", (int)nulls);
     if (key->length >= kSortMaxRows)
         return fail(BOWGPU_ERR_UNSUPPORTED, "column to sort by has %lld rows: the device sort serves fewer than 2^31 = 2147483648 rows",
                     (long long)key->length);
-    return 0;
-}
-
-int out_checks(const bowgpu_out *out, int64_t slots) {
-    if (out->length < slots) return fail(BOWGPU_ERR_ARG, "output column has %lld slots, %lld needed", (long long)out->length, (long long)slots);
-    if (slots > 0 && (!out->values || !out->validity)) return fail(BOWGPU_ERR_ARG, "output column lacks a values or validity buffer");
     return 0;
 }
 
@@ -117,51 +90,44 @@ int argsort_device(Ctx *c, const bowgpu_col *key, const DevCol &dk, SortWork *w,
 // (a key whose nulls were counted on the host - none - goes without its bitmap: nothing is staged or counted a second time)
 int key_prepare(Ctx *c, const bowgpu_col *key, DevCol *dk) {
     bowgpu_col k = *key;
-    if (host_null_count(key) == 0) { k.validity = nullptr; k.null_count = 0; }
+    if (host_count_nulls(key) == 0) { k.validity = nullptr; k.null_count = 0; }
     return devcol_prepare(c, &k, dk, true, true);
 }
 
-void kernel_done(Ctx *c, int passes) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) != hipSuccess) (void)hipGetLastError();
-    c->last_kernel_ms = ms;
+// what last_kernel_ms of an argsort / a frame sort is reported under
+const char *passes_name(int passes) {
     snprintf(g_kernel_name, sizeof g_kernel_name, "sort_scatter_kernel<%d of 8 passes>", passes);
-    c->last_kernel_name = g_kernel_name;
+    return g_kernel_name;
 }
 
-// one gather launch: out[j] = col[idx[j]] for up to kGatherCols columns, then the outputs' null counts and copy-back
-int gather_group(Ctx *c, const DevCol *const *cols, const int32_t *types, int32_t ncols, int64_t length, const uint32_t *idx32, const int64_t *idx64,
-                 int64_t n_idx, bowgpu_out *const *outs, bool *bad) {
-    void *scr;
-    BG_TRY(ctx_scratch(c, kScrBytes, &scr));
-    char *s = reinterpret_cast<char *>(scr);
-    DevOut douts[kGatherCols];
+// one gather launch over a prepared group: out[j] = col[idx[j]], then the outputs' null counts and *bad (synchronises)
+int gather_launch(Ctx *c, const MoveGroup &g, int64_t length, const uint32_t *idx32, const int64_t *idx64, int64_t n_idx, int64_t *nulls, bool *bad) {
+    char *s = g.scratch;
     GatherArgs a;
-    memset(&a, 0, sizeof a);
-    a.ncols = ncols;
+    a.cols = g.cols;
     a.n_idx = n_idx;
     a.length = length;
     a.null_counts = reinterpret_cast<unsigned long long *>(s + kScrNulls);
     a.bad = reinterpret_cast<uint32_t *>(s + kScrFlags) + 2;
-    for (int i = 0; i < ncols; i++) {
-        BG_TRY(devout_prepare(c, outs[i], n_idx, &douts[i]));
-        a.values[i] = reinterpret_cast<const uint64_t *>(cols[i]->values);
-        a.vbits[i] = cols[i]->vbits;
-        a.vbit0[i] = cols[i]->vbit0;
-        a.out_values[i] = reinterpret_cast<uint64_t *>(douts[i].values);
-        // (the working copy of devout_prepare, ((ceil(n/8)+3)&~3)+4 bytes, always holds the ceil(n/64) whole words the waves store)
-        a.out_valid[i] = reinterpret_cast<unsigned long long *>(douts[i].validity);
-    }
-    BG_HIP(hipMemsetAsync(s + kScrFlags, 0, 16 + 8 * kGatherCols, c->stream));
+    BG_HIP(hipMemsetAsync(s + kScrFlags, 0, 16 + 8 * kMoveCols, c->stream));
     BG_TRY(launch_gather(c, a, idx32, idx64));
-    struct { uint32_t flags[4]; unsigned long long nulls[kGatherCols]; } back;
+    struct { uint32_t flags[4]; unsigned long long nulls[kMoveCols]; } back;
     BG_HIP(hipMemcpyAsync(&back, s + kScrFlags, sizeof back, hipMemcpyDeviceToHost, c->stream));
     BG_HIP(hipStreamSynchronize(c->stream));
     *bad = back.flags[2] != 0;
-    if (*bad) return 0;
-    for (int i = 0; i < ncols; i++) BG_TRY(devout_finish(c, &douts[i], n_idx, types[i], (int64_t)back.nulls[i]));
-    BG_HIP(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < kMoveCols; i++) nulls[i] = (int64_t)back.nulls[i];
     return 0;
+}
+
+// the columns of the frame from g0 on, up to kMoveCols, gathered into their outputs.  *bad: an index outside the frame - nothing was handed out
+int gather_group(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t g0, const StagedCols &have, const uint32_t *idx32, const int64_t *idx64,
+                 int64_t n_idx, bowgpu_out *outs, bool *bad) {
+    MoveGroup g;
+    BG_TRY(move_group_prepare(c, cols, ncols, g0, have, outs, n_idx, &g));
+    int64_t nulls[kMoveCols];
+    BG_TRY(synced(c, gather_launch(c, g, cols[g0].length, idx32, idx64, n_idx, nulls, bad)));
+    if (*bad) return 0;
+    return move_group_finish(c, &g, cols, g0, n_idx, nulls);
 }
 
 }  // namespace
@@ -170,8 +136,7 @@ extern "C" {
 
 int bowgpu_argsort(const bowgpu_col *key, int64_t *perm, int32_t perm_residency, int32_t *sorted) {
     if (!key || !sorted) return fail(BOWGPU_ERR_ARG, "null argument");
-    if (perm_residency != BOWGPU_HOST && perm_residency != BOWGPU_DEVICE && perm_residency != BOWGPU_HOST_PINNED)
-        return fail(BOWGPU_ERR_ARG, "unknown residency %d", perm_residency);
+    if (!residency_ok(perm_residency)) return fail(BOWGPU_ERR_ARG, "unknown residency %d", perm_residency);
     BG_TRY(key_checks(key));
     const int64_t n = key->length;
     *sorted = 1;
@@ -185,7 +150,7 @@ int bowgpu_argsort(const bowgpu_col *key, int64_t *perm, int32_t perm_residency,
     SortWork w;
     DevBuf wide;
     BG_HIP(hipEventRecord(c->ev0, c->stream));
-    BG_TRY(argsort_device(c, key, dk, &w, sorted));
+    BG_TRY(synced(c, argsort_device(c, key, dk, &w, sorted)));
     if (!*sorted) {
         int64_t *d_perm = perm;
         if (perm_residency != BOWGPU_DEVICE) {
@@ -194,24 +159,22 @@ int bowgpu_argsort(const bowgpu_col *key, int64_t *perm, int32_t perm_residency,
         }
         BG_TRY(launch_sort_widen(c, w.perm(), n, d_perm));
         BG_HIP(hipEventRecord(c->ev1, c->stream));
-        if (perm_residency != BOWGPU_DEVICE) BG_TRY(copy_d2h(c, perm, d_perm, (size_t)n * 8, perm_residency == BOWGPU_HOST_PINNED));
-        else device_write_epoch_bump();
+        BG_TRY(aux_out(c, perm, d_perm, (size_t)n * 8, perm_residency));
     } else {
         BG_HIP(hipEventRecord(c->ev1, c->stream));
     }
     BG_HIP(hipStreamSynchronize(c->stream));
-    kernel_done(c, w.passes);
+    kernel_done(c, passes_name(w.passes));
     return 0;
 }
 
 int bowgpu_take(const bowgpu_col *col, const int64_t *idx, int64_t n_idx, int32_t idx_residency, bowgpu_out *out) {
     if (!col || !out || (!idx && n_idx > 0)) return fail(BOWGPU_ERR_ARG, "null argument");
     if (n_idx < 0) return fail(BOWGPU_ERR_ARG, "negative index count");
-    if (idx_residency != BOWGPU_HOST && idx_residency != BOWGPU_DEVICE && idx_residency != BOWGPU_HOST_PINNED)
-        return fail(BOWGPU_ERR_ARG, "unknown residency %d", idx_residency);
-    if (!sortable(col->type)) return fail(BOWGPU_ERR_UNSUPPORTED, "column is of unsupported type (Int64 / Float64 only)");
+    if (!residency_ok(idx_residency)) return fail(BOWGPU_ERR_ARG, "unknown residency %d", idx_residency);
+    if (!movable_type(col->type)) return fail(BOWGPU_ERR_UNSUPPORTED, "column is of unsupported type (Int64 / Float64 only)");
     if (col->length < 0 || col->offset < 0) return fail(BOWGPU_ERR_ARG, "negative column length/offset");
-    BG_TRY(out_checks(out, n_idx));
+    BG_TRY(outs_checks(out, 1, n_idx));
     if (n_idx == 0) {
         out->length = 0;
         out->null_count = 0;
@@ -221,35 +184,20 @@ int bowgpu_take(const bowgpu_col *col, const int64_t *idx, int64_t n_idx, int32_
     if (col->length == 0) return fail(BOWGPU_ERR_ARG, "index out of range: the column has no rows");
     Ctx *c;
     BG_TRY(ctx_get(&c));
-    DevCol dc;
-    BG_TRY(devcol_prepare(c, col, &dc, true, true));
-    const int64_t *d_idx = idx;
+    StagedCols have;   // a frame of one column, staged here
+    BG_TRY(devcol_prepare(c, col, have.add(0), true, true));
+    const void *d_idx;
     DevBuf staged;
-    if (idx_residency == BOWGPU_HOST_PINNED) {
-        void *dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, const_cast<int64_t *>(idx), 0) != hipSuccess || !dp) {
-            (void)hipGetLastError();
-            return fail(BOWGPU_ERR_ARG, "BOWGPU_HOST_PINNED: the index buffer is not registered (bowgpu_host_register)");
-        }
-        d_idx = reinterpret_cast<const int64_t *>(dp);
-    } else if (idx_residency == BOWGPU_HOST) {
-        BG_TRY(staged.alloc((size_t)n_idx * 8));
-        BG_TRY(copy_h2d(c, staged.p, idx, (size_t)n_idx * 8));
-        d_idx = reinterpret_cast<const int64_t *>(staged.p);
-    }
+    BG_TRY(aux_in(c, idx, (size_t)n_idx * 8, idx_residency, "index", &d_idx, &staged));
     if (reinterpret_cast<uintptr_t>(d_idx) & 7) return fail(BOWGPU_ERR_ARG, "index buffer must be 8-byte aligned");
-    const DevCol *cols[1] = {&dc};
-    bowgpu_out *outs[1] = {out};
     bool bad = false;
     BG_HIP(hipEventRecord(c->ev0, c->stream));
-    const int rc = gather_group(c, cols, &col->type, 1, col->length, nullptr, d_idx, n_idx, outs, &bad);
-    if (rc != 0) { (void)hipStreamSynchronize(c->stream); return rc; }
+    BG_TRY(gather_group(c, col, 1, 0, have, nullptr, reinterpret_cast<const int64_t *>(d_idx), n_idx, out, &bad));
     if (bad) return fail(BOWGPU_ERR_ARG, "index out of range [0, %lld)", (long long)col->length);
     if (out->residency == BOWGPU_DEVICE) device_write_epoch_bump();
     BG_HIP(hipEventRecord(c->ev1, c->stream));
     BG_HIP(hipStreamSynchronize(c->stream));
-    kernel_done(c, 0);
-    c->last_kernel_name = "gather_kernel";
+    kernel_done(c, "gather_kernel");
     return 0;
 }
 
@@ -258,65 +206,41 @@ int bowgpu_sort_by_col(const bowgpu_col *cols, int32_t ncols, int32_t key_col, b
     if (!cols || !outs || !unchanged) return fail(BOWGPU_ERR_ARG, "null argument");
     if (key_col < 0 || key_col > ncols - 1) return fail(BOWGPU_ERR_BAD_COL, "no column '%d'", key_col);
     const bowgpu_col *key = &cols[key_col];
-    if (!sortable(key->type)) return fail(BOWGPU_ERR_TYPE, "column to sort by is of unsupported type (Int64 / Float64 only)");
+    if (!movable_type(key->type)) return fail(BOWGPU_ERR_TYPE, "column to sort by is of unsupported type (Int64 / Float64 only)");
     const int64_t n = key->length;
-    for (int i = 0; i < ncols; i++) {
-        if (cols[i].length != n) return fail(BOWGPU_ERR_ARG, "columns differ in length");
-        if (cols[i].offset < 0) return fail(BOWGPU_ERR_ARG, "negative column length/offset");
-        if (!sortable(cols[i].type)) return fail(BOWGPU_ERR_UNSUPPORTED, "column %d is of unsupported type (Int64 / Float64 only)", i);
-    }
+    BG_TRY(frame_cols_checks(cols, ncols, n, false));
     BG_TRY(key_checks(key));
-    for (int i = 0; i < ncols; i++) BG_TRY(out_checks(&outs[i], n));
+    BG_TRY(outs_checks(outs, ncols, n));
     *unchanged = 1;
     if (n < 2) return 0;   // sort.IsSorted of 0 or 1 rows: the reference returns the receiver
     Ctx *c;
     BG_TRY(ctx_get(&c));
-    DevCol dk;
+    StagedCols have;   // the key: sorted here, moved with its group
+    DevCol &dk = *have.add(key_col);
     BG_TRY(key_prepare(c, key, &dk));
     if (dk.null_count > 0) return fail(BOWGPU_ERR_SORT_NULLS, "column to sort by has %d nil values", (int)dk.null_count);
     SortWork w;
     int32_t sorted = 0;
     BG_HIP(hipEventRecord(c->ev0, c->stream));
-    {
-        const int rc = argsort_device(c, key, dk, &w, &sorted);
-        if (rc != 0) { (void)hipStreamSynchronize(c->stream); return rc; }
-    }
+    BG_TRY(synced(c, argsort_device(c, key, dk, &w, &sorted)));
     if (sorted) {
         BG_HIP(hipEventRecord(c->ev1, c->stream));
         BG_HIP(hipStreamSynchronize(c->stream));
-        kernel_done(c, 0);
+        kernel_done(c, passes_name(0));
         return 0;
     }
     *unchanged = 0;
-    // the value columns in groups: each group's staged inputs and output temporaries are released before the next group's are taken
     bool device_out = false;
-    for (int g0 = 0; g0 < ncols; g0 += kGatherCols) {
-        const int g = ncols - g0 < kGatherCols ? ncols - g0 : kGatherCols;
-        DevCol staged[kGatherCols];
-        const DevCol *gc[kGatherCols];
-        int32_t types[kGatherCols];
-        bowgpu_out *go[kGatherCols];
-        for (int i = 0; i < g; i++) {
-            const int col = g0 + i;
-            if (col == key_col) gc[i] = &dk;
-            else {
-                const int rc = devcol_prepare(c, &cols[col], &staged[i], true, true);
-                if (rc != 0) { (void)hipStreamSynchronize(c->stream); return rc; }   // (the passes may still be running on the work buffers)
-                gc[i] = &staged[i];
-            }
-            types[i] = cols[col].type;
-            go[i] = &outs[col];
-            device_out |= outs[col].residency == BOWGPU_DEVICE;
-        }
+    for (int i = 0; i < ncols; i++) device_out |= outs[i].residency == BOWGPU_DEVICE;
+    for (int g0 = 0; g0 < ncols; g0 += kMoveCols) {
         bool bad = false;
-        const int rc = gather_group(c, gc, types, g, n, w.perm(), nullptr, n, go, &bad);
-        if (rc != 0) { (void)hipStreamSynchronize(c->stream); return rc; }
+        BG_TRY(gather_group(c, cols, ncols, g0, have, w.perm(), nullptr, n, outs, &bad));
         if (bad) return fail(BOWGPU_ERR_HIP, "internal: the sort produced a row index outside the frame");
     }
     BG_HIP(hipEventRecord(c->ev1, c->stream));
     BG_HIP(hipStreamSynchronize(c->stream));
     if (device_out) device_write_epoch_bump();
-    kernel_done(c, w.passes);
+    kernel_done(c, passes_name(w.passes));
     return 0;
 }
 

@@ -20,7 +20,7 @@ POISON = 0x5A5A5A5A5A5A5A5A
 HOST, DEVICE, PINNED = capi.HOST, capi.DEVICE, capi.HOST_PINNED
 
 T = 4096                      # rows per tile (bow_amd/csrc/common.h kFilterTileRows)
-GROUP = 4                     # columns per scatter launch (kFilterCols)
+GROUP = 4                     # columns per scatter launch (kMoveCols)
 # The tile counts are scanned by sort.hip's three-launch scan: one workgroup covers kScanBlock = kThreads * kScanItems = 256 * 16 =
 # 4096 counts, i.e. 4096 tiles = 4096 * 4096 rows.  One row more makes tile 4096, the first count of the scan's second workgroup.
 SCAN_BLOCK_TILES = 256 * 16
@@ -408,6 +408,60 @@ def test_column_counts_cross_the_launch_group(ncols):
             frame.append(Col(rng.standard_normal(N), rng.random(N) < 0.9, offset=(0, 3, 8)[c % 3], null_count_known=c % 4 == 1))
     run_filter(frame, [(0, [1, 3])])
     run_filter(frame, [(ncols - 1, [0.0, 2.0], True)] if ncols % 2 == 0 else [(ncols - 1, [2], ncols > 1)])
+
+
+MOVE_ROWS = [1, 63, 64, 65, T - 1, T, T + 1]          # validity-word and tile edges
+RES3 = (DEVICE, HOST, PINNED)
+
+
+@pytest.mark.parametrize("n", MOVE_ROWS)
+@pytest.mark.parametrize("ncols,pred_cols", [(GROUP + 1, (4,)), (2 * GROUP + 1, (0, 4))], ids=["5cols-pred4", "9cols-pred0+4"])
+def test_predicate_column_in_the_second_group_mixed_columns(ncols, pred_cols, n):
+    """Launch groups of 4 + 1 and 4 + 4 + 1 columns.  Column 4 - pageable host memory with nulls, staged for the predicate pass - is
+    moved with the second group; inside every group the inputs differ in residency and in having nulls, the outputs in residency"""
+    rng = np.random.default_rng(100 * ncols + n)
+    frame = []
+    for c in range(ncols):
+        vals = rng.integers(0, 4, n) if c % 2 == 0 else rng.standard_normal(n)
+        nullable = c % 2 == 1 or c == 4
+        frame.append(Col(vals, rng.random(n) < 0.7 if nullable else None, offset=(0, 3, 8)[c % 3], null_count_known=c % 4 != 1))
+    preds = [(c, [1, 3]) for c in pred_cols]
+    keep = oracle_keep(frame, preds)
+    cols = [place(col, RES3[c % 3]) for c, col in enumerate(frame)]
+    try:
+        outs = [make_outs(1, n, (HOST, DEVICE)[(c // 2) % 2])[0] for c in range(ncols)]
+        outs, first, count, contiguous = capi.filter(cols, preds, outs=outs)
+        assert_result(frame, keep, outs, n, first, count, contiguous)
+    finally:
+        release(cols)
+    assert is_contiguous(keep) == (n == 1)
+
+
+@pytest.mark.parametrize("mask_res", [HOST, DEVICE], ids=["mask-host", "mask-device"])
+@pytest.mark.parametrize("and_res", [HOST, PINNED, DEVICE], ids=["and-host", "and-pinned", "and-device"])
+def test_filter_mask_and_mask_and_output_residencies(and_res, mask_res):
+    n = T + 1
+    frame = mixed_frame(n=n)
+    cols = [c.column() for c in frame]
+    bits = np.random.default_rng(41).random(n) < 0.6
+    preds = [(0, [1, 2, 3])]
+    keep = oracle_keep(frame, preds, bits)
+    rows = np.flatnonzero(keep)
+    am = pack(bits)
+    if and_res == DEVICE:
+        am = capi.DeviceBuffer.from_numpy(am)
+    elif and_res == PINNED:
+        am = capi.page_aligned((n + 7) // 8, np.uint8)
+        am[:] = pack(bits)
+        capi.host_register(am)
+    try:
+        mask, selected, first, last = capi.filter_mask(cols, preds, and_mask=am, out_residency=mask_res, mask_pinned=and_res == PINNED)
+    finally:
+        if and_res == PINNED:
+            capi.host_unregister(am)
+    assert (selected, first, last) == (len(rows), rows[0], rows[-1])
+    got = mask if mask_res == HOST else mask.to_numpy(np.uint8, (n + 7) // 8)
+    assert np.array_equal(got, pack(keep))
 
 
 @pytest.mark.parametrize("offset", [0, 3, 8])

@@ -238,6 +238,69 @@ def test_sort_by_col_other_key_column_float_key_and_odd_offsets():
             compare_taken("float key %s res=%d" % (name, res), o, want, lm, perm, t)   # (-0.0 / +0.0 keep their own bits and their input order)
 
 
+# ------------------------------------------------------------------ frames wider than one gather launch, mixed inside a group
+MOVE_ROWS = [1, 63, 64, 65, 4095, 4096, 4097]          # validity-word and tile edges
+RES3 = (capi.HOST, capi.HOST_PINNED, capi.DEVICE)
+
+
+@pytest.mark.parametrize("n", MOVE_ROWS)
+@pytest.mark.parametrize("ncols,key_col", [(5, 4), (9, 5)], ids=["5cols-key4", "9cols-key5"])
+def test_sort_by_col_key_in_the_second_group_mixed_columns(ncols, key_col, n):
+    """Launch groups of 4 + 1 and 4 + 4 + 1 columns.  The key, staged once for the sort, is moved with the second group; inside every
+    group the inputs differ in residency and in having nulls, the outputs in residency"""
+    rng = np.random.default_rng(100 * ncols + n)
+    frame = _frame(rng, n, ncols, 0.3)
+    frame[0], frame[key_col] = frame[key_col], frame[0]
+    frame = [(v, m if i % 2 and i != key_col else None, t) for i, (v, m, t) in enumerate(frame)]
+    key = frame[key_col][0]
+    perm = stable_perm(key)
+    is_sorted = not (image(key)[1:] < image(key)[:-1]).any()
+    cols = [place(col_of(v, m, t), RES3[i % 3]) for i, (v, m, t) in enumerate(frame)]
+    outs = [capi.OutColumn(n, (capi.HOST, capi.DEVICE)[(i // 2) % 2]) for i in range(ncols)]
+    try:
+        outs, unchanged = capi.sort_by_col(cols, key_col, outs=outs)
+        assert unchanged == is_sorted and is_sorted == (n == 1)
+        if not unchanged:
+            for i, ((v, m, t), o) in enumerate(zip(frame, outs)):
+                want_vals = v if m is None else np.where(m, v.view(np.uint64), np.uint64(0)).view(v.dtype)
+                compare_taken("ncols=%d key=%d n=%d col %d" % (ncols, key_col, n, i), o, want_vals, m, perm, t)
+    finally:
+        for c in cols:
+            if c.residency == capi.HOST_PINNED:
+                c.unpin()
+
+
+@pytest.mark.parametrize("idx_res", RES3, ids=["idx-host", "idx-pinned", "idx-device"])
+def test_take_index_list_residencies(idx_res):
+    """the index list as pageable host memory (staged), registered host memory (read in place) and device memory; capi.take
+    passes the first and the last only, so the call is made here"""
+    rng = np.random.default_rng(31)
+    n = 5000
+    v = rng.integers(-10 ** 9, 10 ** 9, n).astype(np.int64)
+    m = rng.random(n) > 0.3
+    col = col_of(v, m, capi.INT64).to_device()
+    want_vals = np.where(m, v, 0)
+    for k, n_idx in enumerate(MOVE_ROWS):
+        idx = rng.integers(0, n, n_idx).astype(np.int64)
+        held = idx
+        if idx_res == capi.DEVICE:
+            held = capi.DeviceBuffer.from_numpy(idx)
+        elif idx_res == capi.HOST_PINNED:
+            held = capi.page_aligned(n_idx, np.int64)
+            held[:] = idx
+            capi.host_register(held)
+        out = capi.OutColumn(n_idx, (capi.HOST, capi.DEVICE)[k % 2])
+        o, c = out.c(), col.c()
+        try:
+            ptr = C.c_void_p(held.ptr) if idx_res == capi.DEVICE else held.ctypes.data_as(C.c_void_p)
+            capi.check(capi.lib().bowgpu_take(C.byref(c), ptr, C.c_int64(n_idx), idx_res, C.byref(o)))
+        finally:
+            if idx_res == capi.HOST_PINNED:
+                capi.host_unregister(held)
+        out.absorb(o)
+        compare_taken("take idx_res=%d n_idx=%d" % (idx_res, n_idx), out, want_vals, m, idx, capi.INT64)
+
+
 def _sentinel_outs(n, ncols, residency):
     outs = [capi.OutColumn(n, residency) for _ in range(ncols)]
     if residency == capi.DEVICE:
