@@ -28,7 +28,7 @@ MAX_FACTORS = 4
 FILTER_MAX_VALUES = 32
 FILTER_MAX_PREDS = 8
 CARRY_MAX_AGGS = 16
-ABI_VERSION = 10  # include/bowgpu.h BOWGPU_ABI_VERSION (asserted when the library is loaded)
+ABI_VERSION = 11  # include/bowgpu.h BOWGPU_ABI_VERSION (asserted when the library is loaded)
 
 ERR_NAMES = {
     -1: "INTERVAL", -2: "TS_TYPE", -3: "FIRST_TS_NULL", -4: "NO_AGG", -5: "KEEP_INTERVAL", -6: "BAD_COL",
@@ -142,6 +142,7 @@ SYMBOLS = [
     "bowgpu_rolling_aggregate_sharded",
     "bowgpu_argsort", "bowgpu_take", "bowgpu_sort_by_col",
     "bowgpu_filter_mask", "bowgpu_compact", "bowgpu_filter",
+    "bowgpu_valid_mask", "bowgpu_drop_nils", "bowgpu_diff", "bowgpu_distinct",
 ]
 
 _lib = None
@@ -966,6 +967,79 @@ def filter(cols, preds, and_mask=None, out_residency=HOST, outs=None, capacity=N
         for i, o in enumerate(outs):
             o.absorb(oarr[i])
     return outs, first.value, count.value, bool(contiguous.value)
+
+
+def _col_idx(col_idx):
+    idx = list(col_idx) if col_idx is not None else []
+    arr = (C.c_int32 * max(len(idx), 1))(*idx)
+    return arr, len(idx)
+
+
+def valid_mask(cols, col_idx=None, and_mask=None, out_residency=HOST, mask_pinned=False, want_mask=True):
+    """bowgpu_valid_mask -> (mask, selected, first, last): bit i set when every selected column (col_idx; none: all) is valid at row
+    i, ANDed with and_mask; the layout of filter_mask.  want_mask=False: only the three numbers (mask is None)"""
+    n = cols[0].length if cols else 0
+    nb = (n + 7) // 8
+    iarr, n_idx = _col_idx(col_idx)
+    aptr, ares, akeep = _mask_arg(and_mask, mask_pinned)
+    if not want_mask:
+        buf, ptr = None, None
+    elif out_residency == DEVICE:
+        buf = DeviceBuffer(max(nb, 1))
+        ptr = C.c_void_p(buf.ptr)
+    else:
+        buf = np.full(max(nb, 1), 0xA5, dtype=np.uint8)
+        ptr = buf.ctypes.data_as(C.c_void_p)
+    sel, first, last = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    check(lib().bowgpu_valid_mask(_cols(cols), len(cols), iarr, n_idx, aptr, ares, ptr, out_residency,
+                                  C.byref(sel), C.byref(first), C.byref(last)))
+    del akeep
+    if buf is not None and out_residency != DEVICE:
+        buf = buf[:nb]
+    return buf, sel.value, first.value, last.value
+
+
+def drop_nils(cols, col_idx=None, out_residency=HOST, outs=None, capacity=None):
+    """Bow.DropNils (bowgpu_drop_nils) -> (list[OutColumn], first, count, contiguous); col_idx: the columns whose nulls drop a row
+    (none: all).  contiguous: as for compact"""
+    outs, oarr = _filter_outs(cols, out_residency, outs, capacity)
+    iarr, n_idx = _col_idx(col_idx)
+    first, count, contiguous = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    check(lib().bowgpu_drop_nils(_cols(cols), len(cols), iarr, n_idx, oarr, C.byref(first), C.byref(count), C.byref(contiguous)))
+    if not contiguous.value:
+        for i, o in enumerate(outs):
+            o.absorb(oarr[i])
+    return outs, first.value, count.value, bool(contiguous.value)
+
+
+def diff(cols, col_idx=None, out_residency=HOST, outs=None, capacity=None):
+    """Bow.Diff (bowgpu_diff) -> list[OutColumn], one per selected column in ascending column order"""
+    if outs is None:
+        n = cols[0].length if cols else 0
+        nsel = len(cols) if not col_idx else len({i for i in col_idx if 0 <= i < len(cols)})
+        outs = [OutColumn(n if capacity is None else capacity, out_residency) for _ in range(nsel)]
+    oarr = (Out * max(len(outs), 1))()
+    for i, o in enumerate(outs):
+        oarr[i] = o.c()
+    iarr, n_idx = _col_idx(col_idx)
+    check(lib().bowgpu_diff(_cols(cols), len(cols), iarr, n_idx, oarr))
+    for i, o in enumerate(outs):
+        o.absorb(oarr[i])
+    return outs
+
+
+def distinct(col, out_residency=HOST, out=None, capacity=None):
+    """Bow.Distinct (bowgpu_distinct) -> (OutColumn, n_distinct): the non-null values of the column, each once, ascending.
+    n_distinct == 0: the output was not written"""
+    if out is None:
+        out = OutColumn(col.length if capacity is None else capacity, out_residency)
+    o = out.c()
+    c = col.c()
+    nd = C.c_int64(0)
+    check(lib().bowgpu_distinct(C.byref(c), C.byref(o), C.byref(nd)))
+    if nd.value:
+        out.absorb(o)
+    return out, nd.value
 
 
 def out_as_column(out):

@@ -617,6 +617,14 @@ int launch_sort_hist(Ctx *c, const uint64_t *key, int64_t n, int is_float, uint3
 // tile_hist: 256 * ceil(n / kSortTileRows) words; sums: ceil(that / 4096) words
 int launch_sort_pass(Ctx *c, const uint64_t *src, int mode, const uint32_t *src_idx, int64_t n, int shift, uint32_t *tile_hist, uint32_t *sums,
                      uint64_t *dst, uint32_t *dst_idx);
+// sort_api.cpp: the sorted (image, row index) pairs of one key column
+struct SortWork {
+    DevBuf keys[2], idx[2], tiles, sums;
+    int cur = 0;                 // which of the two buffers holds the result
+    int passes = 0;              // radix passes run (8 - passes: digits that are the same in every key)
+    const uint32_t *perm() const { return reinterpret_cast<const uint32_t *>(idx[cur].p); }
+};
+int argsort_device(Ctx *c, const bowgpu_col *key, const DevCol &dk, SortWork *w, int32_t *sorted);
 int launch_sort_widen(Ctx *c, const uint32_t *idx, int64_t n, int64_t *out);
 // exactly one of idx32 (the library's own permutation: trusted) / idx64 (a caller's indices: range-checked) is given
 int launch_gather(Ctx *c, const GatherArgs &a, const uint32_t *idx32, const int64_t *idx64);
@@ -650,8 +658,48 @@ struct FilterScatterArgs {
     const unsigned long long *mask;      // as filter_mask_kernel left it
     const uint32_t *tile_base;           // the scanned tile counts
 };
+// what a mask pass leaves for filter_stats_kernel, the scan and filter_scatter_kernel (filter_mask_kernel and the kernels of frame_ops.hip)
+struct TileRecords {
+    unsigned long long *mask;            // 64 * ceil(n / kFilterTileRows) words, every one stored (rows >= n: clear bits)
+    uint32_t *tile_counts, *tile_spans;  // as in FilterMaskArgs
+    uint32_t *stats, *host_stats;
+};
 int launch_filter_mask(Ctx *c, const FilterMaskArgs &a);
+int launch_filter_stats(Ctx *c, const TileRecords &t, int64_t ntiles);   // (launch_filter_mask ends with it)
 int launch_filter_scatter(Ctx *c, const FilterScatterArgs &a);
+// filter_api.cpp: the bitmap of one call, its tile records and the columns staged for the mask pass (kept for the scatter that follows)
+struct MaskWork {
+    DevBuf mask, tiles, spans, sums, staged_mask;
+    StagedCols pcols;
+    const uint32_t *back = nullptr;      // where filter_stats_kernel stores the three numbers
+    int64_t selected = 0, first = -1, last = -1;
+};
+int mask_work_prepare(Ctx *c, int64_t n, MaskWork *w, TileRecords *t);   // the buffers of a mask pass over n rows, its stats words zeroed
+int mask_work_collect(Ctx *c, MaskWork *w);                              // synchronises; selected / first / last
+int scatter_device(Ctx *c, const bowgpu_col *cols, int32_t ncols, int64_t n, MaskWork *w, bowgpu_out *outs);
+int mask_work_compact(Ctx *c, const bowgpu_col *cols, int32_t ncols, int64_t n, MaskWork *w, const char *mask_kernel, bowgpu_out *outs,
+                      int64_t *first, int64_t *count, int32_t *contiguous);
+
+// frame_ops.hip: Bow.DropNils / Bow.Diff / Bow.Distinct - the three kernels in front of the scan, the scatter and the sort
+// (host side: frame_ops_api.cpp)
+constexpr int kValidMaskCols = 8;       // bitmaps ANDed per launch of valid_mask_kernel
+struct ValidMaskArgs {
+    int64_t n;
+    int32_t ncols, accumulate;           // accumulate: AND into the mask words an earlier launch of the same call left
+    const uint8_t *and_mask;             // nullable, as in FilterMaskArgs
+    const uint32_t *vbits[kValidMaskCols];
+    int64_t vbit0[kValidMaskCols], vwords[kValidMaskCols];
+    TileRecords t;
+};
+int launch_valid_mask(Ctx *c, const ValidMaskArgs &a);   // (without the stats kernel: the caller launches it after the last group)
+struct DiffArgs {
+    MoveCols cols;                       // out_valid: ceil(n / 64) words, every one stored whole
+    int64_t n;
+    uint32_t float_mask, _pad;           // bit c: column c is Float64
+};
+int launch_diff(Ctx *c, const DiffArgs &a);
+// s: n keys in non-descending order of Buffer.Less (raw Int64 / Float64 payloads, no NaN); flags the last row of each group of equals
+int launch_distinct_tail(Ctx *c, const uint64_t *s, int64_t n, int is_float, const TileRecords &t);
 
 // generate.hip
 int launch_gen_dense(Ctx *c, int64_t row0, int64_t n, uint64_t seed, int64_t *ts, double *val);

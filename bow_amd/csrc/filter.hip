@@ -257,14 +257,24 @@ __global__ __launch_bounds__(kThreads) void filter_scatter_kernel(FilterScatterA
 
 }  // namespace
 
+int launch_filter_stats(Ctx *c, const TileRecords &t, int64_t ntiles) {
+    const int64_t per_block = (int64_t)kThreads * kStatItems;
+    hipLaunchKernelGGL(filter_stats_kernel, dim3((unsigned)((ntiles + per_block - 1) / per_block)), dim3(kThreads), 0, c->stream, t.tile_counts,
+                       t.tile_spans, ntiles, t.stats, t.host_stats);
+    BG_HIP(hipGetLastError());
+    return 0;
+}
+
 int launch_filter_mask(Ctx *c, const FilterMaskArgs &a) {
     const int64_t ntiles = (a.n + kTile - 1) / kTile;
     hipLaunchKernelGGL(filter_mask_kernel, dim3((unsigned)ntiles), dim3(kThreads), 0, c->stream, a);
-    const int64_t per_block = (int64_t)kThreads * kStatItems;
-    hipLaunchKernelGGL(filter_stats_kernel, dim3((unsigned)((ntiles + per_block - 1) / per_block)), dim3(kThreads), 0, c->stream, a.tile_counts,
-                       a.tile_spans, ntiles, a.stats, a.host_stats);
-    BG_HIP(hipGetLastError());
-    return 0;
+    TileRecords t;
+    t.mask = a.mask;
+    t.tile_counts = a.tile_counts;
+    t.tile_spans = a.tile_spans;
+    t.stats = a.stats;
+    t.host_stats = a.host_stats;
+    return launch_filter_stats(c, t, ntiles);
 }
 
 int launch_filter_scatter(Ctx *c, const FilterScatterArgs &a) {

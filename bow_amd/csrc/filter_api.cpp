@@ -33,17 +33,9 @@ int frame_checks(const bowgpu_col *cols, int32_t ncols, const bowgpu_filter_pred
     return 0;
 }
 
-// the bitmap of one call, its tile counts and the predicate columns (kept staged for the scatter that follows)
-struct MaskWork {
-    DevBuf mask, tiles, spans, sums, staged_mask;
-    StagedCols pcols;
-    int64_t selected = 0, first = -1, last = -1;
-};
-
 // the predicate pass (bracketed by the context's events) and its three numbers; synchronises
 int mask_device(Ctx *c, const bowgpu_col *cols, const bowgpu_filter_pred *preds, int32_t npreds, const uint8_t *and_mask, int32_t and_residency,
                 int64_t n, MaskWork *w) {
-    const int64_t ntiles = (n + kFilterTileRows - 1) / kFilterTileRows;
     FilterMaskArgs a;
     memset(&a, 0, sizeof a);
     a.n = n;
@@ -71,28 +63,17 @@ int mask_device(Ctx *c, const bowgpu_col *cols, const bowgpu_filter_pred *preds,
         P.is_float = cols[col].type == BOWGPU_FLOAT64;
         if (P.n_values > 0) memcpy(P.set, preds[p].values, (size_t)P.n_values * 8);
     }
-    void *scr;
-    BG_TRY(ctx_scratch(c, kScrBytes, &scr));
-    char *s = reinterpret_cast<char *>(scr);
-    BG_TRY(w->mask.alloc((size_t)ntiles * (kFilterTileRows / 8)));
-    BG_TRY(w->tiles.alloc((size_t)ntiles * 4));
-    BG_TRY(w->spans.alloc((size_t)ntiles * 4));
-    a.mask = reinterpret_cast<unsigned long long *>(w->mask.p);
-    a.tile_counts = reinterpret_cast<uint32_t *>(w->tiles.p);
-    a.tile_spans = reinterpret_cast<uint32_t *>(w->spans.p);
-    a.stats = reinterpret_cast<uint32_t *>(s + kScrFlags);
-    volatile uint32_t *back;   // the context's registered block: filter_stats_kernel stores the three numbers there itself
-    BG_TRY(ctx_pinned(c, 16384, reinterpret_cast<void **>(const_cast<uint32_t **>(&back))));
-    a.host_stats = const_cast<uint32_t *>(back);
-    BG_HIP(hipMemsetAsync(s + kScrFlags, 0, 16, c->stream));
+    TileRecords t;
+    BG_TRY(mask_work_prepare(c, n, w, &t));
+    a.mask = t.mask;
+    a.tile_counts = t.tile_counts;
+    a.tile_spans = t.tile_spans;
+    a.stats = t.stats;
+    a.host_stats = t.host_stats;
     BG_HIP(hipEventRecord(c->ev0, c->stream));
     BG_TRY(launch_filter_mask(c, a));
     BG_HIP(hipEventRecord(c->ev1, c->stream));
-    BG_HIP(hipStreamSynchronize(c->stream));
-    w->selected = back[0];
-    w->first = back[0] ? (int64_t)back[1] : -1;
-    w->last = back[0] ? (int64_t)back[2] : -1;
-    return 0;
+    return mask_work_collect(c, w);
 }
 
 // one scatter launch over a prepared group, and the counts of valid rows of its nullable columns on their way to valid[] (no synchronise)
@@ -118,6 +99,39 @@ int scatter_launch(Ctx *c, const MoveGroup &g, int64_t n, const MaskWork &w, uns
     return 0;
 }
 
+}  // namespace
+
+namespace bowgpu {
+
+int mask_work_prepare(Ctx *c, int64_t n, MaskWork *w, TileRecords *t) {
+    const int64_t ntiles = (n + kFilterTileRows - 1) / kFilterTileRows;
+    void *scr;
+    BG_TRY(ctx_scratch(c, kScrBytes, &scr));
+    char *s = reinterpret_cast<char *>(scr);
+    BG_TRY(w->mask.alloc((size_t)ntiles * (kFilterTileRows / 8)));
+    BG_TRY(w->tiles.alloc((size_t)ntiles * 4));
+    BG_TRY(w->spans.alloc((size_t)ntiles * 4));
+    t->mask = reinterpret_cast<unsigned long long *>(w->mask.p);
+    t->tile_counts = reinterpret_cast<uint32_t *>(w->tiles.p);
+    t->tile_spans = reinterpret_cast<uint32_t *>(w->spans.p);
+    t->stats = reinterpret_cast<uint32_t *>(s + kScrFlags);
+    void *back;   // the context's registered block: filter_stats_kernel stores the three numbers there itself
+    BG_TRY(ctx_pinned(c, 16384, &back));
+    t->host_stats = reinterpret_cast<uint32_t *>(back);
+    w->back = t->host_stats;
+    BG_HIP(hipMemsetAsync(s + kScrFlags, 0, 16, c->stream));
+    return 0;
+}
+
+int mask_work_collect(Ctx *c, MaskWork *w) {
+    BG_HIP(hipStreamSynchronize(c->stream));
+    const volatile uint32_t *back = w->back;
+    w->selected = back[0];
+    w->first = back[0] ? (int64_t)back[1] : -1;
+    w->last = back[0] ? (int64_t)back[2] : -1;
+    return 0;
+}
+
 // outs[i] = the selected rows of cols[i], for every column of the frame (the caller has checked the capacities)
 int scatter_device(Ctx *c, const bowgpu_col *cols, int32_t ncols, int64_t n, MaskWork *w, bowgpu_out *outs) {
     const int64_t ntiles = (n + kFilterTileRows - 1) / kFilterTileRows, count = w->selected;
@@ -140,6 +154,33 @@ int scatter_device(Ctx *c, const bowgpu_col *cols, int32_t ncols, int64_t n, Mas
     return 0;
 }
 
+// what follows the mask pass of a call that moves rows: the contiguous answer, or the capacity check, the scan and the scatter
+int mask_work_compact(Ctx *c, const bowgpu_col *cols, int32_t ncols, int64_t n, MaskWork *w, const char *mask_kernel, bowgpu_out *outs,
+                      int64_t *first, int64_t *count, int32_t *contiguous) {
+    *count = w->selected;
+    *first = w->selected ? w->first : 0;
+    *contiguous = w->selected == 0 || w->selected == w->last - w->first + 1;
+    if (*contiguous) {   // bowsetters.go:74-82: the empty slice, or a slice of the receiver
+        kernel_done(c, mask_kernel);
+        return 0;
+    }
+    bool device_out = false;
+    for (int i = 0; i < ncols; i++) {
+        if (outs[i].length < w->selected)
+            return fail(BOWGPU_ERR_ARG, "output column %d has %lld slots, %lld needed", i, (long long)outs[i].length, (long long)w->selected);
+        device_out |= outs[i].residency == BOWGPU_DEVICE;
+    }
+    BG_TRY(synced(c, scatter_device(c, cols, ncols, n, w, outs)));
+    BG_HIP(hipStreamSynchronize(c->stream));
+    if (device_out) device_write_epoch_bump();
+    kernel_done(c, "filter_scatter_kernel");
+    return 0;
+}
+
+}  // namespace bowgpu
+
+namespace {
+
 // bowgpu_filter and bowgpu_compact after their argument checks
 int filter_run(const bowgpu_col *cols, int32_t ncols, const bowgpu_filter_pred *preds, int32_t npreds, const uint8_t *and_mask,
                int32_t and_residency, int64_t n, bowgpu_out *outs, int64_t *first, int64_t *count, int32_t *contiguous) {
@@ -147,24 +188,7 @@ int filter_run(const bowgpu_col *cols, int32_t ncols, const bowgpu_filter_pred *
     BG_TRY(ctx_get(&c));
     MaskWork w;
     BG_TRY(synced(c, mask_device(c, cols, preds, npreds, and_mask, and_residency, n, &w)));
-    *count = w.selected;
-    *first = w.selected ? w.first : 0;
-    *contiguous = w.selected == 0 || w.selected == w.last - w.first + 1;
-    if (*contiguous) {   // bowsetters.go:74-82: the empty slice, or a slice of the receiver
-        kernel_done(c, "filter_mask_kernel");
-        return 0;
-    }
-    bool device_out = false;
-    for (int i = 0; i < ncols; i++) {
-        if (outs[i].length < w.selected)
-            return fail(BOWGPU_ERR_ARG, "output column %d has %lld slots, %lld needed", i, (long long)outs[i].length, (long long)w.selected);
-        device_out |= outs[i].residency == BOWGPU_DEVICE;
-    }
-    BG_TRY(synced(c, scatter_device(c, cols, ncols, n, &w, outs)));
-    BG_HIP(hipStreamSynchronize(c->stream));
-    if (device_out) device_write_epoch_bump();
-    kernel_done(c, "filter_scatter_kernel");
-    return 0;
+    return mask_work_compact(c, cols, ncols, n, &w, "filter_mask_kernel", outs, first, count, contiguous);
 }
 
 }  // namespace

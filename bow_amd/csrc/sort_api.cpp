@@ -25,13 +25,9 @@ int key_checks(const bowgpu_col *key) {
     return 0;
 }
 
-// the sorted (image, row index) pairs of one key column
-struct SortWork {
-    DevBuf keys[2], idx[2], tiles, sums;
-    int cur = 0;                 // which of the two buffers holds the result
-    int passes = 0;              // radix passes run (8 - passes: digits that are the same in every key)
-    const uint32_t *perm() const { return reinterpret_cast<const uint32_t *>(idx[cur].p); }
-};
+}  // namespace
+
+namespace bowgpu {
 
 // Histogram + checks, then the passes.  *sorted = 1: the key is in order (sort.IsSorted) and nothing else was done.
 // The caller brackets the call with the context's events and synchronises.
@@ -86,6 +82,10 @@ int argsort_device(Ctx *c, const bowgpu_col *key, const DevCol &dk, SortWork *w,
     }
     return 0;
 }
+
+}  // namespace bowgpu
+
+namespace {
 
 // (a key whose nulls were counted on the host - none - goes without its bitmap: nothing is staged or counted a second time)
 int key_prepare(Ctx *c, const bowgpu_col *key, DevCol *dk) {

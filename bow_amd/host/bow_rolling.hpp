@@ -268,6 +268,12 @@ class Bow : public std::enable_shared_from_this<Bow> {
     template <typename... V> RowCmp MakeFilterValues(int colIndex, V... values) const;
     std::pair<BowPtr, Error> FilterV(const std::vector<RowCmp> &cmps) const;
     template <typename... C> std::pair<BowPtr, Error> Filter(const C &...cmps) const;
+    // DropNils: bow.go:188-224 ; Diff: bowdiff.go:8-73 ; Distinct: bowgetters.go:333-358 (device; colIndices defaults to all columns).
+    // DropNils returns the receiver when nothing is dropped, a slice when the kept rows are consecutive.  (The reference's Distinct
+    // returns a Bow alone and panics; the Error carries what the device path can answer, e.g. a NaN in the column.)
+    std::pair<BowPtr, Error> DropNils(std::vector<int> colIndices = {}) const;
+    std::pair<BowPtr, Error> Diff(std::vector<int> colIndices = {}) const;
+    std::pair<BowPtr, Error> Distinct(int colIndex) const;
 
 private:
     std::pair<BowPtr, Error> fill(int method, const std::vector<int> &colIndices) const;
@@ -511,6 +517,66 @@ inline std::pair<BowPtr, Error> Bow::FilterV(const std::vector<RowCmp> &cmps) co
 }
 template <typename... C> inline std::pair<BowPtr, Error> Bow::Filter(const C &...cmps) const {
     return FilterV(std::vector<RowCmp>{RowCmp(cmps)...});
+}
+
+inline std::pair<BowPtr, Error> Bow::DropNils(std::vector<int> colIndices) const {
+    const int n = NumRows();
+    std::vector<int32_t> idx(colIndices.begin(), colIndices.end());
+    std::vector<bowgpu_col> c;
+    for (int i = 0; i < NumCols(); i++) c.push_back(ArrowCol(i));
+    std::vector<detail::OutStore> st((size_t)NumCols());
+    std::vector<bowgpu_out> o;
+    for (int i = 0; i < NumCols(); i++) o.push_back(st[(size_t)i].Make(n));
+    int64_t first = 0, count = 0;
+    int32_t contiguous = 0;
+    const int rc = bowgpu_drop_nils(c.data(), NumCols(), idx.data(), (int32_t)idx.size(), o.data(), &first, &count, &contiguous);
+    if (rc) return {nullptr, detail::AbiError(rc)};
+    if (contiguous) {
+        if (count == n) {   // bow.go:210-212 returns b itself (a copy where the receiver is not held by a shared_ptr)
+            BowPtr self = weak_from_this().lock();
+            return {self ? self : std::make_shared<Bow>(*this), Error()};
+        }
+        return {NewSlice((int)first, (int)(first + count)), Error()};
+    }
+    auto out = std::make_shared<Bow>();
+    for (int i = 0; i < NumCols(); i++) out->cols.push_back(st[(size_t)i].ToSeries(cols[i].Name, o[(size_t)i]));
+    return {out, Error()};
+}
+
+inline std::pair<BowPtr, Error> Bow::Diff(std::vector<int> colIndices) const {
+    std::vector<bool> selected(NumCols(), colIndices.empty());  // selectCols: bowfill.go:268-288
+    for (int ci : colIndices) {
+        if (ci < 0 || ci > NumCols() - 1) return {nullptr, Errorf("selectCols: colIndex '" + std::to_string(ci) + "' out of range")};
+        selected[ci] = true;
+    }
+    std::vector<int32_t> idx(colIndices.begin(), colIndices.end());
+    std::vector<bowgpu_col> c;
+    for (int i = 0; i < NumCols(); i++) c.push_back(ArrowCol(i));
+    int nsel = 0;
+    for (int i = 0; i < NumCols(); i++) nsel += selected[i];
+    std::vector<detail::OutStore> st((size_t)nsel);
+    std::vector<bowgpu_out> o;
+    for (int i = 0; i < nsel; i++) o.push_back(st[(size_t)i].Make(NumRows()));
+    const int rc = bowgpu_diff(c.data(), NumCols(), idx.data(), (int32_t)idx.size(), o.data());
+    if (rc) return {nullptr, detail::AbiError(rc)};
+    auto out = std::make_shared<Bow>(*this);   // unselected columns pass through: bowdiff.go:33-36
+    for (int ci = 0, k = 0; ci < NumCols(); ci++)
+        if (selected[ci]) { out->cols[ci] = st[(size_t)k].ToSeries(cols[ci].Name, o[(size_t)k]); k++; }
+    return {out, Error()};
+}
+
+inline std::pair<BowPtr, Error> Bow::Distinct(int colIndex) const {
+    if (colIndex < 0 || colIndex > NumCols() - 1) return {nullptr, Errorf("no column '" + std::to_string(colIndex) + "'")};
+    bowgpu_col c = ArrowCol(colIndex);
+    detail::OutStore st;
+    bowgpu_out o = st.Make(NumRows());
+    int64_t nd = 0;
+    const int rc = bowgpu_distinct(&c, &o, &nd);
+    if (rc) return {nullptr, detail::AbiError(rc)};
+    if (nd == 0) { o.length = 0; o.null_count = 0; o.type = c.type; }   // (nothing was written)
+    auto out = std::make_shared<Bow>();
+    out->cols.push_back(st.ToSeries(cols[colIndex].Name, o));
+    return {out, Error()};
 }
 
 inline bool Bow::IsColSorted(int colIndex) const {

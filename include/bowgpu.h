@@ -37,7 +37,7 @@ extern "C" {
  * changed. */
 /* 10: bowgpu_filter_mask / bowgpu_compact / bowgpu_filter and the bowgpu_filter_pred struct added (Bow.Filter on the device); no existing
  * struct changed. */
-#define BOWGPU_ABI_VERSION 10
+#define BOWGPU_ABI_VERSION 11
 
 /* bow.Type (reference bowtypes.go:17-32) */
 enum {
@@ -575,6 +575,71 @@ int bowgpu_compact(const bowgpu_col *cols, int32_t ncols, const uint8_t *mask, i
 int bowgpu_filter(const bowgpu_col *cols, int32_t ncols, const bowgpu_filter_pred *preds, int32_t npreds,
                   const uint8_t *and_mask, int32_t and_mask_residency,
                   bowgpu_out *outs, int64_t *first, int64_t *count, int32_t *contiguous);
+
+/* ---- Bow.DropNils / Bow.Diff / Bow.Distinct ------------------------------------------ */
+
+/* The three steps the reference's users run between a Parquet read and a rolling call: Bow.DropNils (bow.go:188-224), Bow.Diff
+ * (bowdiff.go:8-73) and Bow.Distinct (bowgetters.go:333-358).  The conventions are those of the sort and filter entry points: ONE device,
+ * any residency for inputs and outputs (BOWGPU_HOST staged through HBM at most 4 columns at a time, BOWGPU_HOST_PINNED and BOWGPU_DEVICE
+ * read where they lie), per-thread contexts and streams; bowgpu_set_devices does not apply.  Int64 / Float64 columns with or without
+ * validity at any Arrow offset (bit offsets that are no multiple of 8 included); Boolean / String anywhere in the frame:
+ * BOWGPU_ERR_UNSUPPORTED.  Columns of unequal length: BOWGPU_ERR_ARG.  Fewer than 2^31 rows; more is BOWGPU_ERR_UNSUPPORTED naming the
+ * limit.  For host-resident arguments all of this is decided before the device is touched; a valid call that has rows to look at is
+ * BOWGPU_ERR_NO_DEVICE on a box without a GPU - no CPU fallback.  Outputs are what Buffer.SetOrDropStrict leaves: null slots hold 0, the
+ * padding bits of the last validity byte are clear, nothing is written past the slots produced.
+ *   COLUMN SELECTION is selectCols (bowfill.go:268-288): col_idx[n_idx] names the columns, n_idx == 0 means every column, an index
+ * outside the frame is BOWGPU_ERR_BAD_COL, a repeated index is the same as naming it once.
+ *   A COLUMN HAS NO NULLS TO LOOK AT when its validity is NULL or its null_count is stated as 0; null_count == -1 means the bitmap is
+ * read (it is not counted first).
+ *   THE METHOD (bow_amd/csrc/frame_ops.hip): one small streaming kernel per operation in front of the layers of Bow.Filter and
+ * Bow.SortByCol - a pass over validity bitmaps alone (1/8 byte per row and selected column, no value byte), a difference pass (8 bytes
+ * read and written per row and column), a pass that flags the last row of each group of equal sorted keys.  No workgroup waits on
+ * another; the same call gives the same bytes. */
+
+/* mask_out bit i (LSB first, no offset) = every selected column is valid at row i AND (and_mask == NULL or its bit i).  The byte layout
+ * and *selected / *first / *last are exactly those of bowgpu_filter_mask, so the result can be handed to bowgpu_compact or passed as the
+ * and_mask of bowgpu_filter (a Filter and a DropNils then cost one compaction).  mask_out may be NULL: only the three numbers are wanted.
+ * When no selected column has nulls to look at and there is no and_mask, every row is selected and a host-resident mask_out is filled
+ * (all ones, padding clear) without the device.  HBM WORKSPACE: that of bowgpu_filter_mask (1/8 byte per row + 8 bytes per 4096 rows)
+ * + the staged bitmaps (never the values) of BOWGPU_HOST columns, 1/8 byte per row each, + the staged copy of a BOWGPU_HOST and_mask. */
+int bowgpu_valid_mask(const bowgpu_col *cols, int32_t ncols, const int32_t *col_idx, int32_t n_idx,
+                      const uint8_t *and_mask, int32_t and_mask_residency, uint8_t *mask_out, int32_t mask_residency,
+                      int64_t *selected, int64_t *first, int64_t *last);
+
+/* Bow.DropNils in one call: the mask above, kept in the workspace, then the scan and the scatter of bowgpu_filter.  outs[ncols]: one
+ * output per column of the frame; the contract is bowgpu_filter's, capacity rule included (bowgpu_out.length on entry; the number of
+ * rows always suffices; too small is BOWGPU_ERR_ARG naming the size needed, and nothing is written).  THE CONTIGUOUS CASE: nothing is
+ * dropped, or the kept rows are consecutive, or there are none: *contiguous = 1 with *first / *count (*first = 0 when there are none),
+ * and the outputs are NOT written.  The reference returns the receiver itself only when nothing is dropped (bow.go:210-212) and
+ * materialises a new frame otherwise; the values of that frame are those of the slice [*first, *first + *count) of the inputs.  When no
+ * selected column has nulls to look at the answer is contiguous, *first = 0, *count = rows, without the device.  HBM WORKSPACE: that of
+ * bowgpu_valid_mask + that of bowgpu_filter's scatter (4 bytes per 4096 * 4096 rows for the scan; the staged copies of BOWGPU_HOST columns
+ * and the device temporaries of host-resident outputs, at most 4 columns at a time). */
+int bowgpu_drop_nils(const bowgpu_col *cols, int32_t ncols, const int32_t *col_idx, int32_t n_idx,
+                     bowgpu_out *outs, int64_t *first, int64_t *count, int32_t *contiguous);
+
+/* Bow.Diff.  outs: one output per SELECTED column, in ascending column order (unselected columns pass through the reference untouched
+ * and are not the library's business); capacity >= rows.  out[i] = col[i] - col[i-1], valid when both rows are valid; row 0 is always
+ * null.  Int64 differences wrap as Go's do; Float64 is one IEEE subtraction (nothing contracted or reassociated); the sign and
+ * payload of a NaN the subtraction GENERATES (inf - inf) are the device's.  length = rows, null_count is set.  Zero rows: length 0,
+ * nothing written, no device.  An output that overlaps an input is not supported.  HBM WORKSPACE: none beyond the staged copies of
+ * BOWGPU_HOST columns, the device temporaries of host-resident outputs and the validity working copies (1/8 byte per row), at most 4
+ * columns at a time. */
+int bowgpu_diff(const bowgpu_col *cols, int32_t ncols, const int32_t *col_idx, int32_t n_idx, bowgpu_out *outs);
+
+/* Bow.Distinct: the non-null values of one column, each once, ascending by Buffer.Less (bowbuffer.go:126-139).  The output has no nulls:
+ * length = *n_distinct, null_count = 0, validity all set, padding clear.  CAPACITY: bowgpu_out.length on entry; the column's count of
+ * valid rows always suffices; too small is BOWGPU_ERR_ARG naming the size needed, and nothing is written (the count is known before the
+ * compaction).  A Float64 column holding a NaN among its valid rows is BOWGPU_ERR_UNSUPPORTED, as for the sort: the reference's map makes
+ * every NaN a key of its own, and Less is no order there.  -0.0 and +0.0 are ONE value (Go's == on the map key); the survivor is the LAST
+ * zero in row order, because Go's map assignment rewrites the stored key when an equal float or interface key is assigned again.  That
+ * rests on a reading of the Go runtime (map assignment with needkeyupdate), not on a run of the reference; it is the contract here.
+ * All null, or zero rows: *n_distinct = 0 and nothing is written - neither the buffers nor length / null_count / type.
+ *   HBM WORKSPACE: a column with nulls is first compacted by its own validity (8 bytes per valid row + bowgpu_valid_mask's); a column
+ * that is not already in order takes bowgpu_argsort's 24 bytes per row and 8 bytes per row for the keys gathered through the
+ * permutation; then bowgpu_filter_mask's workspace for the flags.  A column in order (sort.IsSorted) and without nulls takes only that
+ * last part: it is read twice and nothing is sorted. */
+int bowgpu_distinct(const bowgpu_col *col, bowgpu_out *out, int64_t *n_distinct);
 
 /* ---- Parquet column chunk -> device column --------------------------- */
 
