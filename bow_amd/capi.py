@@ -28,7 +28,7 @@ MAX_FACTORS = 4
 FILTER_MAX_VALUES = 32
 FILTER_MAX_PREDS = 8
 CARRY_MAX_AGGS = 16
-ABI_VERSION = 11  # include/bowgpu.h BOWGPU_ABI_VERSION (asserted when the library is loaded)
+ABI_VERSION = 12  # include/bowgpu.h BOWGPU_ABI_VERSION (asserted when the library is loaded)
 
 ERR_NAMES = {
     -1: "INTERVAL", -2: "TS_TYPE", -3: "FIRST_TS_NULL", -4: "NO_AGG", -5: "KEEP_INTERVAL", -6: "BAD_COL",
@@ -143,6 +143,7 @@ SYMBOLS = [
     "bowgpu_argsort", "bowgpu_take", "bowgpu_sort_by_col",
     "bowgpu_filter_mask", "bowgpu_compact", "bowgpu_filter",
     "bowgpu_valid_mask", "bowgpu_drop_nils", "bowgpu_diff", "bowgpu_distinct",
+    "bowgpu_append", "bowgpu_find_next",
 ]
 
 _lib = None
@@ -1040,6 +1041,40 @@ def distinct(col, out_residency=HOST, out=None, capacity=None):
     if nd.value:
         out.absorb(o)
     return out, nd.value
+
+
+def append(frames, out_residency=HOST, outs=None, capacity=None):
+    """AppendBows (bowgpu_append) -> (list[OutColumn], unchanged); frames: the pieces, each a list of Columns.  unchanged: one piece -
+    the reference returns its argument and the outputs were not written"""
+    ncols = len(frames[0]) if frames else 0
+    if outs is None:
+        total = sum(f[0].length for f in frames if f)
+        outs = [OutColumn(total if capacity is None else capacity, out_residency) for _ in range(ncols)]
+    oarr = (Out * max(ncols, 1))()
+    for i, o in enumerate(outs):
+        oarr[i] = o.c()
+    pieces = [_cols(f) for f in frames]
+    parr = (C.POINTER(Col) * max(len(frames), 1))(*[C.cast(p, C.POINTER(Col)) for p in pieces])
+    unchanged = C.c_int32(0)
+    check(lib().bowgpu_append(parr, len(frames), ncols, oarr, C.byref(unchanged)))
+    if not unchanged.value:
+        for i, o in enumerate(outs):
+            o.absorb(oarr[i])
+    return outs, bool(unchanged.value)
+
+
+def find_next(col, value, row_start=0):
+    """Bow.FindNext (bowgpu_find_next) -> row, -1: none; value: a number of the column's type, or None for nil (the first null row of
+    the column, whatever row_start says).  Find is row_start = 0, Contains is the result != -1"""
+    c = col.c()
+    row = C.c_int64(0)
+    if value is None:
+        ptr = None
+    else:
+        v = np.array([value], dtype=np.int64 if col.type == INT64 else np.float64) if not isinstance(value, np.ndarray) else value
+        ptr = v.ctypes.data_as(C.c_void_p)
+    check(lib().bowgpu_find_next(C.byref(c), C.c_int64(row_start), ptr, C.byref(row)))
+    return row.value
 
 
 def out_as_column(out):

@@ -167,6 +167,10 @@ bool movable_type(int32_t t);         // Int64 / Float64
 bool residency_ok(int32_t r);
 // nulls of a column where that is known without the device (host-resident bitmaps are counted here); -1: ask the device
 int64_t host_count_nulls(const bowgpu_col *col);
+// a column whose bitmap has to be read: it has one, and its null count is not stated to be 0
+bool has_bitmap(const bowgpu_col &col);
+// the column as the kernels that read the bitmap anyway want it staged: an unknown null count is NOT counted first
+bowgpu_col uncounted(const bowgpu_col &col);
 // the per-column checks of a frame of n rows, in the order the entry points report them.  Filter's form (residencies = true) reports a
 // negative length before a differing one and checks the residencies; Sort's leaves both to the key's checks and to devcol_prepare
 int frame_cols_checks(const bowgpu_col *cols, int32_t ncols, int64_t n, bool residencies);
@@ -201,6 +205,9 @@ struct MoveGroup {
     DevOut douts[kMoveCols];
 };
 int move_group_prepare(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t g0, const StagedCols &have, bowgpu_out *outs, int64_t count, MoveGroup *g);
+// the second half of prepare alone, for a call whose inputs are not one column each (AppendBows: a list of pieces): ncols, the
+// outputs, the scratch block; the caller describes its inputs to its kernel itself
+int move_group_outputs(Ctx *c, int32_t ncols, int32_t g0, bowgpu_out *outs, int64_t count, MoveGroup *g);
 int move_group_finish(Ctx *c, MoveGroup *g, const bowgpu_col *cols, int32_t g0, int64_t count, const int64_t *null_counts);
 
 // ---------------------------------------------------------------- division by the interval
@@ -496,7 +503,9 @@ constexpr int kPoolGaps = 32;    // window_first_rows: queued runs of empty wind
 constexpr int kPoolWhole = 33;        // bowgpu_aggregate_whole: partial states, the reducers' values and validity bytes
 constexpr int kPoolInterpEdge = 31;   // Interpolate: the trips' edge words (interp_wave3_kernel)
 constexpr int kPoolInterp = 20;  // context pool slots 20..30: tile counts, their scan, scan sums, one neighbour index per column
-// every user its own slot: 0..15 the outputs' validity working copies, 17..19, 20..30 (kPoolInterp + 0..10), 31, 32, 33, kPoolSlots - 1 the long windows
+constexpr int kPoolAppend = 34;  // AppendBows: the piece table of one launch group
+// every user its own slot: 0..15 the outputs' validity working copies, 17..19, 20..30 (kPoolInterp + 0..10), 31, 32, 33, 34, kPoolSlots - 1 the long windows
+static_assert(kPoolAppend > kPoolWhole && kPoolAppend < Ctx::kPoolSlots - 1, "context pool slots must be distinct");
 static_assert(kPoolMode != kPoolColOrder && kPoolColOrder != kPoolShard && kPoolMode != kPoolShard && kPoolMode > 15 && kPoolShard < kPoolInterp &&
               kPoolInterp + 10 < kPoolInterpEdge && kPoolInterpEdge < kPoolGaps && kPoolGaps < kPoolWhole && kPoolWhole < Ctx::kPoolSlots - 1,
               "context pool slots must be distinct");
@@ -700,6 +709,36 @@ struct DiffArgs {
 int launch_diff(Ctx *c, const DiffArgs &a);
 // s: n keys in non-descending order of Buffer.Less (raw Int64 / Float64 payloads, no NaN); flags the last row of each group of equals
 int launch_distinct_tail(Ctx *c, const uint64_t *s, int64_t n, int is_float, const TileRecords &t);
+
+// append.hip: AppendBows / Bow.Find - the concatenation of the pieces of a frame and the linear search of a column (host side:
+// append_api.cpp)
+struct AppendPiece {                     // one piece of one column, addressed by OUTPUT row
+    const uint64_t *values;              // values[row] is output row `row` (the piece's element 0 minus the piece's start row)
+    const uint32_t *vbits;               // nullptr: no nulls to look at
+    int64_t vadj;                        // bit (vadj + row) of vbits is output row `row`'s
+};
+struct AppendArgs {
+    MoveCols cols;                       // ncols, out_values, out_valid (ceil(n / 64) words, every one stored whole); the inputs are the pieces'
+    int64_t n;                           // rows of the result
+    int32_t npieces;
+    uint32_t bitmap_mask;                // bit c: some piece of column c has a bitmap to read
+    const uint32_t *starts;              // [npieces + 1] first output row of each piece; starts[npieces] = n
+    const AppendPiece *pieces[kMoveCols];   // [npieces] per column of the launch
+};
+size_t append_table_bytes(int32_t npieces);   // starts + kMoveCols piece arrays, each 16-byte aligned, in one block
+int launch_append(Ctx *c, const AppendArgs &a);
+constexpr uint32_t kFindNone = 0xFFFFFFFFu;
+struct FindArgs {
+    const uint64_t *values;              // nullptr: the search for the first null (bitmaps only)
+    const uint32_t *vbits;
+    int64_t vbit0, vwords;
+    int64_t n, row_start;
+    uint64_t value;                      // raw payload of the column's type
+    int32_t is_float, _pad;
+    uint32_t *result;                    // device word, kFindNone on entry: lowered to the lowest matching row
+    uint32_t *host_result;               // registered host memory: receives *result behind the search
+};
+int launch_find(Ctx *c, const FindArgs &a);   // presets *result, searches, hands the word to host_result
 
 // generate.hip
 int launch_gen_dense(Ctx *c, int64_t row0, int64_t n, uint64_t seed, int64_t *ts, double *val);

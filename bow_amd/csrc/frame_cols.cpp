@@ -81,6 +81,14 @@ int synced(Ctx *c, int rc) {
     return rc;
 }
 
+bool has_bitmap(const bowgpu_col &col) { return col.validity != nullptr && col.null_count != 0; }
+
+bowgpu_col uncounted(const bowgpu_col &col) {
+    bowgpu_col k = col;
+    if (k.validity && k.null_count < 0) k.null_count = 1;
+    return k;
+}
+
 int move_group_prepare(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t g0, const StagedCols &have, bowgpu_out *outs, int64_t count, MoveGroup *g) {
     MoveCols &m = g->cols;
     m = MoveCols();
@@ -96,6 +104,12 @@ int move_group_prepare(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t g0
         m.vbits[i] = dc->vbits;
         m.vbit0[i] = dc->vbit0;
     }
+    return move_group_outputs(c, ncols, g0, outs, count, g);
+}
+
+int move_group_outputs(Ctx *c, int32_t ncols, int32_t g0, bowgpu_out *outs, int64_t count, MoveGroup *g) {
+    MoveCols &m = g->cols;
+    m.ncols = ncols - g0 < kMoveCols ? ncols - g0 : kMoveCols;
     for (int i = 0; i < m.ncols; i++) {
         const int rc = devout_prepare(c, &outs[g0 + i], count, &g->douts[i]);
         if (rc != 0) return synced(c, rc);

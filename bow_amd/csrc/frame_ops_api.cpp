@@ -34,16 +34,6 @@ int frame_checks(const bowgpu_col *cols, int32_t ncols, const int32_t *col_idx, 
     return 0;
 }
 
-// a column whose bitmap has to be read: it has one, and its null count is not stated to be 0
-bool has_bitmap(const bowgpu_col &col) { return col.validity != nullptr && col.null_count != 0; }
-
-// the column as the kernels of this file want it staged: an unknown null count is NOT counted first - they read the bitmap anyway
-bowgpu_col uncounted(const bowgpu_col &col) {
-    bowgpu_col k = col;
-    if (k.validity && k.null_count < 0) k.null_count = 1;
-    return k;
-}
-
 // valid_mask_kernel over the bitmaps of the selected columns (kValidMaskCols a launch, ANDed into the same words), then the call's
 // three numbers; bracketed by the context's events; synchronises
 int valid_mask_device(Ctx *c, const bowgpu_col *cols, const std::vector<int32_t> &sel, const uint8_t *and_mask, int32_t and_residency, int64_t n,

@@ -2,7 +2,7 @@
 //
 // The reference is Go (no Go toolchain in this image), so the host side above include/bowgpu.h is
 // written in C++ with the SAME names, argument meaning and error strings as the reference:
-//   bow::Bow / Series / Type                   <- bow.go, bowseries.go, bowtypes.go
+//   bow::Bow / Series / Type, AppendBows       <- bow.go, bowseries.go, bowtypes.go, bowappend.go, bowfind.go
 //   bow::rolling::IntervalRolling, Rolling, Options, Window, ColAggregation, NewColAggregation,
 //        ColInterpolation, NewColInterpolation  <- rolling/rolling.go, window.go, aggregation.go, interpolation.go
 //   bow::rolling::aggregation::{WindowStart,Sum,ArithmeticMean,Min,Max,Count,First,Last,Mode,IntegralStep,
@@ -274,6 +274,12 @@ class Bow : public std::enable_shared_from_this<Bow> {
     std::pair<BowPtr, Error> DropNils(std::vector<int> colIndices = {}) const;
     std::pair<BowPtr, Error> Diff(std::vector<int> colIndices = {}) const;
     std::pair<BowPtr, Error> Distinct(int colIndex) const;
+    // Find / FindNext / Contains: bowfind.go:3-32 (device).  nil finds the first null row, whatever rowIndex says, as the reference
+    // does; a value boxed as another type than the column's finds nothing, without a device call (bowfind_test.go:31-32).  A failed
+    // device call (e.g. no device) finds nothing: the reference's signature has no error to carry it.
+    int Find(int colIndex, const Value &value) const { return FindNext(colIndex, 0, value); }
+    int FindNext(int colIndex, int rowIndex, const Value &value) const;
+    bool Contains(int colIndex, const Value &value) const { return Find(colIndex, value) != -1; }
 
 private:
     std::pair<BowPtr, Error> fill(int method, const std::vector<int> &colIndices) const;
@@ -576,6 +582,59 @@ inline std::pair<BowPtr, Error> Bow::Distinct(int colIndex) const {
     if (nd == 0) { o.length = 0; o.null_count = 0; o.type = c.type; }   // (nothing was written)
     auto out = std::make_shared<Bow>();
     out->cols.push_back(st.ToSeries(cols[colIndex].Name, o));
+    return {out, Error()};
+}
+
+inline int Bow::FindNext(int colIndex, int rowIndex, const Value &value) const {
+    if (colIndex < 0 || colIndex > NumCols() - 1 || rowIndex < 0) return -1;
+    const Type typ = ColumnType(colIndex);
+    uint64_t bits = 0;
+    if (value) {
+        if (typ == Type::Int64 && std::holds_alternative<int64_t>(*value)) { const int64_t x = std::get<int64_t>(*value); memcpy(&bits, &x, 8); }
+        else if (typ == Type::Float64 && std::holds_alternative<double>(*value)) { const double x = std::get<double>(*value); memcpy(&bits, &x, 8); }
+        else return -1;   // another type than the column's: Go's == on the boxed values is false on every row
+    }
+    const bowgpu_col c = ArrowCol(colIndex);
+    int64_t row = -1;
+    if (bowgpu_find_next(&c, rowIndex, value ? &bits : nullptr, &row)) return -1;
+    return (int)row;
+}
+
+// AppendBows: bowappend.go:11-103 (device).  No bows: a null pointer and no error; one bow: the bow itself.  Column names come from the
+// first bow (this mirror models no Arrow metadata).  Where the reference panics on bows of different schemas - a missing bow, another
+// number of columns - this returns an Error, as FilterV does.
+inline std::pair<BowPtr, Error> AppendBows(const std::vector<BowPtr> &bows) {
+    if (bows.empty()) return {nullptr, Error()};
+    if (bows.size() == 1) return {bows[0], Error()};
+    for (const BowPtr &b : bows)
+        if (!b || b->NumCols() != bows[0]->NumCols()) return {nullptr, Errorf("bow.AppendBows: bows have different schemas")};
+    const BowPtr &ref = bows[0];
+    const int ncols = ref->NumCols();
+    for (int ci = 0; ci < ncols; ci++)
+        for (const BowPtr &b : bows)   // bowappend.go:40-42
+            if (b->ColumnType(ci) != ref->ColumnType(ci))
+                return {nullptr, Errorf("incompatible types '" + TypeString(ref->ColumnType(ci)) + "' and '" + TypeString(b->ColumnType(ci)) + "'")};
+    std::vector<std::vector<bowgpu_col>> pieces;
+    std::vector<const bowgpu_col *> frames;
+    int64_t total = 0;
+    for (const BowPtr &b : bows) {
+        std::vector<bowgpu_col> c;
+        for (int i = 0; i < ncols; i++) c.push_back(b->ArrowCol(i));
+        pieces.push_back(std::move(c));
+        total += b->NumRows();
+    }
+    for (const auto &p : pieces) frames.push_back(p.data());
+    std::vector<detail::OutStore> st((size_t)ncols);
+    std::vector<bowgpu_out> o;
+    for (int i = 0; i < ncols; i++) o.push_back(st[(size_t)i].Make(total));
+    int32_t unchanged = 0;
+    const int rc = bowgpu_append(frames.data(), (int32_t)frames.size(), ncols, o.data(), &unchanged);
+    if (rc) return {nullptr, detail::AbiError(rc)};
+    auto out = std::make_shared<Bow>();
+    for (int i = 0; i < ncols; i++) {
+        if (total == 0) o[(size_t)i].type = (int32_t)ref->ColumnType(i);
+        out->cols.push_back(st[(size_t)i].ToSeries(ref->ColumnName(i), o[(size_t)i]));
+    }
     return {out, Error()};
 }
 

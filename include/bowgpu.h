@@ -37,7 +37,7 @@ extern "C" {
  * changed. */
 /* 10: bowgpu_filter_mask / bowgpu_compact / bowgpu_filter and the bowgpu_filter_pred struct added (Bow.Filter on the device); no existing
  * struct changed. */
-#define BOWGPU_ABI_VERSION 11
+#define BOWGPU_ABI_VERSION 12
 
 /* bow.Type (reference bowtypes.go:17-32) */
 enum {
@@ -640,6 +640,52 @@ int bowgpu_diff(const bowgpu_col *cols, int32_t ncols, const int32_t *col_idx, i
  * permutation; then bowgpu_filter_mask's workspace for the flags.  A column in order (sort.IsSorted) and without nulls takes only that
  * last part: it is read twice and nothing is sorted. */
 int bowgpu_distinct(const bowgpu_col *col, bowgpu_out *out, int64_t *n_distinct);
+
+/* ---- AppendBows / Bow.Find / FindNext / Contains -------------------------------------- */
+
+/* Putting a frame together from pieces and finding a row by value: AppendBows (bowappend.go:11-103) and Bow.Find / FindNext / Contains
+ * (bowfind.go:3-32).  The conventions are those of the sort, filter and frame-ops entry points: ONE device, any residency per piece and
+ * per output (BOWGPU_HOST staged through HBM at most 4 columns at a time, BOWGPU_HOST_PINNED and BOWGPU_DEVICE read where they lie),
+ * per-thread contexts and streams; bowgpu_set_devices does not apply.  Int64 / Float64 columns with or without validity at any Arrow
+ * offset (bit offsets that are no multiple of 8 included); Boolean / String anywhere: BOWGPU_ERR_UNSUPPORTED.  Fewer than 2^31 rows (in
+ * total, for the append); more is BOWGPU_ERR_UNSUPPORTED naming the limit.  For host-resident arguments all of this is decided before the
+ * device is touched; a valid call that has rows to move or to look at is BOWGPU_ERR_NO_DEVICE on a box without a GPU - no CPU fallback.
+ *   A COLUMN HAS NO NULLS TO LOOK AT when its validity is NULL or its null_count is stated as 0 (the rule of the block above).
+ *   THE METHOD (bow_amd/csrc/append.hip): the append divides the OUTPUT rows over workgroups; a row finds its piece by a search in the
+ * prefix array of the pieces' start rows (once per row for up to 4 columns; wave-uniform, and then free, when the 1024 rows of a wave
+ * lie in one piece), and a wave stores the 64-bit validity word of its 64 rows whole - however many pieces meet inside it.  The search
+ * lowers one device word to the lowest matching row by an integer atomic min, and a wave whose rows lie above that word leaves without
+ * loading.  Every output byte has one writer; the same call gives the same bytes and the same row. */
+
+/* AppendBows.  frames[f] points at the ncols columns of piece f; outs[ncols] receives the concatenation in piece order.  Every piece
+ * must have ncols columns of equal length within the piece (unequal: BOWGPU_ERR_ARG); a column's type must be the same in every piece,
+ * else BOWGPU_ERR_TYPE with the reference's text, "incompatible types 'int64' and 'float64'" (bowappend.go:40-42), and nothing is
+ * written.  nframes < 1: BOWGPU_ERR_ARG.  More than 2^18 = 262144 pieces: BOWGPU_ERR_UNSUPPORTED naming the limit.
+ *   nframes == 1 is where the reference returns its argument (bowappend.go:19-21): *unchanged = 1 and the outputs are NOT written -
+ * neither the buffers nor length / null_count / type.  Zero rows in total: length = 0, null_count = 0, type set, nothing else written,
+ * no device.  Pieces of zero rows are legal anywhere and contribute nothing (bowappend_test.go:29-55).
+ *   Otherwise outs[c].length is the total and type is set.  Values move as raw 64-bit payloads (a NaN's bits survive).  The validity bit
+ * of every row is set from the source, a source without a bitmap being all valid; NULL SLOTS HOLD 0 whatever the source held there; the
+ * padding bits of the last validity byte are clear; nothing is written past slot total - 1 or validity byte ceil(total / 8) - 1.
+ * null_count is set: when every piece of a column states its null_count (or has no nulls to look at, or is host-resident) the sum is the
+ * answer and nothing is counted on the device; otherwise the finished bitmap is counted.
+ *   CAPACITY: bowgpu_out.length on entry; too small is BOWGPU_ERR_ARG naming the size needed, and nothing is written.  An output that
+ * overlaps an input is not supported.
+ *   HBM WORKSPACE: the piece table (4 bytes a piece + 24 bytes a piece and column, at most 4 columns at a time), the staged copies of
+ * BOWGPU_HOST pieces, the device temporaries of host-resident outputs and the validity working copies (1/8 byte per row), at most 4
+ * columns at a time. */
+int bowgpu_append(const bowgpu_col *const *frames, int32_t nframes, int32_t ncols, bowgpu_out *outs, int32_t *unchanged);
+
+/* Bow.FindNext.  value is HOST memory: one item of the column's type (8 bytes), after the caller's type check - a value boxed as another
+ * type than the column's finds nothing and needs no call (bowfind_test.go:31-32).  *row is the first row >= row_start that is valid and
+ * whose value equals *value by Go's == on the boxed value: Int64 exactly; Float64 by IEEE == (a NaN in the column or as the value matches
+ * nothing, -0.0 equals +0.0); -1 when there is none.  row_start < 0: BOWGPU_ERR_ARG; row_start >= length: -1.
+ *   value == NULL is Go's nil: *row is the first NULL row of the column COUNTED FROM ROW 0 - row_start is ignored.  That is the
+ * reference's behaviour (bowfind.go:12-19 loops from 0 whatever rowIndex is), kept as it is.  The search reads bitmaps only.
+ *   Bow.Find is row_start = 0; Bow.Contains is *row != -1.
+ *   No device is needed for zero rows, a row_start past the end, a NaN value, and nil on a column with no nulls to look at.
+ *   HBM WORKSPACE: none beyond the staged copy of a BOWGPU_HOST column (for nil: of its bitmap alone). */
+int bowgpu_find_next(const bowgpu_col *col, int64_t row_start, const void *value, int64_t *row);
 
 /* ---- Parquet column chunk -> device column --------------------------- */
 
