@@ -28,7 +28,8 @@ MAX_FACTORS = 4
 FILTER_MAX_VALUES = 32
 FILTER_MAX_PREDS = 8
 CARRY_MAX_AGGS = 16
-ABI_VERSION = 12  # include/bowgpu.h BOWGPU_ABI_VERSION (asserted when the library is loaded)
+JOIN_INNER, JOIN_OUTER = 0, 1
+ABI_VERSION = 13  # include/bowgpu.h BOWGPU_ABI_VERSION (asserted when the library is loaded)
 
 ERR_NAMES = {
     -1: "INTERVAL", -2: "TS_TYPE", -3: "FIRST_TS_NULL", -4: "NO_AGG", -5: "KEEP_INTERVAL", -6: "BAD_COL",
@@ -144,6 +145,7 @@ SYMBOLS = [
     "bowgpu_filter_mask", "bowgpu_compact", "bowgpu_filter",
     "bowgpu_valid_mask", "bowgpu_drop_nils", "bowgpu_diff", "bowgpu_distinct",
     "bowgpu_append", "bowgpu_find_next",
+    "bowgpu_join_rows", "bowgpu_join",
 ]
 
 _lib = None
@@ -1075,6 +1077,57 @@ def find_next(col, value, row_start=0):
         ptr = v.ctypes.data_as(C.c_void_p)
     check(lib().bowgpu_find_next(C.byref(c), C.c_int64(row_start), ptr, C.byref(row)))
     return row.value
+
+
+def join_rows(left_key, right_key, kind, out_residency=HOST, capacity=None, count_only=False):
+    """bowgpu_join_rows -> (l_idx, r_idx, rows, pairs): the rows of Bow.InnerJoin / OuterJoin (kind: JOIN_INNER / JOIN_OUTER) of two key
+    Columns (both None: no common column, no rows; one None: ERR_ARG) as int64 row numbers, -1 for "no row" - numpy arrays (HOST) or DeviceBuffers (DEVICE) of
+    `capacity` slots (default: what the count call says).  count_only: NULL index buffers - (None, None, rows, pairs)"""
+    lk = None if left_key is None else left_key.c()
+    rk = None if right_key is None else right_key.c()
+    lp = None if lk is None else C.byref(lk)
+    rp = None if rk is None else C.byref(rk)
+    rows, pairs = C.c_int64(0), C.c_int64(0)
+    if count_only or capacity is None:
+        check(lib().bowgpu_join_rows(lp, rp, kind, None, None, C.c_int64(0), HOST, C.byref(rows), C.byref(pairs)))
+        if count_only:
+            return None, None, rows.value, pairs.value
+        capacity = rows.value
+    if out_residency == DEVICE:
+        bl, br = DeviceBuffer(max(capacity, 1) * 8), DeviceBuffer(max(capacity, 1) * 8)
+        pl, pr = C.c_void_p(bl.ptr), C.c_void_p(br.ptr)
+    else:
+        bl, br = np.full(max(capacity, 1), -7, dtype=np.int64), np.full(max(capacity, 1), -7, dtype=np.int64)
+        pl, pr = bl.ctypes.data_as(C.c_void_p), br.ctypes.data_as(C.c_void_p)
+    check(lib().bowgpu_join_rows(lp, rp, kind, pl, pr, C.c_int64(capacity), out_residency, C.byref(rows), C.byref(pairs)))
+    return bl, br, rows.value, pairs.value
+
+
+def join(left, left_key, right, right_key, kind, out_residency=HOST, outs=None, capacity=None):
+    """Bow.InnerJoin / OuterJoin (bowgpu_join) -> (list[OutColumn], rows): every left column, then every right column except the key
+    (left_key == right_key == -1: no common column - all right columns).  outs / capacity: the output columns or their slots; by
+    default the count call (join_rows) sizes them, and bowgpu_join then sorts the right key and probes a second time - a caller who
+    knows a bound, or holds outputs from an earlier call, passes `capacity` or `outs` and pays for one pass"""
+    n_outs = len(left) + len(right) - (0 if left_key == -1 and right_key == -1 else 1)
+    if outs is None:
+        if capacity is None:
+            lk = left[left_key] if 0 <= left_key < len(left) else None
+            rk = right[right_key] if 0 <= right_key < len(right) else None
+            if lk is not None and rk is not None:
+                capacity = join_rows(lk, rk, kind, count_only=True)[2]
+            elif left_key == -1 and right_key == -1:
+                capacity = (left[0].length if left else 0) + (right[0].length if right else 0) if kind == JOIN_OUTER else 0
+            else:
+                capacity = 0      # a key index outside its frame: bowgpu_join says so
+        outs = [OutColumn(capacity, out_residency) for _ in range(max(n_outs, 0))]
+    oarr = (Out * max(len(outs), 1))()
+    for i, o in enumerate(outs):
+        oarr[i] = o.c()
+    rows = C.c_int64(0)
+    check(lib().bowgpu_join(_cols(left), len(left), left_key, _cols(right), len(right), right_key, kind, oarr, C.byref(rows)))
+    for i, o in enumerate(outs):
+        o.absorb(oarr[i])
+    return outs, rows.value
 
 
 def out_as_column(out):

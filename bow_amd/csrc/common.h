@@ -740,6 +740,65 @@ struct FindArgs {
 };
 int launch_find(Ctx *c, const FindArgs &a);   // presets *result, searches, hands the word to host_result
 
+// join.hip: Bow.InnerJoin / OuterJoin - the left-ordered lookup join on one key (host side: join_api.cpp)
+struct JoinStats {                       // one device block of a call, zeroed by the host
+    unsigned long long pairs;            // length of the reference's commonRows
+    unsigned long long matched_left;     // left rows with at least one match
+    uint32_t nan, left_null;             // a NaN among the valid left keys; a null left key
+    uint32_t _pad[2];
+};
+// the rows of a mask pass as 32-bit row numbers, in row order: set bits -> set_rows (and values[row] -> set_values), clear bits of rows
+// below n -> clear_rows; each of the three may be nullptr.  mask / tile_base: as filter_scatter_kernel takes them (scanned counts)
+int launch_join_split_rows(Ctx *c, const unsigned long long *mask, const uint32_t *tile_base, int64_t n, const uint64_t *values, uint32_t *set_rows,
+                           uint64_t *set_values, uint32_t *clear_rows);
+struct JoinRightArgs {
+    const uint32_t *perm;                // nullptr: the keys are in order as they lie
+    const uint32_t *vrows;               // nullptr: the key has no null - position p is row p
+    const uint64_t *keys;                // the valid keys in row order (read when img_out is given)
+    uint64_t *img_out;                   // nullptr: the sort left the images
+    uint32_t *index;                     // [rn + rv]: the second part is written here
+    int64_t rn, rv;
+    int32_t is_float, _pad;
+};
+int launch_join_right_index(Ctx *c, const JoinRightArgs &a);
+struct JoinProbeArgs {
+    const uint64_t *keys;                // the left key
+    const uint32_t *vbits;               // nullptr: no nulls
+    int64_t vbit0, n;
+    const uint64_t *simg;                // [rv] sorted images of the right key's values
+    int64_t rn, rv;
+    uint32_t *first, *count, *out_count; // [n]: range in the right index; rows the left row becomes (the scan's input)
+    uint8_t *head;                       // [rv], zeroed: 1 at the first position of every matched group of equals
+    JoinStats *stats;
+    int32_t is_float, outer;
+};
+int launch_join_probe(Ctx *c, const JoinProbeArgs &a);
+// bit `row` of bits (zeroed, 32-bit words) |= the right row occurs in no pair; index / simg / head as above
+int launch_join_unmatched(Ctx *c, const uint32_t *index, const uint64_t *simg, const uint8_t *head, const JoinStats *stats, int64_t rn, int64_t rv,
+                          uint32_t *bits);
+struct JoinExpandArgs {
+    const uint32_t *starts;              // [n_left] scanned out_count; nullptr: left row i is output row i, without a right row
+    const uint32_t *first, *count, *index;
+    const uint32_t *tail_rows;           // [rows - rows_left] right rows of the tail; nullptr: 0, 1, 2, ...
+    int64_t n_left, rows_left, rows;
+    int32_t *out_l, *out_r;              // [rows]: -1 = no row
+    int32_t outer, _pad;
+};
+int launch_join_expand(Ctx *c, const JoinExpandArgs &a);
+struct JoinGatherArgs {
+    MoveCols cols;                       // out_valid: ceil(n / 64) words, every one stored whole by its wave
+    int64_t n;
+    const int32_t *idx;                  // [n] source row of cols, -1: none
+    const int32_t *idx2;                 // [n] source row of the second source (column key_slot only)
+    const uint64_t *values2;             // the key column's second source: the other frame's key
+    const uint32_t *vbits2;
+    int64_t vbit02;
+    int32_t key_slot, _pad;              // -1: no column of this launch has a second source
+    unsigned long long *null_counts;     // [kMoveCols], zeroed by the host
+};
+int launch_join_gather(Ctx *c, const JoinGatherArgs &a);
+int launch_join_widen(Ctx *c, const int32_t *idx, int64_t n, int64_t *out);   // (sign-extending: -1 stays -1)
+
 // generate.hip
 int launch_gen_dense(Ctx *c, int64_t row0, int64_t n, uint64_t seed, int64_t *ts, double *val);
 int launch_gen_sparse(Ctx *c, int64_t row0, int64_t n, uint64_t seed, int64_t *ts, double *val, uint8_t *validity);

@@ -15,6 +15,7 @@
 // stored whole; the at most two words a run shares with its neighbours are combined with atomic OR into a zeroed bitmap, so the bytes
 // are a function of the input, never of scheduling.
 #include "common.h"
+#include "wave_scan.h"
 
 namespace bowgpu {
 
@@ -157,15 +158,6 @@ __global__ __launch_bounds__(kThreads) void filter_stats_kernel(const uint32_t *
     }
 }
 
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(v, o);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-
 // A tile's time is a chain of memory latencies, not bytes (measured: the same 1.4 ms at selectivity 0.5 and 0.99, whatever the staging),
 // so the chain is kept short: the rows of ALL columns of the group are loaded together, half a tile at a time, and stored straight to
 // their slots - the kept rows of 64 consecutive rows go to consecutive slots, so a wave's store instruction writes one dense run.
@@ -179,11 +171,7 @@ __global__ __launch_bounds__(kThreads) void filter_scatter_kernel(FilterScatterA
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t tile0 = (int64_t)blockIdx.x * kTile;
     if (w == 0) {
-        const unsigned long long word = a.mask[(int64_t)blockIdx.x * kTileWords + lane];
-        const uint32_t pc = (uint32_t)__popcll(word);
-        const uint32_t incl = wave_inclusive_scan(pc, lane);
-        sword[lane] = word;
-        sbase[lane] = incl - pc;
+        const uint32_t incl = tile_word_bases(a.mask + (int64_t)blockIdx.x * kTileWords, lane, sword, sbase);
         if (lane == 63) sbase[kTileWords] = incl;
     }
     __syncthreads();

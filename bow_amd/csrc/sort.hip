@@ -10,6 +10,8 @@
 // Every count is an integer added in an order-free way (LDS / global atomics) or scanned in a fixed order; the position of a row
 // after a pass is a function of the keys alone, never of scheduling.
 #include "common.h"
+#include "key_image.h"
+#include "wave_scan.h"
 
 namespace bowgpu {
 
@@ -21,17 +23,6 @@ constexpr int kItems = 16;
 constexpr int kTile = kThreads * kItems;   // rows per scatter tile
 constexpr int kWaveRows = kTile / kWaves;  // consecutive rows of a tile that one wave ranks
 static_assert(kTile == kSortTileRows, "sort_api.cpp sizes the tile histograms with kSortTileRows");
-
-// The order of Buffer.Less (bowbuffer.go:126-139) as an unsigned 64-bit image: x ^ 2^63 for Int64; for Float64 the sign-flip map
-// with -0.0 folded onto +0.0 (equal under Less: they keep their input order).
-__device__ __forceinline__ uint64_t key_image(uint64_t bits, int is_float) {
-    if (is_float) {
-        if ((bits << 1) == 0) bits = 0;
-        return (bits >> 63) ? ~bits : bits ^ 0x8000000000000000ull;
-    }
-    return bits ^ 0x8000000000000000ull;
-}
-__device__ __forceinline__ bool is_nan_bits(uint64_t bits) { return (bits & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull; }
 
 // mode 0 / 1: src holds raw Int64 / Float64 keys; 2: images
 __device__ __forceinline__ uint64_t load_image(const uint64_t *src, int64_t i, int mode) {
@@ -50,14 +41,6 @@ __device__ __forceinline__ void count_digit(uint32_t *h, uint32_t d, bool valid,
     }
 }
 
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(v, o);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
 // exclusive scan of one value per thread over the workgroup (kThreads threads); wtot: kWaves LDS words
 __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *wtot, uint32_t *total) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;

@@ -2,7 +2,7 @@
 //
 // The reference is Go (no Go toolchain in this image), so the host side above include/bowgpu.h is
 // written in C++ with the SAME names, argument meaning and error strings as the reference:
-//   bow::Bow / Series / Type, AppendBows       <- bow.go, bowseries.go, bowtypes.go, bowappend.go, bowfind.go
+//   bow::Bow / Series / Type, AppendBows       <- bow.go, bowseries.go, bowtypes.go, bowappend.go, bowfind.go, bowjoin.go
 //   bow::rolling::IntervalRolling, Rolling, Options, Window, ColAggregation, NewColAggregation,
 //        ColInterpolation, NewColInterpolation  <- rolling/rolling.go, window.go, aggregation.go, interpolation.go
 //   bow::rolling::aggregation::{WindowStart,Sum,ArithmeticMean,Min,Max,Count,First,Last,Mode,IntegralStep,
@@ -280,9 +280,16 @@ class Bow : public std::enable_shared_from_this<Bow> {
     int Find(int colIndex, const Value &value) const { return FindNext(colIndex, 0, value); }
     int FindNext(int colIndex, int rowIndex, const Value &value) const;
     bool Contains(int colIndex, const Value &value) const { return Find(colIndex, value) != -1; }
+    // InnerJoin: bowjoin.go:12-62 ; OuterJoin: bowjoin.go:66-125 (device).  The common columns are found by name as getCommonCols does
+    // (bowjoin.go:128-155); none: no pair, an OuterJoin is all left rows then all right rows.  Where the reference panics - a name twice in
+    // the right bow, common columns of different types - this returns an Error with the reference's text.  More than one common column
+    // is an Error too: the device join takes one key per side.  (This mirror models no Arrow metadata.)
+    std::pair<BowPtr, Error> InnerJoin(const BowPtr &other) const { return join(other, BOWGPU_JOIN_INNER); }
+    std::pair<BowPtr, Error> OuterJoin(const BowPtr &other) const { return join(other, BOWGPU_JOIN_OUTER); }
 
 private:
     std::pair<BowPtr, Error> fill(int method, const std::vector<int> &colIndices) const;
+    std::pair<BowPtr, Error> join(const BowPtr &other, int32_t kind) const;
 };
 
 // NewBow: bow.go:109-116 (all series must have the same length)
@@ -635,6 +642,45 @@ inline std::pair<BowPtr, Error> AppendBows(const std::vector<BowPtr> &bows) {
         if (total == 0) o[(size_t)i].type = (int32_t)ref->ColumnType(i);
         out->cols.push_back(st[(size_t)i].ToSeries(ref->ColumnName(i), o[(size_t)i]));
     }
+    return {out, Error()};
+}
+
+inline std::pair<BowPtr, Error> Bow::join(const BowPtr &other, int32_t kind) const {
+    if (!other) return {nullptr, Errorf("non bow object passed as argument")};
+    const Bow &right = *other;
+    if (kind == BOWGPU_JOIN_INNER && (NumCols() == 0 || right.NumCols() == 0))   // bowjoin.go:19-29
+        return {NumCols() == 0 && right.NumCols() > 0 ? right.NewEmptySlice() : NewEmptySlice(), Error()};
+    int lk = -1, rk = -1, common = 0;
+    for (int i = 0; i < NumCols(); i++) {   // getCommonCols: bowjoin.go:128-155
+        int found = -1, n = 0;
+        for (int j = 0; j < right.NumCols(); j++)
+            if (right.cols[j].Name == cols[i].Name) { if (found < 0) found = j; n++; }
+        if (n == 0) continue;
+        if (n > 1) return {nullptr, Errorf("too many columns have the same name: right:" + right.String() + " left:" + String())};
+        if (right.cols[found].typ != cols[i].typ)
+            return {nullptr, Errorf("left and right bow on join columns are of incompatible types: " + cols[i].Name)};
+        if (common++ == 0) { lk = i; rk = found; }
+    }
+    if (common > 1) return {nullptr, Errorf("bow.Join: " + std::to_string(common) + " common columns, the device join takes one")};
+    std::vector<bowgpu_col> lc, rc;
+    for (int i = 0; i < NumCols(); i++) lc.push_back(ArrowCol(i));
+    for (int i = 0; i < right.NumCols(); i++) rc.push_back(right.ArrowCol(i));
+    int64_t rows = 0, pairs = 0;   // no input size bounds a join's rows: the count call sizes the outputs
+    if (common == 0) rows = kind == BOWGPU_JOIN_OUTER ? (int64_t)NumRows() + right.NumRows() : 0;
+    else if (int rcode = bowgpu_join_rows(&lc[(size_t)lk], &rc[(size_t)rk], kind, nullptr, nullptr, 0, BOWGPU_HOST, &rows, &pairs))
+        return {nullptr, detail::AbiError(rcode)};
+    std::vector<std::string> names;
+    for (int i = 0; i < NumCols(); i++) names.push_back(cols[i].Name);
+    for (int i = 0; i < right.NumCols(); i++)
+        if (i != rk) names.push_back(right.cols[i].Name);
+    std::vector<detail::OutStore> st(names.size());
+    std::vector<bowgpu_out> o(names.size() + 1);
+    for (size_t i = 0; i < names.size(); i++) o[i] = st[i].Make(rows);
+    int64_t got = 0;
+    const int rcode = bowgpu_join(lc.data(), NumCols(), lk, rc.data(), right.NumCols(), rk, kind, o.data(), &got);
+    if (rcode) return {nullptr, detail::AbiError(rcode)};
+    auto out = std::make_shared<Bow>();
+    for (size_t i = 0; i < names.size(); i++) out->cols.push_back(st[i].ToSeries(names[i], o[i]));
     return {out, Error()};
 }
 

@@ -37,7 +37,9 @@ extern "C" {
  * changed. */
 /* 10: bowgpu_filter_mask / bowgpu_compact / bowgpu_filter and the bowgpu_filter_pred struct added (Bow.Filter on the device); no existing
  * struct changed. */
-#define BOWGPU_ABI_VERSION 12
+/* 11: bowgpu_valid_mask / bowgpu_drop_nils / bowgpu_diff / bowgpu_distinct added; 12: bowgpu_append / bowgpu_find_next added; 13: bowgpu_join_rows /
+ * bowgpu_join added (Bow.InnerJoin / OuterJoin on the device); no existing struct changed. */
+#define BOWGPU_ABI_VERSION 13
 
 /* bow.Type (reference bowtypes.go:17-32) */
 enum {
@@ -686,6 +688,70 @@ int bowgpu_append(const bowgpu_col *const *frames, int32_t nframes, int32_t ncol
  *   No device is needed for zero rows, a row_start past the end, a NaN value, and nil on a column with no nulls to look at.
  *   HBM WORKSPACE: none beyond the staged copy of a BOWGPU_HOST column (for nil: of its bitmap alone). */
 int bowgpu_find_next(const bowgpu_col *col, int64_t row_start, const void *value, int64_t *row);
+
+/* ---- Bow.InnerJoin / Bow.OuterJoin ----------------------------------------------------- */
+
+/* Two frames that share one column put into one frame: Bow.InnerJoin (bowjoin.go:12-62, the fill :188-277) and Bow.OuterJoin
+ * (bowjoin.go:66-125, the fills :279-574) on ONE key column per side - the reference's single common column.  The conventions are those of
+ * the sort, filter, frame-ops and append entry points: ONE device, any residency per column and per output (BOWGPU_HOST staged through HBM
+ * at most 4 columns at a time, BOWGPU_HOST_PINNED and BOWGPU_DEVICE read where they lie), per-thread contexts and streams;
+ * bowgpu_set_devices does not apply.  Int64 / Float64 columns with or without validity at any Arrow offset (bit offsets that are no
+ * multiple of 8 included); Boolean / String anywhere: BOWGPU_ERR_UNSUPPORTED.  Columns of unequal length within a frame: BOWGPU_ERR_ARG.  A
+ * key index outside its frame: BOWGPU_ERR_BAD_COL.  Left rows, right rows and output rows are each fewer than 2^31; more is
+ * BOWGPU_ERR_UNSUPPORTED naming the limit (for the output rows: known after the probe, before anything is written).  For host-resident
+ * arguments every check above is made before the device is touched.
+ *   THE PAIR LIST is getCommonRows (bowjoin.go:161-186): every pair (l, r) of a left and a right row whose keys are equal, ordered by l,
+ * then by r.  KEY EQUALITY is Go's == on the boxed GetValue: Int64 exactly; Float64 by IEEE == (-0.0 equals +0.0); a null key equals a
+ * null key (nil == nil: bowjoin_test.go:418-463 and :626-668, "with only nils in common rows") and never a value.  A Float64 key with a NaN
+ * among its valid rows, on either side, is BOWGPU_ERR_UNSUPPORTED as for the sort and bowgpu_distinct: the reference matches it with
+ * nothing, and the caller keeps the reference path.  Key types that differ: BOWGPU_ERR_TYPE, "left and right bow on join columns are of
+ * incompatible types" (the reference's text up to the column name: the library knows no names).
+ *   BOWGPU_JOIN_INNER: one output row per pair, in pair order.  BOWGPU_JOIN_OUTER: every left row in left order - a left row with m >= 1
+ * matches becomes m rows, one per matching right row in ascending right row, a left row without a match one row whose right columns are
+ * null - then every right row that occurs in no pair, in right row order, its left columns null.  Row count = L + (pairs - distinct l in
+ * pairs) + (R - distinct r in pairs) (bowjoin.go:98-99).
+ *   COLUMNS of the result: every left column in order, then every right column except the key, in order.  The key column holds the left
+ * row's value; on a right-only row it takes the RIGHT key's value and validity (bowjoin.go:397: a right-only row with a null key keeps a
+ * null key).  NO COMMON COLUMN (left_key == right_key == -1; bowjoin_test.go:363-396 and :581-604): the pair list is empty, InnerJoin has
+ * zero rows, OuterJoin is all left rows then all right rows, and the result has all left columns then ALL right columns.  MORE THAN ONE
+ * COMMON COLUMN is not expressible - one key per side - and not offered: the caller keeps the reference path.
+ *   OUTPUTS are what Buffer.SetOrDropStrict leaves and what bowgpu_take leaves: values moved as raw 64-bit payloads (a NaN's bits in a
+ * VALUE column survive), validity bit and null_count set, length / type set, null slots 0, the padding bits of the last validity byte
+ * clear, nothing written past the slots produced.  CAPACITY is Filter's rule: bowgpu_out.length on entry; too small is BOWGPU_ERR_ARG
+ * naming the size needed, and nothing is written.  No input size bounds a join's row count: bowgpu_join_rows with NULL index buffers is the
+ * count that sizes the outputs.
+ *   NO DEVICE IS NEEDED when both frames have zero rows, when an InnerJoin has an empty side or no common column (zero rows), and for the
+ * COUNT of an OuterJoin with an empty side or no common column (L + R rows, no pair).  The ROWS of such an OuterJoin - the other side's
+ * rows padded with nulls - are the gather's work and need the device.  Every other valid call has rows to look at and is
+ * BOWGPU_ERR_NO_DEVICE on a box without a GPU - no CPU fallback.  The same call gives the same bytes.
+ *   HBM WORKSPACE, from the calling thread's scratch cache (exhaustion: BOWGPU_ERR_OOM).  Per RIGHT row: bowgpu_argsort's 24 bytes (none
+ * when the right key is already in order), 8 for the sorted key images, 4 for the index, 1 for the group-head flags, 1/4 for the two row
+ * bitmaps (+ 8 bytes per 4096 rows of tile records each); a right key with nulls adds 12 per valid row (its row numbers and values, in
+ * row order); an OuterJoin adds 4 per right-only row.  Per LEFT row: 12 bytes ((first, count) and the scanned start).  Per OUTPUT row: 8
+ * bytes (the pair, two 32-bit rows), + 16 when bowgpu_join_rows hands host-resident index buffers out.  + the staged copies of BOWGPU_HOST
+ * columns and the device temporaries of host-resident outputs: the two keys for the whole call, the others at most 4 columns at a time.
+ *   THE METHOD (bow_amd/csrc/join.hip): the output keeps the LEFT frame's order, so only the right key is sorted - its null rows are set
+ * aside in row order by bowgpu_valid_mask's pass, its values go through the stable radix argsort (a right key already in order, the
+ * time-series case, costs the one read that finds it so).  One lane per left row then finds the lower and upper bound of its key's image
+ * in the sorted images; the per-row counts are scanned; the right-only rows are the right rows whose group of equals no left row hit,
+ * flagged per right ROW and brought into row order by the mask pass; an expand pass over OUTPUT rows writes the (left row, right row)
+ * pairs and a gather with a "no row" index moves the columns. */
+#define BOWGPU_JOIN_INNER 0
+#define BOWGPU_JOIN_OUTER 1
+
+/* The rows of the join without moving a column.  *rows: output rows; *pairs: the length of the reference's commonRows.  Row j of the
+ * result comes from left row l_idx[j] and right row r_idx[j], -1 for "no row"; idx_capacity slots each (too few: BOWGPU_ERR_ARG naming
+ * the size, nothing written), residency as given.  l_idx == r_idx == NULL: the call is the count that sizes the outputs and writes
+ * nothing.  left_key == right_key == NULL stands for "no common column": the pair list is empty, and since the call cannot know the
+ * frames' lengths *rows is 0 for both kinds - the no-common-column join, whose OuterJoin has L + R rows, is bowgpu_join with -1 / -1.  ONE
+ * NULL key is BOWGPU_ERR_ARG: the rows of the side that is given alone would be a partial answer. */
+int bowgpu_join_rows(const bowgpu_col *left_key, const bowgpu_col *right_key, int32_t kind, int64_t *l_idx, int64_t *r_idx,
+                     int64_t idx_capacity, int32_t idx_residency, int64_t *rows, int64_t *pairs);
+
+/* The whole join in one call: outs[n_left + n_right - 1] (n_left + n_right without a common column), *rows output rows.  The index pairs
+ * stay in the workspace as 32-bit rows. */
+int bowgpu_join(const bowgpu_col *left_cols, int32_t n_left, int32_t left_key, const bowgpu_col *right_cols, int32_t n_right,
+                int32_t right_key, int32_t kind, bowgpu_out *outs, int64_t *rows);
 
 /* ---- Parquet column chunk -> device column --------------------------- */
 
