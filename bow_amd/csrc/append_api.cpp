@@ -115,19 +115,14 @@ int bowgpu_append(const bowgpu_col *const *frames, int32_t nframes, int32_t ncol
         return 0;
     }
     if (total == 0) {
-        for (int i = 0; i < ncols; i++) {
-            outs[i].length = 0;
-            outs[i].null_count = 0;
-            outs[i].type = frames[0][i].type;
-        }
+        for (int i = 0; i < ncols; i++) out_empty(&outs[i], frames[0][i].type);
         return 0;
     }
     BG_TRY(outs_checks(outs, ncols, total));
     if (ncols == 0) return 0;
     Ctx *c;
     BG_TRY(ctx_get(&c));
-    bool device_out = false;
-    for (int i = 0; i < ncols; i++) device_out |= outs[i].residency == BOWGPU_DEVICE;
+    const bool device_out = any_device_out(outs, ncols);
     PieceTable table(nframes);
     BG_HIP(hipEventRecord(c->ev0, c->stream));
     for (int g0 = 0; g0 < ncols; g0 += kMoveCols) {

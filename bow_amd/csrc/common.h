@@ -110,6 +110,7 @@ struct DevBuf {
     }
     ~DevBuf() { if (p) devbuf_release(p, cap); }
     int alloc(size_t n);
+    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
 // A column made device-resident: aliases the caller's pointers (BOWGPU_DEVICE) or owns an
@@ -178,6 +179,10 @@ int frame_cols_checks(const bowgpu_col *cols, int32_t ncols, int64_t n, bool res
 int outs_checks(const bowgpu_out *outs, int32_t ncols, int64_t slots);
 // a caller's side buffer (`what`: "index", "mask") on the device: as is, through its registration, or staged into *own
 int aux_in(Ctx *c, const void *p, size_t bytes, int32_t residency, const char *what, const void **dptr, DevBuf *own);
+// a device buffer as the only column of a frame without nulls (what the scatter and the argsort take)
+bowgpu_col device_col(const void *values, int64_t n, int32_t type);
+bool any_device_out(const bowgpu_out *outs, int32_t n);   // some output column is device-resident (the write epoch moves with the call)
+void out_empty(bowgpu_out *out, int32_t type);            // an output column of a result without rows
 // a result buffer handed to the caller: dst in device memory is src itself or gets a device-to-device copy (and the write epoch moves)
 int aux_out(Ctx *c, void *dst, const void *src, size_t bytes, int32_t residency);
 int synced(Ctx *c, int rc);            // rc - a failure only after the stream has drained: the call's kernels may still be running on its work buffers
@@ -620,6 +625,21 @@ struct GatherArgs {
     unsigned long long *null_counts;             // [kMoveCols], zeroed by the host
     uint32_t *bad;                               // |= 1: a caller's index outside [0, length)
 };
+// what the join's gather takes: an index of -1 is "no row" (a null output slot), and on such rows the column key_slot reads a second
+// source - the other frame's key - through idx2.  Passed to that instantiation alone: the other two take GatherArgs as it is
+struct GatherNoRowArgs : GatherArgs {
+    const int32_t *idx2;                         // [n_idx] source row of the second source, -1: none
+    const uint64_t *values2;
+    const uint32_t *vbits2;
+    int64_t vbit02;
+    int32_t key_slot, _pad;                      // -1: no column of this launch has a second source
+};
+// workgroups of a grid-stride kernel over n rows
+inline int64_t stream_grid(int64_t n, int threads) {
+    int64_t grid = (n + threads - 1) / threads;
+    if (grid > 256 * 8) grid = 256 * 8;
+    return grid < 1 ? 1 : grid;
+}
 // hist: [8][256] digit counts, flags: [0] not ascending, [1] NaN seen (both zeroed by the host); img_out: nullable
 int launch_sort_hist(Ctx *c, const uint64_t *key, int64_t n, int is_float, uint32_t *d_hist, uint32_t *d_flags, uint64_t *img_out);
 // one stable pass on digit `shift / 8`.  mode 0 / 1: src holds raw Int64 / Float64 keys, 2: images; src_idx == nullptr: row i carries index i.
@@ -631,12 +651,33 @@ struct SortWork {
     DevBuf keys[2], idx[2], tiles, sums;
     int cur = 0;                 // which of the two buffers holds the result
     int passes = 0;              // radix passes run (8 - passes: digits that are the same in every key)
-    const uint32_t *perm() const { return reinterpret_cast<const uint32_t *>(idx[cur].p); }
+    const uint32_t *perm() const { return idx[cur].as<const uint32_t>(); }
 };
 int argsort_device(Ctx *c, const bowgpu_col *key, const DevCol &dk, SortWork *w, int32_t *sorted);
-int launch_sort_widen(Ctx *c, const uint32_t *idx, int64_t n, int64_t *out);
-// exactly one of idx32 (the library's own permutation: trusted) / idx64 (a caller's indices: range-checked) is given
-int launch_gather(Ctx *c, const GatherArgs &a, const uint32_t *idx32, const int64_t *idx64);
+// out[i] = idx[i] as 64 bits: idx32 (row numbers) zero-extended, else idx32s sign-extended (-1 stays -1)
+int launch_widen(Ctx *c, const uint32_t *idx32, const int32_t *idx32s, int64_t n, int64_t *out);
+// The index of a gather, exactly one of three: u32 (the library's own permutation: trusted), i64 (a caller's indices: range-checked,
+// *bad), i32 (the join's: -1 = no row, else in range).  With i32, frame column key_col (-1: none) reads *key2 through i32_2 on the
+// rows where i32 says "no row"
+struct GatherIdx {
+    const uint32_t *u32 = nullptr;
+    const int64_t *i64 = nullptr;
+    const int32_t *i32 = nullptr, *i32_2 = nullptr;
+    int32_t key_col = -1;
+    const DevCol *key2 = nullptr;
+};
+// gather_kernel's instantiation for ix (the second-source fields of `a` are read with ix.i32 alone)
+int launch_gather(Ctx *c, const GatherNoRowArgs &a, const GatherIdx &ix);
+// sort_api.cpp, next to argsort_device: the host side of every gather (Sort, take, Distinct, Join).
+// the launch half of a gather of the columns `cols` (frame columns g0 ..) of `length` rows: the scratch words zeroed, the kernel, ev1
+// recorded behind it (no synchronise)
+int gather_enqueue(Ctx *c, char *scratch, const MoveCols &cols, int32_t g0, int64_t length, const GatherIdx &ix, int64_t n_idx);
+// ... over a prepared group, then the outputs' null counts and *bad (synchronises)
+int gather_launch(Ctx *c, const MoveGroup &g, int32_t g0, int64_t length, const GatherIdx &ix, int64_t n_idx, int64_t *nulls, bool *bad);
+// the columns of a frame, kMoveCols a launch, gathered through ix into outs.  *bad: an index outside the frame - nothing of that
+// group was handed out
+int gather_frame(Ctx *c, const bowgpu_col *cols, int32_t ncols, const StagedCols &have, const GatherIdx &ix, int64_t n_idx, bowgpu_out *outs,
+                 bool *bad);
 
 // exclusive scan of m 32-bit counts in place (their total below 2^32); sums: ceil(m / 4096) words of scratch
 int launch_scan_u32(Ctx *c, uint32_t *v, int64_t m, uint32_t *sums);
@@ -650,15 +691,19 @@ struct FilterPredDev {
     int32_t n_values, match_null, is_float, _pad;
     uint64_t set[BOWGPU_FILTER_MAX_VALUES];   // raw 64-bit payloads of the column's type; compared with wave-uniform operands
 };
-struct FilterMaskArgs {
-    int64_t n;
-    int32_t npreds, _pad;
-    const uint8_t *and_mask;             // nullable: bit i (LSB first) of byte i / 8; any alignment
+// what a mask pass leaves for filter_stats_kernel, the scan and filter_scatter_kernel (filter_mask_kernel and the kernels of frame_ops.hip)
+struct TileRecords {
     unsigned long long *mask;            // 64 * ceil(n / kFilterTileRows) words, every one stored (rows >= n: clear bits)
     uint32_t *tile_counts;               // ceil(n / kFilterTileRows)
     uint32_t *tile_spans;                // ... per tile: lowest | highest << 16 selected row of the tile (tile-relative)
     uint32_t *stats;                     // 4 words zeroed by the host (filter_stats_kernel)
     uint32_t *host_stats;                // registered host memory: receives [0] selected rows, [1] lowest, [2] highest selected row
+};
+struct FilterMaskArgs {
+    int64_t n;
+    int32_t npreds, _pad;
+    const uint8_t *and_mask;             // nullable: bit i (LSB first) of byte i / 8; any alignment
+    TileRecords t;
     FilterPredDev preds[BOWGPU_FILTER_MAX_PREDS];
 };
 struct FilterScatterArgs {
@@ -666,12 +711,6 @@ struct FilterScatterArgs {
     int64_t n;
     const unsigned long long *mask;      // as filter_mask_kernel left it
     const uint32_t *tile_base;           // the scanned tile counts
-};
-// what a mask pass leaves for filter_stats_kernel, the scan and filter_scatter_kernel (filter_mask_kernel and the kernels of frame_ops.hip)
-struct TileRecords {
-    unsigned long long *mask;            // 64 * ceil(n / kFilterTileRows) words, every one stored (rows >= n: clear bits)
-    uint32_t *tile_counts, *tile_spans;  // as in FilterMaskArgs
-    uint32_t *stats, *host_stats;
 };
 int launch_filter_mask(Ctx *c, const FilterMaskArgs &a);
 int launch_filter_stats(Ctx *c, const TileRecords &t, int64_t ntiles);   // (launch_filter_mask ends with it)
@@ -685,6 +724,9 @@ struct MaskWork {
 };
 int mask_work_prepare(Ctx *c, int64_t n, MaskWork *w, TileRecords *t);   // the buffers of a mask pass over n rows, its stats words zeroed
 int mask_work_collect(Ctx *c, MaskWork *w);                              // synchronises; selected / first / last
+// frame_ops_api.cpp: the rows of one column that hold a value, as a finished mask pass: its own validity through valid_mask_kernel,
+// the stats (w->selected), the tile counts scanned in place.  *t: the mask and the scanned counts, for the caller's scatter or split
+int valid_rows_scanned(Ctx *c, const DevCol &dk, MaskWork *w, TileRecords *t);
 int scatter_device(Ctx *c, const bowgpu_col *cols, int32_t ncols, int64_t n, MaskWork *w, bowgpu_out *outs);
 int mask_work_compact(Ctx *c, const bowgpu_col *cols, int32_t ncols, int64_t n, MaskWork *w, const char *mask_kernel, bowgpu_out *outs,
                       int64_t *first, int64_t *count, int32_t *contiguous);
@@ -785,19 +827,6 @@ struct JoinExpandArgs {
     int32_t outer, _pad;
 };
 int launch_join_expand(Ctx *c, const JoinExpandArgs &a);
-struct JoinGatherArgs {
-    MoveCols cols;                       // out_valid: ceil(n / 64) words, every one stored whole by its wave
-    int64_t n;
-    const int32_t *idx;                  // [n] source row of cols, -1: none
-    const int32_t *idx2;                 // [n] source row of the second source (column key_slot only)
-    const uint64_t *values2;             // the key column's second source: the other frame's key
-    const uint32_t *vbits2;
-    int64_t vbit02;
-    int32_t key_slot, _pad;              // -1: no column of this launch has a second source
-    unsigned long long *null_counts;     // [kMoveCols], zeroed by the host
-};
-int launch_join_gather(Ctx *c, const JoinGatherArgs &a);
-int launch_join_widen(Ctx *c, const int32_t *idx, int64_t n, int64_t *out);   // (sign-extending: -1 stays -1)
 
 // generate.hip
 int launch_gen_dense(Ctx *c, int64_t row0, int64_t n, uint64_t seed, int64_t *ts, double *val);

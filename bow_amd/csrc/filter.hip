@@ -86,7 +86,7 @@ __global__ __launch_bounds__(kThreads) void filter_mask_kernel(FilterMaskArgs a)
                 }
             }
             const unsigned long long word = __ballot(sel);
-            if (lane == 0) a.mask[(int64_t)blockIdx.x * kTileWords + wi] = word;   // (rows >= n: clear bits; every word of the tile is stored)
+            if (lane == 0) a.t.mask[(int64_t)blockIdx.x * kTileWords + wi] = word;   // (rows >= n: clear bits; every word of the tile is stored)
             if (word) {
                 cnt += (uint32_t)__popcll(word);
                 const uint32_t first = (uint32_t)(wi * 64 + __ffsll((long long)word) - 1), last = (uint32_t)(wi * 64 + 63 - __clzll((long long)word));
@@ -105,8 +105,8 @@ __global__ __launch_bounds__(kThreads) void filter_mask_kernel(FilterMaskArgs a)
             l = wlo[i] < l ? wlo[i] : l;
             h = whi[i] > h ? whi[i] : h;
         }
-        a.tile_counts[blockIdx.x] = total;
-        a.tile_spans[blockIdx.x] = l | (h << 16);   // (tile-relative, below 4096 each; meaningless where total == 0)
+        a.t.tile_counts[blockIdx.x] = total;
+        a.t.tile_spans[blockIdx.x] = l | (h << 16);   // (tile-relative, below 4096 each; meaningless where total == 0)
     }
 }
 
@@ -256,13 +256,7 @@ int launch_filter_stats(Ctx *c, const TileRecords &t, int64_t ntiles) {
 int launch_filter_mask(Ctx *c, const FilterMaskArgs &a) {
     const int64_t ntiles = (a.n + kTile - 1) / kTile;
     hipLaunchKernelGGL(filter_mask_kernel, dim3((unsigned)ntiles), dim3(kThreads), 0, c->stream, a);
-    TileRecords t;
-    t.mask = a.mask;
-    t.tile_counts = a.tile_counts;
-    t.tile_spans = a.tile_spans;
-    t.stats = a.stats;
-    t.host_stats = a.host_stats;
-    return launch_filter_stats(c, t, ntiles);
+    return launch_filter_stats(c, a.t, ntiles);
 }
 
 int launch_filter_scatter(Ctx *c, const FilterScatterArgs &a) {

@@ -63,13 +63,7 @@ int mask_device(Ctx *c, const bowgpu_col *cols, const bowgpu_filter_pred *preds,
         P.is_float = cols[col].type == BOWGPU_FLOAT64;
         if (P.n_values > 0) memcpy(P.set, preds[p].values, (size_t)P.n_values * 8);
     }
-    TileRecords t;
-    BG_TRY(mask_work_prepare(c, n, w, &t));
-    a.mask = t.mask;
-    a.tile_counts = t.tile_counts;
-    a.tile_spans = t.tile_spans;
-    a.stats = t.stats;
-    a.host_stats = t.host_stats;
+    BG_TRY(mask_work_prepare(c, n, w, &a.t));
     BG_HIP(hipEventRecord(c->ev0, c->stream));
     BG_TRY(launch_filter_mask(c, a));
     BG_HIP(hipEventRecord(c->ev1, c->stream));
@@ -82,8 +76,8 @@ int scatter_launch(Ctx *c, const MoveGroup &g, int64_t n, const MaskWork &w, uns
     FilterScatterArgs a;
     a.cols = g.cols;
     a.n = n;
-    a.mask = reinterpret_cast<const unsigned long long *>(w.mask.p);
-    a.tile_base = reinterpret_cast<const uint32_t *>(w.tiles.p);
+    a.mask = w.mask.as<const unsigned long long>();
+    a.tile_base = w.tiles.as<const uint32_t>();
     for (int i = 0; i < g.cols.ncols; i++) BG_HIP(hipMemsetAsync(g.cols.out_valid[i], 0, (size_t)((count + 63) >> 6) * 8, c->stream));
     BG_TRY(launch_filter_scatter(c, a));
     BG_HIP(hipEventRecord(c->ev1, c->stream));
@@ -111,9 +105,9 @@ int mask_work_prepare(Ctx *c, int64_t n, MaskWork *w, TileRecords *t) {
     BG_TRY(w->mask.alloc((size_t)ntiles * (kFilterTileRows / 8)));
     BG_TRY(w->tiles.alloc((size_t)ntiles * 4));
     BG_TRY(w->spans.alloc((size_t)ntiles * 4));
-    t->mask = reinterpret_cast<unsigned long long *>(w->mask.p);
-    t->tile_counts = reinterpret_cast<uint32_t *>(w->tiles.p);
-    t->tile_spans = reinterpret_cast<uint32_t *>(w->spans.p);
+    t->mask = w->mask.as<unsigned long long>();
+    t->tile_counts = w->tiles.as<uint32_t>();
+    t->tile_spans = w->spans.as<uint32_t>();
     t->stats = reinterpret_cast<uint32_t *>(s + kScrFlags);
     void *back;   // the context's registered block: filter_stats_kernel stores the three numbers there itself
     BG_TRY(ctx_pinned(c, 16384, &back));
@@ -139,7 +133,7 @@ int scatter_device(Ctx *c, const bowgpu_col *cols, int32_t ncols, int64_t n, Mas
     // the context's events: from the scan to the last scatter launch.  For a frame of up to kMoveCols device-resident columns that is
     // the scan, the memsets and the scatter kernel; with more groups or host-resident columns their staging and copies fall inside
     BG_HIP(hipEventRecord(c->ev0, c->stream));
-    BG_TRY(launch_scan_u32(c, reinterpret_cast<uint32_t *>(w->tiles.p), ntiles, reinterpret_cast<uint32_t *>(w->sums.p)));
+    BG_TRY(launch_scan_u32(c, w->tiles.as<uint32_t>(), ntiles, w->sums.as<uint32_t>()));
     for (int g0 = 0; g0 < ncols; g0 += kMoveCols) {
         MoveGroup g;
         BG_TRY(move_group_prepare(c, cols, ncols, g0, w->pcols, outs, count, &g));
@@ -164,12 +158,10 @@ int mask_work_compact(Ctx *c, const bowgpu_col *cols, int32_t ncols, int64_t n, 
         kernel_done(c, mask_kernel);
         return 0;
     }
-    bool device_out = false;
-    for (int i = 0; i < ncols; i++) {
+    for (int i = 0; i < ncols; i++)
         if (outs[i].length < w->selected)
             return fail(BOWGPU_ERR_ARG, "output column %d has %lld slots, %lld needed", i, (long long)outs[i].length, (long long)w->selected);
-        device_out |= outs[i].residency == BOWGPU_DEVICE;
-    }
+    const bool device_out = any_device_out(outs, ncols);
     BG_TRY(synced(c, scatter_device(c, cols, ncols, n, w, outs)));
     BG_HIP(hipStreamSynchronize(c->stream));
     if (device_out) device_write_epoch_bump();

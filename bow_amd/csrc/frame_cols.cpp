@@ -1,6 +1,8 @@
-// frame_cols.cpp — the host layer under the frame-level operations (sort_api.cpp, filter_api.cpp): argument checks of a frame and its
-// output columns, a caller's side buffers in and out, and the staging of the columns of a frame, kMoveCols a launch, around the kernel
-// that moves their rows.  No kernel is launched here.
+// frame_cols.cpp — the host layer under the frame-level operations (the *_api.cpp files of Sort, Filter, DropNils / Diff / Distinct,
+// Append / Find and Join): argument checks of a frame and its output columns, a caller's side buffers in and out, and the staging of
+// the columns of a frame, kMoveCols a launch, around the kernel that moves their rows.  No kernel is launched here.
+#include <string.h>
+
 #include "common.h"
 
 namespace bowgpu {
@@ -43,6 +45,28 @@ int outs_checks(const bowgpu_out *outs, int32_t ncols, int64_t slots) {
         if ((slots < 0 ? o.length : slots) > 0 && (!o.values || !o.validity)) return fail(BOWGPU_ERR_ARG, "output column lacks a values or validity buffer");
     }
     return 0;
+}
+
+bowgpu_col device_col(const void *values, int64_t n, int32_t type) {
+    bowgpu_col k;
+    memset(&k, 0, sizeof k);
+    k.values = values;
+    k.length = n;
+    k.type = type;
+    k.residency = BOWGPU_DEVICE;
+    return k;
+}
+
+bool any_device_out(const bowgpu_out *outs, int32_t n) {
+    bool device_out = false;
+    for (int i = 0; i < n; i++) device_out |= outs[i].residency == BOWGPU_DEVICE;
+    return device_out;
+}
+
+void out_empty(bowgpu_out *out, int32_t type) {
+    out->length = 0;
+    out->null_count = 0;
+    out->type = type;
 }
 
 int aux_in(Ctx *c, const void *p, size_t bytes, int32_t residency, const char *what, const void **dptr, DevBuf *own) {

@@ -92,68 +92,41 @@ int diff_launch(Ctx *c, const MoveGroup &g, const bowgpu_col *scols, int32_t g0,
     return 0;
 }
 
-// a device buffer as the only column of a frame without nulls (what the scatter and the argsort take)
-bowgpu_col device_col(const void *values, int64_t n, int32_t type) {
-    bowgpu_col k;
-    memset(&k, 0, sizeof k);
-    k.values = values;
-    k.length = n;
-    k.type = type;
-    k.residency = BOWGPU_DEVICE;
-    return k;
-}
-
-// the column's valid rows, in row order, into *vals (its own validity through valid_mask_kernel, the scan, the scatter); *m of them
+// the column's valid rows, in row order, into *vals (the scanned mask of its own validity, then the scatter); *m of them
 int compact_valid_device(Ctx *c, const DevCol &dk, MaskWork *w, DevBuf *vals, DevBuf *bits, int64_t *m) {
-    const int64_t n = dk.length, ntiles = (n + kFilterTileRows - 1) / kFilterTileRows;
-    ValidMaskArgs a;
-    memset(&a, 0, sizeof a);
-    a.n = n;
-    a.ncols = 1;
-    a.vbits[0] = dk.vbits;
-    a.vbit0[0] = dk.vbit0;
-    a.vwords[0] = dk.vwords;
-    BG_TRY(mask_work_prepare(c, n, w, &a.t));
-    BG_TRY(launch_valid_mask(c, a));
-    BG_TRY(launch_filter_stats(c, a.t, ntiles));
-    BG_TRY(mask_work_collect(c, w));
+    TileRecords t;
+    BG_TRY(valid_rows_scanned(c, dk, w, &t));
     *m = w->selected;
     if (*m == 0) return 0;
     BG_TRY(vals->alloc((size_t)*m * 8));
     BG_TRY(bits->alloc((size_t)((*m + 63) >> 6) * 8));
-    BG_TRY(w->sums.alloc((size_t)((ntiles + 4095) / 4096) * 4));
-    BG_TRY(launch_scan_u32(c, reinterpret_cast<uint32_t *>(w->tiles.p), ntiles, reinterpret_cast<uint32_t *>(w->sums.p)));
     FilterScatterArgs s;
     memset(&s, 0, sizeof s);
     s.cols.ncols = 1;
     s.cols.values[0] = reinterpret_cast<const uint64_t *>(dk.values);   // (every kept row is valid: the bitmap is not read again)
-    s.cols.out_values[0] = reinterpret_cast<uint64_t *>(vals->p);
-    s.cols.out_valid[0] = reinterpret_cast<unsigned long long *>(bits->p);
-    s.n = n;
-    s.mask = a.t.mask;
-    s.tile_base = a.t.tile_counts;
+    s.cols.out_values[0] = vals->as<uint64_t>();
+    s.cols.out_valid[0] = bits->as<unsigned long long>();
+    s.n = dk.length;
+    s.mask = t.mask;
+    s.tile_base = t.tile_counts;
     BG_HIP(hipMemsetAsync(bits->p, 0, bits->bytes, c->stream));
     return launch_filter_scatter(c, s);
 }
 
-// keys[perm[j]] for j < m into *vals: the gather of Bow.SortByCol over one column without nulls
+// keys[perm[j]] for j < m into *vals: the gather of Bow.SortByCol over one column without nulls (no synchronise)
 int gather_keys_device(Ctx *c, const uint64_t *keys, int64_t m, const uint32_t *perm, DevBuf *vals, DevBuf *bits) {
     BG_TRY(vals->alloc((size_t)m * 8));
     BG_TRY(bits->alloc((size_t)((m + 63) >> 6) * 8));
     void *scr;
     BG_TRY(ctx_scratch(c, kScrBytes, &scr));
-    char *s = reinterpret_cast<char *>(scr);
-    GatherArgs a;
-    memset(&a, 0, sizeof a);
-    a.cols.ncols = 1;
-    a.cols.values[0] = keys;
-    a.cols.out_values[0] = reinterpret_cast<uint64_t *>(vals->p);
-    a.cols.out_valid[0] = reinterpret_cast<unsigned long long *>(bits->p);
-    a.n_idx = a.length = m;
-    a.null_counts = reinterpret_cast<unsigned long long *>(s + kScrNulls);
-    a.bad = reinterpret_cast<uint32_t *>(s + kScrFlags) + 2;
-    BG_HIP(hipMemsetAsync(s + kScrFlags, 0, 16 + 8 * kMoveCols, c->stream));
-    return launch_gather(c, a, perm, nullptr);
+    MoveCols cols = MoveCols();
+    cols.ncols = 1;
+    cols.values[0] = keys;
+    cols.out_values[0] = vals->as<uint64_t>();
+    cols.out_valid[0] = bits->as<unsigned long long>();
+    GatherIdx ix;
+    ix.u32 = perm;
+    return gather_enqueue(c, reinterpret_cast<char *>(scr), cols, 0, m, ix, m);
 }
 
 int distinct_device(Ctx *c, const bowgpu_col *col, bowgpu_out *out, int64_t *n_distinct) {
@@ -172,7 +145,7 @@ int distinct_device(Ctx *c, const bowgpu_col *col, bowgpu_out *out, int64_t *n_d
     if (dk.vbits) {
         BG_TRY(synced(c, compact_valid_device(c, dk, &vw, &cvals, &cbits, &m)));
         if (m == 0) return 0;
-        keys = reinterpret_cast<const uint64_t *>(cvals.p);
+        keys = cvals.as<const uint64_t>();
         key = device_col(keys, m, col->type);
         ck.values = keys;
         ck.length = m;
@@ -188,7 +161,7 @@ int distinct_device(Ctx *c, const bowgpu_col *col, bowgpu_out *out, int64_t *n_d
     BG_TRY(rc);
     if (!sorted) {
         BG_TRY(synced(c, gather_keys_device(c, keys, m, sw.perm(), &gvals, &gbits)));
-        keys = reinterpret_cast<const uint64_t *>(gvals.p);
+        keys = gvals.as<const uint64_t>();
     }
     TileRecords t;
     BG_TRY(synced(c, mask_work_prepare(c, m, &tw, &t)));
@@ -208,6 +181,29 @@ int distinct_device(Ctx *c, const bowgpu_col *col, bowgpu_out *out, int64_t *n_d
 }
 
 }  // namespace
+
+namespace bowgpu {
+
+int valid_rows_scanned(Ctx *c, const DevCol &dk, MaskWork *w, TileRecords *t) {
+    const int64_t n = dk.length, ntiles = (n + kFilterTileRows - 1) / kFilterTileRows;
+    ValidMaskArgs a;
+    memset(&a, 0, sizeof a);
+    a.n = n;
+    a.ncols = 1;
+    a.vbits[0] = dk.vbits;
+    a.vbit0[0] = dk.vbit0;
+    a.vwords[0] = dk.vwords;
+    BG_TRY(mask_work_prepare(c, n, w, &a.t));
+    BG_TRY(launch_valid_mask(c, a));
+    BG_TRY(launch_filter_stats(c, a.t, ntiles));
+    BG_TRY(mask_work_collect(c, w));
+    *t = a.t;
+    if (w->selected == 0) return 0;   // (the counts are all 0 and so is their scan: nothing is left running behind the synchronise)
+    BG_TRY(w->sums.alloc((size_t)((ntiles + 4095) / 4096) * 4));
+    return launch_scan_u32(c, w->tiles.as<uint32_t>(), ntiles, w->sums.as<uint32_t>());
+}
+
+}  // namespace bowgpu
 
 extern "C" {
 
@@ -279,11 +275,7 @@ int bowgpu_diff(const bowgpu_col *cols, int32_t ncols, const int32_t *col_idx, i
     BG_TRY(outs_checks(outs, nsel, -1));
     BG_TRY(outs_checks(outs, nsel, n));
     if (n == 0) {
-        for (int i = 0; i < nsel; i++) {
-            outs[i].length = 0;
-            outs[i].null_count = 0;
-            outs[i].type = cols[sel[(size_t)i]].type;
-        }
+        for (int i = 0; i < nsel; i++) out_empty(&outs[i], cols[sel[(size_t)i]].type);
         return 0;
     }
     if (nsel == 0) return 0;
@@ -291,8 +283,7 @@ int bowgpu_diff(const bowgpu_col *cols, int32_t ncols, const int32_t *col_idx, i
     BG_TRY(ctx_get(&c));
     std::vector<bowgpu_col> scols;
     for (int32_t i : sel) scols.push_back(uncounted(cols[i]));
-    bool device_out = false;
-    for (int i = 0; i < nsel; i++) device_out |= outs[i].residency == BOWGPU_DEVICE;
+    const bool device_out = any_device_out(outs, nsel);
     StagedCols none_staged;
     BG_HIP(hipEventRecord(c->ev0, c->stream));
     for (int g0 = 0; g0 < nsel; g0 += kMoveCols) {

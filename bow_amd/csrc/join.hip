@@ -19,10 +19,9 @@
 //   join_expand_kernel        work divided over OUTPUT rows in tiles of 4096, as append_kernel's: a row finds its left row as the last
 //                             scanned start <= the row; the wave looks its first and last row up with scalar loads and searches
 //                             nothing when both fall into one left row or into a run of count-1 rows; the pair is two 32-bit words
-//   join_gather_kernel        out[j] = idx[j] >= 0 ? col[idx[j]] : null for up to kMoveCols columns; the key column reads the other
-//                             frame's key where its own index says "no row".  gather_kernel's shape (a wave ballots its 64 rows and
-//                             stores the validity word whole, nulls popcounted per wave) with a "no row" index and a second source;
-//                             kept here so that gather_kernel stays the same machine code for the sort and bowgpu_take
+//
+// The rows themselves are moved by sort.hip's gather_kernel, in its <int32_t, true> form: an index of -1 is "no row" and gives a null
+// slot, and the key column reads the other frame's key where its own index says so.
 //
 // Every count is an integer added in an order-free way or scanned in a fixed order; every output byte has one writer or receives the
 // same value from all of them: the same call gives the same bytes.
@@ -41,12 +40,6 @@ constexpr int kTileWords = kTile / 64;
 constexpr int kWaveWords = kTileWords / kWaves;
 constexpr int kWaveRows = kTile / kWaves;
 static_assert(kTileWords == 64, "tile_word_bases scans a tile's word counts with one wave");
-
-int64_t stream_grid(int64_t n) {
-    int64_t grid = (n + kThreads - 1) / kThreads;
-    if (grid > 256 * 8) grid = 256 * 8;
-    return grid < 1 ? 1 : grid;
-}
 
 // first position in s[0, n) whose image is >= x (lo given: the search starts there)
 __device__ __forceinline__ uint32_t lower_bound(const uint64_t *__restrict__ s, uint32_t lo, uint32_t n, uint64_t x) {
@@ -220,57 +213,6 @@ __global__ __launch_bounds__(kThreads) void join_expand_kernel(JoinExpandArgs a)
     }
 }
 
-__global__ __launch_bounds__(kThreads) void join_gather_kernel(JoinGatherArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int64_t stride = (int64_t)gridDim.x * kThreads;
-    const int64_t rounds = (a.n + stride - 1) / stride;
-    uint32_t nulls[kMoveCols] = {};
-    int64_t j = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    for (int64_t r = 0; r < rounds; r++, j += stride) {   // (every lane runs every round: the ballots need whole waves)
-        const bool in = j < a.n;
-        int32_t p = -1, p2 = -1;
-        if (in) {
-            p = a.idx[j];
-            if (a.key_slot >= 0 && p < 0) p2 = a.idx2[j];
-        }
-#pragma unroll
-        for (int c = 0; c < kMoveCols; c++) {
-            if (c < a.cols.ncols) {
-                const bool second = c == a.key_slot && p < 0;
-                const uint64_t *vals = second ? a.values2 : a.cols.values[c];
-                const uint32_t *vb = second ? a.vbits2 : a.cols.vbits[c];
-                const int64_t row = second ? p2 : p;
-                bool valid = in && row >= 0;
-                uint64_t v = 0;
-                if (valid && vb) {
-                    const int64_t bit = (second ? a.vbit02 : a.cols.vbit0[c]) + row;
-                    valid = (vb[bit >> 5] >> (bit & 31)) & 1u;
-                }
-                if (valid) v = vals[row];
-                if (in) a.cols.out_values[c][j] = v;   // a null slot holds 0
-                const unsigned long long word = __ballot(valid);
-                const unsigned long long rows = __ballot(in);
-                if (lane == 0 && rows) {
-                    // whole 64-bit words, ceil(n / 64) of them: at most 8 * ceil(n / 64) <= ((ceil(n / 8) + 3) & ~3) + 4 bytes, which is
-                    // what devout_prepare gives every output's validity working copy (equal when n % 64 is 1 .. 32)
-                    a.cols.out_valid[c][j >> 6] = word;   // (rows >= n: clear bits)
-                    nulls[c] += (uint32_t)__popcll(rows & ~word);
-                }
-            }
-        }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < kMoveCols; c++)
-            if (c < a.cols.ncols && nulls[c]) atomicAdd(&a.null_counts[c], (unsigned long long)nulls[c]);
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void join_widen_kernel(const int32_t *idx, int64_t n, int64_t *out) {
-    const int64_t stride = (int64_t)gridDim.x * kThreads;
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) out[i] = (int64_t)idx[i];
-}
-
 }  // namespace
 
 int launch_join_split_rows(Ctx *c, const unsigned long long *mask, const uint32_t *tile_base, int64_t n, const uint64_t *values, uint32_t *set_rows,
@@ -283,20 +225,20 @@ int launch_join_split_rows(Ctx *c, const unsigned long long *mask, const uint32_
 }
 
 int launch_join_right_index(Ctx *c, const JoinRightArgs &a) {
-    hipLaunchKernelGGL(join_right_index_kernel, dim3((unsigned)stream_grid(a.rv)), dim3(kThreads), 0, c->stream, a);
+    hipLaunchKernelGGL(join_right_index_kernel, dim3((unsigned)stream_grid(a.rv, kThreads)), dim3(kThreads), 0, c->stream, a);
     BG_HIP(hipGetLastError());
     return 0;
 }
 
 int launch_join_probe(Ctx *c, const JoinProbeArgs &a) {
-    hipLaunchKernelGGL(join_probe_kernel, dim3((unsigned)stream_grid(a.n)), dim3(kThreads), 0, c->stream, a);
+    hipLaunchKernelGGL(join_probe_kernel, dim3((unsigned)stream_grid(a.n, kThreads)), dim3(kThreads), 0, c->stream, a);
     BG_HIP(hipGetLastError());
     return 0;
 }
 
 int launch_join_unmatched(Ctx *c, const uint32_t *index, const uint64_t *simg, const uint8_t *head, const JoinStats *stats, int64_t rn, int64_t rv,
                           uint32_t *bits) {
-    hipLaunchKernelGGL(join_unmatched_kernel, dim3((unsigned)stream_grid(rn + rv)), dim3(kThreads), 0, c->stream, index, simg, head, stats, rn, rv, bits);
+    hipLaunchKernelGGL(join_unmatched_kernel, dim3((unsigned)stream_grid(rn + rv, kThreads)), dim3(kThreads), 0, c->stream, index, simg, head, stats, rn, rv, bits);
     BG_HIP(hipGetLastError());
     return 0;
 }
@@ -304,18 +246,6 @@ int launch_join_unmatched(Ctx *c, const uint32_t *index, const uint64_t *simg, c
 int launch_join_expand(Ctx *c, const JoinExpandArgs &a) {
     const int64_t ntiles = (a.rows + kTile - 1) / kTile;
     hipLaunchKernelGGL(join_expand_kernel, dim3((unsigned)ntiles), dim3(kThreads), 0, c->stream, a);
-    BG_HIP(hipGetLastError());
-    return 0;
-}
-
-int launch_join_gather(Ctx *c, const JoinGatherArgs &a) {
-    hipLaunchKernelGGL(join_gather_kernel, dim3((unsigned)stream_grid(a.n)), dim3(kThreads), 0, c->stream, a);
-    BG_HIP(hipGetLastError());
-    return 0;
-}
-
-int launch_join_widen(Ctx *c, const int32_t *idx, int64_t n, int64_t *out) {
-    hipLaunchKernelGGL(join_widen_kernel, dim3((unsigned)stream_grid(n)), dim3(kThreads), 0, c->stream, idx, n, out);
     BG_HIP(hipGetLastError());
     return 0;
 }

@@ -25,16 +25,6 @@ struct JoinWork {
     bool probed = false;       // false: no pair list (an empty side, no common column) - identity rows
 };
 
-bowgpu_col device_col(const void *values, int64_t n, int32_t type) {
-    bowgpu_col k;
-    memset(&k, 0, sizeof k);
-    k.values = values;
-    k.length = n;
-    k.type = type;
-    k.residency = BOWGPU_DEVICE;
-    return k;
-}
-
 int side_limit(int64_t n, const char *side) {
     if (n >= kJoinMaxRows)
         return fail(BOWGPU_ERR_UNSUPPORTED, "the %s frame has %lld rows: the device join serves fewer than 2^31 = 2147483648 rows", side, (long long)n);
@@ -74,27 +64,14 @@ int right_side(Ctx *c, const bowgpu_col *rkey, JoinWork *w) {
     const uint64_t *keys = reinterpret_cast<const uint64_t *>(w->rk.values);
     const uint32_t *vrows = nullptr;
     if (w->rn > 0) {   // the validity mask, its scan, and the rows of both kinds with the values of the valid ones
-        const int64_t ntiles = (r + kFilterTileRows - 1) / kFilterTileRows;
-        ValidMaskArgs a;
-        memset(&a, 0, sizeof a);
-        a.n = r;
-        a.ncols = 1;
-        a.vbits[0] = w->rk.vbits;
-        a.vbit0[0] = w->rk.vbit0;
-        a.vwords[0] = w->rk.vwords;
-        BG_TRY(mask_work_prepare(c, r, &w->vw, &a.t));
-        BG_TRY(launch_valid_mask(c, a));
-        BG_TRY(launch_filter_stats(c, a.t, ntiles));
-        BG_TRY(mask_work_collect(c, &w->vw));
+        TileRecords t;
+        BG_TRY(valid_rows_scanned(c, w->rk, &w->vw, &t));
         if (w->vw.selected != w->rv) return fail(BOWGPU_ERR_ARG, "right join column states %lld nulls, its bitmap has %lld", (long long)w->rn, (long long)(r - w->vw.selected));
-        BG_TRY(w->vw.sums.alloc((size_t)((ntiles + 4095) / 4096) * 4));
-        BG_TRY(launch_scan_u32(c, reinterpret_cast<uint32_t *>(w->vw.tiles.p), ntiles, reinterpret_cast<uint32_t *>(w->vw.sums.p)));
         BG_TRY(w->vrows.alloc((size_t)(w->rv > 0 ? w->rv : 1) * 4));
         BG_TRY(w->ckeys.alloc((size_t)(w->rv > 0 ? w->rv : 1) * 8));
-        BG_TRY(launch_join_split_rows(c, a.t.mask, a.t.tile_counts, r, keys, reinterpret_cast<uint32_t *>(w->vrows.p),
-                                      reinterpret_cast<uint64_t *>(w->ckeys.p), reinterpret_cast<uint32_t *>(w->index.p)));
-        keys = reinterpret_cast<const uint64_t *>(w->ckeys.p);
-        vrows = reinterpret_cast<const uint32_t *>(w->vrows.p);
+        BG_TRY(launch_join_split_rows(c, t.mask, t.tile_counts, r, keys, w->vrows.as<uint32_t>(), w->ckeys.as<uint64_t>(), w->index.as<uint32_t>()));
+        keys = w->ckeys.as<const uint64_t>();
+        vrows = w->vrows.as<const uint32_t>();
     }
     if (w->rv == 0) return 0;
     int32_t sorted = 0;
@@ -117,13 +94,13 @@ int right_side(Ctx *c, const bowgpu_col *rkey, JoinWork *w) {
     memset(&a, 0, sizeof a);
     a.vrows = vrows;
     a.keys = keys;
-    a.index = reinterpret_cast<uint32_t *>(w->index.p);
+    a.index = w->index.as<uint32_t>();
     a.rn = w->rn;
     a.rv = w->rv;
     a.is_float = rkey->type == BOWGPU_FLOAT64;
     if (sorted) {   // a key already in order cost the one read that found it so: the images are made here
         BG_TRY(w->simg.alloc((size_t)w->rv * 8));
-        a.img_out = reinterpret_cast<uint64_t *>(w->simg.p);
+        a.img_out = w->simg.as<uint64_t>();
     } else {
         a.perm = w->sw.perm();
     }
@@ -131,7 +108,7 @@ int right_side(Ctx *c, const bowgpu_col *rkey, JoinWork *w) {
 }
 
 const uint64_t *sorted_images(const JoinWork &w) {
-    return reinterpret_cast<const uint64_t *>(w.simg.p ? w.simg.p : w.sw.keys[w.sw.cur].p);
+    return w.simg.p ? w.simg.as<const uint64_t>() : w.sw.keys[w.sw.cur].as<const uint64_t>();
 }
 
 // the count: the right side, the probe, the right-only rows.  *rows / *pairs; nothing of the caller's is written.  Synchronises
@@ -162,11 +139,11 @@ int join_count_device(Ctx *c, const bowgpu_col *lkey, int32_t lkey_col, const bo
     p.simg = w->rv > 0 ? sorted_images(*w) : nullptr;
     p.rn = w->rn;
     p.rv = w->rv;
-    p.first = reinterpret_cast<uint32_t *>(w->first.p);
-    p.count = reinterpret_cast<uint32_t *>(w->count.p);
-    p.out_count = reinterpret_cast<uint32_t *>(w->starts.p);
-    p.head = reinterpret_cast<uint8_t *>(w->head.p);
-    p.stats = reinterpret_cast<JoinStats *>(w->stats.p);
+    p.first = w->first.as<uint32_t>();
+    p.count = w->count.as<uint32_t>();
+    p.out_count = w->starts.as<uint32_t>();
+    p.head = w->head.as<uint8_t>();
+    p.stats = w->stats.as<JoinStats>();
     p.is_float = lkey->type == BOWGPU_FLOAT64;
     p.outer = outer;
     BG_TRY(launch_join_probe(c, p));
@@ -183,19 +160,12 @@ int join_count_device(Ctx *c, const bowgpu_col *lkey, int32_t lkey_col, const bo
     if (outer) {   // one bit per right ROW that occurs in no pair, then the mask pass that counts them per tile
         BG_TRY(w->ubits.alloc((size_t)((n_right + 31) >> 5) * 4 + 8));
         BG_HIP(hipMemsetAsync(w->ubits.p, 0, w->ubits.bytes, c->stream));
-        BG_TRY(launch_join_unmatched(c, reinterpret_cast<const uint32_t *>(w->index.p), p.simg, p.head, p.stats, w->rn, w->rv,
-                                     reinterpret_cast<uint32_t *>(w->ubits.p)));
+        BG_TRY(launch_join_unmatched(c, w->index.as<const uint32_t>(), p.simg, p.head, p.stats, w->rn, w->rv, w->ubits.as<uint32_t>()));
         FilterMaskArgs m;
         memset(&m, 0, sizeof m);
         m.n = n_right;
-        m.and_mask = reinterpret_cast<const uint8_t *>(w->ubits.p);
-        TileRecords t;
-        BG_TRY(mask_work_prepare(c, n_right, &w->uw, &t));
-        m.mask = t.mask;
-        m.tile_counts = t.tile_counts;
-        m.tile_spans = t.tile_spans;
-        m.stats = t.stats;
-        m.host_stats = t.host_stats;
+        m.and_mask = w->ubits.as<const uint8_t>();
+        BG_TRY(mask_work_prepare(c, n_right, &w->uw, &m.t));
         BG_TRY(launch_filter_mask(c, m));
         BG_TRY(mask_work_collect(c, &w->uw));
         w->tail = w->uw.selected;
@@ -213,79 +183,27 @@ int join_expand_device(Ctx *c, int32_t kind, JoinWork *w, int64_t rows) {
     e.n_left = w->n_left;
     e.rows_left = w->rows_left;
     e.rows = rows;
-    e.out_l = reinterpret_cast<int32_t *>(w->out_l.p);
-    e.out_r = reinterpret_cast<int32_t *>(w->out_r.p);
+    e.out_l = w->out_l.as<int32_t>();
+    e.out_r = w->out_r.as<int32_t>();
     e.outer = kind == BOWGPU_JOIN_OUTER;
     if (w->probed) {
         BG_TRY(w->sums.alloc((size_t)((w->n_left + 4095) / 4096) * 4));
-        BG_TRY(launch_scan_u32(c, reinterpret_cast<uint32_t *>(w->starts.p), w->n_left, reinterpret_cast<uint32_t *>(w->sums.p)));
-        e.starts = reinterpret_cast<const uint32_t *>(w->starts.p);
-        e.first = reinterpret_cast<const uint32_t *>(w->first.p);
-        e.count = reinterpret_cast<const uint32_t *>(w->count.p);
-        e.index = reinterpret_cast<const uint32_t *>(w->index.p);
+        BG_TRY(launch_scan_u32(c, w->starts.as<uint32_t>(), w->n_left, w->sums.as<uint32_t>()));
+        e.starts = w->starts.as<const uint32_t>();
+        e.first = w->first.as<const uint32_t>();
+        e.count = w->count.as<const uint32_t>();
+        e.index = w->index.as<const uint32_t>();
         if (w->tail > 0) {   // the right-only rows in row order: the scan of the tile counts and the rows of the set bits
             const int64_t ntiles = (w->n_right + kFilterTileRows - 1) / kFilterTileRows;
             BG_TRY(w->uw.sums.alloc((size_t)((ntiles + 4095) / 4096) * 4));
-            BG_TRY(launch_scan_u32(c, reinterpret_cast<uint32_t *>(w->uw.tiles.p), ntiles, reinterpret_cast<uint32_t *>(w->uw.sums.p)));
+            BG_TRY(launch_scan_u32(c, w->uw.tiles.as<uint32_t>(), ntiles, w->uw.sums.as<uint32_t>()));
             BG_TRY(w->urows.alloc((size_t)w->tail * 4));
-            BG_TRY(launch_join_split_rows(c, reinterpret_cast<const unsigned long long *>(w->uw.mask.p), reinterpret_cast<const uint32_t *>(w->uw.tiles.p),
-                                          w->n_right, nullptr, reinterpret_cast<uint32_t *>(w->urows.p), nullptr, nullptr));
-            e.tail_rows = reinterpret_cast<const uint32_t *>(w->urows.p);
+            BG_TRY(launch_join_split_rows(c, w->uw.mask.as<const unsigned long long>(), w->uw.tiles.as<const uint32_t>(), w->n_right, nullptr,
+                                          w->urows.as<uint32_t>(), nullptr, nullptr));
+            e.tail_rows = w->urows.as<const uint32_t>();
         }
     }
     return launch_join_expand(c, e);
-}
-
-// one gather launch over a prepared group and the outputs' null counts (synchronises)
-int gather_launch(Ctx *c, const MoveGroup &g, int64_t rows, const int32_t *idx, const int32_t *idx2, int key_slot, const DevCol *key2, int64_t *nulls) {
-    char *s = g.scratch;
-    JoinGatherArgs a;
-    memset(&a, 0, sizeof a);
-    a.cols = g.cols;
-    a.n = rows;
-    a.idx = idx;
-    a.idx2 = idx2;
-    a.key_slot = key_slot;
-    if (key_slot >= 0) {
-        a.values2 = reinterpret_cast<const uint64_t *>(key2->values);
-        a.vbits2 = key2->vbits;
-        a.vbit02 = key2->vbit0;
-    }
-    a.null_counts = reinterpret_cast<unsigned long long *>(s + kScrNulls);
-    BG_HIP(hipMemsetAsync(s + kScrNulls, 0, 8 * kMoveCols, c->stream));
-    BG_TRY(launch_join_gather(c, a));
-    BG_HIP(hipEventRecord(c->ev1, c->stream));
-    unsigned long long back[kMoveCols];
-    BG_HIP(hipMemcpyAsync(back, s + kScrNulls, sizeof back, hipMemcpyDeviceToHost, c->stream));
-    BG_HIP(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < kMoveCols; i++) nulls[i] = (int64_t)back[i];
-    return 0;
-}
-
-// the columns of one frame, kMoveCols a launch, gathered through idx into outs.  key_col >= 0: that column reads *key2 through idx2 where
-// idx says "no row"
-int gather_frame(Ctx *c, const bowgpu_col *cols, int32_t ncols, const StagedCols &have, bowgpu_out *outs, int64_t rows, const int32_t *idx,
-                 const int32_t *idx2, int32_t key_col, const DevCol *key2) {
-    for (int g0 = 0; g0 < ncols; g0 += kMoveCols) {
-        MoveGroup g;
-        BG_TRY(move_group_prepare(c, cols, ncols, g0, have, outs, rows, &g));
-        const int key_slot = key_col >= g0 && key_col < g0 + kMoveCols ? key_col - g0 : -1;
-        int64_t nulls[kMoveCols];
-        BG_TRY(synced(c, gather_launch(c, g, rows, idx, idx2, key_slot, key2, nulls)));
-        BG_TRY(move_group_finish(c, &g, cols, g0, rows, nulls));
-    }
-    return 0;
-}
-
-void outs_empty(bowgpu_out *outs, const bowgpu_col *cols, int32_t ncols, int32_t skip) {
-    int k = 0;
-    for (int i = 0; i < ncols; i++) {
-        if (i == skip) continue;
-        outs[k].length = 0;
-        outs[k].null_count = 0;
-        outs[k].type = cols[i].type;
-        k++;
-    }
 }
 
 }  // namespace
@@ -348,14 +266,14 @@ int bowgpu_join_rows(const bowgpu_col *left_key, const bowgpu_col *right_key, in
     if (idx_residency != BOWGPU_DEVICE) {
         BG_TRY(wide_l.alloc((size_t)n * 8));
         BG_TRY(wide_r.alloc((size_t)n * 8));
-        dl = reinterpret_cast<int64_t *>(wide_l.p);
-        dr = reinterpret_cast<int64_t *>(wide_r.p);
+        dl = wide_l.as<int64_t>();
+        dr = wide_r.as<int64_t>();
     } else if ((reinterpret_cast<uintptr_t>(l_idx) | reinterpret_cast<uintptr_t>(r_idx)) & 7) {
         return fail(BOWGPU_ERR_ARG, "index buffer must be 8-byte aligned");
     }
     BG_TRY(synced(c, join_expand_device(c, kind, &w, n)));
-    BG_TRY(synced(c, launch_join_widen(c, reinterpret_cast<const int32_t *>(w.out_l.p), n, dl)));
-    BG_TRY(synced(c, launch_join_widen(c, reinterpret_cast<const int32_t *>(w.out_r.p), n, dr)));
+    BG_TRY(synced(c, launch_widen(c, nullptr, w.out_l.as<const int32_t>(), n, dl)));
+    BG_TRY(synced(c, launch_widen(c, nullptr, w.out_r.as<const int32_t>(), n, dr)));
     BG_HIP(hipEventRecord(c->ev1, c->stream));
     BG_TRY(synced(c, aux_out(c, l_idx, dl, (size_t)n * 8, idx_residency)));
     BG_TRY(synced(c, aux_out(c, r_idx, dr, (size_t)n * 8, idx_residency)));
@@ -407,8 +325,8 @@ int bowgpu_join(const bowgpu_col *left_cols, int32_t n_left_cols, int32_t left_k
     BG_TRY(outs_checks(outs, n_outs, total));
     *rows = total;
     if (total == 0) {
-        outs_empty(outs, left_cols, n_left_cols, -1);
-        outs_empty(outs + n_left_cols, rcols.data(), n_rest, -1);
+        for (int i = 0; i < n_left_cols; i++) out_empty(&outs[i], left_cols[i].type);
+        for (int i = 0; i < n_rest; i++) out_empty(&outs[n_left_cols + i], rcols[(size_t)i].type);
         return 0;
     }
     if (n_outs == 0) return 0;
@@ -420,16 +338,20 @@ int bowgpu_join(const bowgpu_col *left_cols, int32_t n_left_cols, int32_t left_k
         if (keyed) BG_TRY(devcol_prepare(c, &right_cols[right_key], &w.rk, true, true));
     }
     BG_TRY(synced(c, join_expand_device(c, kind, &w, total)));
-    const int32_t *il = reinterpret_cast<const int32_t *>(w.out_l.p), *ir = reinterpret_cast<const int32_t *>(w.out_r.p);
-    bool device_out = false;
-    for (int i = 0; i < n_outs; i++) device_out |= outs[i].residency == BOWGPU_DEVICE;
+    const bool device_out = any_device_out(outs, n_outs);
     // the key column takes the left row's value, and the RIGHT key's value and validity on a right-only row (bowjoin.go:397)
-    BG_TRY(synced(c, gather_frame(c, left_cols, n_left_cols, w.left, outs, total, il, ir, keyed ? left_key : -1, &w.rk)));
+    GatherIdx il, ir;
+    il.i32 = w.out_l.as<const int32_t>();
+    ir.i32 = il.i32_2 = w.out_r.as<const int32_t>();
+    il.key_col = keyed ? left_key : -1;
+    il.key2 = &w.rk;
+    bool bad;   // (never raised: the pairs are -1 or in range)
+    BG_TRY(synced(c, gather_frame(c, left_cols, n_left_cols, w.left, il, total, outs, &bad)));
     StagedCols none;
-    BG_TRY(synced(c, gather_frame(c, rcols.data(), n_rest, none, outs + n_left_cols, total, ir, nullptr, -1, nullptr)));
+    BG_TRY(synced(c, gather_frame(c, rcols.data(), n_rest, none, ir, total, outs + n_left_cols, &bad)));
     BG_HIP(hipStreamSynchronize(c->stream));
     if (device_out) device_write_epoch_bump();
-    kernel_done(c, "join_gather_kernel");
+    kernel_done(c, "gather_kernel");
     return 0;
 }
 

@@ -5,10 +5,13 @@
 //   per radix pass         sort_tile_hist_kernel (digit counts per 4096-row tile, digit-major) -> exclusive scan over (digit, tile)
 //                          -> sort_scatter_kernel (stable: ranks by ballot matching inside a wave, waves combined in wave order in LDS,
 //                          the tile staged in LDS in digit order so that global stores leave in runs per digit)
-//   gather_kernel          out[j] = in[idx[j]] for up to kMoveCols columns; a wave owns its 64-bit validity word
+//   gather_kernel          out[j] = in[idx[j]] for up to kMoveCols columns; a wave owns its 64-bit validity word.  The one gather of the
+//                          library: the sort's permutation, a caller's indices (bowgpu_take), the join's pairs with their "no row"
 //
 // Every count is an integer added in an order-free way (LDS / global atomics) or scanned in a fixed order; the position of a row
 // after a pass is a function of the keys alone, never of scheduling.
+#include <type_traits>
+
 #include "common.h"
 #include "key_image.h"
 #include "wave_scan.h"
@@ -238,44 +241,67 @@ __global__ __launch_bounds__(kThreads) void sort_scatter_kernel(const uint64_t *
     }
 }
 
-__global__ __launch_bounds__(kThreads) void sort_widen_kernel(const uint32_t *idx, int64_t n, int64_t *out) {
+// out[i] = idx[i] as 64 bits: uint32_t (the sort's row numbers) zero-extends, int32_t (the join's) sign-extends so that -1 stays -1
+template <typename SrcT>
+__global__ __launch_bounds__(kThreads) void widen_kernel(const SrcT *idx, int64_t n, int64_t *out) {
     const int64_t stride = (int64_t)gridDim.x * kThreads;
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) out[i] = (int64_t)idx[i];
 }
 
 // ---------------------------------------------------------------- gather
 // out[j] = col[idx[j]] for every column of the group: the index is read once.  A wave covers rows 64q .. 64q + 63 and stores their
-// validity word whole (bits of rows >= n_idx: 0); null slots hold 0.  An index outside [0, length) - a caller's, bowgpu_take -
-// raises *bad and reads nothing.
-template <typename IdxT>
-__global__ __launch_bounds__(kThreads) void gather_kernel(GatherArgs a, const IdxT *idx) {
+// validity word whole (bits of rows >= n_idx: 0); null slots hold 0.  Three instantiations:
+//   <uint32_t, false>  the sort's own permutation                  } an index outside [0, length) raises *bad and reads nothing
+//   <int64_t, false>   a caller's indices (bowgpu_take)            }
+//   <int32_t, true>    the join's: an index < 0 is "no row" and gives a null slot, every other one is in range (join_expand_kernel
+//                      wrote them); on a "no row" row the column key_slot reads the second source through idx2.  Its argument block
+//                      is GatherNoRowArgs; the other two take GatherArgs and hold no trace of the second source
+template <typename IdxT, bool kNoRow>
+__global__ __launch_bounds__(kThreads) void gather_kernel(std::conditional_t<kNoRow, GatherNoRowArgs, GatherArgs> a, const IdxT *idx) {
     const int lane = threadIdx.x & 63;
     const int64_t stride = (int64_t)gridDim.x * kThreads;
     const int64_t rounds = (a.n_idx + stride - 1) / stride;
     uint32_t nulls[kMoveCols] = {};
     bool bad = false;
     int64_t j = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    for (int64_t r = 0; r < rounds; r++, j += stride) {
+    for (int64_t r = 0; r < rounds; r++, j += stride) {   // (every lane runs every round: the ballots below need whole waves)
         bool in = j < a.n_idx;
-        int64_t p = 0;
+        std::conditional_t<kNoRow, int32_t, int64_t> p = kNoRow ? -1 : 0, p2 = -1;
         if (in) {
-            p = (int64_t)idx[j];
-            if (p < 0 || p >= a.length) { bad = true; p = -1; }   // (the library's own permutation never trips this: it guards the reads all the same)
+            p = idx[j];
+            if constexpr (kNoRow) {
+                if (a.key_slot >= 0 && p < 0) p2 = a.idx2[j];
+            } else if (p < 0 || p >= a.length) {   // (the library's own permutation never trips this: it guards the reads all the same)
+                bad = true;
+                p = -1;
+            }
         }
 #pragma unroll
         for (int c = 0; c < kMoveCols; c++) {
             if (c < a.cols.ncols) {
-                bool valid = in && p >= 0;
-                uint64_t v = 0;
-                if (valid && a.cols.vbits[c]) {
-                    const int64_t bit = a.cols.vbit0[c] + p;
-                    valid = (a.cols.vbits[c][bit >> 5] >> (bit & 31)) & 1u;
+                const uint64_t *vals = a.cols.values[c];
+                const uint32_t *vb = a.cols.vbits[c];
+                int64_t vb0 = a.cols.vbit0[c], row = p;
+                if constexpr (kNoRow) {
+                    const bool second = c == a.key_slot && p < 0;
+                    vals = second ? a.values2 : vals;
+                    vb = second ? a.vbits2 : vb;
+                    vb0 = second ? a.vbit02 : vb0;
+                    row = second ? p2 : p;
                 }
-                if (valid) v = a.cols.values[c][p];
+                bool valid = in && row >= 0;
+                uint64_t v = 0;
+                if (valid && vb) {
+                    const int64_t bit = vb0 + row;
+                    valid = (vb[bit >> 5] >> (bit & 31)) & 1u;
+                }
+                if (valid) v = vals[row];
                 if (in) a.cols.out_values[c][j] = v;
                 const unsigned long long word = __ballot(valid);
                 const unsigned long long rows = __ballot(in);
                 if (lane == 0 && rows) {
+                    // whole 64-bit words, ceil(n_idx / 64) of them: at most 8 * ceil(n / 64) <= ((ceil(n / 8) + 3) & ~3) + 4 bytes, which
+                    // is what devout_prepare gives every output's validity working copy (equal when n % 64 is 1 .. 32)
                     a.cols.out_valid[c][j >> 6] = word;
                     nulls[c] += (uint32_t)__popcll(rows & ~word);
                 }
@@ -287,19 +313,15 @@ __global__ __launch_bounds__(kThreads) void gather_kernel(GatherArgs a, const Id
         for (int c = 0; c < kMoveCols; c++)
             if (c < a.cols.ncols && nulls[c]) atomicAdd(&a.null_counts[c], (unsigned long long)nulls[c]);
     }
-    if (__any(bad) && lane == 0) atomicOr(a.bad, 1u);
-}
-
-int64_t stream_grid(int64_t n) {
-    int64_t grid = (n + kThreads - 1) / kThreads;
-    if (grid > 256 * 8) grid = 256 * 8;
-    return grid < 1 ? 1 : grid;
+    if constexpr (!kNoRow) {
+        if (__any(bad) && lane == 0) atomicOr(a.bad, 1u);
+    }
 }
 
 }  // namespace
 
 int launch_sort_hist(Ctx *c, const uint64_t *key, int64_t n, int is_float, uint32_t *d_hist, uint32_t *d_flags, uint64_t *img_out) {
-    hipLaunchKernelGGL(sort_hist_kernel, dim3((unsigned)stream_grid(n)), dim3(kThreads), 0, c->stream, key, n, is_float, d_hist, d_flags, img_out);
+    hipLaunchKernelGGL(sort_hist_kernel, dim3((unsigned)stream_grid(n, kThreads)), dim3(kThreads), 0, c->stream, key, n, is_float, d_hist, d_flags, img_out);
     BG_HIP(hipGetLastError());
     return 0;
 }
@@ -326,16 +348,20 @@ int launch_sort_pass(Ctx *c, const uint64_t *src, int mode, const uint32_t *src_
     return 0;
 }
 
-int launch_sort_widen(Ctx *c, const uint32_t *idx, int64_t n, int64_t *out) {
-    hipLaunchKernelGGL(sort_widen_kernel, dim3((unsigned)stream_grid(n)), dim3(kThreads), 0, c->stream, idx, n, out);
+int launch_widen(Ctx *c, const uint32_t *idx32, const int32_t *idx32s, int64_t n, int64_t *out) {
+    const dim3 grid((unsigned)stream_grid(n, kThreads));
+    if (idx32) hipLaunchKernelGGL((widen_kernel<uint32_t>), grid, dim3(kThreads), 0, c->stream, idx32, n, out);
+    else hipLaunchKernelGGL((widen_kernel<int32_t>), grid, dim3(kThreads), 0, c->stream, idx32s, n, out);
     BG_HIP(hipGetLastError());
     return 0;
 }
 
-int launch_gather(Ctx *c, const GatherArgs &a, const uint32_t *idx32, const int64_t *idx64) {
-    const dim3 grid((unsigned)stream_grid(a.n_idx));
-    if (idx32) hipLaunchKernelGGL((gather_kernel<uint32_t>), grid, dim3(kThreads), 0, c->stream, a, idx32);
-    else hipLaunchKernelGGL((gather_kernel<int64_t>), grid, dim3(kThreads), 0, c->stream, a, idx64);
+int launch_gather(Ctx *c, const GatherNoRowArgs &a, const GatherIdx &ix) {
+    const dim3 grid((unsigned)stream_grid(a.n_idx, kThreads));
+    const GatherArgs &plain = a;
+    if (ix.u32) hipLaunchKernelGGL((gather_kernel<uint32_t, false>), grid, dim3(kThreads), 0, c->stream, plain, ix.u32);
+    else if (ix.i64) hipLaunchKernelGGL((gather_kernel<int64_t, false>), grid, dim3(kThreads), 0, c->stream, plain, ix.i64);
+    else hipLaunchKernelGGL((gather_kernel<int32_t, true>), grid, dim3(kThreads), 0, c->stream, a, ix.i32);
     BG_HIP(hipGetLastError());
     return 0;
 }

@@ -43,7 +43,7 @@ int argsort_device(Ctx *c, const bowgpu_col *key, const DevCol &dk, SortWork *w,
     const bool in_place_host = key->residency == BOWGPU_HOST_PINNED && !dk.own_values.p;
     if (in_place_host) BG_TRY(w->keys[1].alloc((size_t)n * 8));
     BG_HIP(hipMemsetAsync(s, 0, kScrFlags + 16, c->stream));
-    BG_TRY(launch_sort_hist(c, raw, n, is_float, d_hist, d_flags, in_place_host ? reinterpret_cast<uint64_t *>(w->keys[1].p) : nullptr));
+    BG_TRY(launch_sort_hist(c, raw, n, is_float, d_hist, d_flags, in_place_host ? w->keys[1].as<uint64_t>() : nullptr));
     uint32_t back[8 * 256 + 4];
     BG_HIP(hipMemcpyAsync(back, s, sizeof back, hipMemcpyDeviceToHost, c->stream));
     BG_HIP(hipStreamSynchronize(c->stream));
@@ -65,20 +65,66 @@ int argsort_device(Ctx *c, const bowgpu_col *key, const DevCol &dk, SortWork *w,
     }
     BG_TRY(w->tiles.alloc((size_t)m * 4));
     BG_TRY(w->sums.alloc((size_t)((m + 4095) / 4096) * 4));
-    const uint64_t *src = in_place_host ? reinterpret_cast<const uint64_t *>(w->keys[1].p) : raw;
+    const uint64_t *src = in_place_host ? w->keys[1].as<const uint64_t>() : raw;
     int mode = in_place_host ? 2 : is_float;
     const uint32_t *src_idx = nullptr;
     int dst = in_place_host ? 0 : 1;
     for (int p = 0; p < 8; p++) {
         if (!active[p]) continue;
-        BG_TRY(launch_sort_pass(c, src, mode, src_idx, n, 8 * p, reinterpret_cast<uint32_t *>(w->tiles.p), reinterpret_cast<uint32_t *>(w->sums.p),
-                                reinterpret_cast<uint64_t *>(w->keys[dst].p), reinterpret_cast<uint32_t *>(w->idx[dst].p)));
-        src = reinterpret_cast<const uint64_t *>(w->keys[dst].p);
-        src_idx = reinterpret_cast<const uint32_t *>(w->idx[dst].p);
+        BG_TRY(launch_sort_pass(c, src, mode, src_idx, n, 8 * p, w->tiles.as<uint32_t>(), w->sums.as<uint32_t>(), w->keys[dst].as<uint64_t>(),
+                                w->idx[dst].as<uint32_t>()));
+        src = w->keys[dst].as<const uint64_t>();
+        src_idx = w->idx[dst].as<const uint32_t>();
         mode = 2;
         w->cur = dst;
         dst ^= 1;
         w->passes++;
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- the gather's host side
+int gather_enqueue(Ctx *c, char *scratch, const MoveCols &cols, int32_t g0, int64_t length, const GatherIdx &ix, int64_t n_idx) {
+    GatherNoRowArgs a;
+    memset(&a, 0, sizeof a);
+    a.cols = cols;
+    a.n_idx = n_idx;
+    a.length = length;
+    a.null_counts = reinterpret_cast<unsigned long long *>(scratch + kScrNulls);
+    a.bad = reinterpret_cast<uint32_t *>(scratch + kScrFlags) + 2;
+    a.key_slot = ix.key_col >= g0 && ix.key_col < g0 + kMoveCols ? ix.key_col - g0 : -1;
+    if (a.key_slot >= 0) {
+        a.idx2 = ix.i32_2;
+        a.values2 = reinterpret_cast<const uint64_t *>(ix.key2->values);
+        a.vbits2 = ix.key2->vbits;
+        a.vbit02 = ix.key2->vbit0;
+    }
+    BG_HIP(hipMemsetAsync(scratch + kScrFlags, 0, 16 + 8 * kMoveCols, c->stream));
+    BG_TRY(launch_gather(c, a, ix));
+    BG_HIP(hipEventRecord(c->ev1, c->stream));
+    return 0;
+}
+
+int gather_launch(Ctx *c, const MoveGroup &g, int32_t g0, int64_t length, const GatherIdx &ix, int64_t n_idx, int64_t *nulls, bool *bad) {
+    BG_TRY(gather_enqueue(c, g.scratch, g.cols, g0, length, ix, n_idx));
+    struct { uint32_t flags[4]; unsigned long long nulls[kMoveCols]; } back;
+    BG_HIP(hipMemcpyAsync(&back, g.scratch + kScrFlags, sizeof back, hipMemcpyDeviceToHost, c->stream));
+    BG_HIP(hipStreamSynchronize(c->stream));
+    *bad = back.flags[2] != 0;
+    for (int i = 0; i < kMoveCols; i++) nulls[i] = (int64_t)back.nulls[i];
+    return 0;
+}
+
+int gather_frame(Ctx *c, const bowgpu_col *cols, int32_t ncols, const StagedCols &have, const GatherIdx &ix, int64_t n_idx, bowgpu_out *outs,
+                 bool *bad) {
+    *bad = false;
+    for (int g0 = 0; g0 < ncols; g0 += kMoveCols) {
+        MoveGroup g;
+        BG_TRY(move_group_prepare(c, cols, ncols, g0, have, outs, n_idx, &g));
+        int64_t nulls[kMoveCols];
+        BG_TRY(synced(c, gather_launch(c, g, g0, cols[g0].length, ix, n_idx, nulls, bad)));
+        if (*bad) return 0;
+        BG_TRY(move_group_finish(c, &g, cols, g0, n_idx, nulls));
     }
     return 0;
 }
@@ -98,36 +144,6 @@ int key_prepare(Ctx *c, const bowgpu_col *key, DevCol *dk) {
 const char *passes_name(int passes) {
     snprintf(g_kernel_name, sizeof g_kernel_name, "sort_scatter_kernel<%d of 8 passes>", passes);
     return g_kernel_name;
-}
-
-// one gather launch over a prepared group: out[j] = col[idx[j]], then the outputs' null counts and *bad (synchronises)
-int gather_launch(Ctx *c, const MoveGroup &g, int64_t length, const uint32_t *idx32, const int64_t *idx64, int64_t n_idx, int64_t *nulls, bool *bad) {
-    char *s = g.scratch;
-    GatherArgs a;
-    a.cols = g.cols;
-    a.n_idx = n_idx;
-    a.length = length;
-    a.null_counts = reinterpret_cast<unsigned long long *>(s + kScrNulls);
-    a.bad = reinterpret_cast<uint32_t *>(s + kScrFlags) + 2;
-    BG_HIP(hipMemsetAsync(s + kScrFlags, 0, 16 + 8 * kMoveCols, c->stream));
-    BG_TRY(launch_gather(c, a, idx32, idx64));
-    struct { uint32_t flags[4]; unsigned long long nulls[kMoveCols]; } back;
-    BG_HIP(hipMemcpyAsync(&back, s + kScrFlags, sizeof back, hipMemcpyDeviceToHost, c->stream));
-    BG_HIP(hipStreamSynchronize(c->stream));
-    *bad = back.flags[2] != 0;
-    for (int i = 0; i < kMoveCols; i++) nulls[i] = (int64_t)back.nulls[i];
-    return 0;
-}
-
-// the columns of the frame from g0 on, up to kMoveCols, gathered into their outputs.  *bad: an index outside the frame - nothing was handed out
-int gather_group(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t g0, const StagedCols &have, const uint32_t *idx32, const int64_t *idx64,
-                 int64_t n_idx, bowgpu_out *outs, bool *bad) {
-    MoveGroup g;
-    BG_TRY(move_group_prepare(c, cols, ncols, g0, have, outs, n_idx, &g));
-    int64_t nulls[kMoveCols];
-    BG_TRY(synced(c, gather_launch(c, g, cols[g0].length, idx32, idx64, n_idx, nulls, bad)));
-    if (*bad) return 0;
-    return move_group_finish(c, &g, cols, g0, n_idx, nulls);
 }
 
 }  // namespace
@@ -155,9 +171,9 @@ int bowgpu_argsort(const bowgpu_col *key, int64_t *perm, int32_t perm_residency,
         int64_t *d_perm = perm;
         if (perm_residency != BOWGPU_DEVICE) {
             BG_TRY(wide.alloc((size_t)n * 8));
-            d_perm = reinterpret_cast<int64_t *>(wide.p);
+            d_perm = wide.as<int64_t>();
         }
-        BG_TRY(launch_sort_widen(c, w.perm(), n, d_perm));
+        BG_TRY(launch_widen(c, w.perm(), nullptr, n, d_perm));
         BG_HIP(hipEventRecord(c->ev1, c->stream));
         BG_TRY(aux_out(c, perm, d_perm, (size_t)n * 8, perm_residency));
     } else {
@@ -176,9 +192,7 @@ int bowgpu_take(const bowgpu_col *col, const int64_t *idx, int64_t n_idx, int32_
     if (col->length < 0 || col->offset < 0) return fail(BOWGPU_ERR_ARG, "negative column length/offset");
     BG_TRY(outs_checks(out, 1, n_idx));
     if (n_idx == 0) {
-        out->length = 0;
-        out->null_count = 0;
-        out->type = col->type;
+        out_empty(out, col->type);
         return 0;
     }
     if (col->length == 0) return fail(BOWGPU_ERR_ARG, "index out of range: the column has no rows");
@@ -190,9 +204,11 @@ int bowgpu_take(const bowgpu_col *col, const int64_t *idx, int64_t n_idx, int32_
     DevBuf staged;
     BG_TRY(aux_in(c, idx, (size_t)n_idx * 8, idx_residency, "index", &d_idx, &staged));
     if (reinterpret_cast<uintptr_t>(d_idx) & 7) return fail(BOWGPU_ERR_ARG, "index buffer must be 8-byte aligned");
+    GatherIdx ix;
+    ix.i64 = reinterpret_cast<const int64_t *>(d_idx);
     bool bad = false;
     BG_HIP(hipEventRecord(c->ev0, c->stream));
-    BG_TRY(gather_group(c, col, 1, 0, have, nullptr, reinterpret_cast<const int64_t *>(d_idx), n_idx, out, &bad));
+    BG_TRY(gather_frame(c, col, 1, have, ix, n_idx, out, &bad));
     if (bad) return fail(BOWGPU_ERR_ARG, "index out of range [0, %lld)", (long long)col->length);
     if (out->residency == BOWGPU_DEVICE) device_write_epoch_bump();
     BG_HIP(hipEventRecord(c->ev1, c->stream));
@@ -230,13 +246,12 @@ int bowgpu_sort_by_col(const bowgpu_col *cols, int32_t ncols, int32_t key_col, b
         return 0;
     }
     *unchanged = 0;
-    bool device_out = false;
-    for (int i = 0; i < ncols; i++) device_out |= outs[i].residency == BOWGPU_DEVICE;
-    for (int g0 = 0; g0 < ncols; g0 += kMoveCols) {
-        bool bad = false;
-        BG_TRY(gather_group(c, cols, ncols, g0, have, w.perm(), nullptr, n, outs, &bad));
-        if (bad) return fail(BOWGPU_ERR_HIP, "internal: the sort produced a row index outside the frame");
-    }
+    const bool device_out = any_device_out(outs, ncols);
+    GatherIdx ix;
+    ix.u32 = w.perm();
+    bool bad = false;
+    BG_TRY(gather_frame(c, cols, ncols, have, ix, n, outs, &bad));
+    if (bad) return fail(BOWGPU_ERR_HIP, "internal: the sort produced a row index outside the frame");   // (nothing of that group was handed out)
     BG_HIP(hipEventRecord(c->ev1, c->stream));
     BG_HIP(hipStreamSynchronize(c->stream));
     if (device_out) device_write_epoch_bump();

@@ -314,9 +314,10 @@ def test_residencies_mixed_within_a_frame(out_res):
             run_join(frame(lkey, 1), 0, frame(rkey, 2), 0, kind, lambda side, i: mix[(side + i + shift) % 3], out_res, extra=70)
 
 
-@pytest.mark.parametrize("ncols,key", [(1, 0), (9, 0), (9, 4), (9, 8)])
+@pytest.mark.parametrize("ncols,key", [(1, 0), (9, 0), (9, 4), (9, 5), (9, 8)])
 def test_frames_of_one_and_nine_columns_key_anywhere(ncols, key):
-    """nine columns: more than two launch groups of four; the key first, in the middle, last - at a different place in each frame"""
+    """nine columns: more than two launch groups of four; the key first, in the middle (the first and the second column of the second
+    group: a right-only row reads the right key into either slot), last - at a different place in each frame"""
     rng = np.random.default_rng(ncols * 10 + key)
     nl, nr = 333, 411
 
@@ -329,8 +330,24 @@ def test_frames_of_one_and_nine_columns_key_anywhere(ncols, key):
 
     rk = (ncols - 1) - key
     for kind in (INNER, OUTER):
-        run_join(wide(nl, key, 1), key, wide(nr, rk, 2), rk, kind, DEVICE if key else HOST)
+        outs, li, ri = run_join(wide(nl, key, 1), key, wide(nr, rk, 2), rk, kind, DEVICE if key else HOST)
+    assert (li < 0).any() and (ri < 0).any()      # OUTER: right-only rows (the key column's second source) and left-only rows
     run_join(wide(nl, key, 1), -1, wide(nr, rk, 2), -1, OUTER)      # no common column: all columns of both
+
+
+def test_outer_join_into_the_second_round_of_the_gather_grid():
+    """the gather's grid is capped at 2048 workgroups of 256 threads, so 524 288 output rows are one round of its grid-stride loop; the
+    65 rows behind them hold left rows with a pair, left rows without one and right-only rows"""
+    rng = np.random.default_rng(41)
+    rows, n_tail = 2048 * 256 + 65, 20
+    nl = rows - n_tail
+    rvals = np.concatenate([np.arange(0, nl, 2), nl + np.arange(n_tail)])      # every second left key, and keys no left row has
+    left = frame(ikey(np.arange(nl)), 1)[:2]
+    right = frame(ikey(rvals[rng.permutation(len(rvals))]), 2, offset=3)[:2]
+    outs, li, ri = run_join(left, 0, right, 0, OUTER, DEVICE, HOST, rows_too=False)
+    assert len(li) == rows
+    last = slice(2048 * 256, rows)
+    assert ((li[last] >= 0) & (ri[last] >= 0)).any() and ((li[last] >= 0) & (ri[last] < 0)).any() and (li[last] < 0).sum() == n_tail
 
 
 # ------------------------------------------------------------------ capacity and count

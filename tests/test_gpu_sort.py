@@ -379,7 +379,9 @@ def test_take():
     m = rng.random(n) > 0.4
     for res in (capi.HOST, capi.DEVICE):
         col = place(col_of(v, m, capi.FLOAT64), res)
-        for n_idx in (1, 63, 64, 65, 7, 100_003):            # repeated indices, n_idx != length
+        # repeated indices, n_idx != length; the last: 65 rows into the second round of the gather's grid-stride loop (its grid is capped
+        # at 2048 workgroups of 256 threads)
+        for n_idx in (1, 63, 64, 65, 7, 100_003, 2048 * 256 + 65):
             idx = rng.integers(0, n, n_idx).astype(np.int64)
             want_vals = np.where(m, v.view(np.uint64), np.uint64(0)).view(np.float64)
             compare_taken("take host idx n=%d" % n_idx, capi.take(col, idx, out_residency=res), want_vals, m, idx, capi.FLOAT64)
