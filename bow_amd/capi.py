@@ -29,7 +29,8 @@ FILTER_MAX_VALUES = 32
 FILTER_MAX_PREDS = 8
 CARRY_MAX_AGGS = 16
 JOIN_INNER, JOIN_OUTER = 0, 1
-ABI_VERSION = 13  # include/bowgpu.h BOWGPU_ABI_VERSION (asserted when the library is loaded)
+MERGE_TILE_ROWS = 2048  # bow_amd/csrc/common.h kMergeTileRows: output rows per workgroup of merge_runs_kernel (bowgpu_sort_by_col_sharded)
+ABI_VERSION = 14  # include/bowgpu.h BOWGPU_ABI_VERSION (asserted when the library is loaded)
 
 ERR_NAMES = {
     -1: "INTERVAL", -2: "TS_TYPE", -3: "FIRST_TS_NULL", -4: "NO_AGG", -5: "KEEP_INTERVAL", -6: "BAD_COL",
@@ -125,6 +126,12 @@ class ShardDecision(C.Structure):
                 ("seed_first_rank", C.c_int32), ("next_rank", C.c_int32), ("finish_last", C.c_int32), ("retry_with_s0", C.c_int32)]
 
 
+class SortShardInfo(C.Structure):
+    """bowgpu_sort_shard_info: what the calling thread's last bowgpu_sort_by_col_sharded did and where its time went"""
+    _fields_ = [("splitter_rounds", C.c_int32), ("merge_rounds", C.c_int32), ("sort_passes", C.c_int32), ("merged_ranks", C.c_int32),
+                ("local_sort_ms", C.c_double), ("splitter_ms", C.c_double), ("merge_ms", C.c_double)]
+
+
 # every symbol include/bowgpu.h declares (checked by tests/test_abi_symbols.py)
 SYMBOLS = [
     "bowgpu_abi_version", "bowgpu_rolling_interpolate_aggregate", "bowgpu_last_error", "bowgpu_device_count", "bowgpu_set_device", "bowgpu_device_name",
@@ -141,7 +148,7 @@ SYMBOLS = [
     "bowgpu_debug_set_route", "bowgpu_debug_get_route", "bowgpu_checksum64_at",
     "bowgpu_set_devices", "bowgpu_get_devices", "bowgpu_set_fanout_min_rows", "bowgpu_last_call_ranks", "bowgpu_fanout_counts",
     "bowgpu_rolling_aggregate_sharded",
-    "bowgpu_argsort", "bowgpu_take", "bowgpu_sort_by_col",
+    "bowgpu_argsort", "bowgpu_take", "bowgpu_sort_by_col", "bowgpu_sort_by_col_sharded", "bowgpu_sort_by_col_sharded_info",
     "bowgpu_filter_mask", "bowgpu_compact", "bowgpu_filter",
     "bowgpu_valid_mask", "bowgpu_drop_nils", "bowgpu_diff", "bowgpu_distinct",
     "bowgpu_append", "bowgpu_find_next",
@@ -643,6 +650,42 @@ def rolling_aggregate_sharded(cols_by_rank, ts_col, interval, aggs, device_ids, 
         for i, o in enumerate(outs):
             o.absorb(oarr[i])
     return outs_by_rank, decisions, info
+
+
+def sort_by_col_sharded(cols_by_rank, key_col, device_ids, out_residency=HOST, outs=None):
+    """Bow.SortByCol over a frame held as row-range shards (cols_by_rank[r]: rank r's columns, on device_ids[r]) -
+    bowgpu_sort_by_col_sharded.  Returns (outs_by_rank, unchanged): outs_by_rank[r][i] holds rank r's rows of column i of the sorted
+    frame (as many as the rank gave); unchanged: the whole frame is in order and the outputs were not written"""
+    world = len(cols_by_rank)
+    if len(device_ids) != world:
+        raise ValueError("one device id per rank: %d ranks, %d ids" % (world, len(device_ids)))
+    ncols = len(cols_by_rank[0]) if world else 0
+    if outs is None:
+        outs = [[OutColumn(cols[key_col].length if 0 <= key_col < len(cols) else 0, out_residency) for _ in cols] for cols in cols_by_rank]
+    carrs = [_cols(cols) for cols in cols_by_rank]
+    cptrs = (C.POINTER(Col) * max(world, 1))(*[C.cast(a, C.POINTER(Col)) for a in carrs])
+    oarrs = []
+    for o_rank in outs:
+        oarr = (Out * max(len(o_rank), 1))()
+        for i, o in enumerate(o_rank):
+            oarr[i] = o.c()
+        oarrs.append(oarr)
+    optrs = (C.POINTER(Out) * max(world, 1))(*[C.cast(a, C.POINTER(Out)) for a in oarrs])
+    ids = (C.c_int32 * max(world, 1))(*device_ids)
+    unchanged = C.c_int32(0)
+    check(lib().bowgpu_sort_by_col_sharded(cptrs, ids, world, ncols, key_col, optrs, C.byref(unchanged)))
+    if not unchanged.value:
+        for o_rank, oarr in zip(outs, oarrs):
+            for i, o in enumerate(o_rank):
+                o.absorb(oarr[i])
+    return outs, bool(unchanged.value)
+
+
+def sort_by_col_sharded_info():
+    """SortShardInfo of the calling thread's last sort_by_col_sharded (bowgpu_sort_by_col_sharded_info)"""
+    info = SortShardInfo()
+    check(lib().bowgpu_sort_by_col_sharded_info(C.byref(info)))
+    return info
 
 
 def window_bounds(ts, interval, offset=0, inclusive=False):

@@ -42,16 +42,9 @@ int pieces_checks(const bowgpu_col *const *frames, int32_t nframes, int32_t ncol
     return 0;
 }
 
-// the piece table of one launch group in host memory, laid out as the device block is: starts, then kMoveCols arrays of pieces
-struct PieceTable {
-    std::vector<char> bytes;
-    size_t pieces_at = 0;
-    int32_t npieces = 0;
-    explicit PieceTable(int32_t n) : bytes(append_table_bytes(n), 0), pieces_at(((((size_t)n + 1) * 4) + 15) & ~(size_t)15), npieces(n) {}
-    uint32_t *starts() { return reinterpret_cast<uint32_t *>(bytes.data()); }
-    AppendPiece *pieces(int i) { return reinterpret_cast<AppendPiece *>(bytes.data() + pieces_at) + (size_t)i * (size_t)npieces; }
-    size_t pieces_offset(int i) const { return pieces_at + (size_t)i * (size_t)npieces * sizeof(AppendPiece); }
-};
+}  // namespace
+
+namespace bowgpu {
 
 // one group of up to kMoveCols columns: every piece staged, the table built and uploaded, one append launch, the counts of valid rows
 // of the columns whose nulls the arguments do not state on their way to valid[] (no synchronise)
@@ -100,7 +93,7 @@ int append_launch(Ctx *c, const bowgpu_col *const *frames, int32_t nframes, int3
     return 0;
 }
 
-}  // namespace
+}  // namespace bowgpu
 
 extern "C" {
 

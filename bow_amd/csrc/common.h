@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/bowgpu.h"
 #include "debug_routes.h"
@@ -769,6 +770,22 @@ struct AppendArgs {
 };
 size_t append_table_bytes(int32_t npieces);   // starts + kMoveCols piece arrays, each 16-byte aligned, in one block
 int launch_append(Ctx *c, const AppendArgs &a);
+// append_api.cpp (also the destination side of the sharded sort).
+// the piece table of one launch group in host memory, laid out as the device block is: starts, then kMoveCols arrays of pieces
+struct PieceTable {
+    std::vector<char> bytes;
+    size_t pieces_at = 0;
+    int32_t npieces = 0;
+    explicit PieceTable(int32_t n) : bytes(append_table_bytes(n), 0), pieces_at(((((size_t)n + 1) * 4) + 15) & ~(size_t)15), npieces(n) {}
+    uint32_t *starts() { return reinterpret_cast<uint32_t *>(bytes.data()); }
+    AppendPiece *pieces(int i) { return reinterpret_cast<AppendPiece *>(bytes.data() + pieces_at) + (size_t)i * (size_t)npieces; }
+    size_t pieces_offset(int i) const { return pieces_at + (size_t)i * (size_t)npieces * sizeof(AppendPiece); }
+};
+// one group of up to kMoveCols columns of the pieces frames[f][g0 ..]: every piece staged (copies of BOWGPU_HOST pieces are kept in
+// *staged until the group is done), the table built and uploaded, one append launch into g's outputs, and the counts of valid rows of
+// the columns marked in count_on_device on their way to valid[kMoveCols] (no synchronise)
+int append_launch(Ctx *c, const bowgpu_col *const *frames, int32_t nframes, int32_t g0, int64_t total, const MoveGroup &g,
+                  std::vector<DevCol> *staged, PieceTable *t, const bool *count_on_device, unsigned long long *valid);
 constexpr uint32_t kFindNone = 0xFFFFFFFFu;
 struct FindArgs {
     const uint64_t *values;              // nullptr: the search for the first null (bitmaps only)
@@ -827,6 +844,43 @@ struct JoinExpandArgs {
     int32_t outer, _pad;
 };
 int launch_join_expand(Ctx *c, const JoinExpandArgs &a);
+
+// sort_shard.hip: Bow.SortByCol over row-range shards - the splitter search over a rank's sorted key and the stable merge of the
+// sorted runs a destination rank has pulled (host side: sort_shard_api.cpp)
+constexpr int kShardMaxWorld = 64;
+constexpr int kMergeTileRows = 2048;   // output rows per workgroup of merge_runs_kernel (also what one merge_partition_kernel thread answers for)
+// how a sorted key is read: raw Int64 / raw Float64 payloads of a key that lies in order (imaged on the fly, key_image.h), or images
+enum : int32_t { kKeyRawInt = 0, kKeyRawFloat = 1, kKeyImages = 2 };
+struct SplitBoundsArgs {
+    const uint64_t *keys;                // n sorted keys, read as `mode` says
+    int64_t n;
+    int32_t mode, ncand;
+    uint64_t cand[kShardMaxWorld];       // candidate images
+    uint32_t *out;                       // [2 * ncand]: rows with an image below cand[j], rows with an image <= cand[j]
+};
+int launch_split_bounds(Ctx *c, const SplitBoundsArgs &a);
+struct ImageAtArgs {
+    const uint64_t *keys;
+    int32_t mode, npos;
+    uint32_t pos[2 * kShardMaxWorld + 2];   // rows of keys, each below the key's length
+    uint64_t *out;                          // [npos] their images
+};
+int launch_image_at(Ctx *c, const ImageAtArgs &a);
+// img[i] = image of keys[i] (raw payloads, no NaN), idx[i] = i: the runs of a staging frame before their first merge round
+int launch_merge_init(Ctx *c, const uint64_t *keys, int64_t n, int is_float, uint64_t *img, uint32_t *idx);
+// one round: adjacent runs merged pairwise, stable (on equal images the left run's rows come first).  start[0 .. nruns]: first row of
+// each run, start[nruns] = rows in all; an unpaired last run is copied.  part: one word per tile of scratch
+struct MergeRoundArgs {
+    const uint64_t *img_in;
+    const uint32_t *idx_in;
+    uint64_t *img_out;
+    uint32_t *idx_out;
+    uint32_t *part;                      // [tiles of the round <= rows / kMergeTileRows + pairs]: rows of the LEFT run among the outputs in front of the tile
+    int32_t npairs, ntiles;
+    uint32_t start[kShardMaxWorld + 1];          // start[2j], start[2j + 1], start[2j + 2]: pair j
+    uint32_t tile0[kShardMaxWorld / 2 + 1];      // first tile of pair j; tile0[npairs] = ntiles
+};
+int launch_merge_round(Ctx *c, MergeRoundArgs *a, int nruns);  // fills npairs / ntiles / tile0 from start[0 .. nruns], launches both kernels and the copy
 
 // generate.hip
 int launch_gen_dense(Ctx *c, int64_t row0, int64_t n, uint64_t seed, int64_t *ts, double *val);

@@ -33,32 +33,13 @@
 #include <vector>
 
 #include "common.h"
+#include "fanout.h"
 
 namespace bowgpu {
 
 int current_device_of_thread();   // api.cpp: the device the calling thread's context is (or will be) on
 
 namespace {
-
-// ---------------------------------------------------------------- the workers: one persistent thread per listed device
-struct Worker {
-    int device = 0;
-    std::thread th;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::function<void()> job;
-    bool has_job = false, quit = false;
-    bool device_set = false;
-};
-
-struct Fanout {
-    std::mutex call_mu;            // one fanned-out call at a time (the devices are busy with it anyway)
-    std::vector<Worker *> workers;
-    std::vector<int> ids;          // what the workers were started for
-    std::mutex done_mu;
-    std::condition_variable done_cv;
-    int pending = 0;
-};
 
 std::atomic<int64_t> g_calls_listed{0}, g_calls_served{0};   // bowgpu_fanout_counts
 thread_local int g_last_ranks = 1;            // ranks that served the calling thread's last Rolling.Aggregate (bowgpu_last_call_ranks)
@@ -127,6 +108,8 @@ void fan_start_locked(Fanout *f, const std::vector<int> &ids) {
     f->ids = ids;
 }
 
+}  // namespace
+
 // runs fn(rank) on worker `rank` for rank in [0, world) and waits for all of them
 void fan_run(Fanout *f, int world, const std::function<void(int)> &fn) {
     { std::lock_guard<std::mutex> g(f->done_mu); f->pending = world; }
@@ -146,6 +129,8 @@ void fan_run(Fanout *f, int world, const std::function<void(int)> &fn) {
     std::unique_lock<std::mutex> lk(f->done_mu);
     f->done_cv.wait(lk, [&] { return f->pending == 0; });
 }
+
+namespace {
 
 // ---------------------------------------------------------------- bit placement on the host
 // A rank's bitmap (slot k at bit k) goes to bits [d0, d0 + nbits) of the frame's bitmap.  Whole bytes in the middle are stored by the
@@ -419,29 +404,6 @@ void rank_cleanup(Worker *w, Call *call, int r) {
 bool is_decline(int rc) { return rc == BOWGPU_ERR_UNSUPPORTED || rc == BOWGPU_ERR_TS_NULLS; }
 
 // ---------------------------------------------------------------- bowgpu_rolling_aggregate_sharded: the caller's shards, one dispatch, one join
-// A barrier among the workers of one call.  Sticky abort: once a rank has failed, every wait - now or later - returns false, so no
-// worker is left waiting for a rank that will not come.
-struct Barrier {
-    std::mutex mu;
-    std::condition_variable cv;
-    int n = 0, arrived = 0;
-    uint64_t gen = 0;
-    bool aborted = false;
-    bool wait() {
-        std::unique_lock<std::mutex> lk(mu);
-        if (aborted) return false;
-        const uint64_t g = gen;
-        if (++arrived == n) { arrived = 0; gen++; cv.notify_all(); return true; }
-        cv.wait(lk, [&] { return gen != g || aborted; });
-        return gen != g;
-    }
-    void abort() {
-        std::lock_guard<std::mutex> g(mu);
-        aborted = true;
-        cv.notify_all();
-    }
-};
-
 struct ShardedCall {
     const bowgpu_col *const *cols_by_rank;
     const int32_t *ids;
@@ -471,7 +433,9 @@ struct ShardedCall {
     }
 };
 
-Fanout *g_sharded = nullptr;   // the workers of bowgpu_rolling_aggregate_sharded (not the fan-out's); never destroyed, like g_fan
+}  // namespace
+
+static Fanout *g_sharded = nullptr;   // the workers of bowgpu_rolling_aggregate_sharded (not the fan-out's); never destroyed, like g_fan
 
 Fanout *sharded_pool() {
     std::lock_guard<std::mutex> g(g_cfg_mu);
@@ -497,6 +461,8 @@ int sharded_enter(Worker *w, int device, uint32_t route, Ctx **c) {
     BG_TRY(bowgpu_debug_set_route(route));
     return ctx_get(c);
 }
+
+namespace {
 
 // a rank that wrote a window it does not own (drops_last): the slot out of its outputs.  Device-resident outputs: shard_tail_kernel and
 // the one synchronisation of the rank's stream it needs anyway; host-resident ones are on the host already (the finish has synchronised)
@@ -626,6 +592,8 @@ void sharded_layout_rank(Worker *w, ShardedCall *sc, int r) {
     if (rc < 0) sc->fail_rank(rc);
 }
 
+}  // namespace
+
 int device_of(const void *p, int *dev) {
     hipPointerAttribute_t a;
     memset(&a, 0, sizeof a);
@@ -634,8 +602,6 @@ int device_of(const void *p, int *dev) {
     *dev = a.device;
     return 0;
 }
-
-}  // namespace
 
 // One fanned-out call.  *done = false (and 0 returned): the call is not one for the fan-out - the caller goes on with the one-device
 // path.  plan: the frame's (newIntervalRolling's s0 / numWindows), against which the ranks' decisions are checked.  interps != nullptr:

@@ -39,7 +39,9 @@ extern "C" {
  * struct changed. */
 /* 11: bowgpu_valid_mask / bowgpu_drop_nils / bowgpu_diff / bowgpu_distinct added; 12: bowgpu_append / bowgpu_find_next added; 13: bowgpu_join_rows /
  * bowgpu_join added (Bow.InnerJoin / OuterJoin on the device); no existing struct changed. */
-#define BOWGPU_ABI_VERSION 13
+/* 14: bowgpu_sort_by_col_sharded and bowgpu_sort_by_col_sharded_info (with the bowgpu_sort_shard_info struct) added: Bow.SortByCol over
+ * row-range shards held on several devices; no existing struct changed. */
+#define BOWGPU_ABI_VERSION 14
 
 /* bow.Type (reference bowtypes.go:17-32) */
 enum {
@@ -473,7 +475,7 @@ int bowgpu_is_col_sorted(const bowgpu_col *col, int32_t *sorted);
  * BOWGPU_HOST inputs are staged through HBM as bowgpu_rolling_aggregate stages them, BOWGPU_HOST_PINNED inputs are read where they lie,
  * BOWGPU_DEVICE inputs are used where they lie; outputs may have any residency.  Per-thread contexts and streams as for every other
  * call (callable from several OS threads at once).  bowgpu_set_devices does not apply.  A sort ACROSS row-range shards on several
- * devices is a different algorithm (sample / merge exchange) and is not offered: sort each shard, or bring the key to one device.
+ * devices is a different algorithm (exact splitters, an exchange, a merge) and a call of its own: bowgpu_sort_by_col_sharded below.
  *   THE KEY COLUMN: Int64 or Float64, else BOWGPU_ERR_TYPE.  A key with nulls (null_count as given; counted when -1) is
  * BOWGPU_ERR_SORT_NULLS with the reference's message.  key_col out of range: BOWGPU_ERR_BAD_COL.  Columns of unequal length:
  * BOWGPU_ERR_ARG.  For host-resident columns these are decided before the device is touched (as bowgpu_plan_windows does), so they
@@ -512,6 +514,60 @@ int bowgpu_take(const bowgpu_col *col, const int64_t *idx, int64_t n_idx, int32_
  * reference returns the receiver itself (already sorted, or fewer than 2 rows): the outputs are then not written - neither their
  * buffers nor their length / null_count / type. */
 int bowgpu_sort_by_col(const bowgpu_col *cols, int32_t ncols, int32_t key_col, bowgpu_out *outs, int32_t *unchanged);
+
+/* Bow.SortByCol over a frame held as row-range shards on several devices - the remedy for BOWGPU_ERR_TS_UNSORTED of
+ * bowgpu_rolling_aggregate_sharded, whose frame no single device holds.
+ *   FRAME, RESIDENCY, ORDERING, SERIALISATION as for bowgpu_rolling_aggregate_sharded: cols_by_rank[r] holds ncols columns, rank r's
+ * rows, on device_ids[r]; an id may repeat (how a one-GPU box runs the path); 1 <= world <= 64; ranks may be empty, all of them too;
+ * any residency, a BOWGPU_DEVICE buffer of rank r must live on device_ids[r] (BOWGPU_ERR_ARG naming the rank); inputs must be complete
+ * at the call (the calling thread's stream is synchronised first), outputs are complete on return; calls are serialised process-wide
+ * (with bowgpu_rolling_aggregate_sharded's: one pool of library threads serves both); independent of bowgpu_set_devices.
+ *   THE GUARANTEE.  outs_by_rank[r][i]: column i of output rank r, capacity (length on entry) >= rank r's row count.  Output rank r
+ * gets exactly the row count of input rank r - the sorted frame keeps the caller's shard layout - and the outputs concatenated in rank
+ * order are, bit for bit, what bowgpu_sort_by_col gives for the inputs concatenated in rank order: values, validity, null slots
+ * holding 0, clear padding bits.  Ascending by Buffer.Less and STABLE: equal keys keep their (rank, row) order.  null_count of an
+ * output counts that output's own rows.  Each rank holds fewer than 2^31 rows; the total is not bounded by that.
+ *   *unchanged = 1 and nothing is written (buffers, length, null_count, type), as in the one-device call, when the whole frame is in
+ * order: every rank is (sort.IsSorted, ties included) and no non-empty rank's first key is below the last key of the non-empty rank
+ * before it; fewer than 2 rows in total are in order.
+ *   ERRORS are those of bowgpu_sort_by_col for the concatenated frame: BOWGPU_ERR_SORT_NULLS with the reference's message and the
+ * null count summed over the ranks; a Float64 key with a NaN on any rank BOWGPU_ERR_UNSUPPORTED; a key that is not Int64 / Float64
+ * BOWGPU_ERR_TYPE; Boolean / String columns BOWGPU_ERR_UNSUPPORTED; key_col out of range BOWGPU_ERR_BAD_COL.  A rank whose columns
+ * differ in length, or whose types differ from rank 0's: BOWGPU_ERR_ARG.  A capacity too small: BOWGPU_ERR_ARG naming rank and size,
+ * nothing written.  world out of range or a NULL list: BOWGPU_ERR_ARG.  A rank of 2^31 rows or more: BOWGPU_ERR_UNSUPPORTED naming
+ * the limit.  For host-resident columns all of these are decided before a device is touched; a valid call of two or more rows without
+ * a GPU is BOWGPU_ERR_NO_DEVICE.  The first error is the call's; on an error the outputs are undefined.  An error on one rank never
+ * leaves another waiting: every rank reaches every barrier of the call, whatever its status.
+ *   THE METHOD (bow_amd/csrc/sort_shard_api.cpp, sort_shard.hip): each rank sorts its key (the radix argsort above); the
+ * host bisects the 64-bit key image for the image of the row at every rank boundary of the global order - at most 65 rounds, each one
+ * launch per rank and one small read back - and cuts ties there in rank order; a rank that was not in order gathers its columns into
+ * sorted order; every destination pulls its pieces in source-rank order (hipMemcpyPeerAsync, or a device-to-device copy on one
+ * device; no peer access is enabled, no device setting changed) and puts them together with bowgpu_append's kernel - straight into
+ * its outputs when the pulled runs do not interleave, else into a staging frame whose runs a stable two-run merge (left run first on
+ * equal keys, ceil(log2 runs) rounds) turns into one permutation for the gather.  The sorted images are NOT pulled with the pieces:
+ * the destination forms them again from the staging frame's key column (one more kernel and one more read of that column there,
+ * against 8 bytes per row not copied between devices; which of the two costs less has not been measured).  The same call gives the
+ * same bytes.
+ *   HBM WORKSPACE per rank, transient, from the rank thread's scratch cache (exhaustion: BOWGPU_ERR_OOM): the sort's 24 bytes per
+ * row; one sorted copy of the shard (values + validity of every column) unless the rank was in order; the pulled pieces of at most 4
+ * columns at a time; when a merge runs, the staging frame (values + validity of every column) and 24 bytes per row for the merge
+ * (12 bytes - image and row - double-buffered); the staged copies of BOWGPU_HOST columns and the device temporaries of host-resident
+ * outputs as in the one-device call. */
+int bowgpu_sort_by_col_sharded(const bowgpu_col *const *cols_by_rank, const int32_t *device_ids, int32_t world, int32_t ncols,
+                               int32_t key_col, bowgpu_out *const *outs_by_rank, int32_t *unchanged);
+
+/* What the calling thread's last bowgpu_sort_by_col_sharded did and where its time went (all 0 after a call that returned before
+ * its ranks ran: an error found on the host, fewer than 2 rows).  A measurement aid: scratch/sort_sharded_wall.py. */
+typedef struct bowgpu_sort_shard_info {
+    int32_t splitter_rounds;   /* rounds of the splitter search (0: the frame was in order, or a rank failed before it) */
+    int32_t merge_rounds;      /* most merge rounds on any destination rank (0: no rank had to merge) */
+    int32_t sort_passes;       /* most radix passes in any rank's local sort (of 8) */
+    int32_t merged_ranks;      /* destination ranks whose pulled runs interleaved */
+    double local_sort_ms;      /* slowest rank: the kernels of its local sort, the read of the key included (device events) */
+    double splitter_ms;        /* slowest rank: wall time of the splitter search, its launches, read backs and barriers */
+    double merge_ms;           /* slowest rank: merge_init_kernel + the merge rounds (device events) */
+} bowgpu_sort_shard_info;
+int bowgpu_sort_by_col_sharded_info(bowgpu_sort_shard_info *info);
 
 /* ---- Bow.Filter -------------------------------------------------------------------- */
 
