@@ -1496,14 +1496,7 @@ static int run_modes(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t ts_c
             // (Mode is bit-exact in every size class; the classes beyond a lane's are reported for the tests - not under strict_order,
             // whose contract is long_windows == 0)
             if (long_windows && !g_strict_order) *long_windows += n_mid + n_long;
-            void *dscr;
-            BG_TRY(ctx_scratch(c, 8192, &dscr));
-            uint64_t *dcnt = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(dscr) + 1024);
-            uint64_t hcnt = 0;
-            BG_TRY(launch_popcount(c, reinterpret_cast<const uint32_t *>(d.validity), 0, W, dcnt));
-            BG_HIP(hipMemcpyAsync(&hcnt, dcnt, 8, hipMemcpyDeviceToHost, c->stream));
-            BG_HIP(hipStreamSynchronize(c->stream));
-            nulls = W - (int64_t)hcnt;
+            BG_TRY(recount_nulls(c, d.validity, W, &nulls));
         }
         BG_TRY(devout_finish(c, &d, W, cols[col].type, nulls));
         BG_HIP(hipStreamSynchronize(c->stream));
@@ -1631,20 +1624,13 @@ static int run_aggregate_null_ts(Ctx *c, const bowgpu_col *cols, int32_t ncols, 
         aggs2[i].col = slot;
     }
     // the ordinary path, into device temporaries
-    const size_t vb = (size_t)((W + 7) >> 3);
-    std::vector<DevBuf> tvals(naggs), tbits(naggs);
-    std::vector<bowgpu_out> touts(naggs);
-    for (int i = 0; i < naggs; i++) {
-        BG_TRY(tvals[i].alloc((size_t)W * 8 + 8));
-        BG_TRY(tbits[i].alloc(((vb + 3) & ~(size_t)3) + 8));
-        bowgpu_out &t = touts[i];
-        t.values = tvals[i].p; t.validity = reinterpret_cast<uint8_t *>(tbits[i].p); t.length = W; t.null_count = 0; t.type = 0; t.residency = BOWGPU_DEVICE;
-    }
-    BG_TRY(run_aggregate(c, cols2.data(), (int32_t)cols2.size(), ts_col, plan, inclusive, aggs2.data(), naggs, touts.data(), 0, W, long_windows, kernel_ms));
+    DevFrame tmp;
+    BG_TRY(tmp.alloc(c, naggs, W, false));
+    BG_TRY(run_aggregate(c, cols2.data(), (int32_t)cols2.size(), ts_col, plan, inclusive, aggs2.data(), naggs, tmp.outs.data(), 0, W, long_windows, kernel_ms));
     for (int i = 0; i < naggs; i++)
         if (aggs[i].kind == BOWGPU_AGG_NUM_ROWS) {
-            BG_TRY(launch_count_to_f64(c, reinterpret_cast<uint64_t *>(tvals[i].p), W));
-            touts[i].type = BOWGPU_FLOAT64;
+            BG_TRY(launch_count_to_f64(c, tmp.values[i].as<uint64_t>(), W));
+            tmp.outs[i].type = BOWGPU_FLOAT64;
         }
     if (inclusive && any_linear) {
         unsigned long long *d_fixed = reinterpret_cast<unsigned long long *>(dropped.p) + 1;
@@ -1662,7 +1648,7 @@ static int run_aggregate_null_ts(Ctx *c, const bowgpu_col *cols, int32_t ncols, 
             if (!kind_needs_inclusive(aggs[i].kind)) continue;
             QuirkFixAgg &fa = fx.a[fx.naggs++];
             BG_TRY(device_col(aggs[i].col, &fa.values, &fa.vbits, &fa.vbit0));
-            fa.out_values = reinterpret_cast<uint64_t *>(tvals[i].p); fa.out_valid = reinterpret_cast<uint32_t *>(tbits[i].p);
+            fa.out_values = tmp.values[i].as<uint64_t>(); fa.out_valid = tmp.bits[i].as<uint32_t>();
             fa.type = cols[aggs[i].col].type; fa.kind = aggs[i].kind; fa.n_factors = aggs[i].n_factors; fa._pad = 0;
             for (int f = 0; f < BOWGPU_MAX_FACTORS; f++) fa.factors[f] = aggs[i].factors[f];
             fixed.push_back(i);
@@ -1670,26 +1656,10 @@ static int run_aggregate_null_ts(Ctx *c, const bowgpu_col *cols, int32_t ncols, 
         }
         BG_TRY(flush());
         // their null counts again
-        void *dscr;
-        BG_TRY(ctx_scratch(c, 8192, &dscr));
-        uint64_t *dcnt = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(dscr) + 1024);
-        for (int i : fixed) {
-            uint64_t hcnt = 0;
-            BG_TRY(launch_popcount(c, reinterpret_cast<const uint32_t *>(tbits[i].p), 0, W, dcnt));
-            BG_HIP(hipMemcpyAsync(&hcnt, dcnt, 8, hipMemcpyDeviceToHost, c->stream));
-            BG_HIP(hipStreamSynchronize(c->stream));
-            touts[i].null_count = W - (int64_t)hcnt;
-        }
+        for (int i : fixed) BG_TRY(recount_nulls(c, tmp.bits[i].p, W, &tmp.outs[i].null_count));
     }
     // ... and on to the caller's columns
-    for (int i = 0; i < naggs; i++) {
-        DevOut d;
-        BG_TRY(devout_prepare(c, &outs[i], W, &d, i));
-        BG_HIP(hipMemcpyAsync(d.values, tvals[i].p, (size_t)W * 8, hipMemcpyDeviceToDevice, c->stream));
-        BG_HIP(hipMemcpyAsync(d.validity, tbits[i].p, vb, hipMemcpyDeviceToDevice, c->stream));
-        BG_TRY(devout_finish(c, &d, W, touts[i].type, touts[i].null_count, true));
-        BG_HIP(hipStreamSynchronize(c->stream));
-    }
+    for (int i = 0; i < naggs; i++) BG_TRY(temp_to_caller(c, tmp, i, W, tmp.outs[i].type, tmp.outs[i].null_count, &outs[i], i));
     return 0;
 }
 
@@ -2225,23 +2195,11 @@ int bowgpu_rolling_interpolate_aggregate(const bowgpu_col *cols, int32_t ncols, 
     // the two calls.  The interpolated frame lives in device temporaries and is aggregated where it lies.
     int64_t n_out = 0;
     BG_TRY(bowgpu_rolling_interpolate_count(cols, ncols, ts_col, interval, &o, interps, ninterps, &n_out));
-    std::vector<DevBuf> vals(ncols), bits(ncols);
-    std::vector<bowgpu_out> mid(ncols);
+    DevFrame mid;
     std::vector<bowgpu_col> icols(ncols);
-    for (int i = 0; i < ncols; i++) {
-        BG_TRY(vals[i].alloc((size_t)n_out * 8 + 16));
-        BG_TRY(bits[i].alloc((size_t)((n_out + 7) >> 3) + 16));
-        memset(&mid[i], 0, sizeof mid[i]);
-        mid[i].values = vals[i].p; mid[i].validity = reinterpret_cast<uint8_t *>(bits[i].p);
-        mid[i].length = n_out; mid[i].residency = BOWGPU_DEVICE;
-    }
-    if (n_out > 0) BG_TRY(bowgpu_rolling_interpolate_fill(cols, ncols, ts_col, interval, &o, interps, ninterps, mid.data()));
-    for (int i = 0; i < ncols; i++) {
-        memset(&icols[i], 0, sizeof icols[i]);
-        icols[i].values = mid[i].values; icols[i].validity = mid[i].validity;
-        icols[i].offset = 0; icols[i].length = n_out; icols[i].null_count = n_out > 0 ? mid[i].null_count : 0;
-        icols[i].type = cols[i].type; icols[i].residency = BOWGPU_DEVICE;
-    }
+    BG_TRY(mid.alloc(c, ncols, n_out, false));
+    if (n_out > 0) BG_TRY(bowgpu_rolling_interpolate_fill(cols, ncols, ts_col, interval, &o, interps, ninterps, mid.outs.data()));
+    mid.as_cols(cols, n_out, icols.data());
     const int rc = bowgpu_rolling_aggregate(icols.data(), ncols, ts_col, interval, &o, aggs, naggs, outs, info);
     // (the temporaries go back to the block cache: every entry point above has synchronised the stream)
     return rc;

@@ -216,6 +216,38 @@ int move_group_prepare(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t g0
 int move_group_outputs(Ctx *c, int32_t ncols, int32_t g0, bowgpu_out *outs, int64_t count, MoveGroup *g);
 int move_group_finish(Ctx *c, MoveGroup *g, const bowgpu_col *cols, int32_t g0, int64_t count, const int64_t *null_counts);
 
+// The one size rule of device temporaries that hold rows of a frame.  Values: 8 bytes a row + 16, the margin devcol_prepare's
+// uploads carry too, against the kernels' 16-byte loads (the sites this rule replaced added 0, 8 or 16; none is known to need it).
+// Bitmap: its bytes rounded up to whole 32-bit words + 16: the kernels that fill a frame store whole 32- or 64-bit validity words,
+// and a 64-bit word may begin at the last 32-bit word of the rows and be followed by a reader's look at the word behind it.
+inline size_t temp_values_bytes(int64_t rows) { return (size_t)rows * 8 + 16; }
+inline size_t temp_bits_bytes(size_t bitmap_bytes) { return ((bitmap_bytes + 3) & ~(size_t)3) + 16; }
+// A frame of device temporaries: `rows` slots by ncols columns that live only in HBM, filled by one call (which takes `outs`)
+// and read by the next (which takes as_cols).  A caller whose fill writes bitmaps in place rounds `rows` up itself.
+struct DevFrame {
+    std::vector<DevBuf> values, bits;
+    std::vector<bowgpu_out> outs;     // the frame as output columns of `rows` slots; the filling call leaves length / null_count / type
+    int alloc(Ctx *c, int32_t ncols, int64_t rows, bool zero_bits);   // zero_bits: for a fill that only sets bits (one memset a column, no synchronise)
+    // The first n <= rows rows of the filled frame as input columns, types from schema.  The bitmap pointer always stays and the
+    // null count is carried (0 for n == 0): every reader of such a column - devcol_prepare, has_bitmap, and through them
+    // gather_frame, stage_rows and the aggregate's checks - looks at a bitmap only where `validity && null_count != 0`, so a
+    // column without nulls reads like one without a bitmap.  (plan_make alone asks a bitmap that is there for row 0 and the last
+    // row before it reads them; it finds them valid and computes the same plan.)
+    void as_cols(const bowgpu_col *schema, int64_t n, bowgpu_col *cols) const;
+    // on the owning thread: the blocks go back to THAT thread's (device's) cache.  What the fill reported in outs stays, the pointers do not
+    void clear();
+};
+// Rows [a, b) of a column of any residency (device-resident: on device src_dev) into two buffers of the current device dst_dev, on
+// its stream: values from an 8-row boundary of the source buffer, so that one Arrow offset serves values and bits, and - where the
+// column has a bitmap to read - the validity bytes that cover the rows, in a zeroed, padded block.  *out: the piece as a
+// device-resident column (null_count -1 with a bitmap, else 0).  Host and registered sources go through copy_h2d, the same device
+// through hipMemcpyAsync, another device through hipMemcpyPeerAsync.  No synchronise
+int stage_rows(Ctx *c, int dst_dev, int src_dev, const bowgpu_col &sc, int64_t a, int64_t b, DevBuf *values, DevBuf *bits, bowgpu_col *out);
+// the nulls among the first n bits of a device bitmap (32-bit aligned): popcount through the context scratch, read back, synchronised
+int recount_nulls(Ctx *c, const void *bits, int64_t n, int64_t *nulls);
+// column i of a filled temporary frame, n rows, handed to the caller's output column (pool_slot: devout_prepare's); synchronises
+int temp_to_caller(Ctx *c, const DevFrame &f, int32_t i, int64_t n, int32_t type, int64_t null_count, bowgpu_out *out, int pool_slot);
+
 // ---------------------------------------------------------------- division by the interval
 // Granlund–Montgomery round-up method (N = 64): exact floor(n / d) for every 0 <= n < 2^64.
 struct MagicDiv {

@@ -699,20 +699,12 @@ static int interp_null_ts(const bowgpu_col *cols, int32_t ncols, int32_t ts_col,
         return 0;
     }
     if (m_out == 0) return nothing();
-    const size_t vb = (size_t)((m_out + 7) >> 3);
-    std::vector<DevBuf> tvals(ncols + 1), tbits(ncols + 1);
-    std::vector<bowgpu_out> touts(ncols + 1);
-    for (int i = 0; i <= ncols; i++) {
-        BG_TRY(tvals[i].alloc((size_t)m_out * 8 + 16));
-        BG_TRY(tbits[i].alloc(((vb + 3) & ~(size_t)3) + 8));
-        BG_HIP(hipMemsetAsync(tbits[i].p, 0, ((vb + 3) & ~(size_t)3) + 8, c->stream));
-        bowgpu_out &t = touts[i];
-        t.values = tvals[i].p; t.validity = reinterpret_cast<uint8_t *>(tbits[i].p); t.length = m_out; t.null_count = 0; t.type = 0; t.residency = BOWGPU_DEVICE;
-        if (i < ncols) { cc.patch_values[i] = reinterpret_cast<uint64_t *>(tvals[i].p); cc.patch_valid[i] = reinterpret_cast<uint32_t *>(tbits[i].p); }
-    }
-    BG_TRY(interp_fill_impl(cols2.data(), ncols + 1, ts_col, interval, &o, interps2.data(), ninterps + 1, touts.data(), nullptr, nullptr));
+    DevFrame tmp;   // the compacted call's outputs: the Bow's columns and the marker
+    BG_TRY(tmp.alloc(c, ncols + 1, m_out, true));
+    for (int i = 0; i < ncols; i++) { cc.patch_values[i] = tmp.values[i].as<uint64_t>(); cc.patch_valid[i] = tmp.bits[i].as<uint32_t>(); }
+    BG_TRY(interp_fill_impl(cols2.data(), ncols + 1, ts_col, interval, &o, interps2.data(), ninterps + 1, tmp.outs.data(), nullptr, nullptr));
     c->interp_cache.valid = false;
-    if (touts[0].length != m_out) return fail(BOWGPU_ERR_ARG, "internal: Interpolate over an interval column with nulls produced %lld rows, counted %lld", (long long)touts[0].length, (long long)m_out);
+    if (tmp.outs[0].length != m_out) return fail(BOWGPU_ERR_ARG, "internal: Interpolate over an interval column with nulls produced %lld rows, counted %lld", (long long)tmp.outs[0].length, (long long)m_out);
     PatchInterps px;
     memset(&px, 0, sizeof px);
     px.m = m;
@@ -727,23 +719,13 @@ static int interp_null_ts(const bowgpu_col *cols, int32_t ncols, int32_t ts_col,
             px.prev_t[i] = interps[i].prev_t; px.prev_v[i] = interps[i].prev_v; px.prev_v_i64[i] = interps[i].prev_v_i64;
         }
     }
-    BG_TRY(launch_interp_patch(c, reinterpret_cast<const int64_t *>(tvals[ncols].p), reinterpret_cast<const uint32_t *>(tbits[ncols].p), m_out,
+    BG_TRY(launch_interp_patch(c, tmp.values[ncols].as<const int64_t>(), tmp.bits[ncols].as<const uint32_t>(), m_out,
                                reinterpret_cast<const uint32_t *>(flags.p), cc, px));
     BG_HIP(hipStreamSynchronize(c->stream));       // (nbrbufs are released at the end of this scope)
-    void *dscr;
-    BG_TRY(ctx_scratch(c, 8192, &dscr));
-    uint64_t *dcnt = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(dscr) + 1024);
     for (int i = 0; i < ncols; i++) {
-        uint64_t hcnt = 0;
-        BG_TRY(launch_popcount(c, reinterpret_cast<const uint32_t *>(tbits[i].p), 0, m_out, dcnt));
-        BG_HIP(hipMemcpyAsync(&hcnt, dcnt, 8, hipMemcpyDeviceToHost, c->stream));
-        BG_HIP(hipStreamSynchronize(c->stream));
-        DevOut d;
-        BG_TRY(devout_prepare(c, &outs[i], m_out, &d, i < 16 ? i : -1));
-        BG_HIP(hipMemcpyAsync(d.values, tvals[i].p, (size_t)m_out * 8, hipMemcpyDeviceToDevice, c->stream));
-        BG_HIP(hipMemcpyAsync(d.validity, tbits[i].p, vb, hipMemcpyDeviceToDevice, c->stream));
-        BG_TRY(devout_finish(c, &d, m_out, cols[i].type, m_out - (int64_t)hcnt, true));
-        BG_HIP(hipStreamSynchronize(c->stream));
+        int64_t nulls = 0;
+        BG_TRY(recount_nulls(c, tmp.bits[i].p, m_out, &nulls));
+        BG_TRY(temp_to_caller(c, tmp, i, m_out, cols[i].type, nulls, &outs[i], i < 16 ? i : -1));
     }
     device_write_epoch_bump();
     return 0;

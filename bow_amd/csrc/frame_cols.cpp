@@ -1,6 +1,8 @@
 // frame_cols.cpp — the host layer under the frame-level operations (the *_api.cpp files of Sort, Filter, DropNils / Diff / Distinct,
 // Append / Find and Join): argument checks of a frame and its output columns, a caller's side buffers in and out, and the staging of
-// the columns of a frame, kMoveCols a launch, around the kernel that moves their rows.  No kernel is launched here.
+// the columns of a frame, kMoveCols a launch, around the kernel that moves their rows; and what the calls that keep a frame in
+// device temporaries between two steps share (DevFrame, stage_rows, temp_to_caller).  No kernel of its own: recount_nulls goes
+// through the library's popcount.
 #include <string.h>
 
 #include "common.h"
@@ -151,6 +153,82 @@ int move_group_finish(Ctx *c, MoveGroup *g, const bowgpu_col *cols, int32_t g0, 
         const int rc = devout_finish(c, &g->douts[i], count, cols[g0 + i].type, null_counts[i]);
         if (rc != 0) return synced(c, rc);
     }
+    BG_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int DevFrame::alloc(Ctx *c, int32_t ncols, int64_t rows, bool zero_bits) {
+    values.resize(ncols); bits.resize(ncols); outs.resize(ncols);
+    for (int i = 0; i < ncols; i++) {
+        BG_TRY(values[i].alloc(temp_values_bytes(rows)));
+        BG_TRY(bits[i].alloc(temp_bits_bytes((size_t)((rows + 7) >> 3))));
+        if (zero_bits) BG_HIP(hipMemsetAsync(bits[i].p, 0, bits[i].bytes, c->stream));
+        memset(&outs[i], 0, sizeof outs[i]);
+        outs[i].values = values[i].p;
+        outs[i].validity = bits[i].as<uint8_t>();
+        outs[i].length = rows;
+        outs[i].residency = BOWGPU_DEVICE;
+    }
+    return 0;
+}
+
+void DevFrame::as_cols(const bowgpu_col *schema, int64_t n, bowgpu_col *cols) const {
+    for (size_t i = 0; i < outs.size(); i++) {
+        cols[i] = device_col(outs[i].values, n, schema[i].type);
+        cols[i].validity = outs[i].validity;
+        cols[i].null_count = n > 0 ? outs[i].null_count : 0;
+    }
+}
+
+void DevFrame::clear() {
+    values.clear(); bits.clear();
+    for (bowgpu_out &o : outs) { o.values = nullptr; o.validity = nullptr; }
+}
+
+// bytes of a source column into a buffer of the destination's device, on the destination's stream
+static int pull_bytes(Ctx *c, int dst_dev, int src_dev, void *dst, const void *src, size_t bytes, int32_t residency) {
+    if (bytes == 0) return 0;
+    if (residency != BOWGPU_DEVICE) return copy_h2d(c, dst, src, bytes, residency == BOWGPU_HOST_PINNED);
+    if (dst_dev == src_dev) BG_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
+    else BG_HIP(hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, c->stream));
+    return 0;
+}
+
+int stage_rows(Ctx *c, int dst_dev, int src_dev, const bowgpu_col &sc, int64_t a, int64_t b, DevBuf *values, DevBuf *bits, bowgpu_col *out) {
+    const int64_t r0 = sc.offset + a, r1 = sc.offset + b, v0 = r0 & ~(int64_t)7;
+    BG_TRY(values->alloc(temp_values_bytes(r1 - v0)));
+    BG_TRY(pull_bytes(c, dst_dev, src_dev, values->p, reinterpret_cast<const char *>(sc.values) + 8 * v0, (size_t)(r1 - v0) * 8, sc.residency));
+    *out = device_col(values->p, b - a, sc.type);
+    out->offset = r0 - v0;
+    if (has_bitmap(sc)) {
+        const int64_t b0 = r0 >> 3, b1 = (r1 + 7) >> 3;
+        BG_TRY(bits->alloc(temp_bits_bytes((size_t)(b1 - b0))));
+        BG_HIP(hipMemsetAsync(bits->p, 0, bits->bytes, c->stream));
+        BG_TRY(pull_bytes(c, dst_dev, src_dev, bits->p, sc.validity + b0, (size_t)(b1 - b0), sc.residency));
+        out->validity = bits->as<const uint8_t>();
+        out->null_count = -1;
+    }
+    return 0;
+}
+
+int recount_nulls(Ctx *c, const void *bits, int64_t n, int64_t *nulls) {
+    void *scr;
+    BG_TRY(ctx_scratch(c, 8192, &scr));
+    uint64_t *d_count = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(scr) + 1024);
+    uint64_t set = 0;
+    BG_TRY(launch_popcount(c, reinterpret_cast<const uint32_t *>(bits), 0, n, d_count));
+    BG_HIP(hipMemcpyAsync(&set, d_count, 8, hipMemcpyDeviceToHost, c->stream));
+    BG_HIP(hipStreamSynchronize(c->stream));
+    *nulls = n - (int64_t)set;
+    return 0;
+}
+
+int temp_to_caller(Ctx *c, const DevFrame &f, int32_t i, int64_t n, int32_t type, int64_t null_count, bowgpu_out *out, int pool_slot) {
+    DevOut d;
+    BG_TRY(devout_prepare(c, out, n, &d, pool_slot));
+    BG_HIP(hipMemcpyAsync(d.values, f.values[i].p, (size_t)n * 8, hipMemcpyDeviceToDevice, c->stream));
+    BG_HIP(hipMemcpyAsync(d.validity, f.bits[i].p, (size_t)((n + 7) >> 3), hipMemcpyDeviceToDevice, c->stream));
+    BG_TRY(devout_finish(c, &d, n, type, null_count, true));
     BG_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -187,11 +187,9 @@ struct Rank {
     // the rank's columns as the record protocol sees them; pageable columns are staged ONCE (the record pass and the rank's pass both
     // read the staged copy: each row crosses the host link once)
     std::vector<bowgpu_col> cols;
-    std::vector<DevBuf> staged_values, staged_bits;
+    std::vector<DevBuf> staged_bufs;                  // [2 * ncols]: the values and the bits of column i
     bool staged = false;
-    // its outputs: device temporaries
-    std::vector<DevBuf> out_values, out_bits;
-    std::vector<bowgpu_out> outs;
+    DevFrame out;                                     // its outputs: device temporaries
     std::vector<std::vector<uint8_t>> host_bits;     // the rank's bitmaps on the host (padded)
     std::vector<std::vector<EdgeByte>> edges;         // per output
     std::vector<int64_t> valid;                       // per output: valid slots among the owned ones
@@ -202,14 +200,14 @@ struct Rank {
     bowgpu_interp_points points;
     bowgpu_interp_edge edge;
     std::vector<bowgpu_interp> interps;
-    std::vector<DevBuf> mid_values, mid_bits;
+    DevFrame mid;
     std::vector<bowgpu_col> raw_cols;   // the rank's rows as given (cols becomes the interpolated frame once it exists)
     bool interpolated = false;
     int rc = 0;
     std::string err;
     void fail_from_thread(int code) { rc = code; err = bowgpu_last_error(); }
     void release() {   // on the rank's own thread: the blocks go back to THAT thread's (device's) cache
-        staged_values.clear(); staged_bits.clear(); out_values.clear(); out_bits.clear(); mid_values.clear(); mid_bits.clear();
+        staged_bufs.clear(); out.clear(); mid.clear();
         staged = false; interpolated = false;
     }
 };
@@ -245,32 +243,18 @@ int rank_stage(Ctx *c, const Call &call, Rank *rk) {
     used[call.ts_col] = 1;
     for (int a = 0; a < call.naggs; a++) used[call.aggs[a].col] = 1;
     rk->cols.resize(call.ncols);
-    rk->staged_values.resize(call.ncols);
-    rk->staged_bits.resize(call.ncols);
+    rk->staged_bufs.resize((size_t)2 * call.ncols);
     for (int i = 0; i < call.ncols; i++) {
-        bowgpu_col s = call.cols[i];
-        const int64_t off = call.cols[i].offset + rk->row0;
-        s.offset = off;
-        s.length = rk->nrows;
-        s.null_count = (call.cols[i].validity && call.cols[i].null_count != 0) ? -1 : 0;
-        if (used[i] && call.cols[i].residency == BOWGPU_HOST && rk->nrows > 0) {
-            const int64_t a = off & ~(int64_t)7, rows = off + rk->nrows - a;
-            BG_TRY(rk->staged_values[i].alloc((size_t)rows * 8 + 16));
-            BG_TRY(copy_h2d(c, rk->staged_values[i].p, reinterpret_cast<const char *>(call.cols[i].values) + 8 * a, (size_t)rows * 8));
-            s.values = rk->staged_values[i].p;
-            if (s.null_count != 0) {
-                const size_t nb = (size_t)((rows + 7) >> 3);
-                BG_TRY(rk->staged_bits[i].alloc(((nb + 3) & ~(size_t)3) + 8));
-                BG_HIP(hipMemsetAsync(rk->staged_bits[i].p, 0, rk->staged_bits[i].bytes, c->stream));
-                BG_TRY(copy_h2d(c, rk->staged_bits[i].p, call.cols[i].validity + (a >> 3), nb));
-                s.validity = reinterpret_cast<const uint8_t *>(rk->staged_bits[i].p);
-            } else {
-                s.validity = nullptr;
-            }
-            s.offset = off - a;
-            s.residency = BOWGPU_DEVICE;
+        bowgpu_col &s = rk->cols[i];
+        if (used[i] && call.cols[i].residency == BOWGPU_HOST && rk->nrows > 0) {   // (pageable: the device ids are not looked at)
+            BG_TRY(stage_rows(c, c->device, c->device, call.cols[i], rk->row0, rk->row0 + rk->nrows, &rk->staged_bufs[2 * i],
+                              &rk->staged_bufs[2 * i + 1], &s));
+            continue;
         }
-        rk->cols[i] = s;
+        s = call.cols[i];
+        s.offset = call.cols[i].offset + rk->row0;
+        s.length = rk->nrows;
+        s.null_count = has_bitmap(call.cols[i]) ? -1 : 0;
     }
     BG_HIP(hipStreamSynchronize(c->stream));   // (the staging halves are free again; the copies are in HBM)
     rk->staged = true;
@@ -296,30 +280,15 @@ int rank_interpolate_impl(Ctx *c, Call *call, int r) {
     BG_TRY(bowgpu_shard_interpolate_count(rk->cols.data(), nc, call->ts_col, call->interval, &call->opts, call->global_s0, rk->interps.data(),
                                           call->ninterps, &rk->edge, &n_out));
     const int64_t cap = (n_out + 31) & ~(int64_t)31;   // (whole bitmap words: the fill writes device bitmaps in place)
-    rk->mid_values.resize(nc); rk->mid_bits.resize(nc);
-    std::vector<bowgpu_out> mid(nc);
-    for (int i = 0; i < nc; i++) {
-        BG_TRY(rk->mid_values[i].alloc((size_t)cap * 8 + 16));
-        BG_TRY(rk->mid_bits[i].alloc((size_t)(cap >> 3) + 16));
-        memset(&mid[i], 0, sizeof mid[i]);
-        mid[i].values = rk->mid_values[i].p; mid[i].validity = reinterpret_cast<uint8_t *>(rk->mid_bits[i].p);
-        mid[i].length = cap; mid[i].residency = BOWGPU_DEVICE;
-    }
+    BG_TRY(rk->mid.alloc(c, nc, cap, false));
     if (n_out > 0)
         BG_TRY(bowgpu_shard_interpolate_fill(rk->cols.data(), nc, call->ts_col, call->interval, &call->opts, call->global_s0, rk->interps.data(),
-                                             call->ninterps, &rk->edge, mid.data()));
+                                             call->ninterps, &rk->edge, rk->mid.outs.data()));
     rk->raw_cols = rk->cols;
-    for (int i = 0; i < nc; i++) {
-        bowgpu_col ic;
-        memset(&ic, 0, sizeof ic);
-        ic.values = mid[i].values; ic.validity = mid[i].validity; ic.offset = 0; ic.length = n_out;
-        ic.null_count = n_out > 0 ? mid[i].null_count : 0;
-        ic.type = call->cols[i].type; ic.residency = BOWGPU_DEVICE;
-        rk->cols[i] = ic;
-    }
+    rk->mid.as_cols(call->cols, n_out, rk->cols.data());
     // the staged copies of the input rows have served
     BG_HIP(hipStreamSynchronize(c->stream));
-    rk->staged_values.clear(); rk->staged_bits.clear();
+    rk->staged_bufs.clear();
     rk->interpolated = true;
     return 0;
 }
@@ -349,18 +318,8 @@ int rank_finish_impl(Ctx *c, Call *call, int r) {
     const bowgpu_shard_decision &d = rk->decision;
     const int na = call->naggs;
     const int64_t cap = std::max<int64_t>(d.windows_local, 1);
-    rk->out_values.resize(na); rk->out_bits.resize(na); rk->outs.resize(na);
-    const size_t vb = (size_t)((cap + 7) >> 3);
-    for (int i = 0; i < na; i++) {
-        BG_TRY(rk->out_values[i].alloc((size_t)cap * 8));
-        BG_TRY(rk->out_bits[i].alloc(((vb + 3) & ~(size_t)3) + 8));
-        memset(&rk->outs[i], 0, sizeof(bowgpu_out));
-        rk->outs[i].values = rk->out_values[i].p;
-        rk->outs[i].validity = reinterpret_cast<uint8_t *>(rk->out_bits[i].p);
-        rk->outs[i].length = cap;
-        rk->outs[i].residency = BOWGPU_DEVICE;
-    }
-    const int rc = bowgpu_shard_finish(rk->cols.data(), call->ncols, call->ts_col, call->interval, &call->opts, call->aggs, na, rk->outs.data(),
+    BG_TRY(rk->out.alloc(c, na, cap, false));
+    const int rc = bowgpu_shard_finish(rk->cols.data(), call->ncols, call->ts_col, call->interval, &call->opts, call->aggs, na, rk->out.outs.data(),
                                        call->records.data(), call->world, r, &rk->decision, &rk->info);
     if (rc != 0) return rc;   // (BOWGPU_SHARD_RETRY included: the calling thread decides)
     const int64_t owned = d.windows_owned, slot0 = d.first_slot_window_id;
@@ -372,10 +331,10 @@ int rank_finish_impl(Ctx *c, Call *call, int r) {
     for (int i = 0; i < na; i++) {
         bowgpu_out *u = &call->outs[i];
         char *dst = reinterpret_cast<char *>(u->values) + 8 * slot0;
-        if (u->residency == BOWGPU_DEVICE) BG_HIP(hipMemcpyAsync(dst, rk->outs[i].values, (size_t)owned * 8, hipMemcpyDeviceToDevice, c->stream));
-        else BG_TRY(copy_d2h(c, dst, rk->outs[i].values, (size_t)owned * 8, u->residency == BOWGPU_HOST_PINNED));
+        if (u->residency == BOWGPU_DEVICE) BG_HIP(hipMemcpyAsync(dst, rk->out.outs[i].values, (size_t)owned * 8, hipMemcpyDeviceToDevice, c->stream));
+        else BG_TRY(copy_d2h(c, dst, rk->out.outs[i].values, (size_t)owned * 8, u->residency == BOWGPU_HOST_PINNED));
         rk->host_bits[i].assign(((size_t)(owned + 7) >> 3) + 24, 0);
-        BG_TRY(copy_d2h(c, rk->host_bits[i].data(), rk->outs[i].validity, (size_t)((owned + 7) >> 3)));
+        BG_TRY(copy_d2h(c, rk->host_bits[i].data(), rk->out.outs[i].validity, (size_t)((owned + 7) >> 3)));
     }
     BG_HIP(hipStreamSynchronize(c->stream));
     for (int i = 0; i < na; i++)
@@ -780,7 +739,7 @@ static int fan_call(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, const
         outs[i].length = W;
         outs[i].null_count = W - valid;
         for (int r = 0; r < world; r++)   // (the types were resolved by every rank alike)
-            if (!call.ranks[r].outs.empty()) { outs[i].type = call.ranks[r].outs[i].type; break; }
+            if (!call.ranks[r].out.outs.empty()) { outs[i].type = call.ranks[r].out.outs[i].type; break; }
     }
     bool any_dev_out = false;
     for (int i = 0; i < naggs; i++) any_dev_out |= outs[i].residency == BOWGPU_DEVICE;

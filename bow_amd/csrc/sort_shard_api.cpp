@@ -35,7 +35,7 @@ struct RankState {
     const uint64_t *skeys = nullptr; // the key in sorted order as the splitter kernels read it
     int32_t smode = kKeyImages;
     uint64_t first_img = 0, last_img = 0;
-    std::vector<DevBuf> tmp_values, tmp_bits;   // the rank's columns in sorted order (a rank that was not in order)
+    DevFrame tmp;                               // the rank's columns in sorted order (a rank that was not in order)
     std::vector<bowgpu_col> src;                // what the destinations pull from: the temporaries, or the input as it lies
     std::vector<int64_t> cut;                   // [world][world + 1], the same on every rank
     std::vector<uint64_t> ends;                 // [world][2]: first / last image of piece (this rank -> d)
@@ -44,7 +44,7 @@ struct RankState {
     int rc = 0;
     std::string err;
     void release() {   // on the rank's own thread: the blocks go back to THAT thread's (device's) cache
-        tmp_values.clear(); tmp_bits.clear();
+        tmp.clear();
         w = SortWork();
         have = StagedCols();
         dk = nullptr;
@@ -219,29 +219,13 @@ int rank_source(Ctx *c, ShardSort *ss, int r) {
     me.ends.assign((size_t)2 * world, 0);
     if (me.n == 0) return 0;
     if (!me.sorted) {
-        me.tmp_values.resize(nc); me.tmp_bits.resize(nc);
-        std::vector<bowgpu_out> tmp(nc);
-        const size_t vb = (size_t)((me.n + 7) >> 3);
-        for (int i = 0; i < nc; i++) {
-            BG_TRY(me.tmp_values[i].alloc((size_t)me.n * 8));
-            BG_TRY(me.tmp_bits[i].alloc(((vb + 3) & ~(size_t)3) + 8));
-            BG_HIP(hipMemsetAsync(me.tmp_bits[i].p, 0, me.tmp_bits[i].bytes, c->stream));
-            memset(&tmp[i], 0, sizeof tmp[i]);
-            tmp[i].values = me.tmp_values[i].p; tmp[i].validity = me.tmp_bits[i].as<uint8_t>();
-            tmp[i].length = me.n; tmp[i].residency = BOWGPU_DEVICE;
-        }
+        BG_TRY(me.tmp.alloc(c, nc, me.n, true));
         GatherIdx ix;
         ix.u32 = me.w.perm();
         bool bad = false;
-        BG_TRY(gather_frame(c, cols, nc, me.have, ix, me.n, tmp.data(), &bad));
+        BG_TRY(gather_frame(c, cols, nc, me.have, ix, me.n, me.tmp.outs.data(), &bad));
         if (bad) return fail(BOWGPU_ERR_HIP, "internal: the sort produced a row index outside the frame");
-        for (int i = 0; i < nc; i++) {
-            bowgpu_col &s = me.src[i];
-            memset(&s, 0, sizeof s);
-            s.values = tmp[i].values;
-            s.validity = tmp[i].null_count > 0 ? tmp[i].validity : nullptr;
-            s.length = me.n; s.null_count = tmp[i].null_count; s.type = cols[i].type; s.residency = BOWGPU_DEVICE;
-        }
+        me.tmp.as_cols(cols, me.n, me.src.data());
     }
     uint32_t pos[2 * kShardMaxWorld];
     int at[kShardMaxWorld], np = 0;
@@ -255,40 +239,6 @@ int rank_source(Ctx *c, ShardSort *ss, int r) {
     for (int d = 0; d < world; d++)
         if (at[d] >= 0) { me.ends[2 * d] = img[at[d]]; me.ends[2 * d + 1] = img[at[d] + 1]; }
     return 0;   // (the gather's groups and read_images have synchronised: the pieces are complete)
-}
-
-// step 4: bytes of a source column into a buffer of the destination's device, on the destination's stream
-int pull_bytes(Ctx *c, int dst_dev, int src_dev, void *dst, const void *src, size_t bytes, int32_t residency) {
-    if (bytes == 0) return 0;
-    if (residency != BOWGPU_DEVICE) return copy_h2d(c, dst, src, bytes, residency == BOWGPU_HOST_PINNED);
-    if (dst_dev == src_dev) BG_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
-    else BG_HIP(hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, c->stream));
-    return 0;
-}
-
-// rows [a, b) of a source column: values from an 8-row boundary of its buffer (one Arrow offset then serves values and bits) and
-// the validity bytes that cover the rows; *out: the piece as a device-resident column of the destination
-int pull_piece(Ctx *c, int dst_dev, int src_dev, const bowgpu_col &sc, int64_t a, int64_t b, DevBuf *lv, DevBuf *lb, bowgpu_col *out) {
-    const int64_t r0 = sc.offset + a, r1 = sc.offset + b, v0 = r0 & ~(int64_t)7;
-    const size_t vbytes = (size_t)(r1 - v0) * 8;
-    BG_TRY(lv->alloc(vbytes));
-    BG_TRY(pull_bytes(c, dst_dev, src_dev, lv->p, reinterpret_cast<const char *>(sc.values) + 8 * v0, vbytes, sc.residency));
-    memset(out, 0, sizeof *out);
-    out->values = lv->p;
-    out->offset = r0 - v0;
-    out->length = b - a;
-    out->type = sc.type;
-    out->residency = BOWGPU_DEVICE;
-    if (has_bitmap(sc)) {
-        const int64_t b0 = r0 >> 3, b1 = (r1 + 7) >> 3;
-        const size_t nb = (size_t)(b1 - b0);
-        BG_TRY(lb->alloc(((nb + 3) & ~(size_t)3) + 8));
-        BG_HIP(hipMemsetAsync(lb->p, 0, lb->bytes, c->stream));
-        BG_TRY(pull_bytes(c, dst_dev, src_dev, lb->p, sc.validity + b0, nb, sc.residency));
-        out->validity = lb->as<const uint8_t>();
-        out->null_count = -1;
-    }
-    return 0;
 }
 
 // the k sorted runs of a staging frame's key into one permutation: ceil(log2 k) rounds of pairwise stable merges
@@ -343,21 +293,9 @@ int rank_dest(Ctx *c, ShardSort *ss, int d) {
     for (int j = 0; j + 1 < np; j++)
         interleave |= ss->ranks[pieces[j].src].ends[2 * d + 1] > ss->ranks[pieces[j + 1].src].ends[2 * d];
     // a staging frame when the runs have to be merged
-    std::vector<DevBuf> stage_values, stage_bits;
-    std::vector<bowgpu_out> stage;
-    if (interleave) {
-        stage_values.resize(nc); stage_bits.resize(nc); stage.resize(nc);
-        const size_t vb = (size_t)((nd + 7) >> 3);
-        for (int i = 0; i < nc; i++) {
-            BG_TRY(stage_values[i].alloc((size_t)nd * 8));
-            BG_TRY(stage_bits[i].alloc(((vb + 3) & ~(size_t)3) + 8));
-            BG_HIP(hipMemsetAsync(stage_bits[i].p, 0, stage_bits[i].bytes, c->stream));
-            memset(&stage[i], 0, sizeof stage[i]);
-            stage[i].values = stage_values[i].p; stage[i].validity = stage_bits[i].as<uint8_t>();
-            stage[i].length = nd; stage[i].residency = BOWGPU_DEVICE;
-        }
-    }
-    bowgpu_out *target = interleave ? stage.data() : outs;
+    DevFrame stage;
+    if (interleave) BG_TRY(stage.alloc(c, nc, nd, true));
+    bowgpu_out *target = interleave ? stage.outs.data() : outs;
     std::vector<std::vector<bowgpu_col>> frames(np, std::vector<bowgpu_col>(nc));
     std::vector<const bowgpu_col *> fptr(np);
     for (int f = 0; f < np; f++) fptr[f] = frames[f].data();
@@ -370,8 +308,9 @@ int rank_dest(Ctx *c, ShardSort *ss, int d) {
         for (int f = 0; f < np; f++) {
             const Piece &p = pieces[f];
             for (int i = 0; i < gc; i++) {
-                // (queued on this rank's stream behind one another; lv / lb live until the group is done, so only a failure synchronises)
-                BG_TRY(synced(c, pull_piece(c, ss->ids[d], ss->ids[p.src], ss->ranks[p.src].src[g0 + i], p.a, p.b, &lv[(size_t)f * gc + i],
+                // step 4, the exchange (queued on this rank's stream behind one another; lv / lb live until the group is done, so only a
+                // failure synchronises)
+                BG_TRY(synced(c, stage_rows(c, ss->ids[d], ss->ids[p.src], ss->ranks[p.src].src[g0 + i], p.a, p.b, &lv[(size_t)f * gc + i],
                                             &lb[(size_t)f * gc + i], &frames[f][g0 + i])));
                 if (frames[f][g0 + i].validity) count_on_device[i] = true;
             }
@@ -395,7 +334,7 @@ int rank_dest(Ctx *c, ShardSort *ss, int d) {
         int cur = 0;
         RankState &me = ss->ranks[d];
         BG_HIP(hipEventRecord(c->ev0, c->stream));
-        BG_TRY(synced(c, merge_runs(c, reinterpret_cast<const uint64_t *>(stage[ss->key_col].values), schema[ss->key_col].type == BOWGPU_FLOAT64,
+        BG_TRY(synced(c, merge_runs(c, reinterpret_cast<const uint64_t *>(stage.outs[ss->key_col].values), schema[ss->key_col].type == BOWGPU_FLOAT64,
                                     starts, img, idx, &part, &cur, &me.merge_rounds)));
         BG_HIP(hipEventRecord(c->ev1, c->stream));
         BG_HIP(hipEventSynchronize(c->ev1));   // (the gather below records ev1 again)
@@ -403,12 +342,7 @@ int rank_dest(Ctx *c, ShardSort *ss, int d) {
         if (hipEventElapsedTime(&ms, c->ev0, c->ev1) != hipSuccess) (void)hipGetLastError();
         me.merge_ms = ms;
         std::vector<bowgpu_col> scols(nc);
-        for (int i = 0; i < nc; i++) {
-            memset(&scols[i], 0, sizeof scols[i]);
-            scols[i].values = stage[i].values;
-            scols[i].validity = stage[i].null_count > 0 ? stage[i].validity : nullptr;
-            scols[i].length = nd; scols[i].null_count = stage[i].null_count; scols[i].type = schema[i].type; scols[i].residency = BOWGPU_DEVICE;
-        }
+        stage.as_cols(schema, nd, scols.data());
         GatherIdx ix;
         ix.u32 = idx[cur].as<const uint32_t>();
         bool bad = false;

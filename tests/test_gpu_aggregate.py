@@ -988,6 +988,25 @@ def test_null_timestamps_runs_at_window_edges_and_the_null_last_row():
     assert want[0].length == 3 and all(x is None for w in want for x in w.to_list())
 
 
+@pytest.mark.parametrize("tail", [1, 63])
+def test_null_timestamps_window_count_beside_a_bitmap_word(tail):
+    """the rewritten call reduces into device temporaries and hands them on: 129 windows (one past a 64-bit validity word) or 191
+    (one short of one), the last four of them without a value - nil results in the last word of every nullable output"""
+    W = 129 if tail == 1 else 191
+    n = 10 * W
+    rng = np.random.default_rng(tail)
+    ts = np.arange(n, dtype=np.int64)
+    tvalid = rng.random(n) >= 0.2
+    tvalid[0] = tvalid[-1] = True
+    vals = np.round(rng.standard_normal(n) * 100, 3)
+    vvalid = rng.random(n) >= 0.2
+    vvalid[-45:] = False
+    want = _run_null_ts(ts, tvalid, vals, vvalid, 10)
+    assert want[0].length == W and want[0].length % 64 == tail and want[2].to_list()[-4:] == [None] * 4
+    want = _run_null_ts(ts, tvalid, vals, vvalid, 10, aggs=NULL_TS_AGGS_INCL, device=True, inclusive=True)
+    assert want[0].length == W
+
+
 def test_null_timestamps_large_frame_on_the_device():
     """2e6 rows, 5 % null timestamps, device-resident: the rewritten call takes the ordinary tile kernel"""
     rng = np.random.default_rng(99)

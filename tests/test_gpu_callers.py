@@ -1037,3 +1037,39 @@ def test_interpolate_over_an_interval_column_with_nulls(null_frac):
     got = capi.rolling_interpolate(cols, 0, 10, ip)
     assert got[0].length == want[0].length == 0
     assert seen_incl[0] > 20 or null_frac > 0.5      # (rows on a window start with a null behind them went through the inclusive path)
+
+
+@pytest.mark.parametrize("tail", [1, 63])
+def test_interpolate_over_an_interval_column_with_nulls_row_count_beside_a_bitmap_word(tail):
+    """the compacted call fills device temporaries that are handed to the caller's columns: an output of 64 k + 1 rows (one past a
+    validity word) or 64 k + 63, nulls in that last word (interpolation.None keeps the value column's), host and device columns"""
+    rng = np.random.default_rng(5)
+    N, interval = 2400, 20
+    ts = 2 * np.arange(N, dtype=np.int64) + 1
+    tvalid = rng.random(N) >= 0.2
+    tvalid[0] = True
+    tvalid[-100:] = True                          # (every candidate frame below ends on a valid timestamp)
+    vals = np.round(rng.standard_normal(N) * 100, 2)
+    ivals = rng.integers(-1000, 1000, N).astype(np.int64)
+    v1, v2 = rng.random(N) >= 0.3, rng.random(N) >= 0.1
+    ip = [{"kind": "WindowStart", "col": 0}, {"kind": "None", "col": 1}, {"kind": "Linear", "col": 2}]
+
+    def frame(n):
+        w1 = v1[:n].copy()
+        w1[-20:] = False
+        tbm, b1, b2 = (np.packbits(x, bitorder="little") for x in (tvalid[:n], w1, v2[:n]))
+        ccols = [capi.Column(ts[:n].copy(), tbm, capi.INT64, 0, n, -1), capi.Column(vals[:n].copy(), b1, capi.FLOAT64, 0, n, -1),
+                 capi.Column(ivals[:n].copy(), b2, capi.INT64, 0, n, -1)]
+        ocols = [orc.Column(ts[:n].copy(), tbm, orc.INT64), orc.Column(vals[:n].copy(), b1, orc.FLOAT64), orc.Column(ivals[:n].copy(), b2, orc.INT64)]
+        return ccols, ocols
+
+    for n in range(N, N - 100, -1):                # the longest frame whose output has the row count looked for
+        ccols, ocols = frame(n)
+        want = orc.interpolate(ocols, 0, interval, ip)
+        if want[0].length % 64 == tail:
+            break
+    assert want[0].length % 64 == tail and want[1].to_list()[-1] is None
+    for cols in (ccols, [c.to_device() for c in ccols]):
+        got = both_interp_kernels(lambda: capi.rolling_interpolate(cols, 0, interval, ip))
+        for k in range(3):
+            cmp_out("col %d n=%d rows=%d" % (k, n, want[0].length), got[k], want[k])

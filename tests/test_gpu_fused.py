@@ -171,6 +171,16 @@ def test_fused_declines_what_it_cannot_describe_and_the_answer_stays_the_same():
     run_fused(ts, [(v, valid)], 60, [{"kind": "WindowStart", "col": 0}, {"kind": "Const", "col": 1, "const": 9.9}], aggs, expect="two-call")
     # nanosecond epochs: wider than 2^32 from the first window
     run_fused(ts * 1_000_000 + 1_700_000_000_000_000_000, [(v, valid)], 60_000_000, ip, aggs, expect="two-call")
+    # the two-call form's interpolated frame (device temporaries) one row past a 64-row validity word, and one row short of one:
+    # m rows and a synthetic row for each of their (3 m - 2) // 60 + 1 windows; its last rows null (interpolation.None keeps them so)
+    ipn = [{"kind": "WindowStart", "col": 0}, {"kind": "None", "col": 1}]
+    for tail in (1, 63):
+        m = next(m for m in range(3000, 3100) if (m + (3 * m - 2) // 60 + 1) % 64 == tail)
+        vt = valid[:m].copy()
+        vt[-40:] = False
+        assert orc.interpolate(_cols(ts[:m], [(v[:m], vt)])[1], 0, 60, ipn)[0].length % 64 == tail
+        run_fused(ts[:m], [(v[:m], vt)], 60, ipn, aggs + [("WeightedAverageStep", 1), ("Last", 1), ("NumRows", 1)], expect="two-call")
+        run_fused(ts[:m], [(v[:m], vt)], 60, ipn, aggs + [("Last", 1), ("NumRows", 1)])
 
 
 def test_fused_nan_zero_and_signalling_nan_semantics_with_a_synthetic_seed():

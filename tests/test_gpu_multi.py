@@ -136,6 +136,28 @@ def test_one_call_over_four_and_eight_ranks(mode, residency):
             c.unpin()
 
 
+@pytest.mark.parametrize("tail", [1, 63])
+def test_ranks_whose_windows_end_beside_a_bitmap_word_from_pageable_columns_at_offset_seven(tail):
+    """a rank's device temporaries sized at a bitmap tail: every whole rank (4096 rows) holds 65 windows (tail 1: one past a 64-bit
+    validity word) or 63, with nil results in that last word; the pageable columns lie at Arrow offset 7, so every rank's staged
+    piece starts on row 7 of an 8-row boundary of its buffers"""
+    n, off = 2 * 4096 + 1500, 7
+    interval = 64 if tail == 1 else 66
+    rng = np.random.default_rng(tail)
+    ts = np.arange(-off, n, dtype=np.int64) + (1 if tail == 1 else 0)
+    vals = rng.standard_normal(n + off) * 100
+    valid = rng.random(n + off) >= 0.3
+    for end in (4096, 8192, n):
+        valid[off + end - 150:off + end + 150] = False      # whole windows without a value on both sides of every rank boundary
+    wid = ts[off:] // interval
+    for lo in (0, 4096):
+        assert (wid[lo + 4095] - wid[lo] + 1) % 64 == tail
+    bm = np.packbits(valid, bitorder="little")
+    ccols = [capi.Column(ts, None, capi.INT64, off, n, 0), capi.Column(vals, bm, capi.FLOAT64, off, n, -1)]
+    ocols = [orc.Column(ts[off:].copy(), None, orc.INT64), orc.Column(vals[off:].copy(), np.packbits(valid[off:], bitorder="little"), orc.FLOAT64)]
+    check_case(ccols, ocols, interval, PLAIN, 0, False, "bitmap tail %d" % tail, [0, 0, 0], 1000, expect_ranks=3)
+
+
 def test_int64_values_no_nulls_and_strict_order():
     n = 120_000
     ts, vals, _ = frame(n, "irregular", 3, nulls=0, int_values=True)
@@ -324,6 +346,29 @@ def test_interpolate_then_aggregate_as_one_call_over_ranks(kind, residency):
     finally:
         for c in ccols:
             c.unpin()
+
+
+def test_pipeline_ranks_whose_interpolated_rows_end_one_past_a_bitmap_word():
+    """every whole rank's interpolated frame (device temporaries, rounded up to 32-row bitmap words) has 4096 + 33 rows: one row past
+    a 32-bit validity word, that row and the ones in front of it null (interpolation.None leaves them so)"""
+    n, interval = 2 * 4096 + 1500, 250
+    rng = np.random.default_rng(8)
+    ts = 2 * np.arange(n, dtype=np.int64) + 1          # odd timestamps, even window starts: every window gets a synthetic row
+    v = np.round(rng.standard_normal(n) * 100, 2)
+    valid = rng.random(n) >= 0.3
+    for end in (4096, 8192, n):
+        valid[end - 200:end] = False
+    bm = np.packbits(valid, bitorder="little")
+    ccols = [capi.Column(ts, None, capi.INT64), capi.Column(v, bm, capi.FLOAT64, 0, n, -1)]
+    ocols = [orc.Column(ts, None, orc.INT64), orc.Column(v, bm, orc.FLOAT64)]
+    ip = [{"kind": "WindowStart", "col": 0}, {"kind": "None", "col": 1}]
+    # (a synthetic row goes in front of the first row of its window: the rank that holds that row produces it)
+    mid_ts = np.asarray(orc.interpolate(ocols, 0, interval, ip)[0].to_list(), dtype=np.int64)
+    for lo in (0, 4096):
+        rows = np.searchsorted(mid_ts, ts[lo + 4095], "right") - (np.searchsorted(mid_ts, ts[lo - 1], "right") if lo else 0)
+        assert rows % 32 == 1, rows
+    aggs = [("WindowStart", 0), ("ArithmeticMean", 1), ("Count", 1), ("Last", 1), ("NumRows", 1)]
+    assert check_pipeline(ccols, ocols, interval, ip, aggs, 0, [0, 0, 0], 1000, "interpolated rows past a bitmap word") == 3
 
 
 def test_pipeline_shapes_the_fan_out_leaves_to_one_device():
