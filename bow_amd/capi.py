@@ -144,7 +144,7 @@ SYMBOLS = [
     "bowgpu_is_col_sorted", "bowgpu_carry_merge",
     "bowgpu_shard_begin", "bowgpu_shard_pass_begin", "bowgpu_shard_plan", "bowgpu_shard_finish", "bowgpu_gen_dense",
     "bowgpu_gen_sparse", "bowgpu_stream_read_ceiling", "bowgpu_stream_rw_probe", "bowgpu_debug_status", "bowgpu_debug_host_copy", "bowgpu_checksum64", "bowgpu_parquet_open", "bowgpu_parquet_close",
-    "bowgpu_parquet_info", "bowgpu_parquet_column", "bowgpu_parquet_read_column",
+    "bowgpu_parquet_info", "bowgpu_parquet_column", "bowgpu_parquet_read_column", "bowgpu_parquet_column_check",
     "bowgpu_debug_set_route", "bowgpu_debug_get_route", "bowgpu_checksum64_at",
     "bowgpu_set_devices", "bowgpu_get_devices", "bowgpu_set_fanout_min_rows", "bowgpu_last_call_ranks", "bowgpu_fanout_counts",
     "bowgpu_rolling_aggregate_sharded",
@@ -1211,6 +1211,11 @@ def stream_rw_probe(buf_a, buf_b, bytes_each, out_a, out_b, rows_per_slot):
     return g.value, ms.value
 
 
+# bits of ParquetFile.check_column's mask: 1 << (Parquet Encoding value), as in include/bowgpu.h (BOWGPU_PARQUET_ENC_*)
+PARQUET_ENC_PLAIN, PARQUET_ENC_PLAIN_DICTIONARY, PARQUET_ENC_DELTA_BINARY_PACKED = 1 << 0, 1 << 2, 1 << 5
+PARQUET_ENC_RLE_DICTIONARY, PARQUET_ENC_BYTE_STREAM_SPLIT = 1 << 8, 1 << 9
+
+
 class ParquetFile:
     """Parquet column chunks decoded on the device (bowgpu_parquet_*): the reference's NewBowFromParquet for INT64 / DOUBLE columns"""
 
@@ -1233,6 +1238,13 @@ class ParquetFile:
         check(lib().bowgpu_parquet_read_column(self.h, i, C.byref(o)))
         out.absorb(o)
         return out
+
+    def check_column(self, i):
+        """bowgpu_parquet_column_check: raises what read_column(i) would raise about the column's structure, without touching a
+        device; returns the mask of value encodings found on its data pages (PARQUET_ENC_*)"""
+        m = C.c_uint32(0)
+        check(lib().bowgpu_parquet_column_check(self.h, i, C.byref(m)))
+        return m.value
 
     def close(self):
         if self.h:

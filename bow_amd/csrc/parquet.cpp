@@ -5,8 +5,9 @@
 //
 // Scope: what the reference writes (bowparquet.go:326-338: SNAPPY, PLAIN, data page v1, RLE definition levels, flat schema
 // of OPTIONAL columns) and what pyarrow / pandas write by default (a dictionary page per column chunk, RLE_DICTIONARY data
-// pages, PLAIN fall-back pages, data page v2 when asked for); INT64 and DOUBLE columns (the device path's types).  Other codecs /
-// encodings and nested schemas are declined with BOWGPU_ERR_UNSUPPORTED.
+// pages, PLAIN fall-back pages, data page v2 when asked for), plus what Parquet v2 writers choose for these types:
+// DELTA_BINARY_PACKED on INT64 and BYTE_STREAM_SPLIT on INT64 / DOUBLE; INT64 and DOUBLE columns (the device path's types).
+// Other codecs / encodings and nested schemas are declined with BOWGPU_ERR_UNSUPPORTED.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -33,7 +34,7 @@ struct PqPage {  // must match parquet_decode.hip
     int32_t dict_in_raw, _pad;
 };
 int launch_parquet_decode(Ctx *c, const uint8_t *chunk, const PqPage *pages, int64_t npages, bool any_compressed, uint8_t *raw,
-                          int optional, bool any_dict, uint32_t *indices, uint64_t *out_values, uint32_t *out_valid,
+                          int optional, uint32_t kinds, uint32_t *indices, uint64_t *expanded, uint64_t *out_values, uint32_t *out_valid,
                           unsigned long long *valid_count, uint32_t *status);
 
 namespace {
@@ -264,6 +265,30 @@ bool parse_page_header(const uint8_t *b, size_t n, PageHdr *h) {
     return r.ok;
 }
 
+// What a column's structure comes to: the page table of every row group's chunk (page headers parsed in place, on the mapped
+// file), the chunks laid out back to back as they will lie in the device buffer.  Everything bowgpu_parquet_read_column declines
+// or rejects about a column's structure is found here; no device is touched.
+struct PqSpan { int64_t file_off, len, dev_off; };
+struct PqWalk {
+    std::vector<PqSpan> spans;
+    std::vector<PqPage> pages;
+    int64_t raw_total = 0, dev_total = 0;
+    bool any_comp = false;
+    uint32_t kinds = 0;       // bit k: some page has PqPage.kind k
+    uint32_t encodings = 0;   // bit e: some data page has Parquet Encoding e
+};
+
+// the checks that need no page: index, schema shape, physical type
+int check_column_type(const ParquetFile *pf, int32_t i) {
+    if (i < 0 || i >= (int32_t)pf->cols.size()) return fail(BOWGPU_ERR_BAD_COL, "parquet: no column with index %d", i);
+    if (!pf->flat) return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: nested / repeated schema is outside the loader");
+    const PqSchemaCol &sc = pf->cols[i];
+    if (sc.type != 2 && sc.type != 5) return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: column '%s' is not INT64 / DOUBLE (physical type %d)", sc.name.c_str(), sc.type);
+    return 0;
+}
+
+int walk_column(const ParquetFile *pf, int32_t i, PqWalk *w);   // (below, in front of its two callers)
+
 }  // namespace
 }  // namespace bowgpu
 
@@ -338,35 +363,19 @@ int bowgpu_parquet_column(const bowgpu_parquet *handle, int32_t i, char *name, i
     return 0;
 }
 
-int bowgpu_parquet_read_column(bowgpu_parquet *handle, int32_t i, bowgpu_out *out) {
-    try { return parquet_read_column_impl(handle, i, out); }
-    catch (const std::exception &e) { return fail(BOWGPU_ERR_ARG, "parquet: malformed file (%s)", e.what()); }
-    catch (...) { return fail(BOWGPU_ERR_ARG, "parquet: malformed file"); }
-}
+}  // extern "C"
 
-static int parquet_read_column_impl(bowgpu_parquet *handle, int32_t i, bowgpu_out *out) {
-    ParquetFile *pf = reinterpret_cast<ParquetFile *>(handle);
-    if (!pf || !out) return fail(BOWGPU_ERR_ARG, "null argument");
-    if (i < 0 || i >= (int32_t)pf->cols.size()) return fail(BOWGPU_ERR_BAD_COL, "parquet: no column with index %d", i);
-    if (!pf->flat) return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: nested / repeated schema is outside the loader");
+namespace bowgpu {
+namespace {
+
+int walk_column(const ParquetFile *pf, int32_t i, PqWalk *w) {
     const PqSchemaCol &sc = pf->cols[i];
-    if (sc.type != 2 && sc.type != 5) return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: column '%s' is not INT64 / DOUBLE (physical type %d)", sc.name.c_str(), sc.type);
     const int optional = sc.repetition == 1 ? 1 : 0;
-    const int64_t n = pf->num_rows;
-    Ctx *c;
-    BG_TRY(ctx_get(&c));
-    DevOut dout;
-    BG_TRY(devout_prepare(c, out, n, &dout, 0));
-    const int32_t otype = sc.type == 2 ? BOWGPU_INT64 : BOWGPU_FLOAT64;
-    if (n == 0) { BG_TRY(devout_finish(c, &dout, 0, otype, 0)); return 0; }
-
-    // ---- page table: walk the page headers of this column in every row group (in place, on the mapped file); the chunks are
-    // laid out back to back in the device buffer
-    struct Span { int64_t file_off, len, dev_off; };
-    std::vector<Span> spans;
-    std::vector<PqPage> pages;
-    int64_t row0 = 0, raw_total = 0, dev_total = 0;
-    bool any_comp = false, any_dict = false;
+    std::vector<PqSpan> &spans = w->spans;
+    std::vector<PqPage> &pages = w->pages;
+    int64_t row0 = 0;
+    int64_t &raw_total = w->raw_total, &dev_total = w->dev_total;
+    bool &any_comp = w->any_comp;
     for (const PqRowGroup &g : pf->groups) {
         const PqColumnChunk &cc = g.cols[i];
         if (cc.codec != 0 && cc.codec != 1) return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: codec %d of column '%s' (UNCOMPRESSED and SNAPPY are read)", cc.codec, sc.name.c_str());
@@ -419,7 +428,11 @@ static int parquet_read_column_impl(bowgpu_parquet *handle, int32_t i, bowgpu_ou
                 pages.push_back(pg);
             } else if (h.type == 0 || (h.type == 3 && h.v2)) {
                 const bool dict_page = h.encoding == 2 || h.encoding == 8;
-                if (h.encoding != 0 && !dict_page) return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: value encoding %d in column '%s' (PLAIN and dictionary are read)", h.encoding, sc.name.c_str());
+                if (h.encoding >= 0 && h.encoding < 32) w->encodings |= 1u << h.encoding;
+                if (h.encoding == 5 && sc.type != 2)
+                    return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: value encoding %d (DELTA_BINARY_PACKED) on the DOUBLE column '%s' (it is read on INT64 columns)", h.encoding, sc.name.c_str());
+                if (h.encoding != 0 && h.encoding != 5 && h.encoding != 9 && !dict_page)
+                    return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: value encoding %d in column '%s' (PLAIN, dictionary, DELTA_BINARY_PACKED and BYTE_STREAM_SPLIT are read)", h.encoding, sc.name.c_str());
                 if (dict_page && dict_off < 0) return fail(BOWGPU_ERR_ARG, "parquet: column '%s' has dictionary-encoded pages but no dictionary", sc.name.c_str());
                 if (optional && !h.v2 && h.def_encoding != 3) return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: definition-level encoding %d in column '%s' (RLE is read)", h.def_encoding, sc.name.c_str());
                 const int32_t lv_bytes = h.v2 ? h.def_len + h.rep_len : 0;
@@ -427,15 +440,15 @@ static int parquet_read_column_impl(bowgpu_parquet *handle, int32_t i, bowgpu_ou
                     return fail(BOWGPU_ERR_ARG, "parquet: implausible level sizes in a v2 page of column '%s'", sc.name.c_str());
                 PqPage pg;
                 memset(&pg, 0, sizeof pg);
-                pg.kind = dict_page ? 1 : 0;
+                pg.kind = dict_page ? 1 : h.encoding == 5 ? 3 : h.encoding == 9 ? 4 : 0;
                 pg.v2 = h.v2 ? 1 : 0;
                 pg.lv_off = base + (int64_t)p + h.rep_len;
                 pg.lv_len = h.def_len;
                 pg.dict_off = dict_off;
                 pg.dict_in_raw = dict_in_raw;
                 pg.dict_count = dict_count;
-                pg.idx_off = row0 + vals;  // (one slot per row is always enough)
-                any_dict = any_dict || dict_page;
+                pg.idx_off = row0 + vals;  // (one slot per row is always enough: of the index array or of the expanded value array)
+                w->kinds |= 1u << pg.kind;
                 pg.src_off = base + (int64_t)p + lv_bytes;
                 pg.comp_size = h.comp_size - lv_bytes;
                 pg.raw_size = h.raw_size - lv_bytes;
@@ -456,14 +469,63 @@ static int parquet_read_column_impl(bowgpu_parquet *handle, int32_t i, bowgpu_ou
         dev_total += (int64_t)chunk_len;
         row0 += g.num_rows;
     }
-    if (row0 != n) return fail(BOWGPU_ERR_ARG, "parquet: row groups hold %lld rows, the footer says %lld", (long long)row0, (long long)n);
+    if (row0 != pf->num_rows) return fail(BOWGPU_ERR_ARG, "parquet: row groups hold %lld rows, the footer says %lld", (long long)row0, (long long)pf->num_rows);
+    return 0;
+}
+
+}  // namespace
+}  // namespace bowgpu
+
+extern "C" {
+
+int bowgpu_parquet_read_column(bowgpu_parquet *handle, int32_t i, bowgpu_out *out) {
+    try { return parquet_read_column_impl(handle, i, out); }
+    catch (const std::exception &e) { return fail(BOWGPU_ERR_ARG, "parquet: malformed file (%s)", e.what()); }
+    catch (...) { return fail(BOWGPU_ERR_ARG, "parquet: malformed file"); }
+}
+
+int bowgpu_parquet_column_check(const bowgpu_parquet *handle, int32_t i, uint32_t *value_encodings) {
+    const ParquetFile *pf = reinterpret_cast<const ParquetFile *>(handle);
+    if (!pf) return fail(BOWGPU_ERR_ARG, "null argument");
+    if (value_encodings) *value_encodings = 0;
+    try {
+        BG_TRY(check_column_type(pf, i));
+        PqWalk walk;
+        const int rc = walk_column(pf, i, &walk);
+        if (value_encodings) *value_encodings = walk.encodings;   // (on an error: what the walk had seen, the declined encoding included)
+        return rc;
+    }
+    catch (const std::exception &e) { return fail(BOWGPU_ERR_ARG, "parquet: malformed file (%s)", e.what()); }
+    catch (...) { return fail(BOWGPU_ERR_ARG, "parquet: malformed file"); }
+}
+
+static int parquet_read_column_impl(bowgpu_parquet *handle, int32_t i, bowgpu_out *out) {
+    ParquetFile *pf = reinterpret_cast<ParquetFile *>(handle);
+    if (!pf || !out) return fail(BOWGPU_ERR_ARG, "null argument");
+    BG_TRY(check_column_type(pf, i));
+    const PqSchemaCol &sc = pf->cols[i];
+    const int optional = sc.repetition == 1 ? 1 : 0;
+    const int64_t n = pf->num_rows;
+    Ctx *c;
+    BG_TRY(ctx_get(&c));
+    DevOut dout;
+    BG_TRY(devout_prepare(c, out, n, &dout, 0));
+    const int32_t otype = sc.type == 2 ? BOWGPU_INT64 : BOWGPU_FLOAT64;
+    if (n == 0) { BG_TRY(devout_finish(c, &dout, 0, otype, 0)); return 0; }
+
+    PqWalk walk;
+    BG_TRY(walk_column(pf, i, &walk));
+    const std::vector<PqSpan> &spans = walk.spans;
+    const std::vector<PqPage> &pages = walk.pages;
+    const int64_t raw_total = walk.raw_total, dev_total = walk.dev_total;
+    const bool any_comp = walk.any_comp;
 
     // ---- upload + decode
     void *d_bytes, *d_pages, *d_raw = nullptr;
     BG_TRY(ctx_pool(c, kPoolInterp + 0, (size_t)dev_total + 32, &d_bytes));
     BG_TRY(ctx_pool(c, kPoolInterp + 1, pages.size() * sizeof(PqPage) + 32, &d_pages));
     if (any_comp) BG_TRY(ctx_pool(c, kPoolInterp + 2, (size_t)raw_total + 32, &d_raw));
-    for (const Span &sp : spans)
+    for (const PqSpan &sp : spans)
         BG_TRY(copy_h2d(c, reinterpret_cast<char *>(d_bytes) + sp.dev_off, pf->map + sp.file_off, (size_t)sp.len));
     BG_HIP(hipMemcpyAsync(d_pages, pages.data(), pages.size() * sizeof(PqPage), hipMemcpyHostToDevice, c->stream));
     void *dscr;
@@ -473,11 +535,12 @@ static int parquet_read_column_impl(bowgpu_parquet *handle, int32_t i, bowgpu_ou
     BG_HIP(hipMemsetAsync(status, 0, 64, c->stream));
     BG_HIP(hipMemsetAsync(dcnt, 0, 8, c->stream));
     BG_HIP(hipMemsetAsync(dout.validity, 0, (size_t)(((n + 7) >> 3) + 3) & ~(size_t)3, c->stream));
-    void *d_idx = nullptr;
-    if (any_dict) BG_TRY(ctx_pool(c, kPoolInterp + 3, (size_t)n * 4 + 32, &d_idx));
+    void *d_idx = nullptr, *d_exp = nullptr;   // 4 B / 8 B per row of workspace, taken only when a page needs it (a chunk may mix encodings)
+    if (walk.kinds & 2u) BG_TRY(ctx_pool(c, kPoolInterp + 3, (size_t)n * 4 + 32, &d_idx));
+    if (walk.kinds & (8u | 16u)) BG_TRY(ctx_pool(c, kPoolInterp + 4, (size_t)n * 8 + 32, &d_exp));
     BG_TRY(launch_parquet_decode(c, reinterpret_cast<const uint8_t *>(d_bytes), reinterpret_cast<const PqPage *>(d_pages), (int64_t)pages.size(),
-                                 any_comp, reinterpret_cast<uint8_t *>(d_raw), optional, any_dict, reinterpret_cast<uint32_t *>(d_idx),
-                                 reinterpret_cast<uint64_t *>(dout.values),
+                                 any_comp, reinterpret_cast<uint8_t *>(d_raw), optional, walk.kinds, reinterpret_cast<uint32_t *>(d_idx),
+                                 reinterpret_cast<uint64_t *>(d_exp), reinterpret_cast<uint64_t *>(dout.values),
                                  reinterpret_cast<uint32_t *>(dout.validity), dcnt, status));
     uint32_t hstat = 0;
     uint64_t hcnt = 0;

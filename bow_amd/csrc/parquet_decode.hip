@@ -7,8 +7,13 @@
 //                         `len` bytes at distance `off` is periodic with period `off` when it overlaps itself, so
 //                         dst[i] = base[off >= len ? i : i % off] is parallel in every case.
 //   dict_indices_kernel   dictionary-encoded data pages: bit width byte + RLE / bit-packed hybrid of indices -> dense uint32 array
-//   page_scatter_kernel   data page (v1 / v2) of a flat OPTIONAL / REQUIRED INT64 / DOUBLE column, PLAIN or dictionary values: definition levels
-//                         (RLE / bit-packed hybrid, bit width 1) -> Arrow validity bits; dense PLAIN values -> row slots
+//   delta_pages_kernel    DELTA_BINARY_PACKED data pages (INT64): header + blocks of bit-packed miniblocks -> dense int64 array, one
+//                         slot per non-null value.  All lanes parse the same block headers; per 64 values of a miniblock each lane
+//                         extracts one delta, a wrapping inclusive wave scan + the carry of the values before give the values.
+//   bss_pages_kernel      BYTE_STREAM_SPLIT data pages (INT64 / DOUBLE): the eight byte streams of a page -> the same dense array
+//                         (lane i assembles value i: every stream is read and the array written in consecutive addresses).
+//   page_scatter_kernel   data page (v1 / v2) of a flat OPTIONAL / REQUIRED INT64 / DOUBLE column: definition levels
+//                         (RLE / bit-packed hybrid, bit width 1) -> Arrow validity bits; dense PLAIN / expanded values -> row slots
 //                         (null slots = 0, as bow.NewBuffer leaves them: bowbuffer.go:22-40).  Lane l owns rows 32k + l ... of the
 //                         page in words of 32: level word, popcount, wave scan = index of its first value.
 #include "agg_device.h"
@@ -22,10 +27,11 @@ struct PqPage {
     int32_t comp_size, raw_size;
     int32_t num_values;     // rows of the page (levels); non-null values = what the levels say
     int32_t compressed;     // 1: Snappy
-    int32_t kind;           // 0: data page, PLAIN values; 1: data page, dictionary indices; 2: the chunk's dictionary page (PLAIN values)
+    int32_t kind;           // 0: data page, PLAIN values; 1: data page, dictionary indices; 2: the chunk's dictionary page (PLAIN values);
+                            // 3: data page, DELTA_BINARY_PACKED; 4: data page, BYTE_STREAM_SPLIT
     int32_t dict_count;     // kind 1: entries of the chunk's dictionary
     int64_t dict_off;       // kind 1: offset of the dictionary's values (same buffer as raw_off)
-    int64_t idx_off;        // kind 1: first slot of this page in the expanded index array
+    int64_t idx_off;        // kind 1: first slot of this page in the expanded index array; kind 3 / 4: in the expanded value array
     int64_t lv_off;         // data page v2: offset of the definition-level bytes inside the chunk bytes (never compressed there)
     int32_t lv_len;         // data page v2: their length (v1 pages carry a 4-byte length in front of the levels instead)
     int32_t v2;             // data page v2: src / raw describe the VALUES section only
@@ -46,6 +52,56 @@ __device__ __forceinline__ uint32_t rd_varint(const uint8_t *p, int64_t *pos, in
         if (sh > 28) break;
     }
     return r;
+}
+
+// ULEB128 of up to 10 bytes (DELTA_BINARY_PACKED: first_value and min_delta are zigzag 64-bit).  false: the bytes ran out or the
+// number did not end within 10 bytes; *pos never passes end.
+__device__ __forceinline__ bool rd_varint64(const uint8_t *p, int64_t *pos, int64_t end, uint64_t *out) {
+    uint64_t r = 0;
+    for (int sh = 0; sh < 70; sh += 7) {
+        if (*pos >= end) return false;
+        const uint8_t c = p[(*pos)++];
+        r |= (uint64_t)(c & 0x7f) << sh;   // (the 10th byte's high bits fall off: wrapping, like the writers' decoders)
+        if (!(c & 0x80)) { *out = r; return true; }
+    }
+    return false;
+}
+
+__device__ __forceinline__ uint64_t unzigzag64(uint64_t v) { return (v >> 1) ^ (0ull - (v & 1ull)); }
+
+// Offset of a data page's values section inside its bytes: v1 pages of an OPTIONAL column carry a 4-byte length and the definition
+// levels in front of it.  -1: the length runs past the page.
+__device__ __forceinline__ int64_t values_offset(const uint8_t *src, const PqPage &P, int optional) {
+    if (!optional || P.v2) return 0;
+    if (P.raw_size < 4) return -1;
+    const uint32_t lbytes = (uint32_t)src[0] | ((uint32_t)src[1] << 8) | ((uint32_t)src[2] << 16) | ((uint32_t)src[3] << 24);
+    if ((int64_t)lbytes + 4 > P.raw_size) return -1;
+    return 4 + (int64_t)lbytes;
+}
+
+// status bits of the expanded encodings (1 .. 16 belong to the kernels below)
+constexpr uint32_t kStPastPage = 32u;     // a position past the page's raw_size
+constexpr uint32_t kStWidth = 64u;        // DELTA_BINARY_PACKED: a miniblock's bit width above 64
+constexpr uint32_t kStBlockSize = 128u;   // DELTA_BINARY_PACKED: illegal block / miniblock size
+constexpr uint32_t kStCount = 256u;       // the values section holds more values than the page has rows
+constexpr uint32_t kStLevels = 512u;      // the definition levels ask for more values than the section holds
+constexpr uint32_t kStBssLength = 1024u;  // BYTE_STREAM_SPLIT: a section length that is no multiple of 8
+
+// Header of a DELTA_BINARY_PACKED values section at src[*pos .. end).  0, or the status bit of what is wrong with it.
+__device__ __forceinline__ uint32_t delta_header(const uint8_t *src, int64_t *pos, int64_t end, int64_t *vals_per_mini, int64_t *minis,
+                                                 int64_t *total, uint64_t *first) {
+    uint64_t bs, mpb, tot, fv;
+    if (!rd_varint64(src, pos, end, &bs) || !rd_varint64(src, pos, end, &mpb) || !rd_varint64(src, pos, end, &tot) ||
+        !rd_varint64(src, pos, end, &fv))
+        return kStPastPage;
+    // legal: block_size a positive multiple of 128, miniblocks_per_block > 0 dividing it, values per miniblock a multiple of 32.
+    // (a page holds fewer than 2^31 values: a larger block is declined with the same bit, and the byte counts below cannot wrap)
+    if (bs == 0 || (bs & 127) || bs > (1ull << 30) || mpb == 0 || bs % mpb || ((bs / mpb) & 31)) return kStBlockSize;
+    *vals_per_mini = (int64_t)(bs / mpb);
+    *minis = (int64_t)mpb;
+    *total = tot > (uint64_t)INT64_MAX ? INT64_MAX : (int64_t)tot;
+    *first = unzigzag64(fv);
+    return 0;
 }
 
 }  // namespace
@@ -169,11 +225,110 @@ __global__ __launch_bounds__(256) void dict_indices_kernel(const uint8_t *__rest
     }
 }
 
-// optional: column has definition levels (max level 1); out_valid must be zeroed; valid_count += non-null rows
+// DELTA_BINARY_PACKED data pages (INT64): <block size> <miniblocks per block> <total value count> <first value (zigzag)>, then per
+// block <min delta (zigzag)> <one bit-width byte per miniblock> <miniblock bodies, LSB-first bit-packed>.  The last miniblock that
+// holds values is padded to its full length; the ones after it keep their width byte and have no body.  value[i] = value[i - 1] +
+// min_delta + delta[i] in wrapping 64-bit arithmetic.  One wavefront per page, every lane parses the same headers; a damaged page
+// raises a status bit and the wavefront leaves it (every read lies below raw_size, every write inside the page's num_values slots).
+__global__ __launch_bounds__(256) void delta_pages_kernel(const uint8_t *__restrict__ raw, const uint8_t *__restrict__ chunk,
+                                                          const PqPage *__restrict__ pages, int64_t npages, int optional,
+                                                          uint64_t *expanded, uint32_t *status) {
+    const int lane = threadIdx.x & 63;
+    const int64_t pg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pg >= npages) return;
+    const PqPage P = pages[pg];
+    if (P.kind != 3) return;
+    const uint8_t *src = (P.compressed ? raw : chunk) + P.raw_off;
+    const int64_t end = P.raw_size;
+    int64_t pos = values_offset(src, P, optional);
+    if (pos < 0) { if (lane == 0) atomicOr(&status[0], 2u); return; }
+    if (pos >= end) return;  // a page of nulls only may carry no values section
+    int64_t V, mpb, total;
+    uint64_t carry;
+    uint32_t bad = delta_header(src, &pos, end, &V, &mpb, &total, &carry);
+    if (!bad && total > (int64_t)P.num_values) bad = kStCount;
+    if (bad) { if (lane == 0) atomicOr(&status[0], bad); return; }
+    if (total == 0) return;
+    uint64_t *dst = expanded + P.idx_off;
+    if (lane == 0) dst[0] = carry;
+    int64_t outp = 1;
+    while (outp < total) {  // one block per trip: its first miniblock always takes at least one value
+        uint64_t md;
+        if (!rd_varint64(src, &pos, end, &md) || pos + mpb > end) { bad = kStPastPage; break; }
+        const uint64_t min_delta = unzigzag64(md);
+        const int64_t wpos = pos;
+        pos += mpb;
+        for (int64_t m = 0; m < mpb && outp < total; m++) {
+            const int w = src[wpos + m];
+            if (w > 64) { bad = kStWidth; break; }
+            const int64_t nbytes = V * w >> 3;   // (V is a multiple of 32: whole bytes)
+            if (pos + nbytes > end) { bad = kStPastPage; break; }
+            const int64_t take = V < total - outp ? V : total - outp;
+            for (int64_t j0 = 0; j0 < take; j0 += 64) {
+                const int64_t j = j0 + lane;
+                uint64_t d = 0;
+                if (j < take) {
+                    uint64_t v = 0;
+                    if (w) {
+                        // w bits at bit j * w of the body: they span up to 9 bytes, all below pos + nbytes <= raw_size.  Two aligned
+                        // 8-byte loads cover 9 bytes from any byte offset (the buffers are padded by 16 bytes, like for PLAIN).
+                        const int64_t bit = j * w;
+                        const uintptr_t addr = reinterpret_cast<uintptr_t>(src + pos + (bit >> 3));
+                        const uint64_t *al = reinterpret_cast<const uint64_t *>(addr & ~(uintptr_t)7);
+                        const int shb = (int)(addr & 7) * 8 + (int)(bit & 7);
+                        v = shb ? ((al[0] >> shb) | (al[1] << (64 - shb))) : al[0];
+                        if (w < 64) v &= (1ull << w) - 1ull;
+                    }
+                    d = v + min_delta;
+                }
+                for (int o = 1; o < 64; o <<= 1) { const uint64_t y = __shfl_up((unsigned long long)d, o); if (lane >= o) d += y; }
+                if (j < take) dst[outp + j] = carry + d;
+                carry += (uint64_t)__shfl((unsigned long long)d, 63);   // (lanes past `take` added 0)
+            }
+            pos += nbytes;
+            outp += take;
+        }
+        if (bad) break;
+    }
+    if (bad && lane == 0) atomicOr(&status[0], bad);
+}
+
+// BYTE_STREAM_SPLIT data pages (INT64 / DOUBLE): with N values in the page, byte k of value i lies at values[k * N + i].  Lane i
+// assembles value i, so each of the eight streams is read in consecutive bytes across the wavefront and the dense array is written
+// in consecutive 8-byte words (read from page_scatter_kernel instead, where a lane owns 32 consecutive rows, neighbouring lanes
+// would sit ~32 bytes apart in every stream).
+__global__ __launch_bounds__(256) void bss_pages_kernel(const uint8_t *__restrict__ raw, const uint8_t *__restrict__ chunk,
+                                                        const PqPage *__restrict__ pages, int64_t npages, int optional,
+                                                        uint64_t *expanded, uint32_t *status) {
+    const int lane = threadIdx.x & 63;
+    const int64_t pg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pg >= npages) return;
+    const PqPage P = pages[pg];
+    if (P.kind != 4) return;
+    const uint8_t *src = (P.compressed ? raw : chunk) + P.raw_off;
+    const int64_t vpos = values_offset(src, P, optional);
+    if (vpos < 0) { if (lane == 0) atomicOr(&status[0], 2u); return; }
+    const int64_t len = P.raw_size - vpos;
+    if (len <= 0) return;
+    const int64_t N = len >> 3;
+    if ((len & 7) || N > (int64_t)P.num_values) { if (lane == 0) atomicOr(&status[0], (len & 7) ? kStBssLength : kStCount); return; }
+    const uint8_t *vals = src + vpos;
+    uint64_t *dst = expanded + P.idx_off;
+    for (int64_t i = lane; i < N; i += 64) {
+        uint64_t v = 0;
+#pragma unroll
+        for (int k = 0; k < 8; k++) v |= (uint64_t)vals[k * N + i] << (8 * k);
+        dst[i] = v;
+    }
+}
+
+// optional: column has definition levels (max level 1); out_valid must be zeroed; valid_count += non-null rows;
+// expanded: the dense values of DELTA_BINARY_PACKED / BYTE_STREAM_SPLIT pages (delta_pages_kernel / bss_pages_kernel)
 __global__ __launch_bounds__(256) void page_scatter_kernel(const uint8_t *__restrict__ raw, const uint8_t *__restrict__ chunk,
                                                            const PqPage *__restrict__ pages, int64_t npages,
-                                                           int optional, const uint32_t *__restrict__ indices, uint64_t *out_values,
-                                                           uint32_t *out_valid, unsigned long long *valid_count, uint32_t *status) {
+                                                           int optional, const uint32_t *__restrict__ indices,
+                                                           const uint64_t *__restrict__ expanded, uint64_t *out_values, uint32_t *out_valid,
+                                                           unsigned long long *valid_count, uint32_t *status) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t pg = (int64_t)blockIdx.x * 4 + wv;
     if (pg >= npages) return;
@@ -197,6 +352,16 @@ __global__ __launch_bounds__(256) void page_scatter_kernel(const uint8_t *__rest
     const uint8_t *vals = src + vpos;
     const int64_t val_bytes = P.raw_size - vpos;
     unsigned long long page_valid = 0;
+    // kind 3 / 4: how many values the page's section holds (what delta_pages_kernel / bss_pages_kernel expanded, never more than nv)
+    int64_t xcount = 0;
+    if (P.kind == 4) {
+        xcount = val_bytes > 0 ? val_bytes >> 3 : 0;
+    } else if (P.kind == 3 && vpos < P.raw_size) {
+        int64_t hp = vpos, V, mpb;
+        uint64_t first;
+        if (delta_header(src, &hp, P.raw_size, &V, &mpb, &xcount, &first)) xcount = 0;  // (the status bit is delta_pages_kernel's)
+    }
+    if (xcount > nv) xcount = nv;
 
     // the levels arrive as runs; rows are handled 2048 at a time (64 lanes x one 32-row word)
     int64_t lpos = 0;        // read position in the level bytes
@@ -266,6 +431,9 @@ __global__ __launch_bounds__(256) void page_scatter_kernel(const uint8_t *__rest
                         } else {
                             atomicOr(&status[0], 8u);
                         }
+                    } else if (P.kind >= 3) {  // the vi-th value of the page, expanded; vi < nv always, so the slot is the page's own
+                        if (vi < xcount) v = expanded[P.idx_off + vi];
+                        else atomicOr(&status[0], kStLevels);
                     } else if ((vi + 1) * 8 <= val_bytes) {
                         // PLAIN: 8 little-endian bytes at any byte offset inside the page: two aligned loads + funnel shift
                         // (the buffers are padded by 16 bytes, so the second load never leaves them)
@@ -295,14 +463,16 @@ __global__ __launch_bounds__(256) void page_scatter_kernel(const uint8_t *__rest
 }
 
 int launch_parquet_decode(Ctx *c, const uint8_t *chunk, const PqPage *pages, int64_t npages, bool any_compressed, uint8_t *raw,
-                          int optional, bool any_dict, uint32_t *indices, uint64_t *out_values, uint32_t *out_valid,
-                          unsigned long long *valid_count, uint32_t *status) {
+                          int optional, uint32_t kinds, uint32_t *indices, uint64_t *expanded, uint64_t *out_values, uint32_t *out_valid,
+                          unsigned long long *valid_count, uint32_t *status) {  // kinds: bit k set = some page has PqPage.kind k
     if (npages <= 0) return 0;
     const unsigned grid = (unsigned)((npages + 3) / 4);
     if (any_compressed) hipLaunchKernelGGL(snappy_pages_kernel, dim3(grid), dim3(256), 0, c->stream, chunk, pages, npages, raw, status);
-    if (any_dict) hipLaunchKernelGGL(dict_indices_kernel, dim3(grid), dim3(256), 0, c->stream, raw, chunk, pages, npages, optional, indices, status);
-    hipLaunchKernelGGL(page_scatter_kernel, dim3(grid), dim3(256), 0, c->stream, raw, chunk, pages, npages, optional, indices, out_values,
-                       out_valid, valid_count, status);
+    if (kinds & 2u) hipLaunchKernelGGL(dict_indices_kernel, dim3(grid), dim3(256), 0, c->stream, raw, chunk, pages, npages, optional, indices, status);
+    if (kinds & 8u) hipLaunchKernelGGL(delta_pages_kernel, dim3(grid), dim3(256), 0, c->stream, raw, chunk, pages, npages, optional, expanded, status);
+    if (kinds & 16u) hipLaunchKernelGGL(bss_pages_kernel, dim3(grid), dim3(256), 0, c->stream, raw, chunk, pages, npages, optional, expanded, status);
+    hipLaunchKernelGGL(page_scatter_kernel, dim3(grid), dim3(256), 0, c->stream, raw, chunk, pages, npages, optional, indices, expanded,
+                       out_values, out_valid, valid_count, status);
     BG_HIP(hipGetLastError());
     return 0;
 }

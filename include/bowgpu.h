@@ -814,9 +814,13 @@ int bowgpu_join(const bowgpu_col *left_cols, int32_t n_left, int32_t left_key, c
 /* Reads INT64 / DOUBLE columns of a Parquet file the way the reference's NewBowFromParquet does (bowparquet.go:44-153), but
  * decodes on the device: the column's compressed pages are uploaded as they lie in the file and decompressed (Snappy), their
  * definition levels turned into an Arrow validity bitmap and their PLAIN values scattered to row slots by HIP kernels.
- * Read: flat schemas, OPTIONAL / REQUIRED columns, UNCOMPRESSED / SNAPPY, PLAIN and dictionary-encoded values (PLAIN_DICTIONARY /
- * RLE_DICTIONARY, with PLAIN fall-back pages), RLE definition levels, data page v1 and v2 - what the reference writes
- * (bowparquet.go:326-338) and what pyarrow / pandas write by default.  Anything else: BOWGPU_ERR_UNSUPPORTED. */
+ * Read: flat schemas, OPTIONAL / REQUIRED columns, UNCOMPRESSED / SNAPPY, RLE definition levels, data page v1 and v2, and these
+ * value encodings, which a column chunk may mix page by page: PLAIN; PLAIN_DICTIONARY / RLE_DICTIONARY (with PLAIN or delta
+ * fall-back pages); DELTA_BINARY_PACKED on INT64 columns (any legal block / miniblock size); BYTE_STREAM_SPLIT on INT64 and
+ * DOUBLE columns - what the reference writes (bowparquet.go:326-338), what pyarrow / pandas write by default, and what Parquet v2
+ * writers (parquet-mr / Spark with writer.version=v2, pyarrow with column_encoding) choose for these two types.  Anything else -
+ * other codecs, types and encodings, DELTA_BINARY_PACKED on a DOUBLE column, nested schemas: BOWGPU_ERR_UNSUPPORTED.  Damaged page
+ * data: BOWGPU_ERR_ARG. */
 typedef struct bowgpu_parquet bowgpu_parquet;
 int bowgpu_parquet_open(const char *path, bowgpu_parquet **handle);
 int bowgpu_parquet_close(bowgpu_parquet *handle);
@@ -826,6 +830,18 @@ int bowgpu_parquet_info(const bowgpu_parquet *handle, int64_t *num_rows, int32_t
 int bowgpu_parquet_column(const bowgpu_parquet *handle, int32_t i, char *name, int32_t name_cap, int32_t *type, int32_t *optional);
 /* out: num_rows slots (HOST or DEVICE residency); values, validity, null_count and type are filled in */
 int bowgpu_parquet_read_column(bowgpu_parquet *handle, int32_t i, bowgpu_out *out);
+/* Whether bowgpu_parquet_read_column would accept column i's structure - type, codec, page types, value and level encodings,
+ * sizes: the same walk over the page headers of every row group, on the host alone (no device is touched, none is needed).  0, or
+ * the error code and bowgpu_last_error text bowgpu_parquet_read_column would give.  value_encodings (may be NULL): bit e set for
+ * every Parquet Encoding value e found on a data page (BOWGPU_PARQUET_ENC_*). */
+enum {
+    BOWGPU_PARQUET_ENC_PLAIN = 1,                  /* 1 << 0 */
+    BOWGPU_PARQUET_ENC_PLAIN_DICTIONARY = 4,       /* 1 << 2 */
+    BOWGPU_PARQUET_ENC_DELTA_BINARY_PACKED = 32,   /* 1 << 5 */
+    BOWGPU_PARQUET_ENC_RLE_DICTIONARY = 256,       /* 1 << 8 */
+    BOWGPU_PARQUET_ENC_BYTE_STREAM_SPLIT = 512     /* 1 << 9 */
+};
+int bowgpu_parquet_column_check(const bowgpu_parquet *handle, int32_t i, uint32_t *value_encodings);
 
 /* ---- row-range sharded Rolling.Aggregate across GPUs: the records the ranks exchange ------------------ */
 
