@@ -720,6 +720,32 @@ static int validate_aggs(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, 
     return 0;
 }
 
+// What every stage of one Aggregate call is given: the frame, its plan and the call's flags
+struct AggCall {
+    const bowgpu_col *cols;
+    int32_t ncols, ts_col;
+    const Plan &plan;
+    int inclusive;
+    bool strict;       // bowgpu_options.strict_order of the call (or BOWGPU_ROUTE_STRICT_ORDER): every window in row order, or the call is declined
+    bool check_plan;   // the plan came from the caller (bowgpu_rolling_aggregate_planned): the pass checks it against the column
+};
+
+// Which kinds of reducer a call has, in the encoding the wave-tile kernels read (common.h kNeed*) + Mode, which only the host asks about
+constexpr uint32_t kNeedMode = 32, kNeedTimeWeighted = kNeedStep | kNeedTrap;
+static uint32_t need_mask(const bowgpu_agg *aggs, int32_t naggs) {
+    uint32_t need = 0;
+    for (int i = 0; i < naggs; i++) {
+        const int k = aggs[i].kind;
+        if (k == BOWGPU_AGG_INTEGRAL_STEP || k == BOWGPU_AGG_WAVG_STEP) need |= kNeedStep;
+        if (k == BOWGPU_AGG_INTEGRAL_TRAPEZOID || k == BOWGPU_AGG_WAVG_LINEAR) need |= kNeedTrap;
+        if (k == BOWGPU_AGG_MIN || k == BOWGPU_AGG_MAX) need |= kNeedMinMax;
+        if (k == BOWGPU_AGG_SUM || k == BOWGPU_AGG_MEAN) need |= kNeedSum;
+        if (k == BOWGPU_AGG_FIRST || k == BOWGPU_AGG_LAST) need |= kNeedFirstLast;
+        if (k == BOWGPU_AGG_MODE) need |= kNeedMode;
+    }
+    return need;
+}
+
 // One aggregate call in three stages so that the sharded entry points can reuse them:
 //   job_build  - device residency of columns / outputs + the kernels' descriptor block
 //   job_run    - bitmap initialisation, tile kernel, long-window kernel
@@ -734,59 +760,95 @@ struct AggJob {
     int inclusive = 0;
     bool counts_used = false;   // the valid counters hold a previous count (they accumulate): zero them before counting again
     bool tail_wrote_host = false;   // the finish launch stores the status words and the counts into the registered host block itself
-    bool check_plan = false;    // the plan came from the caller (bowgpu_rolling_aggregate_planned): the pass checks it against the column
-    bool band_rows = false;     // job_run: a nullable column under extrema / First + Last alone, 129 .. 200 rows per window - rolling_simple.hip + the queue launch, not rolling_twc.hip
+    // the call as job_build was given it - copies, so that a job outlives the entry point that built it (bowgpu_shard_pass_begin)
+    bowgpu_agg aggs[kMaxAggs];
+    int32_t naggs = 0;
+    uint32_t need = 0;          // need_mask of aggs
+    Plan plan;
+    bool strict = false, check_plan = false;   // AggCall's
 };
-static thread_local bool g_plan_from_caller = false;   // set around run_aggregate by the planned entry point
 // Up to which window length (rows on average) a call on a NULLABLE column stays on rolling_twc_kernel with its 256 rows of look-ahead
 // instead of taking the streaming form (0: it does not) - from the 1e8-row sweeps of profiles/r05_stdout_midw_sweep.txt, 30 % nulls, kernel
 // ms compacting / streaming at 144 and 192 rows per window: one kind of integral 0.45 / 0.70 and 0.47 / 0.64, First + Last 0.38 / 0.46 and
 // 0.37 / 0.43 (both up to 255 rows); Min + Max 0.47 / 0.61 and 0.49 / 0.52, both kinds of integral 0.63 / 0.73 and 0.69 / 0.65 (up to 176);
 // sums and counts alone: the streaming form (0.41 / 0.37).  Columns without nulls: the streaming form throughout (it has its dense
 // instantiations; the compacting kernel is 10 - 40 % behind there).
-static int64_t compact_long_max_rows(const bowgpu_agg *aggs, int32_t naggs) {
-    bool step = false, trap = false, mm = false, fl = false;
-    for (int i = 0; i < naggs; i++) {
-        const int k = aggs[i].kind;
-        step |= k == BOWGPU_AGG_INTEGRAL_STEP || k == BOWGPU_AGG_WAVG_STEP;
-        trap |= k == BOWGPU_AGG_INTEGRAL_TRAPEZOID || k == BOWGPU_AGG_WAVG_LINEAR;
-        mm |= k == BOWGPU_AGG_MIN || k == BOWGPU_AGG_MAX;
-        fl |= k == BOWGPU_AGG_FIRST || k == BOWGPU_AGG_LAST;
-    }
-    if ((step && trap) || mm) return kCompactLongBothMaxAvgRows;
-    if (step || trap || fl) return kCompactLongMaxAvgRows;
+static int64_t compact_long_max_rows(uint32_t need) {
+    if ((need & kNeedTimeWeighted) == kNeedTimeWeighted || (need & kNeedMinMax)) return kCompactLongBothMaxAvgRows;
+    if (need & (kNeedTimeWeighted | kNeedFirstLast)) return kCompactLongMaxAvgRows;
     return 0;
 }
-static thread_local bool g_strict_order = false;   // bowgpu_options.strict_order of the call in progress (or BOWGPU_ROUTE_STRICT_ORDER)
+// 32-bit window ids counted from the window that starts at slot0, and timestamps that float64 holds exactly: what the compacting kernel,
+// the 32-bit staged times of rolling_tw.hip and the fused kernel ask of a call
+static bool ids_and_times_fit(const Plan &plan, int64_t slot0, int64_t W) {
+    const int64_t lim53 = 1ll << 53;
+    return plan.first_ts > -lim53 && plan.last_ts < lim53 && (uint64_t)plan.last_ts - (uint64_t)slot0 < 0xFFFFFFF0ull && W < 0xFFFFFFF0ll;
+}
 
-static void pending_drop(Ctx *c);   // a pass put in flight by bowgpu_shard_pass_begin and not collected: settled before the scratch is reused
+// Which column pass (slot) serves each reducer that reads values: its column's, or a new one when the column has none yet or when
+// its slot already serves per_pass nullable reducers (the general kernel takes 4 per pass; rolling_fused.hip has no such limit)
+struct ColSlots {
+    std::vector<int> slot_of, nullable_in_slot;
+    explicit ColSlots(int ncols) : slot_of(ncols, -1) {}
+    int count() const { return (int)nullable_in_slot.size(); }
+    void clear() { nullable_in_slot.clear(); std::fill(slot_of.begin(), slot_of.end(), -1); }
+    int find(const bowgpu_agg &a, int per_pass) const {   // -1: take() would open a slot
+        const int s = slot_of[a.col];
+        return (s >= 0 && !kind_never_nil(a.kind) && nullable_in_slot[s] >= per_pass) ? -1 : s;
+    }
+    int take(const bowgpu_agg &a, int per_pass) {
+        int s = find(a, per_pass);
+        if (s < 0) { s = count(); slot_of[a.col] = s; nullable_in_slot.push_back(0); }
+        if (!kind_never_nil(a.kind)) nullable_in_slot[s]++;
+        return s;
+    }
+};
 
-static int job_build(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t ts_col, const Plan &plan, int inclusive,
-                     const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs, int64_t wid_base, int64_t W,
-                     bool holds_row0, AggJob *job, int nullable_per_pass = 4) {
-    pending_drop(c);
-    const bowgpu_col *tsc = &cols[ts_col];
-    const int64_t n = tsc->length;
+static int check_row_counts(const bowgpu_col *cols, int32_t ncols, int32_t ts_col) {
+    const int64_t n = cols[ts_col].length;
     for (int i = 0; i < ncols; i++)
         if (cols[i].length != n) return fail(BOWGPU_ERR_ARG, "column %d has %lld rows, interval column has %lld", i, (long long)cols[i].length, (long long)n);
-
-    // device path contract: no null timestamps
+    return 0;
+}
+// ... and the device path's contract: no null timestamps (run_aggregate has sent such a call to run_aggregate_null_ts)
+static int front_check(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t ts_col) {
+    BG_TRY(check_row_counts(cols, ncols, ts_col));
+    const bowgpu_col *tsc = &cols[ts_col];
     if (tsc->validity && tsc->null_count != 0) {
         DevCol probe;
         BG_TRY(devcol_prepare(c, tsc, &probe, false, true));
         if (probe.null_count > 0)
             return fail(BOWGPU_ERR_TS_NULLS, "interval column has %lld nulls: outside the device path", (long long)probe.null_count);
     }
+    return 0;
+}
+
+static void pending_drop(Ctx *c);   // a pass put in flight by bowgpu_shard_pass_begin and not collected: settled before the scratch is reused
+
+// (naggs <= kMaxAggs: run_aggregate batches, shard_check and fused_try bound it)
+static int job_build(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs, int64_t wid_base, int64_t W,
+                     bool holds_row0, AggJob *job, int nullable_per_pass = 4) {
+    pending_drop(c);
+    const bowgpu_col *cols = call.cols;
+    const int32_t ncols = call.ncols, ts_col = call.ts_col;
+    const Plan &plan = call.plan;
+    const bowgpu_col *tsc = &cols[ts_col];
+    const int64_t n = tsc->length;
+    BG_TRY(front_check(c, cols, ncols, ts_col));
 
     job->dcols.clear();
     job->dcols.resize(ncols);
     job->douts.clear();
     job->douts.resize(naggs);
     job->W = W;
-    job->inclusive = inclusive;
-    job->check_plan = g_plan_from_caller;
+    job->inclusive = call.inclusive;
+    memcpy(job->aggs, aggs, sizeof(bowgpu_agg) * (size_t)naggs);
+    job->naggs = naggs;
+    job->need = need_mask(aggs, naggs);
+    job->plan = plan;
+    job->strict = call.strict;
+    job->check_plan = call.check_plan;
     std::vector<DevCol> &dcols = job->dcols;
-    std::vector<int> slot_of(ncols, -1);
     AggParams &P = job->P;
     memset(&P, 0, sizeof P);
     {
@@ -804,32 +866,21 @@ static int job_build(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t ts_c
     P.wid_base = wid_base;
     P.magic = plan.magic;
     P.fits32 = ((uint64_t)plan.interval >> 32) == 0;
-    if (P.fits32) {
-        // Granlund & Montgomery fig. 4.1 with N = 32
-        const uint64_t d = (uint64_t)plan.interval;
-        int l = 0;
-        while (l < 32 && (1ull << l) < d) l++;
-        P.m32 = (uint32_t)((((1ull << l) - d) << 32) / d) + 1;
-        P.sh1_32 = l < 1 ? (uint32_t)l : 1u;
-        P.sh2_32 = l > 1 ? (uint32_t)(l - 1) : 0u;
-    }
-    P.inclusive = inclusive;
+    if (P.fits32) interp_magic32(plan.interval, &P.m32, &P.sh1_32, &P.sh2_32);
+    P.inclusive = call.inclusive;
     P.naggs = naggs;
     P.pre_rows = (n > 0 && holds_row0 && plan.s0 > plan.first_ts) ? 1 : 0;
 
     // column slots: each distinct input column whose values some reducer reads
-    std::vector<int> nullable_in_slot;
+    ColSlots slots(ncols);
     for (int i = 0; i < naggs; i++) {
         if (!kind_reads_values(aggs[i].kind)) continue;
         const int col = aggs[i].col;
-        int s = slot_of[col];
-        const bool nullable = !kind_never_nil(aggs[i].kind);
-        if (s >= 0 && nullable && nullable_in_slot[s] >= nullable_per_pass) s = -1;  // at most 4 nullable reducers per pass of the general kernel: open another slot (rolling_fused.hip has no such limit)
-        if (s < 0) {
-            if (P.ncols >= kMaxCols) return fail(BOWGPU_ERR_UNSUPPORTED, "at most %d value columns per call", kMaxCols);
-            s = P.ncols++;
-            slot_of[col] = s;
-            nullable_in_slot.push_back(0);
+        const bool opens = slots.find(aggs[i], nullable_per_pass) < 0;
+        if (opens && P.ncols >= kMaxCols) return fail(BOWGPU_ERR_UNSUPPORTED, "at most %d value columns per call", kMaxCols);
+        const int s = slots.take(aggs[i], nullable_per_pass);
+        if (opens) {
+            P.ncols++;
             DevCol &dc = dcols[col];
             if (dc.values == nullptr && n > 0) {
                 if (col == ts_col) {
@@ -845,7 +896,6 @@ static int job_build(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t ts_c
             cd.vwords = dc.vwords;
             cd.type = cols[col].type;
         }
-        if (nullable) nullable_in_slot[s]++;
         P.aggs[i].slot = s;
     }
 
@@ -906,31 +956,33 @@ constexpr size_t kCountsOffset = 1024;                       // bytes: counts[kM
 constexpr size_t kReadbackBytes = kCountsOffset + 8 * kMaxAggs;
 static_assert(kStatusWords * 4 <= kCountsOffset, "status words overlap the counters");
 
-static void job_bitmaps(AggJob *job, const bowgpu_agg *aggs, int32_t naggs, bool all_ones, BitmapBatch *b) {
+// preset: the check of a caller's plan against the column rides in the launch
+static void job_bitmaps(const AggJob *job, bool all_ones, bool preset, BitmapBatch *b) {
     memset(b, 0, sizeof *b);
-    b->n = naggs;
+    b->n = job->naggs;
     b->status_words = kStatusWords;
     b->nbits = job->W > 0 ? job->W : 0;
     b->status = job->P.status;
     b->counts = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(job->P.status) + kCountsOffset);
-    for (int i = 0; i < naggs; i++) {
+    for (int i = 0; i < job->naggs; i++) {
         b->work[i] = reinterpret_cast<uint32_t *>(job->douts[i].validity);
         const bowgpu_out *u = job->douts[i].user;
         b->user[i] = (u && u->residency == BOWGPU_DEVICE) ? u->validity : nullptr;
         // never-nil reducers: all-ones bitmap; nullable ones start all-null (bowbuffer.go:25) - except under the simple kernels,
         // where every bitmap starts as ones and only the bits of nil results are cleared
-        b->ones[i] = all_ones || kind_never_nil(aggs[i].kind);
-        b->count[i] = !kind_never_nil(aggs[i].kind);
+        b->ones[i] = all_ones || kind_never_nil(job->aggs[i].kind);
+        b->count[i] = !kind_never_nil(job->aggs[i].kind);
     }
+    if (preset && job->check_plan) { b->check_ts = job->P.ts; b->check_n = job->P.n; b->check_first = job->plan.first_ts; b->check_last = job->plan.last_ts; }
 }
 
 // valid counts of the nullable outputs + bitmaps into the caller's buffers (one launch) + copy-back of host-resident outputs,
 // enqueued only (no sync); the counts come back with the status words (job_readback)
-static int job_enqueue_tail(Ctx *c, AggJob *job, const bowgpu_agg *aggs, int32_t naggs) {
+static int job_enqueue_tail(Ctx *c, AggJob *job) {
     const int64_t W = job->W;
     if (W > 0) {
         BitmapBatch b;
-        job_bitmaps(job, aggs, naggs, false, &b);
+        job_bitmaps(job, false, false, &b);
         if (W <= kFinishHostBits) {
             // a small call is a chain of dependent launches and little else: its last launch hands the status words and the counts to
             // the host itself instead of a copy command doing so behind it
@@ -940,7 +992,7 @@ static int job_enqueue_tail(Ctx *c, AggJob *job, const bowgpu_agg *aggs, int32_t
         BG_TRY(launch_finish_bitmaps(c, b));
         job->counts_used = true;
     }
-    for (int i = 0; i < naggs; i++) BG_TRY(devout_finish(c, &job->douts[i], W, job->P.aggs[i].out_type, 0, false));
+    for (int i = 0; i < job->naggs; i++) BG_TRY(devout_finish(c, &job->douts[i], W, job->P.aggs[i].out_type, 0, false));
     return 0;
 }
 
@@ -954,13 +1006,47 @@ static int job_readback(Ctx *c, AggJob *job, uint32_t **hstat, uint64_t **hcnt) 
     return 0;
 }
 
+// The settle step of everything a job has enqueued: [the tail, where the call's outputs are complete with it,] the read-back of the
+// status words and the counts ...
+static int job_settle_enqueue(Ctx *c, AggJob *job, bool tail, uint32_t **hstat, uint64_t **hcnt) {
+    if (tail) BG_TRY(job_enqueue_tail(c, job));
+    return job_readback(c, job, hstat, hcnt);
+}
+// ... and the synchronisation
+static int job_settle(Ctx *c, AggJob *job, bool tail, uint32_t **hstat, uint64_t **hcnt) {
+    BG_TRY(job_settle_enqueue(c, job, tail, hstat, hcnt));
+    BG_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int fail_ts_unsorted() { return fail(BOWGPU_ERR_TS_UNSORTED, "interval column is not ascending: outside the device path"); }
+
+// The Aggregate status words (common.h kAggSt*) that end a call, as its error; `look`: the words this site asks about (a bit per word).
+// kAggStRedo and kAggStFusedDeclines are not errors: job_pass_complete and fused_try act on them.
+constexpr uint32_t kLookPlan = 1u << kAggStPlanMismatch, kLookUnsorted = 1u << kAggStUnsorted, kLookOverflow = 1u << kAggStListOverflow,
+                   kLookStrict = 1u << kAggStStrictTooLong;
+static int agg_status_error(const uint32_t *hstat, uint32_t look) {
+    if ((look & kLookPlan) && hstat[kAggStPlanMismatch])
+        return fail(BOWGPU_ERR_ARG, "the plan was not made for this interval column (its first / last timestamp differ)");
+    if ((look & kLookUnsorted) && hstat[kAggStUnsorted]) return fail_ts_unsorted();
+    if ((look & kLookOverflow) && hstat[kAggStListOverflow]) return fail(BOWGPU_ERR_HIP, "internal: long-window list overflow");
+    if ((look & kLookStrict) && hstat[kAggStStrictTooLong])
+        return fail(BOWGPU_ERR_UNSUPPORTED, "strict_order: some window holds more than 2^20 rows (one lane walks a window in row order: beyond that the call is declined)");
+    return 0;
+}
+
+static void job_null_counts(AggJob *job, const uint64_t *hcnt) {
+    for (int i = 0; i < job->naggs; i++)
+        job->douts[i].user->null_count = (job->W > 0 && !kind_never_nil(job->aggs[i].kind)) ? job->W - (int64_t)hcnt[i] : 0;
+}
+
 // Can the wave-tile kernels (rolling_simple.hip; time_weighted: rolling_tw.hip) take this call?  16-B aligned columns, no rows
 // below s0, interval < 2^32, at most kSimpleMaxAggs outputs; rolling_simple.hip: exclusive windows without time-weighted
 // reducers.  *wide: the rows reach 2^32 or more past output slot 0 (nanosecond timestamps): ids relative to each tile's window.
-static bool simple_applies(const AggJob *job, const bowgpu_agg *aggs, int32_t naggs, const Plan &plan, bool time_weighted, int *need,
-                           bool *is_int, bool *has_nulls, bool *wide) {
+static bool simple_applies(const AggJob *job, bool time_weighted, bool *is_int, bool *has_nulls, bool *wide) {
     const AggParams &P = job->P;
-    if ((job->inclusive && !time_weighted) || !P.fits32 || naggs > kSimpleMaxAggs) return false;
+    const Plan &plan = job->plan;
+    if ((job->inclusive && !time_weighted) || !P.fits32 || job->naggs > kSimpleMaxAggs) return false;
     if (P.W <= 0) return false;
 
     // output slot 0 starts at s0 + wid_base * interval (wid_base != 0: a shard; it never lies above the shard's first row).  Rows
@@ -970,26 +1056,22 @@ static bool simple_applies(const AggJob *job, const bowgpu_agg *aggs, int32_t na
     // rows within 2^32 of slot 0: global 32-bit window ids; else (nanosecond timestamps) ids relative to each tile's first window
     *wide = (uint64_t)plan.last_ts - (uint64_t)slot0_start >= 0xFFFFFFF0ull || P.W >= 0xFFFFFFF0ll;
     // (columns that start on an 8-byte but not a 16-byte boundary - Arrow slices with odd offsets - stay here: 8-byte loads)
-    *need = 0;
     *is_int = true;  // (reducers over the interval column itself)
     *has_nulls = false;
     for (int s = 0; s < P.ncols; s++) {
         *has_nulls = *has_nulls || P.cols[s].vbits != nullptr;
         *is_int = P.cols[0].type == BOWGPU_INT64;
     }
-    for (int i = 0; i < naggs; i++) {
-        const int k = aggs[i].kind;
-        if (k >= BOWGPU_AGG_INTEGRAL_STEP && k <= BOWGPU_AGG_WAVG_LINEAR && !time_weighted) return false;
-        if (k == BOWGPU_AGG_MIN || k == BOWGPU_AGG_MAX) *need |= 1;
-        if (k == BOWGPU_AGG_FIRST || k == BOWGPU_AGG_LAST) *need |= 2;
-    }
+    if ((job->need & kNeedTimeWeighted) && !time_weighted) return false;
     if (route_mask() & BOWGPU_ROUTE_NO_SIMPLE) return false;
     return true;
 }
 
 // the descriptor of the wave-tile kernels (rolling_simple.hip, rolling_tw.hip, rolling_fused.hip) from a built job
-static void simple_params_build(const AggJob *job, const bowgpu_agg *aggs, int32_t naggs, bool wide, SimpleParams *out) {
+static void simple_params_build(const AggJob *job, bool wide, SimpleParams *out) {
     const AggParams &P = job->P;
+    const bowgpu_agg *aggs = job->aggs;
+    const int32_t naggs = job->naggs;
     SimpleParams &S = *out;
     memset(&S, 0, sizeof S);
     S.ts = P.ts;
@@ -1003,12 +1085,7 @@ static void simple_params_build(const AggJob *job, const bowgpu_agg *aggs, int32
         int k = 0;
         while (k < 31 && !(((uint64_t)P.interval >> k) & 1ull)) k++;
         S.shift_k = k;
-        const uint64_t d = (uint64_t)P.interval >> k;
-        int l = 0;
-        while (l < 32 && (1ull << l) < d) l++;
-        S.m32 = (uint32_t)((((1ull << l) - d) << 32) / d) + 1;
-        S.sh1 = l < 1 ? (uint32_t)l : 1u;
-        S.sh2 = l > 1 ? (uint32_t)(l - 1) : 0u;
+        interp_magic32((int64_t)((uint64_t)P.interval >> k), &S.m32, &S.sh1, &S.sh2);
     }
     S.naggs = naggs;
     S.ncols = P.ncols > 0 ? P.ncols : 1;
@@ -1026,13 +1103,9 @@ static void simple_params_build(const AggJob *job, const bowgpu_agg *aggs, int32
         S.out_values[i] = reinterpret_cast<uint64_t *>(P.aggs[i].out_values);
         S.out_valid[i] = P.aggs[i].out_valid;
     }
+    S.need = job->need;
     for (int i = 0; i < naggs; i++) {
         const int k = aggs[i].kind;
-        if (k == BOWGPU_AGG_INTEGRAL_STEP || k == BOWGPU_AGG_WAVG_STEP) S.need |= kNeedStep;
-        if (k == BOWGPU_AGG_INTEGRAL_TRAPEZOID || k == BOWGPU_AGG_WAVG_LINEAR) S.need |= kNeedTrap;
-        if (k == BOWGPU_AGG_MIN || k == BOWGPU_AGG_MAX) S.need |= kNeedMinMax;
-        if (k == BOWGPU_AGG_SUM || k == BOWGPU_AGG_MEAN) S.need |= kNeedSum;
-        if (k == BOWGPU_AGG_FIRST || k == BOWGPU_AGG_LAST) S.need |= kNeedFirstLast;
         const int cls = (k == BOWGPU_AGG_MIN || k == BOWGPU_AGG_MAX) ? 1 : (k == BOWGPU_AGG_INTEGRAL_STEP || k == BOWGPU_AGG_WAVG_STEP) ? 2
                         : (k == BOWGPU_AGG_INTEGRAL_TRAPEZOID || k == BOWGPU_AGG_WAVG_LINEAR) ? 3
                         : (k == BOWGPU_AGG_SUM || k == BOWGPU_AGG_MEAN || k == BOWGPU_AGG_FIRST || k == BOWGPU_AGG_LAST) ? 0 : 4;
@@ -1046,36 +1119,50 @@ static void simple_params_build(const AggJob *job, const bowgpu_agg *aggs, int32
     for (int s = 0; s < S.ncols; s++)
         if (reinterpret_cast<uintptr_t>(S.values[s]) & 15) S.unaligned_mask |= 1u << s;
 }
+// launch_rolling_simple's own encoding of the statistics it walks for: bit 0 extrema, bit 1 First / Last
+static int simple_launch_need(uint32_t need) { return ((need & kNeedMinMax) ? 1 : 0) | ((need & kNeedFirstLast) ? 2 : 0); }
 
-static int job_launch_tiles(Ctx *c, AggJob *job, const bowgpu_agg *aggs, int32_t naggs, const Plan *plan, bool allow_simple,
-                            bool *used_simple, bool force_large_list = false, bool *used_small_list = nullptr) {
+// Windows longer than a tile's look-ahead: workspace from the context pool, then long_windows.hip
+struct LongWork {
+    void *entries; int32_t *nchunks; int64_t *offsets, *sums, *total; int32_t *work_entry; void *parts;
+    int64_t max_work;
+};
+// The attempts of a tile pass.  A wave-tile kernel raises kAggStRedo when some tile is beyond what it can describe - more window heads
+// than its small list holds (clumpy data: a high average of rows per window, yet a dense tile), window ids it cannot encode - and
+// job_pass_complete then makes PassState::redo_with the next attempt
+enum TileAttempt { kAttemptFirst, kAttemptLargeList /* no compacting kernel, the large head list (400 heads per 640 rows) */,
+                   kAttemptNoSimple /* the general lean kernel */, kAttemptNone };
+struct PassState {
+    TileAttempt redo_with = kAttemptNone;   // job_launch_tiles: the attempt that follows the one it launched (kAttemptNone: nothing that raises kAggStRedo ran)
+    bool band_rows = false;     // job_run: a nullable column under extrema / First + Last alone, 129 .. 200 rows per window - rolling_simple.hip + the queue launch, not rolling_twc.hip
+    uint32_t *hstat = nullptr;
+    uint64_t *hcnt = nullptr;
+    bool queue = false;     // long_queue_kernel rides behind the tile kernel: the queued windows are served without the host in between
+    LongWork qw{};          // ... its workspace (sized for the queue's capacity)
+};
+
+static int job_launch_tiles(Ctx *c, AggJob *job, TileAttempt attempt, PassState *ps) {
     AggParams &P = job->P;
+    const Plan &plan = job->plan;
     const int64_t W = job->W;
-    *used_simple = false;
-    bool small_dummy = false;
-    if (!used_small_list) used_small_list = &small_dummy;
-    *used_small_list = false;
+    const bool allow_simple = attempt != kAttemptNoSimple, force_large_list = attempt == kAttemptLargeList;
+    ps->redo_with = kAttemptNone;
     if (W <= 0) { BG_HIP(hipMemsetAsync(P.status, 0, kReadbackBytes, c->stream)); return 0; }
     // The lean kernels cover exclusive windows without time-weighted reducers and without rows below s0; everything
     // else (and BOWGPU_ROUTE_FORCE_GENERAL, used by the tests to cover all of them) takes the general kernel.
-    bool lean = !job->inclusive;   // (rows below s0 - P.pre_rows - are taken by the wave-tile kernels; the lean wave kernel declines them below)
-    for (int i = 0; i < naggs; i++)
-        if (aggs[i].kind >= BOWGPU_AGG_INTEGRAL_STEP && aggs[i].kind <= BOWGPU_AGG_WAVG_LINEAR) lean = false;
+    // (rows below s0 - P.pre_rows - are taken by the wave-tile kernels; the lean wave kernel declines them below)
     const uint32_t route = route_mask();
     const bool force = (route & BOWGPU_ROUTE_FORCE_GENERAL) != 0;
-    if (force) lean = false;
-    int need = 0;
+    const bool lean = !job->inclusive && !(job->need & kNeedTimeWeighted) && !force;
     bool is_int = false, has_nulls = false, wide = false;
-    bool simple = lean && allow_simple && plan && simple_applies(job, aggs, naggs, *plan, false, &need, &is_int, &has_nulls, &wide);
+    bool simple = lean && allow_simple && simple_applies(job, false, &is_int, &has_nulls, &wide);
     // time-weighted reducers / inclusive windows: the same wave-tile structure with ts staged as float64 (rolling_tw.hip)
-    const bool tw = !lean && !force && allow_simple && plan &&
-                    simple_applies(job, aggs, naggs, *plan, true, &need, &is_int, &has_nulls, &wide);
+    const bool tw = !lean && !force && allow_simple && simple_applies(job, true, &is_int, &has_nulls, &wide);
     simple = simple || tw;
     P.bits_preset = simple ? 1 : 0;
     {
         BitmapBatch b;
-        job_bitmaps(job, aggs, naggs, simple, &b);
-        if (job->check_plan && plan) { b.check_ts = P.ts; b.check_n = P.n; b.check_first = plan->first_ts; b.check_last = plan->last_ts; }
+        job_bitmaps(job, simple, true, &b);
         BG_TRY(launch_preset_bitmaps(c, b));   // + status words and counters to zero (+ the check of a caller-supplied plan)
         job->counts_used = false;
     }
@@ -1083,51 +1170,47 @@ static int job_launch_tiles(Ctx *c, AggJob *job, const bowgpu_agg *aggs, int32_t
     BG_HIP(hipEventRecord(c->ev0, c->stream));
     if (simple) {
         SimpleParams S;
-        simple_params_build(job, aggs, naggs, wide, &S);
+        simple_params_build(job, wide, &S);
+        const int64_t avg_rows = P.n / P.W;
+        // 32-bit staged timestamps / the compacting form: exact when float64(s0 of slot 0) + float64(offset) needs no rounding, i.e. every |ts| < 2^53
+        const bool ts32 = !P.pre_rows && ids_and_times_fit(plan, S.s0, P.W) && S.s0 > -(1ll << 53);
+        // a nullable column: the compacting form (rolling_twc.hip) where its 32-bit times and its head list allow; a tile that overflows
+        // the list raises kAggStRedo and the call is redone as kAttemptLargeList, i.e. by rolling_tw.hip / rolling_simple.hip
+        const bool compact_ok = has_nulls && ts32 && !force_large_list && !(route & BOWGPU_ROUTE_TW_ROWS);
+        bool compact;
         if (tw) {
-            // 32-bit staged timestamps: exact when float64(s0 of slot 0) + float64(offset) needs no rounding, i.e. every |ts| < 2^53
             // (BOWGPU_ROUTE_TW_F64: test / A-B switch that keeps the float64 form)
-            const int64_t lim53 = 1ll << 53;
-            const bool ts32 = !wide && !P.pre_rows && plan->first_ts > -lim53 && plan->last_ts < lim53 && S.s0 > -lim53 && !(route & BOWGPU_ROUTE_TW_F64);
-            // a nullable column: the compacting form (rolling_twc.hip) where its 32-bit times and its head list allow; a tile that overflows
-            // the list raises status[4] and the call is redone here with force_large_list (job_pass_complete), i.e. by rolling_tw.hip
-            const bool compact = has_nulls && ts32 && !force_large_list && !(route & BOWGPU_ROUTE_TW_ROWS) && P.n / P.W >= kCompactMinAvgRows;
-            if (compact) {
-                BG_TRY(launch_rolling_twc(c, S, P.n / P.W > 128));   // (windows of 129 .. kCompactLongMaxAvgRows rows on average: 256 rows of look-ahead)
-                *used_small_list = true;
-                c->last_kernel_name = "rolling_twc_kernel";
-            } else {
-                BG_TRY(launch_rolling_tw(c, S, is_int, has_nulls, wide, ts32));
-                c->last_kernel_name = "rolling_tw_kernel";
-            }
-        } else if ([&] {
-                       // a nullable column whose outputs want sums AND extrema, windows of kCompactValuesMinAvgRows rows and more: the compacting
-                       // form walks the valid points once where rolling_simple.hip walks the rows twice (or once under the validity bit) - 1e8
-                       // rows, 30 % nulls, Sum + Min + Max: 0.412 against 0.440 ms at 64 rows per window, 0.451 against 0.558 at 128; below
-                       // that length, and for every other value set, rolling_simple.hip stays ahead (the A/B of round 5, timing only; the sweep that shows the routed
-                       // kernels side by side is profiles/r05_stdout_midw_sweep.txt)
-                       const int64_t lim53 = 1ll << 53;
-                       const bool ts32 = !wide && !P.pre_rows && plan->first_ts > -lim53 && plan->last_ts < lim53 && S.s0 > -lim53;
-                       const bool sums_and_extrema = (S.need & kNeedSum) && (S.need & kNeedMinMax);
-                       // (beyond 128 rows per window the call is here only because job_run kept it off the streaming form: compact_long_max_rows)
-                       if (job->band_rows) return false;   // (job_run: extrema / First + Last alone on a nullable column in the 129 .. 200 band - this kernel + the queue launch)
-                       if (has_nulls && ts32 && !force_large_list && !(route & BOWGPU_ROUTE_TW_ROWS) && P.n / P.W > 128 && P.n / P.W <= compact_long_max_rows(aggs, naggs)) return true;
-                       return has_nulls && ts32 && sums_and_extrema && !force_large_list && !(route & BOWGPU_ROUTE_TW_ROWS) && P.n / P.W >= kCompactValuesMinAvgRows;
-                   }()) {
-            BG_TRY(launch_rolling_twc(c, S, P.n / P.W > 128));
-            *used_small_list = true;
+            compact = compact_ok && !(route & BOWGPU_ROUTE_TW_F64) && avg_rows >= kCompactMinAvgRows;
+        } else if (ps->band_rows) {
+            compact = false;   // (job_run: extrema / First + Last alone on a nullable column in the 129 .. 200 band - rolling_simple.hip + the queue launch)
+        } else {
+            // beyond 128 rows per window the call is here only because job_run kept it off the streaming form (compact_long_max_rows); up to
+            // there: a nullable column whose outputs want sums AND extrema, windows of kCompactValuesMinAvgRows rows and more - the compacting
+            // form walks the valid points once where rolling_simple.hip walks the rows twice (or once under the validity bit) - 1e8
+            // rows, 30 % nulls, Sum + Min + Max: 0.412 against 0.440 ms at 64 rows per window, 0.451 against 0.558 at 128; below
+            // that length, and for every other value set, rolling_simple.hip stays ahead (the A/B of round 5, timing only; the sweep that shows the routed
+            // kernels side by side is profiles/r05_stdout_midw_sweep.txt)
+            compact = compact_ok && ((avg_rows > 128 && avg_rows <= compact_long_max_rows(job->need)) ||
+                                     ((job->need & kNeedSum) && (job->need & kNeedMinMax) && avg_rows >= kCompactValuesMinAvgRows));
+        }
+        if (compact) {
+            BG_TRY(launch_rolling_twc(c, S, avg_rows > 128));   // (windows of 129 .. kCompactLongMaxAvgRows rows on average: 256 rows of look-ahead)
+            ps->redo_with = kAttemptLargeList;
             c->last_kernel_name = "rolling_twc_kernel";
+        } else if (tw) {
+            BG_TRY(launch_rolling_tw(c, S, is_int, has_nulls, wide, ts32 && !(route & BOWGPU_ROUTE_TW_F64)));
+            ps->redo_with = kAttemptNoSimple;
+            c->last_kernel_name = "rolling_tw_kernel";
         } else {
             // (the head list of a tile comes in two sizes - rolling_simple.hip SimpleCap: the small one buys four more resident
             // wavefronts per CU and serves calls whose windows average >= 5 rows; BOWGPU_ROUTE_SIMPLE_LARGE_LIST / _SMALL_LIST force
-            // either, for tests; a call whose tiles overflow the small list is redone with the large one - job_run)
+            // either, for tests; a call whose tiles overflow the small list is redone with the large one - job_pass_complete)
             // (the unpadded instantiation's small list holds 254 heads: windows of 3 rows and more, as before the pads)
             const int64_t small_list_rows = rolling_simple_plain(S, is_int, has_nulls) ? 3 : 5;
-            const bool dense = force_large_list || ((route & BOWGPU_ROUTE_SIMPLE_LARGE_LIST) ? true : (route & BOWGPU_ROUTE_SIMPLE_SMALL_LIST) ? false : P.n / P.W < small_list_rows);
-            *used_small_list = !dense;
-            BG_TRY(launch_rolling_simple(c, S, need, is_int, has_nulls, wide, dense));   // (sets c->last_kernel_name: the instantiation)
+            const bool dense = force_large_list || ((route & BOWGPU_ROUTE_SIMPLE_LARGE_LIST) ? true : (route & BOWGPU_ROUTE_SIMPLE_SMALL_LIST) ? false : avg_rows < small_list_rows);
+            ps->redo_with = dense ? kAttemptNoSimple : kAttemptLargeList;
+            BG_TRY(launch_rolling_simple(c, S, simple_launch_need(job->need), is_int, has_nulls, wide, dense));   // (sets c->last_kernel_name: the instantiation)
         }
-        *used_simple = true;
     } else if (lean && !P.pre_rows) {
         BG_TRY(launch_rolling_fast(c, P));
         c->last_kernel_name = "rolling_wave_kernel";
@@ -1136,8 +1219,8 @@ static int job_launch_tiles(Ctx *c, AggJob *job, const bowgpu_agg *aggs, int32_t
         if (trace && !force && !(route & BOWGPU_ROUTE_NO_SIMPLE) && allow_simple)
             fprintf(stderr, "bowgpu route: general kernel (n=%lld W=%lld interval=%lld inclusive=%d naggs=%d pre_rows=%lld wid_base=%lld "
                             "fits32=%d allow_simple=%d plan=%d first_ts=%lld s0=%lld)\n", (long long)P.n, (long long)P.W,
-                    (long long)P.interval, (int)job->inclusive, naggs, (long long)P.pre_rows, (long long)P.wid_base, (int)P.fits32,
-                    (int)allow_simple, plan ? 1 : 0, plan ? (long long)plan->first_ts : 0ll, (long long)P.s0);
+                    (long long)P.interval, (int)job->inclusive, job->naggs, (long long)P.pre_rows, (long long)P.wid_base, (int)P.fits32,
+                    (int)allow_simple, 1, (long long)plan.first_ts, (long long)P.s0);
         BG_TRY(launch_rolling_aggregate(c, P));
         c->last_kernel_name = "rolling_agg_kernel";
         c->last_slow_rows += P.n;   // (the general kernel: 0.32 of the HBM peak where the wave-tile kernels reach 0.6 - 0.7)
@@ -1146,11 +1229,6 @@ static int job_launch_tiles(Ctx *c, AggJob *job, const bowgpu_agg *aggs, int32_t
     return 0;
 }
 
-// Windows longer than a tile's look-ahead: workspace from the context pool, then long_windows.hip
-struct LongWork {
-    void *entries; int32_t *nchunks; int64_t *offsets, *sums, *total; int32_t *work_entry; void *parts;
-    int64_t max_work;
-};
 static int long_workspace(Ctx *c, const AggParams &P, int64_t n_entries, LongWork *w) {
     const int64_t max_work = n_entries + (P.n + kLongChunkRows - 1) / kLongChunkRows;
     const int64_t scan_blocks = (n_entries + 2047) / 2048;
@@ -1175,7 +1253,7 @@ static int long_workspace(Ctx *c, const AggParams &P, int64_t n_entries, LongWor
     return 0;
 }
 // hstat == nullptr: the long-only pipeline (every window of the call)
-static int run_long_windows(Ctx *c, const AggParams &P, const uint32_t *hstat, int64_t *n_long_out, bool strict = false) {
+static int run_long_windows(Ctx *c, const AggParams &P, const uint32_t *hstat, int64_t *n_long_out, bool strict) {
     LongListStarts starts;
     starts.start[0] = 0;
     if (hstat)
@@ -1192,13 +1270,6 @@ static int run_long_windows(Ctx *c, const AggParams &P, const uint32_t *hstat, i
 static thread_local double g_prof_sync_begin = 0, g_prof_sync_end = 0;
 static double now_us() { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e6 + t.tv_nsec * 1e-3; }
 
-struct PassState {
-    bool used_simple = false, used_small_list = false;
-    uint32_t *hstat = nullptr;
-    uint64_t *hcnt = nullptr;
-    bool queue = false;     // long_queue_kernel rides behind the tile kernel: the queued windows are served without the host in between
-    LongWork qw{};          // ... its workspace (sized for the queue's capacity)
-};
 // From how many rows per window (on average) on a tile pass is followed by long_queue_kernel unconditionally: below, windows longer than a
 // tile's look-ahead are the exception and a call pays nothing for them until one shows up (the host then reads the counts and launches the
 // machinery: rounds 1 - 5); from here on they are expected, and the launch (a few microseconds when the queue is empty) replaces a host
@@ -1207,23 +1278,33 @@ constexpr int64_t kQueueMinAvgRows = 64;
 static int job_queue_enqueue(Ctx *c, AggJob *job, PassState *ps) {
     if (!ps->queue) return 0;
     const AggParams &P = job->P;
-    BG_TRY(launch_long_queue(c, P, P.long_cap * kLongLists, ps->qw.entries, ps->qw.nchunks, g_strict_order ? ((int64_t)1 << 20) : kQueueWalkMaxRows, g_strict_order));
+    BG_TRY(launch_long_queue(c, P, P.long_cap * kLongLists, ps->qw.entries, ps->qw.nchunks, job->strict ? ((int64_t)1 << 20) : kQueueWalkMaxRows, job->strict));
     BG_HIP(hipEventRecord(c->ev1, c->stream));   // (the bracket of kernel_ms: tile kernel + queue)
     return 0;
 }
-static int job_pass_enqueue(Ctx *c, AggJob *job, const bowgpu_agg *aggs, int32_t naggs, const Plan *plan, bool finish, PassState *ps);
-static int job_pass_complete(Ctx *c, AggJob *job, const bowgpu_agg *aggs, int32_t naggs, const Plan *plan, bool finish, PassState *ps,
-                             int64_t *long_windows, double *kernel_ms);
+static int job_pass_enqueue(Ctx *c, AggJob *job, bool finish, PassState *ps);
+static int job_pass_complete(Ctx *c, AggJob *job, bool finish, PassState *ps, int64_t *long_windows, double *kernel_ms);
 
-static int job_run(Ctx *c, AggJob *job, const bowgpu_agg *aggs, int32_t naggs, int64_t *long_windows, double *kernel_ms,
-                   bool finish, const Plan *plan = nullptr, bool allow_long_only = false) {
+// bowgpu_agg_info.kernel_ms: the bracket of the dominant kernel
+static int job_report_ms(Ctx *c, bool ran, double *kernel_ms) {
+    float ms = 0;
+    if (ran) BG_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->last_kernel_ms = ms;
+    if (kernel_ms) *kernel_ms = ms;
+    return 0;
+}
+
+static int job_run(Ctx *c, AggJob *job, int64_t *long_windows, double *kernel_ms, bool finish, bool allow_long_only = false) {
     AggParams &P = job->P;
+    const Plan &plan = job->plan;
     const int64_t W = job->W;
+    const uint32_t need = job->need;
+    const bool strict = job->strict;
     // Long-only pipeline: when the windows of an unsharded call average thousands of rows, nearly all of them would be queued
     // for long_windows.hip by a tile kernel that reads every row just to find that out.  Skip it: order check of the interval
     // column + every window as an entry of the multi-workgroup reduction.  (BOWGPU_ROUTE_NO_LONG_ONLY: test switch.)
     const uint32_t route = route_mask();
-    const bool nlo = (route & BOWGPU_ROUTE_NO_LONG_ONLY) != 0 || g_strict_order;
+    const bool nlo = (route & BOWGPU_ROUTE_NO_LONG_ONLY) != 0 || strict;
     const bool cls = (route & BOWGPU_ROUTE_LONG_CLASSIC) != 0;      // test / A-B switches: only the bisection + per-window chunks form ...
     const bool sall = (route & BOWGPU_ROUTE_LONG_STREAM_ALL) != 0;  // ... / the streaming form for every reducer set
     // Which form?  The streaming form - one read of the rows, long_windows.hip long_short_kernel / long_stream_kernel - for every
@@ -1235,20 +1316,14 @@ static int job_run(Ctx *c, AggJob *job, const bowgpu_agg *aggs, int32_t naggs, i
     // window they beat the streaming form for every set but the calls with both kinds of integral (Mean: 0.283 against 0.319 ms dense,
     // 0.327 against 0.341 with nulls), scratch/midw_sweep.py; from 129 on some window of the call no longer fits a tile's look-ahead and
     // the cooperative path would have to run as well: the streaming form takes over)
-    bool step_k = false, trap_k = false;
-    for (int i = 0; i < naggs; i++) {
-        step_k |= aggs[i].kind == BOWGPU_AGG_INTEGRAL_STEP || aggs[i].kind == BOWGPU_AGG_WAVG_STEP;
-        trap_k |= aggs[i].kind == BOWGPU_AGG_INTEGRAL_TRAPEZOID || aggs[i].kind == BOWGPU_AGG_WAVG_LINEAR;
-    }
+    const bool both_tw = (need & kNeedTimeWeighted) == kNeedTimeWeighted;
     const int64_t avg_rows = W > 0 ? P.n / W : 0;
-    const bool classic_only = cls;
     // (round 5: with a nullable column the tile kernels compact the valid points first - rolling_twc.hip - and beat the streaming form at 128
     // rows per window for both kinds of integral too: 0.53 against 0.72 ms per 1e8 rows)
     bool any_nulls = false;
     for (int s = 0; s < P.ncols; s++) any_nulls = any_nulls || P.cols[s].vbits != nullptr;
     // ... and with 256 rows of look-ahead the same kernel keeps the calls of 129 .. 176 / 255 rows per window on a nullable column whose
     // reducer set the streaming form serves worst (compact_long_max_rows)
-    const int64_t lim53 = 1ll << 53;
     // Round 6: the windows a tile pass queues are served behind it without the host (long_queue_kernel: a lane per queued window, in row
     // order), which moves the hand-over to the streaming form for columns WITHOUT nulls from 129 rows per window to where the streaming
     // form wins on WALL (1e8 rows, dense, wall ms tile route / streaming form at 144, 160, 192, 224 rows per window -
@@ -1259,43 +1334,30 @@ static int job_run(Ctx *c, AggJob *job, const bowgpu_agg *aggs, int32_t naggs, i
     // 1e8 rows, 30 % nulls, wall ms rolling_simple.hip + queue / what round 5 routed (rolling_twc.hip, from 192 rows the streaming form) at 144,
     // 160, 192 rows per window: Min + Max 0.448 / 0.575, 0.454 / 0.581, 0.468 / 0.568 (224 rows: 0.562 / 0.543); First + Last 0.419 / 0.466,
     // 0.422 / 0.466, 0.450 / 0.460; Sum + Min + Max gains nothing (0.594 / 0.608) and keeps round 5's rule (profiles/r06_stdout_nullable_band_ab.txt)
-    int64_t tile_band_rows = 0;
-    bool no_sum_set = false;
-    {
-        bool mm = false, fl = false, sums = false;
-        for (int i = 0; i < naggs; i++) {
-            const int k = aggs[i].kind;
-            mm |= k == BOWGPU_AGG_MIN || k == BOWGPU_AGG_MAX;
-            fl |= k == BOWGPU_AGG_FIRST || k == BOWGPU_AGG_LAST;
-            sums |= k == BOWGPU_AGG_SUM || k == BOWGPU_AGG_MEAN;
-        }
-        no_sum_set = (mm || fl) && !sums && !step_k && !trap_k;
-        if (step_k && trap_k) tile_band_rows = 0;
-        else if (mm && !sums && !step_k && !trap_k) tile_band_rows = 200;   // (240 was tried once the tile kernel found the extrema of long windows with all its lanes: at 224 rows the queue walk costs more than that saves - 0.498 against 0.453 ms wall, profiles/r06_stdout_midw_band.txt)
-        else if (mm || fl || step_k || trap_k) tile_band_rows = 176;
-    }
-    const bool tile_band = !sall && !cls && (!any_nulls || (no_sum_set && !(route & BOWGPU_ROUTE_TW_ROWS))) && plan && avg_rows > 128 && avg_rows <= tile_band_rows && P.fits32 && !P.pre_rows &&
-                           plan->first_ts > -lim53 && plan->last_ts < lim53 && (uint64_t)plan->last_ts - (uint64_t)P.s0 < 0xFFFFFFF0ull &&
-                           W < 0xFFFFFFF0ll && naggs <= kSimpleMaxAggs &&
-                           !(route & (BOWGPU_ROUTE_NO_SIMPLE | BOWGPU_ROUTE_FORCE_GENERAL | BOWGPU_ROUTE_QUEUE_HOST)) && !g_strict_order;
-    const bool compact_long = !sall && !cls && !tile_band && any_nulls && plan && avg_rows > 128 && avg_rows <= compact_long_max_rows(aggs, naggs) && P.fits32 &&
-                              !P.pre_rows && plan->first_ts > -lim53 && plan->last_ts < lim53 &&
-                              (uint64_t)plan->last_ts - (uint64_t)P.s0 < 0xFFFFFFF0ull && W < 0xFFFFFFF0ll && naggs <= kSimpleMaxAggs &&
-                              !(route & (BOWGPU_ROUTE_TW_ROWS | BOWGPU_ROUTE_TW_F64 | BOWGPU_ROUTE_NO_SIMPLE | BOWGPU_ROUTE_FORCE_GENERAL)) && !g_strict_order;
-    job->band_rows = tile_band && any_nulls;
-    const bool stream_ok = !classic_only && !compact_long && !tile_band &&
-                           avg_rows >= ((sall || (step_k && trap_k && !any_nulls)) ? kLongOnlyAvgRows : kLongStreamAnyAvgRows) &&
+    const bool no_sum_set = (need & (kNeedMinMax | kNeedFirstLast)) && !(need & (kNeedSum | kNeedTimeWeighted));
+    int64_t tile_band_rows = 0;   // (both kinds of integral; sums and counts alone)
+    if (both_tw) tile_band_rows = 0;
+    else if ((need & kNeedMinMax) && !(need & (kNeedSum | kNeedTimeWeighted))) tile_band_rows = 200;   // (240 was tried once the tile kernel found the extrema of long windows with all its lanes: at 224 rows the queue walk costs more than that saves - 0.498 against 0.453 ms wall, profiles/r06_stdout_midw_band.txt)
+    else if (need & (kNeedMinMax | kNeedFirstLast | kNeedTimeWeighted)) tile_band_rows = 176;
+    // what both ways of keeping a call of 129+ rows per window on the tile kernels ask for; the route bits and the bound differ
+    const bool tiles_fit = !sall && !cls && avg_rows > 128 && P.fits32 && !P.pre_rows && ids_and_times_fit(plan, P.s0, W) &&
+                           job->naggs <= kSimpleMaxAggs && !(route & (BOWGPU_ROUTE_NO_SIMPLE | BOWGPU_ROUTE_FORCE_GENERAL)) && !strict;
+    const bool tile_band = tiles_fit && (!any_nulls || (no_sum_set && !(route & BOWGPU_ROUTE_TW_ROWS))) && avg_rows <= tile_band_rows &&
+                           !(route & BOWGPU_ROUTE_QUEUE_HOST);
+    const bool compact_long = tiles_fit && !tile_band && any_nulls && avg_rows <= compact_long_max_rows(need) &&
+                              !(route & (BOWGPU_ROUTE_TW_ROWS | BOWGPU_ROUTE_TW_F64));
+    const bool stream_ok = !cls && !compact_long && !tile_band &&
+                           avg_rows >= ((sall || (both_tw && !any_nulls)) ? kLongOnlyAvgRows : kLongStreamAnyAvgRows) &&
                            avg_rows < kLongClassicAvgRows && W < (1ll << 32);
     const bool classic_ok = avg_rows >= kLongBisectAvgRows;
     // bowgpu_options.strict_order on a call of long windows: every window by one lane in row order (long_windows.hip
     // long_strict_kernel) instead of a tile kernel that reads every row only to queue nearly every window
-    const bool strict_long = g_strict_order && avg_rows >= kLongStreamAnyAvgRows && !(route & BOWGPU_ROUTE_NO_LONG_ONLY);
-    if (allow_long_only && plan && W > 0 && P.wid_base == 0 && (((stream_ok || classic_ok) && !nlo) || strict_long)) {
+    const bool strict_long = strict && avg_rows >= kLongStreamAnyAvgRows && !(route & BOWGPU_ROUTE_NO_LONG_ONLY);
+    if (allow_long_only && W > 0 && P.wid_base == 0 && (((stream_ok || classic_ok) && !nlo) || strict_long)) {
         P.bits_preset = 0;
         {
             BitmapBatch b;
-            job_bitmaps(job, aggs, naggs, false, &b);
-            if (job->check_plan) { b.check_ts = P.ts; b.check_n = P.n; b.check_first = plan->first_ts; b.check_last = plan->last_ts; }
+            job_bitmaps(job, false, true, &b);
             BG_TRY(launch_preset_bitmaps(c, b));
         }
         BG_HIP(hipEventRecord(c->ev0, c->stream));
@@ -1305,7 +1367,7 @@ static int job_run(Ctx *c, AggJob *job, const bowgpu_agg *aggs, int32_t naggs, i
             n_all = 0;   // (bowgpu_agg_info.long_windows counts the windows reduced order-free: none)
             c->last_kernel_name = "long_strict_kernel";
         } else if (!stream_ok) {
-            BG_TRY(run_long_windows(c, P, nullptr, &n_all));
+            BG_TRY(run_long_windows(c, P, nullptr, &n_all, false));
             c->last_kernel_name = "long_partial_kernel";
         } else {
             void *w;
@@ -1316,144 +1378,96 @@ static int job_run(Ctx *c, AggJob *job, const bowgpu_agg *aggs, int32_t naggs, i
         BG_HIP(hipEventRecord(c->ev1, c->stream));
         uint32_t *hs;
         uint64_t *hc = nullptr;
-        if (finish) BG_TRY(job_enqueue_tail(c, job, aggs, naggs));
-        BG_TRY(job_readback(c, job, &hs, &hc));
-        BG_HIP(hipStreamSynchronize(c->stream));
-        if (hs[6]) return fail(BOWGPU_ERR_ARG, "the plan was not made for this interval column (its first / last timestamp differ)");
-        if (hs[0]) return fail(BOWGPU_ERR_TS_UNSORTED, "interval column is not ascending: outside the device path");
-        if (hs[7]) return fail(BOWGPU_ERR_UNSUPPORTED, "strict_order: some window holds more than 2^20 rows (one lane walks a window in row order: beyond that the call is declined)");
-        if (finish)
-            for (int i = 0; i < naggs; i++)
-                job->douts[i].user->null_count = !kind_never_nil(aggs[i].kind) ? W - (int64_t)hc[i] : 0;
+        BG_TRY(job_settle(c, job, finish, &hs, &hc));
+        BG_TRY(agg_status_error(hs, kLookPlan | kLookUnsorted | kLookStrict));
+        if (finish) job_null_counts(job, hc);
         if (long_windows) *long_windows = n_all;
-        float ms = 0;
-        BG_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        c->last_kernel_ms = ms;
-        if (kernel_ms) *kernel_ms = ms;
-        return 0;
+        return job_report_ms(c, true, kernel_ms);
     }
     PassState ps;
-    BG_TRY(job_pass_enqueue(c, job, aggs, naggs, plan, finish, &ps));
-    return job_pass_complete(c, job, aggs, naggs, plan, finish, &ps, long_windows, kernel_ms);
+    ps.band_rows = tile_band && any_nulls;
+    BG_TRY(job_pass_enqueue(c, job, finish, &ps));
+    return job_pass_complete(c, job, finish, &ps, long_windows, kernel_ms);
 }
 
 // the tile pass of a call, enqueued only: bitmap preset, tile kernel, (tail), read-back of the status words - no synchronisation
-static int job_pass_enqueue(Ctx *c, AggJob *job, const bowgpu_agg *aggs, int32_t naggs, const Plan *plan, bool finish, PassState *ps) {
+static int job_pass_enqueue(Ctx *c, AggJob *job, bool finish, PassState *ps) {
     {
         const uint32_t route = route_mask();
         const int64_t avg_rows = job->W > 0 ? job->P.n / job->W : 0;
         ps->queue = job->W > 0 && !(route & BOWGPU_ROUTE_QUEUE_HOST) && (avg_rows >= kQueueMinAvgRows || (route & BOWGPU_ROUTE_QUEUE_DEVICE));
         if (ps->queue) BG_TRY(long_workspace(c, job->P, job->P.long_cap * kLongLists, &ps->qw));
     }
-    BG_TRY(job_launch_tiles(c, job, aggs, naggs, plan, true, &ps->used_simple, false, &ps->used_small_list));
+    BG_TRY(job_launch_tiles(c, job, kAttemptFirst, ps));
     BG_TRY(job_queue_enqueue(c, job, ps));
     // status -> host (pinned).  Optimistically enqueue the tail (null counts, copy-back) behind the tile kernel so
     // the common case needs ONE synchronisation; if windows were queued for the cooperative path, run it and redo the tail.
-    if (finish) BG_TRY(job_enqueue_tail(c, job, aggs, naggs));
-    BG_TRY(job_readback(c, job, &ps->hstat, &ps->hcnt));
-    return 0;
+    return job_settle_enqueue(c, job, finish, &ps->hstat, &ps->hcnt);
 }
 
 // ... and its completion: the one synchronisation, the redo of a call the wave-tile kernels could not describe, the queued long windows
-static int job_pass_complete(Ctx *c, AggJob *job, const bowgpu_agg *aggs, int32_t naggs, const Plan *plan, bool finish, PassState *ps,
-                             int64_t *long_windows, double *kernel_ms) {
+static int job_pass_complete(Ctx *c, AggJob *job, bool finish, PassState *ps, int64_t *long_windows, double *kernel_ms) {
     AggParams &P = job->P;
-    const int64_t W = job->W;
-    bool used_simple = ps->used_simple, used_small_list = ps->used_small_list;
     uint32_t *hstat = ps->hstat;
     uint64_t *hcnt = ps->hcnt;
     g_prof_sync_begin = now_us();
     BG_HIP(hipStreamSynchronize(c->stream));
     g_prof_sync_end = now_us();
-    if (hstat[6]) return fail(BOWGPU_ERR_ARG, "the plan was not made for this interval column (its first / last timestamp differ)");
-    if (hstat[0]) return fail(BOWGPU_ERR_TS_UNSORTED, "interval column is not ascending: outside the device path");
-    if (used_simple && hstat[4] && used_small_list) {
-        // clumpy data: a high average of rows per window, but some tile holds more window heads than the small list takes - the
-        // same kernel with its large list (400 heads per 640 rows) before anything slower is tried
-        BG_TRY(job_launch_tiles(c, job, aggs, naggs, plan, true, &used_simple, true, &used_small_list));
+    BG_TRY(agg_status_error(hstat, kLookPlan | kLookUnsorted));
+    // the redo ladder: the same kernel with its large list before anything slower is tried, then the general lean kernel; each attempt
+    // is the whole sequence again - launch, queue, tail, read-back, synchronise - and after it only the order of the rows is asked about
+    while (hstat[kAggStRedo] && ps->redo_with != kAttemptNone) {
+        BG_TRY(job_launch_tiles(c, job, ps->redo_with, ps));
         BG_TRY(job_queue_enqueue(c, job, ps));
-        if (finish) BG_TRY(job_enqueue_tail(c, job, aggs, naggs));
-        BG_TRY(job_readback(c, job, &hstat, &hcnt));
-        BG_HIP(hipStreamSynchronize(c->stream));
-        if (hstat[0]) return fail(BOWGPU_ERR_TS_UNSORTED, "interval column is not ascending: outside the device path");
+        BG_TRY(job_settle(c, job, finish, &hstat, &hcnt));
+        BG_TRY(agg_status_error(hstat, kLookUnsorted));
     }
-    if (used_simple && hstat[4]) {
-        // some tile needs window ids the simple kernel cannot encode: redo the call with the general lean kernel
-        BG_TRY(job_launch_tiles(c, job, aggs, naggs, plan, false, &used_simple));
-        BG_TRY(job_queue_enqueue(c, job, ps));
-        if (finish) BG_TRY(job_enqueue_tail(c, job, aggs, naggs));
-        BG_TRY(job_readback(c, job, &hstat, &hcnt));
-        BG_HIP(hipStreamSynchronize(c->stream));
-        if (hstat[0]) return fail(BOWGPU_ERR_TS_UNSORTED, "interval column is not ascending: outside the device path");
-    }
-    if (hstat[2]) return fail(BOWGPU_ERR_HIP, "internal: long-window list overflow");
+    BG_TRY(agg_status_error(hstat, kLookOverflow));
     int64_t n_long = 0;
     if (ps->queue) {
         // long_queue_kernel has walked the queued windows of up to kQueueWalkMaxRows rows in row order (exact) behind the tile kernel; the
         // longer ones are listed for the chunked order-free machinery - usually none, and the call is done with its one synchronisation
-        if (hstat[7]) return fail(BOWGPU_ERR_UNSUPPORTED, "strict_order: some window holds more than 2^20 rows (one lane walks a window in row order: beyond that the call is declined)");
+        BG_TRY(agg_status_error(hstat, kLookStrict));
         const int64_t n_big = (int64_t)hstat[kQueueBigWord];
         if (n_big > 0) {
             const LongWork &w = ps->qw;
             BG_TRY(launch_long_windows_v2(c, P, nullptr, w.entries, w.nchunks, w.offsets, w.sums, w.total, w.work_entry, w.parts, w.max_work, false, n_big));
-            if (finish) {
-                BG_TRY(job_enqueue_tail(c, job, aggs, naggs));
-                BG_TRY(job_readback(c, job, &hstat, &hcnt));
-                BG_HIP(hipStreamSynchronize(c->stream));
-            }
+            if (finish) BG_TRY(job_settle(c, job, true, &hstat, &hcnt));
         }
         n_long = n_big;
     } else {
         // (strict_order: the windows a tile could not hold are walked in row order by one lane each - long_strict_kernel - instead of
         // being reduced as a tree; a window beyond 2^20 rows declines the call)
-        BG_TRY(run_long_windows(c, P, hstat, &n_long, g_strict_order));
-        if (n_long > 0 && (finish || g_strict_order)) {
-            if (finish) BG_TRY(job_enqueue_tail(c, job, aggs, naggs));
-            BG_TRY(job_readback(c, job, &hstat, &hcnt));
-            BG_HIP(hipStreamSynchronize(c->stream));
-            if (hstat[7]) return fail(BOWGPU_ERR_UNSUPPORTED, "strict_order: some window holds more than 2^20 rows (one lane walks a window in row order: beyond that the call is declined)");
+        BG_TRY(run_long_windows(c, P, hstat, &n_long, job->strict));
+        if (n_long > 0 && (finish || job->strict)) {
+            BG_TRY(job_settle(c, job, finish, &hstat, &hcnt));
+            BG_TRY(agg_status_error(hstat, kLookStrict));
         }
-        if (g_strict_order) n_long = 0;   // (none of them was reduced order-free)
+        if (job->strict) n_long = 0;   // (none of them was reduced order-free)
     }
-    if (finish)
-        for (int i = 0; i < naggs; i++)
-            job->douts[i].user->null_count = (W > 0 && !kind_never_nil(aggs[i].kind)) ? W - (int64_t)hcnt[i] : 0;
+    if (finish) job_null_counts(job, hcnt);
     if (long_windows) *long_windows = n_long;
-    {
-        float ms = 0;
-        if (W > 0) BG_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        c->last_kernel_ms = ms;
-        if (kernel_ms) *kernel_ms = ms;
-    }
-    return 0;
+    return job_report_ms(c, job->W > 0, kernel_ms);
 }
 
-static int job_finish(Ctx *c, AggJob *job, const bowgpu_agg *aggs, int32_t naggs, uint32_t *strict_limit_hit = nullptr) {
+// the tail of a call whose outputs other launches completed (the shard stitch); strict: a window of more than 2^20 rows declines the call
+static int job_finish(Ctx *c, AggJob *job, bool strict) {
     uint32_t *hstat;
     uint64_t *hcnt = nullptr;
-    BG_TRY(job_enqueue_tail(c, job, aggs, naggs));
-    BG_TRY(job_readback(c, job, &hstat, &hcnt));
-    BG_HIP(hipStreamSynchronize(c->stream));
-    if (strict_limit_hit) *strict_limit_hit = hstat[7];
-    for (int i = 0; i < naggs; i++)
-        job->douts[i].user->null_count = (job->W > 0 && !kind_never_nil(aggs[i].kind)) ? job->W - (int64_t)hcnt[i] : 0;
-    return 0;
+    BG_TRY(job_settle(c, job, true, &hstat, &hcnt));
+    job_null_counts(job, hcnt);
+    return agg_status_error(hstat, strict ? kLookStrict : 0);
 }
 
 // aggregation.Mode outputs (mode.go:8-32): not a streaming reducer, so they run apart from the tile kernels, over the
 // windows' row ranges (an inclusive window reaches them without its extra row: window.go:23-31, aggregation.go:207-211)
-static int run_modes(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t ts_col, const Plan &plan, const bowgpu_agg *aggs,
-                     int32_t naggs, bowgpu_out *outs, int inclusive, int64_t *long_windows) {
+static int run_modes(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs, int64_t *long_windows) {
+    const bowgpu_col *cols = call.cols;
+    const int32_t ts_col = call.ts_col;
+    const Plan &plan = call.plan;
     const bowgpu_col *tsc = &cols[ts_col];
     const int64_t n = tsc->length, W = plan.W;
-    for (int i = 0; i < ncols; i++)
-        if (cols[i].length != n) return fail(BOWGPU_ERR_ARG, "column %d has %lld rows, interval column has %lld", i, (long long)cols[i].length, (long long)n);
-    if (tsc->validity && tsc->null_count != 0) {
-        DevCol probe;
-        BG_TRY(devcol_prepare(c, tsc, &probe, false, true));
-        if (probe.null_count > 0)
-            return fail(BOWGPU_ERR_TS_NULLS, "interval column has %lld nulls: outside the device path", (long long)probe.null_count);
-    }
+    BG_TRY(front_check(c, cols, call.ncols, ts_col));
     DevCol dts;
     DevBuf first_idx;
     if (W > 0) {
@@ -1470,7 +1484,7 @@ static int run_modes(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t ts_c
         uint32_t hstat[4] = {0, 0, 0, 0};
         BG_HIP(hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, c->stream));
         BG_HIP(hipStreamSynchronize(c->stream));
-        if (hstat[0]) return fail(BOWGPU_ERR_TS_UNSORTED, "interval column is not ascending: outside the device path");
+        if (hstat[kAggStUnsorted]) return fail_ts_unsorted();   // (window_first_rows_kernel keeps the Aggregate kernels' word for it)
     }
     for (int i = 0; i < naggs; i++) {
         if (aggs[i].kind != BOWGPU_AGG_MODE) continue;
@@ -1491,11 +1505,11 @@ static int run_modes(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t ts_c
             BG_HIP(hipMemsetAsync(d.validity, 0, ((vb + 3) & ~(size_t)3) + 4, c->stream));
             int64_t n_mid = 0, n_long = 0;
             BG_TRY(launch_mode(c, reinterpret_cast<const int64_t *>(dts.values), reinterpret_cast<const int64_t *>(first_idx.p), n, plan.s0, plan.interval, W,
-                               plan.s0 > plan.first_ts ? 1 : 0, inclusive, values, vbits, vbit0, cols[col].type == BOWGPU_INT64, &aggs[i], d.values,
+                               plan.s0 > plan.first_ts ? 1 : 0, call.inclusive, values, vbits, vbit0, cols[col].type == BOWGPU_INT64, &aggs[i], d.values,
                                reinterpret_cast<uint32_t *>(d.validity), &n_mid, &n_long));
             // (Mode is bit-exact in every size class; the classes beyond a lane's are reported for the tests - not under strict_order,
             // whose contract is long_windows == 0)
-            if (long_windows && !g_strict_order) *long_windows += n_mid + n_long;
+            if (long_windows && !call.strict) *long_windows += n_mid + n_long;
             BG_TRY(recount_nulls(c, d.validity, W, &nulls));
         }
         BG_TRY(devout_finish(c, &d, W, cols[col].type, nulls));
@@ -1504,9 +1518,7 @@ static int run_modes(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t ts_c
     return 0;
 }
 
-static int run_aggregate(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t ts_col, const Plan &plan,
-                         int inclusive, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs,
-                         int64_t wid_base, int64_t W, int64_t *long_windows, double *kernel_ms);
+static int run_aggregate(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs, int64_t *long_windows, double *kernel_ms);
 
 // An interval column WITH NULLS (ts_nulls.hip has the semantics: rolling.go:177-239 skips such rows, :143-154 counts windows from the
 // last valid timestamp, :162-173 ends the iteration at once when the physically last timestamp is null).  The call is rewritten
@@ -1515,15 +1527,17 @@ static int run_aggregate(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t 
 // device temporaries; NumRows is counted as Count over the rows that belong to a window; after an inclusive iteration the windows
 // behind a row on a window start with a null timestamp right behind it get the outputs of IntegralTrapezoid / WeightedAverageLinear
 // from ts_quirk_fix_kernel.  Unsharded calls; Mode is declined.
-static int run_aggregate_null_ts(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t ts_col, const Plan &plan, int inclusive,
-                                 const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs, DevCol &dts, int64_t *long_windows, double *kernel_ms) {
+static int run_aggregate_null_ts(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs, DevCol &dts,
+                                 int64_t *long_windows, double *kernel_ms) {
+    const bowgpu_col *cols = call.cols;
+    const int32_t ncols = call.ncols, ts_col = call.ts_col;
+    const Plan &plan = call.plan;
+    const int inclusive = call.inclusive;
     const bowgpu_col *tsc = &cols[ts_col];
     const int64_t n = tsc->length, W = plan.W;
-    for (int i = 0; i < naggs; i++)
-        if (aggs[i].kind == BOWGPU_AGG_MODE)
-            return fail(BOWGPU_ERR_TS_NULLS, "interval column has %lld nulls: Mode over it is outside the device path", (long long)dts.null_count);
-    for (int i = 0; i < ncols; i++)
-        if (cols[i].length != n) return fail(BOWGPU_ERR_ARG, "column %d has %lld rows, interval column has %lld", i, (long long)cols[i].length, (long long)n);
+    if (need_mask(aggs, naggs) & kNeedMode)
+        return fail(BOWGPU_ERR_TS_NULLS, "interval column has %lld nulls: Mode over it is outside the device path", (long long)dts.null_count);
+    BG_TRY(check_row_counts(cols, ncols, ts_col));
     if (long_windows) *long_windows = 0;
     if (kernel_ms) *kernel_ms = 0;
     int last_valid = 1;
@@ -1626,7 +1640,8 @@ static int run_aggregate_null_ts(Ctx *c, const bowgpu_col *cols, int32_t ncols, 
     // the ordinary path, into device temporaries
     DevFrame tmp;
     BG_TRY(tmp.alloc(c, naggs, W, false));
-    BG_TRY(run_aggregate(c, cols2.data(), (int32_t)cols2.size(), ts_col, plan, inclusive, aggs2.data(), naggs, tmp.outs.data(), 0, W, long_windows, kernel_ms));
+    const AggCall dense = {cols2.data(), (int32_t)cols2.size(), ts_col, plan, inclusive, call.strict, call.check_plan};
+    BG_TRY(run_aggregate(c, dense, aggs2.data(), naggs, tmp.outs.data(), long_windows, kernel_ms));
     for (int i = 0; i < naggs; i++)
         if (aggs[i].kind == BOWGPU_AGG_NUM_ROWS) {
             BG_TRY(launch_count_to_f64(c, tmp.values[i].as<uint64_t>(), W));
@@ -1666,45 +1681,34 @@ static int run_aggregate_null_ts(Ctx *c, const bowgpu_col *cols, int32_t ncols, 
 // An unsharded Aggregate call: the streaming reducers in batches that one launch of the tile kernels takes (at most kMaxAggs
 // outputs over at most kMaxCols column passes - the reference has no such limits, aggregation.go:190-238 simply loops), then the
 // Mode outputs.
-static int run_aggregate(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t ts_col, const Plan &plan,
-                         int inclusive, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs,
-                         int64_t wid_base, int64_t W, int64_t *long_windows, double *kernel_ms) {
-    int n_mode = 0;
-    for (int i = 0; i < naggs; i++) n_mode += aggs[i].kind == BOWGPU_AGG_MODE;
-    if (n_mode > 0 && (wid_base != 0 || W != plan.W)) return fail(BOWGPU_ERR_UNSUPPORTED, "Mode runs on unsharded calls only");
-    if (wid_base == 0 && W == plan.W && cols[ts_col].validity && cols[ts_col].null_count != 0 && cols[ts_col].length > 0) {
+static int run_aggregate(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs, int64_t *long_windows, double *kernel_ms) {
+    const bowgpu_col &tsc = call.cols[call.ts_col];
+    const int64_t W = call.plan.W;
+    if (tsc.validity && tsc.null_count != 0 && tsc.length > 0) {
         DevCol dts;   // (values + validity on the device; counts the nulls when the caller did not)
-        BG_TRY(devcol_prepare(c, &cols[ts_col], &dts, true, true));
-        if (dts.null_count > 0) return run_aggregate_null_ts(c, cols, ncols, ts_col, plan, inclusive, aggs, naggs, outs, dts, long_windows, kernel_ms);
+        BG_TRY(devcol_prepare(c, &tsc, &dts, true, true));
+        if (dts.null_count > 0) return run_aggregate_null_ts(c, call, aggs, naggs, outs, dts, long_windows, kernel_ms);
     }
     if (long_windows) *long_windows = 0;
     if (kernel_ms) *kernel_ms = 0;
-    // greedy batches in output order; the column-pass count follows job_build's rule (a pass serves at most 4 nullable reducers)
+    // greedy batches in output order; ColSlots counts the column passes as job_build will
     std::vector<std::vector<int>> batches;
     {
-        std::vector<int> cur, slot_of(ncols, -1), nullable_in_slot;
+        std::vector<int> cur;
+        ColSlots slots(call.ncols);
         auto flush = [&]() {
             if (!cur.empty()) batches.push_back(cur);
-            cur.clear(); nullable_in_slot.clear();
-            std::fill(slot_of.begin(), slot_of.end(), -1);
+            cur.clear();
+            slots.clear();
         };
         for (int i = 0; i < naggs; i++) {
             if (aggs[i].kind == BOWGPU_AGG_MODE) continue;
+            const bool reads = kind_reads_values(aggs[i].kind);
             for (int attempt = 0; attempt < 2; attempt++) {
                 bool fits = (int)cur.size() < kMaxAggs;
-                int s = -1;
-                bool new_slot = false;
-                const bool reads = kind_reads_values(aggs[i].kind), nullable = !kind_never_nil(aggs[i].kind);
-                if (fits && reads) {
-                    s = slot_of[aggs[i].col];
-                    if (s >= 0 && nullable && nullable_in_slot[s] >= 4) s = -1;
-                    if (s < 0) { new_slot = true; fits = (int)nullable_in_slot.size() < kMaxCols; }
-                }
+                if (fits && reads && slots.find(aggs[i], 4) < 0) fits = slots.count() < kMaxCols;
                 if (!fits) { flush(); continue; }  // (an empty batch always takes one reducer)
-                if (reads) {
-                    if (new_slot) { s = (int)nullable_in_slot.size(); nullable_in_slot.push_back(0); slot_of[aggs[i].col] = s; }
-                    if (nullable) nullable_in_slot[s]++;
-                }
+                if (reads) slots.take(aggs[i], 4);
                 cur.push_back(i);
                 break;
             }
@@ -1714,8 +1718,8 @@ static int run_aggregate(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t 
     for (const std::vector<int> &at : batches) {
         if ((int)at.size() == naggs) {  // the usual case: the whole call in one launch
             AggJob job;
-            BG_TRY(job_build(c, cols, ncols, ts_col, plan, inclusive, aggs, naggs, outs, wid_base, W, wid_base == 0, &job));
-            BG_TRY(job_run(c, &job, aggs, naggs, long_windows, kernel_ms, true, &plan, true));
+            BG_TRY(job_build(c, call, aggs, naggs, outs, 0, W, true, &job));
+            BG_TRY(job_run(c, &job, long_windows, kernel_ms, true, true));
             continue;
         }
         std::vector<bowgpu_agg> part;
@@ -1724,13 +1728,13 @@ static int run_aggregate(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t 
         int64_t lw = 0;
         double ms = 0;
         AggJob job;
-        BG_TRY(job_build(c, cols, ncols, ts_col, plan, inclusive, part.data(), (int32_t)part.size(), part_outs.data(), wid_base, W, wid_base == 0, &job));
-        BG_TRY(job_run(c, &job, part.data(), (int32_t)part.size(), &lw, &ms, true, &plan, true));
+        BG_TRY(job_build(c, call, part.data(), (int32_t)part.size(), part_outs.data(), 0, W, true, &job));
+        BG_TRY(job_run(c, &job, &lw, &ms, true, true));
         for (size_t j = 0; j < at.size(); j++) outs[at[j]] = part_outs[j];
         if (long_windows && lw > *long_windows) *long_windows = lw;   // (the same windows in every batch)
         if (kernel_ms) *kernel_ms += ms;
     }
-    if (n_mode > 0) return run_modes(c, cols, ncols, ts_col, plan, aggs, naggs, outs, inclusive, long_windows);
+    if (need_mask(aggs, naggs) & kNeedMode) return run_modes(c, call, aggs, naggs, outs, long_windows);
     return 0;
 }
 
@@ -1747,43 +1751,40 @@ static int fused_try(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t ts_c
     if (route_mask() & (BOWGPU_ROUTE_NO_FUSED | BOWGPU_ROUTE_NO_SIMPLE | BOWGPU_ROUTE_FORCE_GENERAL)) return 0;
     if (n <= 0 || W <= 0 || inclusive || o.inclusive || naggs > kSimpleMaxAggs) return 0;
     if (tsc->validity && tsc->null_count != 0) return 0;                      // (an interval column with nulls: extras.cpp interp_null_ts)
-    const int64_t lim53 = 1ll << 53;
-    if (plan.first_ts < plan.s0 || plan.last_ts >= lim53 || plan.s0 <= -lim53) return 0;   // rows below s0; float64(ts) inexact
+    if (plan.first_ts < plan.s0 || plan.s0 <= -(1ll << 53)) return 0;   // rows below s0; float64(ts) inexact
     // a window that starts at -1, the reference's "no first value" sentinel (interpolation.go:99-105): such a window never gets a synthetic row
     if (plan.s0 <= -1 && (uint64_t)(-1 - plan.s0) % (uint64_t)plan.interval == 0 && (int64_t)((uint64_t)(-1 - plan.s0) / (uint64_t)plan.interval) < W) return 0;
-    if (((uint64_t)plan.interval >> 32) != 0 || (uint64_t)plan.last_ts - (uint64_t)plan.s0 >= 0xFFFFFFF0ull || W >= 0xFFFFFFF0ll) return 0;
+    if (((uint64_t)plan.interval >> 32) != 0 || !ids_and_times_fit(plan, plan.s0, W)) return 0;
     if (n / W < 4 || n / W > 128) return 0;
     for (int i = 0; i < ncols; i++) {
         const int k = interps[i].kind;
         if (k != BOWGPU_INTERP_WINDOW_START && k != BOWGPU_INTERP_LINEAR && k != BOWGPU_INTERP_STEP_PREVIOUS && k != BOWGPU_INTERP_NONE) return 0;
     }
     if (interps[ts_col].kind != BOWGPU_INTERP_WINDOW_START) return 0;           // anything else does not keep the window grid
+    if (need_mask(aggs, naggs) & (kNeedTimeWeighted | kNeedMode)) return 0;
     {
         std::vector<int> used(ncols, 0);
         int distinct = 0;
-        for (int i = 0; i < naggs; i++) {
-            const int k = aggs[i].kind;
-            if ((k >= BOWGPU_AGG_INTEGRAL_STEP && k <= BOWGPU_AGG_WAVG_LINEAR) || k == BOWGPU_AGG_MODE) return 0;
-            if (kind_reads_values(k) && !used[aggs[i].col]++) distinct++;
-        }
+        for (int i = 0; i < naggs; i++)
+            if (kind_reads_values(aggs[i].kind) && !used[aggs[i].col]++) distinct++;
         if (distinct > kMaxCols) return 0;
     }
     AggJob job;
-    BG_TRY(job_build(c, cols, ncols, ts_col, plan, 0, aggs, naggs, outs, 0, W, true, &job, kMaxAggs));   // (one pass per column whatever its reducers)
+    const AggCall call = {cols, ncols, ts_col, plan, 0, false, false};
+    BG_TRY(job_build(c, call, aggs, naggs, outs, 0, W, true, &job, kMaxAggs));   // (one pass per column whatever its reducers)
     AggParams &P = job.P;
-    int need = 0;
     bool is_int = false, has_nulls = false, wide = false;
-    if (P.pre_rows || !simple_applies(&job, aggs, naggs, plan, false, &need, &is_int, &has_nulls, &wide) || wide) return 0;
+    if (P.pre_rows || !simple_applies(&job, false, &is_int, &has_nulls, &wide) || wide) return 0;
     P.bits_preset = 1;
     {
         BitmapBatch b;
-        job_bitmaps(&job, aggs, naggs, true, &b);
+        job_bitmaps(&job, true, true, &b);
         BG_TRY(launch_preset_bitmaps(c, b));
         job.counts_used = false;
     }
     FusedParams F;
     memset(&F, 0, sizeof F);
-    simple_params_build(&job, aggs, naggs, false, &F.s);
+    simple_params_build(&job, false, &F.s);
     for (int s = 0; s < kMaxCols; s++) { F.cols[s].kind = BOWGPU_INTERP_NONE; F.cols[s].type = BOWGPU_INT64; }
     for (int i = 0; i < naggs; i++) {
         if (!kind_reads_values(aggs[i].kind) || P.aggs[i].slot < 0) continue;
@@ -1795,31 +1796,22 @@ static int fused_try(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t ts_c
     }
     F.inv_interval = (1.0 / (double)plan.interval) * (1.0 + 0x1.0p-40);
     BG_HIP(hipEventRecord(c->ev0, c->stream));
-    BG_TRY(launch_rolling_fused(c, F, need, has_nulls));
+    BG_TRY(launch_rolling_fused(c, F, simple_launch_need(job.need), has_nulls));
     BG_HIP(hipEventRecord(c->ev1, c->stream));
     uint32_t *hstat;
     uint64_t *hcnt = nullptr;
-    BG_TRY(job_enqueue_tail(c, &job, aggs, naggs));
-    BG_TRY(job_readback(c, &job, &hstat, &hcnt));
-    BG_HIP(hipStreamSynchronize(c->stream));
-    if (hstat[0]) return fail(BOWGPU_ERR_TS_UNSORTED, "interval column is not ascending: outside the device path");
-    if (hstat[4] || hstat[5]) return 0;   // a tile the fused kernel cannot describe (too many heads, a long window, a far neighbour point)
-    for (int i = 0; i < naggs; i++)
-        job.douts[i].user->null_count = !kind_never_nil(aggs[i].kind) ? W - (int64_t)hcnt[i] : 0;
-    float ms = 0;
-    BG_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    c->last_kernel_ms = ms;
-    if (kernel_ms) *kernel_ms = ms;
+    BG_TRY(job_settle(c, &job, true, &hstat, &hcnt));
+    BG_TRY(agg_status_error(hstat, kLookUnsorted));
+    if (hstat[kAggStRedo] || hstat[kAggStFusedDeclines]) return 0;   // a tile the fused kernel cannot describe (too many heads, a long window, a far neighbour point)
+    job_null_counts(&job, hcnt);
     *done = true;
-    return 0;
+    return job_report_ms(c, true, kernel_ms);
 }
 
 // ---- the pass of a sharded call put in flight BEFORE the exchange (bowgpu_shard_pass_begin): one per thread
 struct PendingPass {
-    AggJob job;
-    Plan plan;
+    AggJob job;   // (with its copies of the aggregations and of the plan)
     PassState ps;
-    std::vector<bowgpu_agg> aggs;
     std::vector<const void *> col_values, out_values;
     int64_t n = 0, interval = 0, raw_offset = 0, base = 0;
     int32_t ts_col = 0, inclusive = 0;
@@ -2097,14 +2089,18 @@ int bowgpu_plan_windows(const bowgpu_col *ts, int64_t interval, int64_t offset, 
     return 0;
 }
 
-static int aggregate_with_plan(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, const Plan &plan, int opt_inclusive,
+static bool strict_wanted(const bowgpu_options *o) { return (o && o->strict_order) || (route_mask() & BOWGPU_ROUTE_STRICT_ORDER); }
+
+static int aggregate_with_plan(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, const Plan &plan, const bowgpu_options *opts, bool check_plan,
                                const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs, bowgpu_agg_info *info) {
+    const int opt_inclusive = opts ? opts->inclusive : 0;
+    const bool strict = strict_wanted(opts);
     int inclusive = opt_inclusive ? 1 : 0, nic = -1;
     BG_TRY(validate_aggs(cols, ncols, ts_col, aggs, naggs, &inclusive, &nic));
     if (!outs) return fail(BOWGPU_ERR_ARG, "no output columns");
     {   // bowgpu_set_devices: the call cut into row ranges over the listed devices (multi.cpp); not taken -> the one-device path below
         bool fanned = false;
-        BG_TRY(multi_aggregate(cols, ncols, ts_col, plan, opt_inclusive, g_strict_order, aggs, naggs, outs, info, &fanned));
+        BG_TRY(multi_aggregate(cols, ncols, ts_col, plan, opt_inclusive, strict, aggs, naggs, outs, info, &fanned));
         if (fanned) return 0;
     }
     Ctx *c;
@@ -2114,7 +2110,8 @@ static int aggregate_with_plan(const bowgpu_col *cols, int32_t ncols, int32_t ts
     double ms = 0;
     static const bool prof = [] { const char *e = getenv("BOWGPU_CALL_PROFILE"); return e && e[0] == '1'; }();
     const double t_in = prof ? now_us() : 0;
-    BG_TRY(run_aggregate(c, cols, ncols, ts_col, plan, inclusive, aggs, naggs, outs, 0, plan.W, &n_long, &ms));
+    const AggCall call = {cols, ncols, ts_col, plan, inclusive, strict, check_plan};
+    BG_TRY(run_aggregate(c, call, aggs, naggs, outs, &n_long, &ms));
     if (prof) {
         static thread_local double acc[3] = {0, 0, 0};
         static thread_local int calls = 0;
@@ -2149,10 +2146,7 @@ int bowgpu_rolling_aggregate(const bowgpu_col *cols, int32_t ncols, int32_t ts_c
     // reference order: the Rolling exists first (newIntervalRolling errors), then Aggregate validates
     Plan plan;
     BG_TRY(plan_make(nullptr, &cols[ts_col], interval, o.offset, &plan));
-    g_strict_order = o.strict_order != 0 || (route_mask() & BOWGPU_ROUTE_STRICT_ORDER) != 0;
-    const int rc = aggregate_with_plan(cols, ncols, ts_col, plan, o.inclusive, aggs, naggs, outs, info);
-    g_strict_order = false;
-    return rc;
+    return aggregate_with_plan(cols, ncols, ts_col, plan, &o, false, aggs, naggs, outs, info);
 }
 
 /* Rolling.Interpolate(interps...) followed by Rolling.Aggregate(aggs...) on the Rolling it returns (reference
@@ -2176,7 +2170,7 @@ int bowgpu_rolling_interpolate_aggregate(const bowgpu_col *cols, int32_t ncols, 
     if (!outs) return fail(BOWGPU_ERR_ARG, "no output columns");
     {   // bowgpu_set_devices: every rank interpolates and aggregates its own row range (multi.cpp); not taken -> one device, below
         bool fanned = false;
-        BG_TRY(multi_interpolate_aggregate(cols, ncols, ts_col, plan, o.inclusive, o.strict_order != 0 || (route_mask() & BOWGPU_ROUTE_STRICT_ORDER) != 0, interps, ninterps, aggs, naggs, outs, info, &fanned));
+        BG_TRY(multi_interpolate_aggregate(cols, ncols, ts_col, plan, o.inclusive, strict_wanted(&o), interps, ninterps, aggs, naggs, outs, info, &fanned));
         if (fanned) return 0;
     }
     Ctx *c;
@@ -2237,12 +2231,7 @@ int bowgpu_rolling_aggregate_planned(const bowgpu_col *cols, int32_t ncols, int3
     plan.interval = pl->interval; plan.offset = pl->offset; plan.s0 = pl->s0; plan.W = pl->num_windows;
     plan.first_ts = pl->first_ts; plan.last_ts = pl->last_ts;
     plan.magic = magic_make((uint64_t)pl->interval);
-    g_plan_from_caller = ts->length > 0;
-    g_strict_order = (opts && opts->strict_order != 0) || (route_mask() & BOWGPU_ROUTE_STRICT_ORDER) != 0;
-    const int rc = aggregate_with_plan(cols, ncols, ts_col, plan, opts ? opts->inclusive : 0, aggs, naggs, outs, info);
-    g_plan_from_caller = false;
-    g_strict_order = false;
-    return rc;
+    return aggregate_with_plan(cols, ncols, ts_col, plan, opts, ts->length > 0, aggs, naggs, outs, info);
 }
 
 // ---- entry points implemented in extras.cpp: window_bounds, aggregate_whole, interpolate,
@@ -2251,8 +2240,6 @@ int bowgpu_rolling_aggregate_planned(const bowgpu_col *cols, int32_t ncols, int3
 
 // ---- row-range sharding: the shard protocol, begin -> one exchange -> finish ---------------------------------------------
 
-static bool strict_wanted(const bowgpu_options *o) { return (o && o->strict_order) || (route_mask() & BOWGPU_ROUTE_STRICT_ORDER); }
-struct StrictScope { bool was; explicit StrictScope(bool on) : was(g_strict_order) { g_strict_order = on; } ~StrictScope() { g_strict_order = was; } };
 // what a window cut by a shard boundary needs on top of validate_aggs: a constant-size running state per reducer (Mode has none)
 // and room for it in the record.  Columns and outputs of any residency: host-resident ones are staged through HBM per call the way
 // the unsharded entry points stage them (the pass put in flight by _pass_begin keeps its staged copies until _finish collects it)
@@ -2416,14 +2403,15 @@ int bowgpu_shard_begin(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, in
         no_outs[i].length = 0; no_outs[i].residency = BOWGPU_DEVICE;
     }
     AggJob job;
-    BG_TRY(job_build(c, cols, ncols, ts_col, plan, 0, aggs, naggs, no_outs.data(), wl, 0, false, &job));
-    bowgpu_carry_state *dst = reinterpret_cast<bowgpu_carry_state *>(dummy);
     const bool strict = strict_wanted(&o);
+    const AggCall call = {cols, ncols, ts_col, plan, 0, strict, false};
+    BG_TRY(job_build(c, call, aggs, naggs, no_outs.data(), wl, 0, false, &job));
+    bowgpu_carry_state *dst = reinterpret_cast<bowgpu_carry_state *>(dummy);
     uint32_t far = 0;
-    if (strict) BG_HIP(hipMemsetAsync(job.P.status + 7, 0, 4, c->stream));
+    if (strict) BG_HIP(hipMemsetAsync(job.P.status + kAggStStrictTooLong, 0, 4, c->stream));
     BG_TRY(launch_range_state(c, job.P, 0, (uint64_t)wl, nullptr, dst, nullptr, 1, strict ? 1 : 0));
     BG_HIP(hipMemcpyAsync(rec->last, dst, sizeof(bowgpu_carry_state) * naggs, hipMemcpyDeviceToHost, c->stream));
-    if (strict) BG_HIP(hipMemcpyAsync(&far, job.P.status + 7, 4, hipMemcpyDeviceToHost, c->stream));
+    if (strict) BG_HIP(hipMemcpyAsync(&far, job.P.status + kAggStStrictTooLong, 4, hipMemcpyDeviceToHost, c->stream));
     BG_HIP(hipStreamSynchronize(c->stream));
     if (far) return fail(BOWGPU_ERR_UNSUPPORTED, "strict_order: the shard's last window holds more than 2^20 rows (one lane walks a window in row order: beyond that the call is declined)");
     return 0;
@@ -2446,7 +2434,6 @@ int bowgpu_shard_pass_begin(const bowgpu_col *cols, int32_t ncols, int32_t ts_co
     if (cols[ts_col].type != BOWGPU_INT64) return fail(BOWGPU_ERR_TS_TYPE, "impossible to create a new intervalRolling on column of type float64");
     if (me->nrows != cols[ts_col].length) return fail(BOWGPU_ERR_ARG, "the record says %lld rows, the interval column has %lld",
                                                       (long long)me->nrows, (long long)cols[ts_col].length);
-    StrictScope strict_scope(strict_wanted(&o));
     PendingOwnerScope owner;
     Ctx *c;
     BG_TRY(ctx_get(&c));
@@ -2456,7 +2443,7 @@ int bowgpu_shard_pass_begin(const bowgpu_col *cols, int32_t ncols, int32_t ts_co
     // a rank's rows (rolling.go:96-99) - that needs the records
     if (me->nrows == 0 || me->first_ts < 0 || me->last_ts < me->first_ts) return BOWGPU_SHARD_PASS_DECLINED;
     PendingPass *pp = new PendingPass();
-    Plan &plan = pp->plan;
+    Plan plan;
     plan.interval = interval;
     int rc = enforce_interval_and_offset(interval, o.offset, &plan.offset);
     int64_t base = 0;
@@ -2469,11 +2456,11 @@ int bowgpu_shard_pass_begin(const bowgpu_col *cols, int32_t ncols, int32_t ts_co
     plan.W = (int64_t)(((uint64_t)me->last_ts - (uint64_t)base) / (uint64_t)interval) + 1;
     pp->base = base;
     pp->n = me->nrows; pp->interval = interval; pp->raw_offset = o.offset; pp->ts_col = ts_col; pp->inclusive = inclusive;
-    pp->aggs.assign(aggs, aggs + naggs);
     for (int i = 0; i < ncols; i++) pp->col_values.push_back(reinterpret_cast<const char *>(cols[i].values) + 8 * cols[i].offset);
     for (int i = 0; i < naggs; i++) pp->out_values.push_back(outs[i].values);
-    rc = job_build(c, cols, ncols, ts_col, plan, inclusive, aggs, naggs, outs, 0, plan.W, false, &pp->job);
-    if (rc == 0) rc = job_pass_enqueue(c, &pp->job, aggs, naggs, &plan, false, &pp->ps);
+    const AggCall call = {cols, ncols, ts_col, plan, inclusive, strict_wanted(&o), false};
+    rc = job_build(c, call, aggs, naggs, outs, 0, plan.W, false, &pp->job);
+    if (rc == 0) rc = job_pass_enqueue(c, &pp->job, false, &pp->ps);
     if (rc != 0) { (void)hipStreamSynchronize(c->stream); delete pp; return rc; }
     g_pending = pp;
     return 0;
@@ -2555,7 +2542,6 @@ int bowgpu_shard_finish(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, i
     BG_TRY(validate_aggs(cols, ncols, ts_col, aggs, naggs, &inclusive, &nic));
     BG_TRY(shard_check(aggs, naggs));
     const bool strict = strict_wanted(&o);
-    StrictScope strict_scope(strict);
     bowgpu_shard_decision d;
     BG_TRY(bowgpu_shard_plan(recs, world, rank, interval, o.offset, &d));
     if (decision) *decision = d;
@@ -2595,16 +2581,17 @@ int bowgpu_shard_finish(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, i
     if (g_pending) {
         PendingPass *pp = g_pending;
         bool same = pp->n == me.nrows && pp->interval == interval && pp->raw_offset == o.offset && pp->ts_col == ts_col &&
-                    pp->inclusive == inclusive && (int32_t)pp->aggs.size() == naggs && (int32_t)pp->col_values.size() == ncols &&
-                    memcmp(pp->aggs.data(), aggs, sizeof(bowgpu_agg) * (size_t)naggs) == 0;
+                    pp->inclusive == inclusive && pp->job.naggs == naggs && (int32_t)pp->col_values.size() == ncols &&
+                    memcmp(pp->job.aggs, aggs, sizeof(bowgpu_agg) * (size_t)naggs) == 0;
         for (int i = 0; same && i < ncols; i++) same = pp->col_values[i] == reinterpret_cast<const char *>(cols[i].values) + 8 * cols[i].offset;
         for (int i = 0; same && i < naggs; i++) same = pp->out_values[i] == outs[i].values;
-        const bool holds = same && wf >= 0 && lead == 0 && !pre_rows_here && pp->plan.W == plan.W &&
+        const bool holds = same && wf >= 0 && lead == 0 && !pre_rows_here && pp->job.plan.W == plan.W &&
                            pp->base == (int64_t)((uint64_t)d.s0 + (uint64_t)wf * (uint64_t)interval);
         if (holds) {
             g_pending = nullptr;
-            job = std::move(pp->job);
-            const int rc = job_pass_complete(c, &job, aggs, naggs, &pp->plan, false, &pp->ps, &n_long, &ms);
+            job = std::move(pp->job);   // (it owns copies of the aggregations and of the plan it was built with: nothing of *pp is referred to)
+            job.strict = strict;        // (this call's options decide how the pass is completed)
+            const int rc = job_pass_complete(c, &job, false, &pp->ps, &n_long, &ms);
             delete pp;
             if (rc != 0) return rc;
             // from the pass's local numbering (slot 0 starts at base) to the frame's: the stitch below speaks global window ids
@@ -2617,8 +2604,9 @@ int bowgpu_shard_finish(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, i
         }
     }
     if (!collected) {
-        BG_TRY(job_build(c, cols, ncols, ts_col, plan, inclusive, aggs, naggs, outs, wf < 0 ? 0 : wf - lead, Wtot, pre_rows_here, &job));
-        BG_TRY(job_run(c, &job, aggs, naggs, &n_long, &ms, false, &plan));
+        const AggCall call = {cols, ncols, ts_col, plan, inclusive, strict, false};
+        BG_TRY(job_build(c, call, aggs, naggs, outs, wf < 0 ? 0 : wf - lead, Wtot, pre_rows_here, &job));
+        BG_TRY(job_run(c, &job, &n_long, &ms, false));
     }
     if (lead > 0) BG_TRY(launch_fill_empty(c, job.P, 0, lead));
     if (plan.W > 0) {
@@ -2667,9 +2655,7 @@ int bowgpu_shard_finish(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, i
             BG_TRY(launch_range_state(c, job.P, 1, (uint64_t)wf, dseed, nullptr, also_last ? dnext : nullptr, seed_alive, strict ? 1 : 0));
         }
     }
-    uint32_t too_long = 0;
-    BG_TRY(job_finish(c, &job, aggs, naggs, strict ? &too_long : nullptr));
-    if (too_long) return fail(BOWGPU_ERR_UNSUPPORTED, "strict_order: some window holds more than 2^20 rows (one lane walks a window in row order: beyond that the call is declined)");
+    BG_TRY(job_finish(c, &job, strict));
     if (info) { info->long_windows = n_long; info->kernel_ms = ms; }
     return 0;
 }

@@ -16,6 +16,7 @@ namespace bowgpu {
 // ---------------------------------------------------------------- errors
 void set_error(const char *fmt, ...);
 int fail(int code, const char *fmt, ...);
+int fail_ts_unsorted();   // BOWGPU_ERR_TS_UNSORTED: what every device path says about an interval column that is not ascending (api.cpp)
 int hip_fail(hipError_t e, const char *what);
 
 #define BG_HIP(expr)                                         \
@@ -344,7 +345,7 @@ struct AggParams {
     int32_t first_pass_slot, last_val_slot, n_nullable_max;
     int32_t bits_preset;    // output bitmaps start as all-ones (rolling_simple.hip): the long-window path clears empties instead of setting valids
     // status block in device memory
-    uint32_t *status;       // [0]=unsorted flag, [1]=long-window count, [2]=overflow flag
+    uint32_t *status;       // kAggSt* words, [kLongCountWord ..) the long-window counts
     int64_t *long_list;     // kLongLists sub-lists of pairs (global window id, first row), long_cap pairs each
     int64_t long_cap;
 };
@@ -377,7 +378,7 @@ struct SimpleParams {
     double fac[kSimpleMaxAggs][BOWGPU_MAX_FACTORS];
     uint64_t *out_values[kSimpleMaxAggs];
     uint32_t *out_valid[kSimpleMaxAggs];   // nullptr for never-nil reducers; all bitmaps are preset to ones by the host
-    uint32_t *status;         // [0] unsorted, [2] list overflow, [4] redo with the general lean kernel, [16..79] long-window counts
+    uint32_t *status;         // kAggSt* words, [kLongCountWord ..) the long-window counts
     int64_t *long_list;
     int64_t long_cap;
 };
@@ -418,6 +419,16 @@ constexpr int64_t kLongClassicAvgRows = 1ll << 22;   // ... and from here on the
 constexpr int kLongLists = 64;      // sub-lists of the long-window queue (agg_device.h push_long_window)
 constexpr int kLongCountWord = 16;  // status[kLongCountWord + s] = entries in sub-list s
 constexpr int kStatusWords = kLongCountWord + kLongLists;
+// the words below kLongCountWord that the Aggregate kernels raise and api.cpp agg_status_error reads (Interpolate keeps a status block
+// of its own whose words 5 - 7 mean other things: interpolate.hip, extras.cpp).  rolling_agg.hip, rolling_fast.hip and shard.hip spell
+// them by name; the wave-tile kernels, long_windows.hip and agg_device.h still write the numbers (an edit to those files asks for the
+// round's counter files again: tests/test_profiles_fresh.py)
+constexpr int kAggStUnsorted = 0;        // the interval column is not ascending
+constexpr int kAggStListOverflow = 2;    // the long-window list overflowed (agg_device.h push_long_window)
+constexpr int kAggStRedo = 4;            // some tile is beyond what the wave-tile kernel that ran can describe: the call is redone (api.cpp job_pass_complete)
+constexpr int kAggStFusedDeclines = 5;   // rolling_fused.hip: a far neighbour point - the call takes the two-call form
+constexpr int kAggStPlanMismatch = 6;    // the preset launch: a caller's plan was not made for this interval column
+constexpr int kAggStStrictTooLong = 7;   // strict_order: a window of more than 2^20 rows
 struct LongListStarts { int64_t start[kLongLists + 1]; };  // prefix sums of the sub-list counts (host side)
 size_t long_entry_size();
 size_t long_part_size();
@@ -448,7 +459,7 @@ struct BitmapBatch {
     char *host_block;              // finish, one workgroup per bitmap (nbits <= kFinishHostBits): registered host memory that receives the status
                                    // words [0, status_words) and, at byte 1024 + 8 a, bitmap a's count - by the kernel's own stores
     const int64_t *check_ts;       // preset: a caller-supplied plan is checked against this interval column (nullptr: no check);
-    int64_t check_n, check_first, check_last;   // status[6] = 1 when its first / last row are not the plan's two timestamps
+    int64_t check_n, check_first, check_last;   // status[kAggStPlanMismatch] = 1 when its first / last row are not the plan's two timestamps
 };
 constexpr int64_t kFinishHostBits = 262144;   // up to here ONE workgroup finishes a bitmap (32 KB: a microsecond) and can hand its count to the host itself
 int launch_preset_bitmaps(Ctx *c, const BitmapBatch &b);
@@ -592,7 +603,7 @@ struct InterpParams {
 int64_t interp_tiles(int64_t n);
 bool interp_fast32(const Plan &plan, int64_t kq);
 bool interp_wide32(const Plan &plan, int64_t kq);   // ... without the bound on the frame's span: 32-bit arithmetic relative to each trip
-void interp_magic32(int64_t interval, uint32_t *m, uint32_t *sh1, uint32_t *sh2);
+void interp_magic32(int64_t interval, uint32_t *m, uint32_t *sh1, uint32_t *sh2);   // the 32-bit magic divisor of an interval < 2^32 (also api.cpp: job_build, simple_params_build)
 constexpr int kInterpSuperRows = 8192;
 constexpr int kInterpEdgeBlocks = 128;   // interp_edge_fix_kernel: workgroups (= partial valid-output counts) per column
 int64_t interp_supers(int64_t n);

@@ -88,7 +88,7 @@ int bowgpu_window_bounds(const bowgpu_col *ts, int64_t interval, const bowgpu_op
         if (is_inclusive) BG_TRY(copy_d2h(c, is_inclusive, pin, (size_t)W));
     }
     BG_HIP(hipStreamSynchronize(c->stream));
-    if (hstat[0]) return fail(BOWGPU_ERR_TS_UNSORTED, "interval column is not ascending: outside the device path");
+    if (hstat[0]) return fail_ts_unsorted();
     return 0;
 }
 
@@ -246,7 +246,7 @@ static int interp_prepare(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t
     BG_HIP(hipStreamSynchronize(c->stream));
     const uint32_t hstat[4] = {(uint32_t)(uint64_t)hback[1], (uint32_t)((uint64_t)hback[1] >> 32), (uint32_t)(uint64_t)hback[2], (uint32_t)((uint64_t)hback[2] >> 32)};
     const int64_t total = hback[0];
-    if (hstat[0]) return fail(BOWGPU_ERR_TS_UNSORTED, "interval column is not ascending: outside the device path");
+    if (hstat[0]) return fail_ts_unsorted();
     job->drop = (int64_t)(((uint64_t)hstat[3] << 32) | hstat[2]);
     job->kq_empty = hstat[1] ? 1 : 0;
     if (o->inclusive) {
@@ -484,7 +484,7 @@ static int interp_fill_impl(const bowgpu_col *cols, int32_t ncols, int32_t ts_co
     // An interval column out of order comes FIRST: a one-pass call derives its row count from the first and the last timestamp alone,
     // so on an unsorted column most trips also fail the "fits the counted range" test below - and the documented answer for such a
     // column is the decline (BOWGPU_ERR_TS_UNSORTED: the caller keeps the reference's own path), not an argument error.
-    if (hstat[0]) return fail(BOWGPU_ERR_TS_UNSORTED, "interval column is not ascending: outside the device path");
+    if (hstat[0]) return fail_ts_unsorted();
     // (a reused count whose column has changed since: interp_wave3_kernel stored nothing for the trips that did not fit and said
     // so; the kernels a redo would use do not check, so the error comes first)
     if (hstat[6]) return fail(BOWGPU_ERR_ARG, "Interpolate: the rows produced do not add up to the count - the interval column changed between "
@@ -506,7 +506,7 @@ static int interp_fill_impl(const bowgpu_col *cols, int32_t ncols, int32_t ts_co
         return fail(BOWGPU_ERR_UNSUPPORTED, "Interpolate on inclusive windows: a 512-row trip that spans 2^31 or more, or holds a gap of "
                                             "millions of empty windows, is outside the device path");
     if (hstat[5]) BG_TRY(run_all(0, true));
-    if (hstat[0]) return fail(BOWGPU_ERR_TS_UNSORTED, "interval column is not ascending: outside the device path");
+    if (hstat[0]) return fail_ts_unsorted();
     for (int i = 0; i < ninterps; i++) BG_TRY(devout_finish(c, &douts[i], n_out, cols[i].type, n_out - (int64_t)hcnt[i], false));
     BG_HIP(hipStreamSynchronize(c->stream));
     return 0;

@@ -141,7 +141,7 @@ __global__ __launch_bounds__(kBlock) void rolling_agg_kernel(const AggParams p, 
         }
     }
     if (tid == 0) { sh.wid0 = wid_a[0]; sh.gap_n = 0; }
-    if (unsorted) atomicOr(&p.status[0], 1u);
+    if (unsorted) atomicOr(&p.status[kAggStUnsorted], 1u);
     __syncthreads();
 
     const uint64_t wid0 = sh.wid0;
@@ -455,10 +455,10 @@ int launch_rolling_aggregate(Ctx *c, const AggParams &p) {
 __global__ __launch_bounds__(256) void preset_bitmaps_kernel(const BitmapBatch b) {
     const int a = blockIdx.y;
     if (a == 0 && blockIdx.x == 0) {
-        // (status[6], thread 6: a caller-supplied plan - bowgpu_rolling_aggregate_planned - against the column it is used on: the two
+        // (status[kAggStPlanMismatch]: a caller-supplied plan - bowgpu_rolling_aggregate_planned - against the column it is used on: the two
         // timestamps it was made from are the column's first and last row, or the call fails instead of taking wrong routes)
         for (int i = threadIdx.x; i < b.status_words; i += blockDim.x)
-            b.status[i] = (i == 6 && b.check_ts && b.check_n > 0 && (b.check_ts[0] != b.check_first || b.check_ts[b.check_n - 1] != b.check_last)) ? 1u : 0u;
+            b.status[i] = (i == kAggStPlanMismatch && b.check_ts && b.check_n > 0 && (b.check_ts[0] != b.check_first || b.check_ts[b.check_n - 1] != b.check_last)) ? 1u : 0u;
         if (threadIdx.x < kMaxAggs) b.counts[threadIdx.x] = 0ull;
     }
     if (a >= b.n) return;

@@ -284,7 +284,7 @@ __global__ __launch_bounds__(kWave, kPersist ? 4 : 5) void rolling_wave_kernel(c
         if (j == kChunksW - 2) nseg_owned = nseg_total;  // heads inside the 512 owned rows
         left_ts = (int64_t)readlane64(tb[j], 63);         // last row of this chunk = left neighbour of the next
     }
-    if (unsorted) atomicOr(&p.status[0], 1u);
+    if (unsorted) atomicOr(&p.status[kAggStUnsorted], 1u);
     if (prefetch_next) load_ts(next_tile, true);  // this tile's ts registers are dead
 
     const bool reaches_end = base + kRowsW >= n;

@@ -46,7 +46,7 @@ constexpr int kSeqLimit = 8192;  // longer ranges are merged from 256 contiguous
 // empty slice unless one of its rows reaches s0 or it takes an inclusive row (rolling.go:194-228: lastRowIndex stays -1) - the
 // "dead window 0" rule of the tile kernels, here for the window as stitched across shards.
 // strict: bowgpu_options.strict_order - the rows are walked by ONE lane in row order whatever their number (the 256 contiguous partials
-// of a long range change the order of a Sum's additions); a range of more than 2^20 rows raises status[7] and is left alone (the
+// of a long range change the order of a Sum's additions); a range of more than 2^20 rows raises status[kAggStStrictTooLong] and is left alone (the
 // stated limit of strict_order: api.cpp turns it into BOWGPU_ERR_UNSUPPORTED)
 __global__ __launch_bounds__(256) void range_state_kernel(const AggParams p, const int mode, const uint64_t wid,
                                                           const bowgpu_carry_state *seeds,
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void range_state_kernel(const AggParams p, con
     const int64_t r0 = s_r0, r1 = s_r1;
     const int64_t len = r1 - r0;
     if (strict && len > (1ll << 20)) {
-        if (tid == 0) atomicOr(&p.status[7], 1u);
+        if (tid == 0) atomicOr(&p.status[kAggStStrictTooLong], 1u);
         return;
     }
     const int64_t win_start = p.s0 + (int64_t)(wid * (uint64_t)p.interval);
