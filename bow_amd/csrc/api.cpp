@@ -1611,6 +1611,7 @@ static int run_aggregate_null_ts(Ctx *c, const AggCall &call, const bowgpu_agg *
             }
             aggs2[i].kind = BOWGPU_AGG_COUNT;
             aggs2[i].col = rows_slot;
+            aggs2[i].n_factors = 0;      // (a Factor chain multiplies float64(NumRows): launch_count_to_f64 below applies it, not the Int64 Count)
             continue;
         }
         if (!kind_reads_values(kind)) continue;
@@ -1644,7 +1645,7 @@ static int run_aggregate_null_ts(Ctx *c, const AggCall &call, const bowgpu_agg *
     BG_TRY(run_aggregate(c, dense, aggs2.data(), naggs, tmp.outs.data(), long_windows, kernel_ms));
     for (int i = 0; i < naggs; i++)
         if (aggs[i].kind == BOWGPU_AGG_NUM_ROWS) {
-            BG_TRY(launch_count_to_f64(c, tmp.values[i].as<uint64_t>(), W));
+            BG_TRY(launch_count_to_f64(c, tmp.values[i].as<uint64_t>(), tmp.bits[i].as<const uint32_t>(), W, aggs[i].n_factors, aggs[i].factors));
             tmp.outs[i].type = BOWGPU_FLOAT64;
         }
     if (inclusive && any_linear) {

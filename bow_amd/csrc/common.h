@@ -494,7 +494,7 @@ struct QuirkFixAgg {
 struct QuirkFix { int32_t naggs, _pad; QuirkFixAgg a[8]; };
 int launch_ts_quirk_fix(Ctx *c, const int64_t *ts, const uint32_t *tbits, int64_t tbit0, int64_t n, const struct NbrIndex &ix, int64_t s0, int64_t interval,
                         const MagicDiv &magic, int64_t W, const QuirkFix &fx, unsigned long long *d_fixed);
-int launch_count_to_f64(Ctx *c, uint64_t *v, int64_t n);
+int launch_count_to_f64(Ctx *c, uint64_t *v, const uint32_t *valid, int64_t n, int n_factors, const double *factors);   // (valid: W bits; the factors go onto the float64)
 int fetch_valid(Ctx *c, const bowgpu_col *col, int64_t row, int *valid);   // (api.cpp) validity bit of one row of a column, wherever it lives
 // Rolling.Interpolate over an interval column with nulls: the kept rows compacted (ts_nulls.hip)
 constexpr int kMaxCompactCols = 16;

@@ -165,9 +165,11 @@ __device__ __forceinline__ void emit_window(const AggParams &p, int slot, const 
     const int64_t oslot = (int64_t)(w.wid - (uint64_t)p.wid_base);
     if ((uint64_t)oslot >= (uint64_t)p.W) return;
     // rebuild the reference's running state from the order-free partial
+    // (window 0 made only of rows below s0 is an empty slice in the reference, rolling.go:194-228: the streaming form merges its chunks'
+    // partials before it knows - entry_close - so they are left out here)
     Stats st;
     stats_init(st);
-    st.sum = acc.sum; st.count = acc.count; st.has_value = acc.first_idx >= 0;
+    if (!w.dead) { st.sum = acc.sum; st.count = acc.count; st.has_value = acc.first_idx >= 0; }
     if (st.has_value) {
         st.first_bits = vp[acc.first_idx]; st.last_bits = vp[acc.last_idx];
         const double f = bits_to_f64(st.first_bits, col_type);

@@ -148,10 +148,17 @@ __global__ __launch_bounds__(256) void ts_quirk_fix_kernel(const int64_t *__rest
 }
 
 // NumRows of a call over an interval column with nulls is counted as Count over the keep bits (Int64): float64(count) in place
-// (aggregation_test.go:28-31 returns float64(w.Bow.NumRows()))
-__global__ __launch_bounds__(256) void count_to_f64_kernel(uint64_t *__restrict__ v, const int64_t n) {
+// (aggregation_test.go:28-31 returns float64(w.Bow.NumRows())).  A Factor chain multiplies that float64: it is applied here, behind the
+// conversion, in the slots that hold a result - on the Int64 count it would truncate every product (3 rows * 0.5 = 1, 0 rows * -1 = 0
+// where the reference has 1.5 and -0) - and a nil slot keeps its zero.
+struct CountFactors { double f[BOWGPU_MAX_FACTORS]; };
+__global__ __launch_bounds__(256) void count_to_f64_kernel(uint64_t *__restrict__ v, const uint32_t *__restrict__ valid, const int64_t n,
+                                                           const int n_factors, const CountFactors fs) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) v[i] = (uint64_t)__double_as_longlong((double)(int64_t)v[i]);
+    if (i >= n) return;
+    uint64_t bits = (uint64_t)__double_as_longlong((double)(int64_t)v[i]);
+    if (n_factors && ((valid[i >> 5] >> (i & 31)) & 1u)) bits = apply_factors(bits, false, n_factors, fs.f);
+    v[i] = bits;
 }
 
 // out (bit 0 = row 0, whole 64-bit words) = a AND b; a / b: Arrow bitmaps at any bit offset, nullptr = all ones
@@ -284,9 +291,11 @@ int launch_ts_quirk_fix(Ctx *c, const int64_t *ts, const uint32_t *tbits, int64_
     return 0;
 }
 
-int launch_count_to_f64(Ctx *c, uint64_t *v, int64_t n) {
+int launch_count_to_f64(Ctx *c, uint64_t *v, const uint32_t *valid, int64_t n, int n_factors, const double *factors) {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(count_to_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, v, n);
+    CountFactors fs;
+    for (int k = 0; k < BOWGPU_MAX_FACTORS; k++) fs.f[k] = k < n_factors ? factors[k] : 1.0;
+    hipLaunchKernelGGL(count_to_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, v, valid, n, n_factors, fs);
     BG_HIP(hipGetLastError());
     return 0;
 }

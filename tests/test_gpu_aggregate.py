@@ -962,6 +962,45 @@ def test_null_timestamps_numrows_counts_the_rows_of_the_slice():
         compare("planned null ts %s" % k, g, w)
 
 
+def test_null_timestamps_numrows_under_a_factor_chain():
+    """found by tests/test_gpu_null_ts_fuzz.py (seed 0): over an interval column with nulls NumRows is counted as an Int64 Count over
+    the rows of the slices, and a Factor chain on it was applied to that integer - every product truncated - before the conversion to
+    float64: 3 rows * 0.5 came out as 1.0, an empty window * -1 as 0.0 where the reference has 1.5 and -0.0"""
+    ts = np.array([10, 11, 12, 20, 21, 40], dtype=np.int64)
+    vals = np.arange(1.0, 7.0)
+    tvalid = np.ones(len(ts), bool)
+    tvalid[1] = False           # between taken rows of [10, 20): inside the slice
+    aggs = [("WindowStart", 0), ("NumRows", 1, [0.5]), ("NumRows", 0, [-1.0]), ("NumRows", 1, [3.0, 0.1]), ("NumRows", 1), ("Count", 1, [0.5])]
+    for device in (False, True):
+        want = _run_null_ts(ts, tvalid, vals, None, 10, aggs=aggs, device=device)
+        assert want[1].to_list() == [1.5, 1.0, 0.0, 0.5] and want[4].to_list() == [3.0, 2.0, 0.0, 1.0]
+        assert want[2].to_list() == [-3.0, -2.0, 0.0, -1.0] and np.signbit(want[2].values[2])       # (the empty window [30, 40): -0.0)
+        assert want[5].to_list() == [1, 1, 0, 0]              # Count stays an Int64: int64(float64(count) * 0.5)
+
+
+@pytest.mark.parametrize("n", [300, 2947])
+def test_window_0_of_nothing_but_rows_below_the_first_window_start_when_it_is_long(n):
+    """found by tests/test_gpu_null_ts_fuzz.py (seeds 1 and 22, "all null but row 0 and the last"): a first timestamp below s0 (Go's
+    truncating division on a negative timestamp), the next valid one two windows on, null timestamps between - forward-filled, the
+    whole run rides below s0 in window 0, which is an empty slice in the reference (rolling.go:194-228: lastRowIndex stays -1).  The
+    streaming form of the long windows merged the chunks' partials of that window before it knew and gave row 0's value back:
+    Min / Sum / Count / First / Last of window 0 came out as row 0's instead of nil / 0 (at 2947 rows; 300 rows take another form).  The
+    frame the rewrite makes of it - n - 1 equal timestamps below s0, no nulls - goes through the ordinary path here too."""
+    aggs = [("WindowStart", 0), ("Min", 1), ("Count", 1), ("NumRows", 1), ("Sum", 1), ("Last", 1), ("ArithmeticMean", 1), ("IntegralStep", 1)]
+    vals = np.arange(1.0, n + 1.0)
+    ts = np.zeros(n, np.int64)
+    ts[0], ts[-1] = -376, 2570
+    tvalid = np.zeros(n, bool)
+    tvalid[0] = tvalid[-1] = True
+    for device in (False, True):
+        want = _run_null_ts(ts, tvalid, vals, None, 1000, offset=988, aggs=aggs, device=device)
+        assert [w.to_list()[0] for w in want] == [-12, None, 0, 0.0, 0.0, None, None, None] and want[1].to_list()[2] == float(n)
+        dense = np.full(n, -376, np.int64)
+        dense[-1] = 2570
+        outs, exp, _info = run_both(dense, [(vals, tvalid)], 1000, aggs, offset=988, device=device)
+        assert [w.to_list()[0] for w in exp] == [-12, None, 0, 0.0, 0.0, None, None, None]
+
+
 def test_null_timestamps_runs_at_window_edges_and_the_null_last_row():
     ts = np.array([10, 11, 12, 13, 20, 21, 22, 30, 31, 45, 46], dtype=np.int64)
     vals = np.arange(1.0, 12.0)
