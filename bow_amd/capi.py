@@ -25,6 +25,7 @@ AGG = {
 INTERP = {"WindowStart": 0, "Linear": 1, "StepPrevious": 2, "None": 3, "Const": 4}
 
 MAX_FACTORS = 4
+BOOL_LANE_ROWS = 256   # csrc/common.h kBoolLaneRows: the class boundary of bool_windows_kernel (one lane a window up to here, a wavefront beyond)
 FILTER_MAX_VALUES = 32
 FILTER_MAX_PREDS = 8
 CARRY_MAX_AGGS = 16
@@ -472,6 +473,10 @@ class OutColumn:
             vals, bm = self.values[:n], self.validity[:nb]
         else:
             vals, bm = self.values.to_numpy(np.uint64, n), self.validity.to_numpy(np.uint8, nb)
+        if self.type == BOOLEAN:   # First / Last / Mode over a Boolean column: bit-packed values, ceil(n / 8) bytes like the validity
+            if self.residency != DEVICE:
+                return self.values.view(np.uint8)[:nb], bm
+            return self.values.to_numpy(np.uint8, nb), bm
         dt = np.int64 if self.type == INT64 else np.float64
         return vals.view(dt), bm
 
@@ -485,6 +490,9 @@ class OutColumn:
     def to_list(self):
         vals, _ = self.host_arrays()
         m = self.valid_mask()
+        if self.type == BOOLEAN:
+            bits = np.unpackbits(vals, bitorder="little")[:self.length] if self.length else np.zeros(0, np.uint8)
+            return [bool(v) if ok else None for v, ok in zip(bits, m)]
         conv = int if self.type == INT64 else float
         return [conv(v) if ok else None for v, ok in zip(vals, m)]
 

@@ -710,8 +710,14 @@ static int validate_aggs(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, 
         if (aggs[i].kind < 0 || aggs[i].kind >= BOWGPU_AGG__COUNT) return fail(BOWGPU_ERR_ARG, "aggregation %d: unknown kind %d", i, aggs[i].kind);
         if (aggs[i].n_factors < 0 || aggs[i].n_factors > BOWGPU_MAX_FACTORS) return fail(BOWGPU_ERR_ARG, "aggregation %d: bad factor count", i);
         const int t = cols[aggs[i].col].type;
-        if (t != BOWGPU_FLOAT64 && t != BOWGPU_INT64)
-            return fail(BOWGPU_ERR_UNSUPPORTED, "aggregation %d: column type %d is outside the device path (Float64/Int64 only)", i, t);
+        if (t == BOWGPU_STRING)
+            return fail(BOWGPU_ERR_UNSUPPORTED, "aggregation %d: a String column is outside the device path (Float64 / Int64 / Boolean)", i);
+        if (t != BOWGPU_FLOAT64 && t != BOWGPU_INT64 && t != BOWGPU_BOOLEAN)
+            return fail(BOWGPU_ERR_UNSUPPORTED, "aggregation %d: column type %d is outside the device path (Float64 / Int64 / Boolean)", i, t);
+        // transformation.Factor on a Boolean result (factor.go:7-20: "factor: invalid type bool" at the first non-nil value): the
+        // caller keeps the reference's path and gets the reference's error
+        if (t == BOWGPU_BOOLEAN && aggs[i].n_factors > 0 && kind_type(aggs[i].kind) == BOWGPU_INPUT_DEPENDENT)
+            return fail(BOWGPU_ERR_UNSUPPORTED, "aggregation %d: factor: invalid type bool (a Factor on the Boolean result of First / Last / Mode is outside the device path)", i);
         if (kind_needs_inclusive(aggs[i].kind)) *inclusive = 1;  // aggregation.go:183-185
         if (aggs[i].col == ts_col) nic = i;                      // aggregation.go:158-160 (last one wins)
     }
@@ -744,6 +750,14 @@ static uint32_t need_mask(const bowgpu_agg *aggs, int32_t naggs) {
         if (k == BOWGPU_AGG_MODE) need |= kNeedMode;
     }
     return need;
+}
+
+// reducers that read a BOOLEAN value column (rolling_bool.hip; run_aggregate_bool)
+static bool kind_time_weighted(int kind) { return kind >= BOWGPU_AGG_INTEGRAL_STEP && kind <= BOWGPU_AGG_WAVG_LINEAR; }
+static bool agg_reads_bool(const bowgpu_col *cols, const bowgpu_agg &a) { return kind_reads_values(a.kind) && cols[a.col].type == BOWGPU_BOOLEAN; }
+static bool any_bool_agg(const bowgpu_col *cols, const bowgpu_agg *aggs, int32_t naggs) {
+    for (int i = 0; i < naggs; i++) if (agg_reads_bool(cols, aggs[i])) return true;
+    return false;
 }
 
 // One aggregate call in three stages so that the sharded entry points can reuse them:
@@ -1459,33 +1473,49 @@ static int job_finish(Ctx *c, AggJob *job, bool strict) {
     return agg_status_error(hstat, strict ? kLookStrict : 0);
 }
 
+// The first row of every window of a call (launch_window_first_rows) and the interval column it was made from: what the passes over
+// window row ranges read (Mode, the Boolean value reducers).  Made once per call, by whichever pass needs it first.
+struct WindowRows {
+    DevCol dts;
+    DevBuf first_idx;   // [W + 1]
+    bool ready = false;
+};
+static int window_rows_make(Ctx *c, const AggCall &call, WindowRows *wr) {
+    if (wr->ready) return 0;
+    const bowgpu_col *tsc = &call.cols[call.ts_col];
+    const int64_t n = tsc->length, W = call.plan.W;
+    bowgpu_col t = *tsc;
+    t.validity = nullptr;
+    t.null_count = 0;
+    BG_TRY(devcol_prepare(c, &t, &wr->dts, true, false));
+    BG_TRY(wr->first_idx.alloc((size_t)(W + 1) * 8));
+    void *dscr;
+    BG_TRY(ctx_scratch(c, 8192, &dscr));
+    uint32_t *status = reinterpret_cast<uint32_t *>(dscr);
+    BG_HIP(hipMemsetAsync(status, 0, 64, c->stream));
+    BG_TRY(launch_window_first_rows(c, reinterpret_cast<const int64_t *>(wr->dts.values), n, call.plan, reinterpret_cast<int64_t *>(wr->first_idx.p), status));
+    uint32_t hstat[4] = {0, 0, 0, 0};
+    BG_HIP(hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, c->stream));
+    BG_HIP(hipStreamSynchronize(c->stream));
+    if (hstat[kAggStUnsorted]) return fail_ts_unsorted();   // (window_first_rows_kernel keeps the Aggregate kernels' word for it)
+    wr->ready = true;
+    return 0;
+}
+
 // aggregation.Mode outputs (mode.go:8-32): not a streaming reducer, so they run apart from the tile kernels, over the
 // windows' row ranges (an inclusive window reaches them without its extra row: window.go:23-31, aggregation.go:207-211)
-static int run_modes(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs, int64_t *long_windows) {
+static int run_modes(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs, int64_t *long_windows, WindowRows *shared) {
     const bowgpu_col *cols = call.cols;
     const int32_t ts_col = call.ts_col;
     const Plan &plan = call.plan;
     const bowgpu_col *tsc = &cols[ts_col];
     const int64_t n = tsc->length, W = plan.W;
     BG_TRY(front_check(c, cols, call.ncols, ts_col));
-    DevCol dts;
-    DevBuf first_idx;
-    if (W > 0) {
-        bowgpu_col t = *tsc;
-        t.validity = nullptr;
-        t.null_count = 0;
-        BG_TRY(devcol_prepare(c, &t, &dts, true, false));
-        BG_TRY(first_idx.alloc((size_t)(W + 1) * 8));
-        void *dscr;
-        BG_TRY(ctx_scratch(c, 8192, &dscr));
-        uint32_t *status = reinterpret_cast<uint32_t *>(dscr);
-        BG_HIP(hipMemsetAsync(status, 0, 64, c->stream));
-        BG_TRY(launch_window_first_rows(c, reinterpret_cast<const int64_t *>(dts.values), n, plan, reinterpret_cast<int64_t *>(first_idx.p), status));
-        uint32_t hstat[4] = {0, 0, 0, 0};
-        BG_HIP(hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, c->stream));
-        BG_HIP(hipStreamSynchronize(c->stream));
-        if (hstat[kAggStUnsorted]) return fail_ts_unsorted();   // (window_first_rows_kernel keeps the Aggregate kernels' word for it)
-    }
+    WindowRows own;
+    WindowRows *wr = shared ? shared : &own;
+    if (W > 0) BG_TRY(window_rows_make(c, call, wr));
+    const DevCol &dts = wr->dts;
+    const DevBuf &first_idx = wr->first_idx;
     for (int i = 0; i < naggs; i++) {
         if (aggs[i].kind != BOWGPU_AGG_MODE) continue;
         const int col = aggs[i].col;
@@ -1518,7 +1548,8 @@ static int run_modes(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, int32_
     return 0;
 }
 
-static int run_aggregate(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs, int64_t *long_windows, double *kernel_ms);
+static int run_aggregate(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs, int64_t *long_windows, double *kernel_ms,
+                         WindowRows *rows = nullptr);
 
 // An interval column WITH NULLS (ts_nulls.hip has the semantics: rolling.go:177-239 skips such rows, :143-154 counts windows from the
 // last valid timestamp, :162-173 ends the iteration at once when the physically last timestamp is null).  The call is rewritten
@@ -1537,6 +1568,8 @@ static int run_aggregate_null_ts(Ctx *c, const AggCall &call, const bowgpu_agg *
     const int64_t n = tsc->length, W = plan.W;
     if (need_mask(aggs, naggs) & kNeedMode)
         return fail(BOWGPU_ERR_TS_NULLS, "interval column has %lld nulls: Mode over it is outside the device path", (long long)dts.null_count);
+    if (any_bool_agg(cols, aggs, naggs))
+        return fail(BOWGPU_ERR_TS_NULLS, "interval column has %lld nulls: a Boolean column over it is outside the device path", (long long)dts.null_count);
     BG_TRY(check_row_counts(cols, ncols, ts_col));
     if (long_windows) *long_windows = 0;
     if (kernel_ms) *kernel_ms = 0;
@@ -1679,10 +1712,226 @@ static int run_aggregate_null_ts(Ctx *c, const AggCall &call, const bowgpu_agg *
     return 0;
 }
 
+// ---- BOOLEAN value columns (rolling_bool.hip) ---------------------------------------------------------------------------------
+
+// n bits from bit `offset` of an Arrow bitmap - a Boolean column's values or a validity bitmap - as aligned 32-bit words on the
+// device: any byte address, any offset (what devcol_prepare does for validity; the 8-byte rule is for 8-byte values)
+struct DevBits {
+    const uint32_t *words = nullptr;
+    int64_t bit0 = 0;
+    DevBuf own;
+};
+static int devbits_prepare(Ctx *c, const uint8_t *bytes, int64_t offset, int64_t n, int32_t residency, const char *what, DevBits *out) {
+    if (residency == BOWGPU_HOST || (residency == BOWGPU_HOST_PINNED && pinned_as_host())) {
+        const int64_t b0 = offset >> 3, b1 = (offset + n + 7) >> 3;
+        const size_t nb = (size_t)(b1 - b0);
+        BG_TRY(out->own.alloc(((nb + 3) & ~(size_t)3) + 8));
+        BG_HIP(hipMemsetAsync(out->own.p, 0, out->own.bytes, c->stream));
+        BG_TRY(copy_h2d(c, out->own.p, bytes + b0, nb, residency == BOWGPU_HOST_PINNED));
+        out->words = reinterpret_cast<const uint32_t *>(out->own.p);
+        out->bit0 = offset & 7;
+        return 0;
+    }
+    const void *dev = bytes;
+    if (residency == BOWGPU_HOST_PINNED) {
+        void *dp = nullptr;
+        if (hipHostGetDevicePointer(&dp, const_cast<uint8_t *>(bytes), 0) != hipSuccess || !dp) {
+            (void)hipGetLastError();
+            return fail(BOWGPU_ERR_ARG, "BOWGPU_HOST_PINNED: the %s buffer is not registered (bowgpu_host_register)", what);
+        }
+        dev = dp;
+    } else if (residency != BOWGPU_DEVICE) {
+        return fail(BOWGPU_ERR_ARG, "unknown residency %d", residency);
+    }
+    const uintptr_t a = reinterpret_cast<uintptr_t>(dev);
+    out->words = reinterpret_cast<const uint32_t *>(a & ~(uintptr_t)3);
+    out->bit0 = (int64_t)(a & 3) * 8 + offset;
+    return 0;
+}
+// a Boolean column's value bits and - where it has a bitmap to read - its validity bits
+struct DevBoolCol { DevBits t, v; };
+static int devboolcol_prepare(Ctx *c, const bowgpu_col *col, DevBoolCol *out) {
+    if (col->length < 0 || col->offset < 0) return fail(BOWGPU_ERR_ARG, "negative column length/offset");
+    if (col->length == 0) return 0;
+    if (!col->values) return fail(BOWGPU_ERR_ARG, "column has no values buffer");
+    BG_TRY(devbits_prepare(c, reinterpret_cast<const uint8_t *>(col->values), col->offset, col->length, col->residency, "values", &out->t));
+    if (col->validity && col->null_count != 0) BG_TRY(devbits_prepare(c, col->validity, col->offset, col->length, col->residency, "validity", &out->v));
+    return 0;
+}
+
+// The value reducers over Boolean columns (aggs[at[.]]: Sum, ArithmeticMean, Min, Max, Count, First, Last, Mode): per column one
+// launch of bool_windows_kernel over the window row ranges for every reducer asked of it (kBoolMaxOuts outputs a launch).  8-byte
+// outputs go the way of every output (devout_prepare / devout_finish: values in place or through a temporary, validity through a
+// word-aligned working copy); a BOOLEAN output (First / Last / Mode) has ceil(W / 8) bytes of values like its validity, so both are
+// assembled in word-aligned temporaries and exactly those bytes copied on.  *ms: the kernels' bracket.
+static int run_bools(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, const std::vector<int> &at, bowgpu_out *outs, WindowRows *wr, double *ms) {
+    const bowgpu_col *cols = call.cols;
+    const Plan &plan = call.plan;
+    const int64_t n = cols[call.ts_col].length, W = plan.W;
+    const size_t vb = (size_t)((W + 7) >> 3), vwords_bytes = ((vb + 3) & ~(size_t)3) + 8;
+    DevBuf counter;
+    if (W > 0) {
+        BG_TRY(window_rows_make(c, call, wr));
+        BG_TRY(counter.alloc(256));
+    }
+    std::vector<char> taken(at.size(), 0);
+    for (size_t j0 = 0; j0 < at.size(); j0++) {
+        if (taken[j0]) continue;
+        const int col = aggs[at[j0]].col;
+        std::vector<int> grp;   // the outputs of this launch: reducers of `col`, in output order
+        for (size_t j = j0; j < at.size() && (int)grp.size() < kBoolMaxOuts; j++)
+            if (!taken[j] && aggs[at[j]].col == col) { grp.push_back(at[j]); taken[j] = 1; }
+        DevBoolCol dc;
+        BoolParams P;
+        memset(&P, 0, sizeof P);
+        if (W > 0) {
+            BG_TRY(devboolcol_prepare(c, &cols[col], &dc));
+            P.ts = reinterpret_cast<const int64_t *>(wr->dts.values);
+            P.first_idx = reinterpret_cast<const int64_t *>(wr->first_idx.p);
+            P.s0 = plan.s0; P.n = n; P.interval = plan.interval; P.W = W;
+            P.pre_rows = plan.s0 > plan.first_ts ? 1 : 0;
+            P.inclusive = call.inclusive;
+            P.tbits = dc.t.words; P.tbit0 = dc.t.bit0;
+            P.vbits = dc.v.words; P.vbit0 = dc.v.bit0;
+            P.null_windows = counter.as<unsigned long long>();
+            P.nouts = (int32_t)grp.size();
+        }
+        std::vector<DevOut> douts(grp.size());
+        std::vector<DevBuf> bvals(grp.size()), bvalid(grp.size());
+        std::vector<int> types(grp.size());
+        for (size_t o = 0; o < grp.size(); o++) {
+            const int i = grp[o];
+            int t = kind_type(aggs[i].kind);
+            if (t == BOWGPU_INPUT_DEPENDENT) t = BOWGPU_BOOLEAN;   // aggregation.go:114-115
+            types[o] = t;
+            BoolOut &q = P.outs[o];
+            q.kind = aggs[i].kind;
+            q.nfac = aggs[i].n_factors;
+            for (int f = 0; f < aggs[i].n_factors; f++) q.fac[f] = aggs[i].factors[f];
+            if (t == BOWGPU_BOOLEAN) {
+                if (outs[i].length < W) return fail(BOWGPU_ERR_ARG, "output column has %lld slots, %lld needed", (long long)outs[i].length, (long long)W);
+                if (W == 0) continue;
+                if (!outs[i].values || !outs[i].validity) return fail(BOWGPU_ERR_ARG, "output column lacks a values or validity buffer");
+                if (outs[i].residency != BOWGPU_HOST && outs[i].residency != BOWGPU_DEVICE && outs[i].residency != BOWGPU_HOST_PINNED)
+                    return fail(BOWGPU_ERR_ARG, "unknown residency %d", outs[i].residency);
+                BG_TRY(bvals[o].alloc(vwords_bytes));
+                BG_TRY(bvalid[o].alloc(vwords_bytes));
+                q.values = bvals[o].p;
+                q.valid = bvalid[o].as<uint32_t>();
+            } else {
+                BG_TRY(devout_prepare(c, &outs[i], W, &douts[o], -1));
+                q.values = douts[o].values;
+                q.valid = reinterpret_cast<uint32_t *>(douts[o].validity);
+            }
+        }
+        unsigned long long null_windows = 0;
+        if (W > 0) {
+            BG_HIP(hipMemsetAsync(P.null_windows, 0, 8, c->stream));
+            BG_HIP(hipEventRecord(c->ev0, c->stream));
+            BG_TRY(launch_bool_windows(c, P));
+            BG_HIP(hipEventRecord(c->ev1, c->stream));
+            BG_HIP(hipMemcpyAsync(&null_windows, P.null_windows, 8, hipMemcpyDeviceToHost, c->stream));
+            BG_HIP(hipStreamSynchronize(c->stream));
+            float t = 0;
+            BG_HIP(hipEventElapsedTime(&t, c->ev0, c->ev1));
+            if (ms) *ms += t;
+        }
+        for (size_t o = 0; o < grp.size(); o++) {
+            const int i = grp[o];
+            const int64_t nulls = kind_never_nil(aggs[i].kind) ? 0 : (int64_t)null_windows;
+            if (types[o] != BOWGPU_BOOLEAN) {
+                BG_TRY(devout_finish(c, &douts[o], W, types[o], nulls));
+                continue;
+            }
+            bowgpu_out *u = &outs[i];
+            u->length = W;
+            u->type = BOWGPU_BOOLEAN;
+            u->null_count = nulls;
+            if (W == 0) continue;
+            if (u->residency == BOWGPU_DEVICE) {
+                BG_HIP(hipMemcpyAsync(u->values, bvals[o].p, vb, hipMemcpyDeviceToDevice, c->stream));
+                BG_HIP(hipMemcpyAsync(u->validity, bvalid[o].p, vb, hipMemcpyDeviceToDevice, c->stream));
+            } else {
+                BG_TRY(copy_d2h(c, u->values, bvals[o].p, vb, u->residency == BOWGPU_HOST_PINNED));
+                BG_TRY(copy_d2h(c, u->validity, bvalid[o].p, vb, u->residency == BOWGPU_HOST_PINNED));
+            }
+        }
+        BG_HIP(hipStreamSynchronize(c->stream));   // (the temporaries of this launch go back to the block cache)
+    }
+    return 0;
+}
+
+// A call that reads Boolean value columns.  The time-weighted reducers over such a column get it widened to a Float64 device
+// temporary of 0.0 / 1.0 (8 bytes per row for the call) with its validity beside it, and go with every reducer over the other
+// columns through the ordinary batches; the value reducers over Boolean columns are set aside, as Mode is, for run_bools.
+static int run_aggregate_bool(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs, int64_t *long_windows,
+                              double *kernel_ms) {
+    const bowgpu_col *cols = call.cols;
+    const int32_t ncols = call.ncols;
+    const int64_t n = cols[call.ts_col].length;
+    BG_TRY(front_check(c, cols, ncols, call.ts_col));
+    std::vector<bowgpu_col> cols2(cols, cols + ncols);
+    std::vector<int> wide_slot(ncols, -1);
+    std::vector<DevBuf> wide_values(ncols), wide_valid(ncols);
+    std::vector<bowgpu_agg> rest;
+    std::vector<bowgpu_out> rest_outs;
+    std::vector<int> rest_at, bool_at;
+    double ms_bool = 0;
+    for (int i = 0; i < naggs; i++) {
+        bowgpu_agg a = aggs[i];
+        if (agg_reads_bool(cols, a)) {
+            if (!kind_time_weighted(a.kind)) { bool_at.push_back(i); continue; }
+            const int col = a.col;
+            if (wide_slot[col] < 0) {
+                bowgpu_col nc = device_col(nullptr, n, BOWGPU_FLOAT64);
+                if (n > 0) {
+                    DevBoolCol dc;
+                    BG_TRY(devboolcol_prepare(c, &cols[col], &dc));
+                    BG_TRY(wide_values[col].alloc(temp_values_bytes(n)));
+                    if (dc.v.words) BG_TRY(wide_valid[col].alloc(temp_bits_bytes((size_t)((n + 7) >> 3))));
+                    BG_HIP(hipEventRecord(c->ev0, c->stream));
+                    BG_TRY(launch_bool_widen(c, dc.t.words, dc.t.bit0, dc.v.words, dc.v.bit0, n, wide_values[col].as<double>(), wide_valid[col].as<uint32_t>()));
+                    BG_HIP(hipEventRecord(c->ev1, c->stream));
+                    BG_HIP(hipStreamSynchronize(c->stream));   // (the staged bits go back to the block cache)
+                    float t = 0;
+                    BG_HIP(hipEventElapsedTime(&t, c->ev0, c->ev1));
+                    ms_bool += t;
+                    nc.values = wide_values[col].p;
+                    if (dc.v.words) { nc.validity = wide_valid[col].as<uint8_t>(); nc.null_count = cols[col].null_count; }
+                }
+                wide_slot[col] = (int)cols2.size();
+                cols2.push_back(nc);
+            }
+            a.col = wide_slot[col];
+        }
+        rest.push_back(a);
+        rest_outs.push_back(outs[i]);
+        rest_at.push_back(i);
+    }
+    if (long_windows) *long_windows = 0;
+    if (kernel_ms) *kernel_ms = 0;
+    WindowRows rows;
+    if (!rest.empty()) {
+        const AggCall call2 = {cols2.data(), (int32_t)cols2.size(), call.ts_col, call.plan, call.inclusive, call.strict, call.check_plan};
+        BG_TRY(run_aggregate(c, call2, rest.data(), (int32_t)rest.size(), rest_outs.data(), long_windows, kernel_ms, &rows));
+        for (size_t j = 0; j < rest_at.size(); j++) outs[rest_at[j]] = rest_outs[j];
+    }
+    if (!bool_at.empty()) {
+        BG_TRY(run_bools(c, call, aggs, bool_at, outs, &rows, &ms_bool));
+        if (rest.empty()) c->last_kernel_name = "bool_windows_kernel";
+    }
+    // bowgpu_agg_info.kernel_ms / bowgpu_last_kernel_ms: the other reducers' bracket + the widening + the Boolean pass
+    const double total = (kernel_ms ? *kernel_ms : rest.empty() ? 0.0 : c->last_kernel_ms) + ms_bool;
+    if (kernel_ms) *kernel_ms = total;
+    c->last_kernel_ms = total;
+    return 0;
+}
+
 // An unsharded Aggregate call: the streaming reducers in batches that one launch of the tile kernels takes (at most kMaxAggs
 // outputs over at most kMaxCols column passes - the reference has no such limits, aggregation.go:190-238 simply loops), then the
 // Mode outputs.
-static int run_aggregate(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs, int64_t *long_windows, double *kernel_ms) {
+static int run_aggregate(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs, int64_t *long_windows, double *kernel_ms,
+                         WindowRows *rows) {
     const bowgpu_col &tsc = call.cols[call.ts_col];
     const int64_t W = call.plan.W;
     if (tsc.validity && tsc.null_count != 0 && tsc.length > 0) {
@@ -1690,6 +1939,7 @@ static int run_aggregate(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, in
         BG_TRY(devcol_prepare(c, &tsc, &dts, true, true));
         if (dts.null_count > 0) return run_aggregate_null_ts(c, call, aggs, naggs, outs, dts, long_windows, kernel_ms);
     }
+    if (any_bool_agg(call.cols, aggs, naggs)) return run_aggregate_bool(c, call, aggs, naggs, outs, long_windows, kernel_ms);
     if (long_windows) *long_windows = 0;
     if (kernel_ms) *kernel_ms = 0;
     // greedy batches in output order; ColSlots counts the column passes as job_build will
@@ -1735,7 +1985,7 @@ static int run_aggregate(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, in
         if (long_windows && lw > *long_windows) *long_windows = lw;   // (the same windows in every batch)
         if (kernel_ms) *kernel_ms += ms;
     }
-    if (need_mask(aggs, naggs) & kNeedMode) return run_modes(c, call, aggs, naggs, outs, long_windows);
+    if (need_mask(aggs, naggs) & kNeedMode) return run_modes(c, call, aggs, naggs, outs, long_windows, rows);
     return 0;
 }
 
@@ -2168,6 +2418,9 @@ int bowgpu_rolling_interpolate_aggregate(const bowgpu_col *cols, int32_t ncols, 
     BG_TRY(interp_validate(cols, ncols, ts_col, &o, interps, ninterps));
     int inclusive = o.inclusive ? 1 : 0, nic = -1;
     BG_TRY(validate_aggs(cols, ncols, ts_col, aggs, naggs, &inclusive, &nic));
+    for (int i = 0; i < naggs; i++)
+        if (cols[aggs[i].col].type == BOWGPU_BOOLEAN)
+            return fail(BOWGPU_ERR_UNSUPPORTED, "aggregation %d: Interpolate does not take a Boolean column on the device, so neither does Interpolate + Aggregate", i);
     if (!outs) return fail(BOWGPU_ERR_ARG, "no output columns");
     {   // bowgpu_set_devices: every rank interpolates and aggregates its own row range (multi.cpp); not taken -> one device, below
         bool fanned = false;
@@ -2244,9 +2497,12 @@ int bowgpu_rolling_aggregate_planned(const bowgpu_col *cols, int32_t ncols, int3
 // what a window cut by a shard boundary needs on top of validate_aggs: a constant-size running state per reducer (Mode has none)
 // and room for it in the record.  Columns and outputs of any residency: host-resident ones are staged through HBM per call the way
 // the unsharded entry points stage them (the pass put in flight by _pass_begin keeps its staged copies until _finish collects it)
-static int shard_check(const bowgpu_agg *aggs, int32_t naggs) {
+static int shard_check(const bowgpu_col *cols, const bowgpu_agg *aggs, int32_t naggs) {
     for (int i = 0; i < naggs; i++)
         if (aggs[i].kind == BOWGPU_AGG_MODE) return fail(BOWGPU_ERR_UNSUPPORTED, "sharded aggregate: Mode is not a mergeable reducer");
+    for (int i = 0; i < naggs; i++)   // (validate_aggs checked aggs[i].col)
+        if (cols[aggs[i].col].type == BOWGPU_BOOLEAN)
+            return fail(BOWGPU_ERR_UNSUPPORTED, "sharded aggregate: Boolean columns are served by the unsharded call only (the record holds no bit ranges)");
     if (naggs > BOWGPU_CARRY_MAX_AGGS) return fail(BOWGPU_ERR_UNSUPPORTED, "sharded aggregate: too many aggregations");
     return 0;
 }
@@ -2264,7 +2520,7 @@ int sharded_validate(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, int6
     BG_TRY(enforce_interval_and_offset(interval, 0, &off));
     int inclusive = 0, nic = -1;
     BG_TRY(validate_aggs(cols, ncols, ts_col, aggs, naggs, &inclusive, &nic));
-    return shard_check(aggs, naggs);
+    return shard_check(cols, aggs, naggs);
 }
 
 int ts_null_rows(Ctx *c, const bowgpu_col *ts, int64_t *nulls) {
@@ -2371,7 +2627,7 @@ int bowgpu_shard_begin(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, in
     if (opts) o = *opts;
     int inclusive = o.inclusive ? 1 : 0, nic = -1;
     BG_TRY(validate_aggs(cols, ncols, ts_col, aggs, naggs, &inclusive, &nic));
-    BG_TRY(shard_check(aggs, naggs));
+    BG_TRY(shard_check(cols, aggs, naggs));
     memset(rec, 0, sizeof *rec);
     rec->naggs = naggs;
     rec->flags = global_s0 ? 1 : 0;
@@ -2431,7 +2687,7 @@ int bowgpu_shard_pass_begin(const bowgpu_col *cols, int32_t ncols, int32_t ts_co
     if (opts) o = *opts;
     int inclusive = o.inclusive ? 1 : 0, nic = -1;
     BG_TRY(validate_aggs(cols, ncols, ts_col, aggs, naggs, &inclusive, &nic));
-    BG_TRY(shard_check(aggs, naggs));
+    BG_TRY(shard_check(cols, aggs, naggs));
     if (cols[ts_col].type != BOWGPU_INT64) return fail(BOWGPU_ERR_TS_TYPE, "impossible to create a new intervalRolling on column of type float64");
     if (me->nrows != cols[ts_col].length) return fail(BOWGPU_ERR_ARG, "the record says %lld rows, the interval column has %lld",
                                                       (long long)me->nrows, (long long)cols[ts_col].length);
@@ -2541,7 +2797,7 @@ int bowgpu_shard_finish(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, i
     if (opts) o = *opts;
     int inclusive = o.inclusive ? 1 : 0, nic = -1;
     BG_TRY(validate_aggs(cols, ncols, ts_col, aggs, naggs, &inclusive, &nic));
-    BG_TRY(shard_check(aggs, naggs));
+    BG_TRY(shard_check(cols, aggs, naggs));
     const bool strict = strict_wanted(&o);
     bowgpu_shard_decision d;
     BG_TRY(bowgpu_shard_plan(recs, world, rank, interval, o.offset, &d));

@@ -473,6 +473,29 @@ int launch_mode(Ctx *c, const int64_t *ts, const int64_t *first_idx, int64_t n, 
                 const uint32_t *vbits, int64_t vbit0, int is_int, const bowgpu_agg *agg, void *out_values, uint32_t *out_valid,
                 int64_t *n_mid, int64_t *n_long);
 
+// rolling_bool.hip: the value reducers of one BOOLEAN column (Arrow bit-packed values) over the same window row ranges, every
+// requested one in one launch
+constexpr int kBoolMaxOuts = 16;     // outputs of one launch
+constexpr int kBoolLaneRows = 256;   // windows up to this many rows: one lane each; longer ones: the 64 lanes of a wavefront together
+struct BoolOut {
+    int32_t kind, nfac;
+    double fac[BOWGPU_MAX_FACTORS];
+    void *values;       // Float64 / Int64 results: W slots of 8 bytes; Boolean results (First / Last / Mode): whole 32-bit words of bits
+    uint32_t *valid;    // whole 32-bit words (a word-aligned working copy)
+};
+struct BoolParams {
+    const int64_t *ts, *first_idx;          // first_idx[W + 1]: launch_window_first_rows
+    int64_t s0, n, interval, W;
+    int32_t pre_rows, inclusive;
+    const uint32_t *tbits, *vbits;          // value / validity words (vbits nullptr: no nulls)
+    int64_t tbit0, vbit0;                   // bit of row 0 in them
+    unsigned long long *null_windows;       // += windows without a valid row: the null count of every nullable output
+    int32_t nouts, _pad;
+    BoolOut outs[kBoolMaxOuts];
+};
+int launch_bool_windows(Ctx *c, const BoolParams &P);
+int launch_bool_widen(Ctx *c, const uint32_t *tbits, int64_t tbit0, const uint32_t *vbits, int64_t vbit0, int64_t n, double *out, uint32_t *out_valid);
+
 // neighbour index of a validity bitmap (interp_fill.hip nbr_index_build)
 struct NbrIndex {
     const int64_t *prev_before;  // [nblocks] last valid row in any earlier block, -1 if none

@@ -26,6 +26,7 @@
 
 #include "agg_device.h"
 #include "bitmap_device.h"
+#include "window_rows.h"
 
 namespace bowgpu {
 
@@ -58,14 +59,10 @@ __device__ __forceinline__ bool mode_eq(uint64_t a, uint64_t b, bool is_int) {
     return is_int ? a == b : __longlong_as_double((long long)a) == __longlong_as_double((long long)b);
 }
 
+// the rows Mode sees of window k: the rule of window_rows.h over this call's plan
 __device__ __forceinline__ void window_rows(const ModeParams &p, int64_t k, int64_t *a, int64_t *b) {
-    int64_t lo = p.first_idx[k], hi = p.first_idx[k + 1];
-    // rows below s0 ride in window 0, but alone they do not make a window (rolling.go:177-239) - unless the call is inclusive
-    // and the next window's first row sits exactly on its start: that row makes window 0 exist, and once it is dropped again
-    // (Window.UnsetInclusive, window.go:23-31) the rows below s0 are what Mode sees
-    if (k == 0 && p.pre_rows && !(hi > 0 && p.ts[hi - 1] >= p.s0) && !(p.inclusive && hi < p.n && p.ts[hi] == p.s0 + p.interval)) hi = lo;
-    *a = lo;
-    *b = hi;
+    const WindowRowsArgs w = {p.ts, p.first_idx, p.s0, p.n, p.interval, p.pre_rows, p.inclusive};
+    window_rows(w, k, a, b);
 }
 
 __device__ __forceinline__ bool row_valid(const ModeParams &p, int64_t row) { return !p.vbits || bit_at(p.vbits, p.vbit0, row); }

@@ -13,7 +13,7 @@
 // Who is served: host-resident columns and outputs (pageable: each rank stages ITS rows once, over ITS device's PCIe link; registered:
 // each device reads its range in place) on any device list; device-resident buffers only when every listed device is the calling
 // thread's device (how a one-GPU box exercises the path: the same id listed N times).  Everything the record protocol declines
-// (Mode, more than 16 aggregators, interval columns with nulls, strict_order windows over three ranks) is served by the one-device
+// (Mode, Boolean value columns, more than 16 aggregators, interval columns with nulls, strict_order windows over three ranks) is served by the one-device
 // path as before.  No CPU implementation of anything here: the ranks run the HIP kernels.
 //
 // bowgpu_rolling_aggregate_sharded (below the fan-out, with a worker pool of its own) serves the frame the CALLER already holds as row
@@ -588,6 +588,7 @@ static int fan_call(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, const
     if (world < 2) return 0;
     if (naggs > BOWGPU_CARRY_MAX_AGGS) return 0;
     for (int i = 0; i < naggs; i++) if (aggs[i].kind == BOWGPU_AGG_MODE) return 0;
+    for (int i = 0; i < naggs; i++) if (cols[aggs[i].col].type == BOWGPU_BOOLEAN) return 0;   // (Boolean columns: no record for bit ranges, the caller's device serves the call)
     if (cols[ts_col].validity && cols[ts_col].null_count != 0) return 0;   // (nulls in the interval column: the one-device path serves them)
     if (interps) {
         // the sharded Interpolate's own limit (include/bowgpu.h): at most 8 columns (bowgpu_interp_edge).  Rows below the first window start

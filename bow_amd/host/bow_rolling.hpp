@@ -76,7 +76,8 @@ inline int64_t GoInt64(double x) {  // float64 -> int64 on amd64
 struct Series {
     std::string Name;
     Type typ = Type::Unknown;
-    std::vector<uint64_t> data;     // 8-byte slots: int64 or float64 bit patterns (Arrow values buffer)
+    std::vector<uint64_t> data;     // 8-byte slots: int64 or float64 bit patterns (Arrow values buffer); a Boolean series holds 0 / 1
+    mutable std::vector<uint8_t> arrow_bits;   // a Boolean series as Arrow holds it - bit i, LSB first - packed by Bow::ArrowCol for the C ABI
     std::vector<uint8_t> validity;  // Arrow LSB-first bitmap, ceil(n/8) bytes (bowseries.go:191-220)
     int64_t length = 0;
 
@@ -101,6 +102,7 @@ inline Series NewSeries(const std::string &name, Type typ, const std::vector<T> 
     std::vector<uint64_t> d(values.size());
     for (size_t i = 0; i < values.size(); i++) {
         if (typ == Type::Int64) { int64_t v = (int64_t)values[i]; memcpy(&d[i], &v, 8); }
+        else if (typ == Type::Boolean) d[i] = values[i] ? 1 : 0;
         else { double v = (double)values[i]; memcpy(&d[i], &v, 8); }
     }
     std::vector<uint8_t> bm((values.size() + 7) / 8, 0);
@@ -176,6 +178,7 @@ class Bow : public std::enable_shared_from_this<Bow> {
         const Series &s = cols[col];
         if (row < 0 || row >= s.length || !s.IsValid(row)) return Nil();
         if (s.typ == Type::Int64) { int64_t v; memcpy(&v, &s.data[row], 8); return Scalar(v); }
+        if (s.typ == Type::Boolean) return Scalar(s.data[row] != 0);
         double v; memcpy(&v, &s.data[row], 8); return Scalar(v);
     }
     // GetFloat64: bowgetters.go:218-247
@@ -183,6 +186,7 @@ class Bow : public std::enable_shared_from_this<Bow> {
         const Series &s = cols[col];
         if (row < 0 || row >= s.length) return {0., false};
         if (s.typ == Type::Int64) { int64_t v; memcpy(&v, &s.data[row], 8); return {(double)v, s.IsValid(row)}; }
+        if (s.typ == Type::Boolean) return {s.data[row] != 0 ? 1. : 0., s.IsValid(row)};   // ToFloat64 of a bool (bowconvert.go)
         double v; memcpy(&v, &s.data[row], 8); return {v, s.IsValid(row)};
     }
     std::pair<int64_t, bool> GetInt64(int col, int row) const {
@@ -245,6 +249,12 @@ class Bow : public std::enable_shared_from_this<Bow> {
         bowgpu_col c;
         memset(&c, 0, sizeof c);
         c.values = s.data.empty() ? nullptr : s.data.data();
+        if (s.typ == Type::Boolean) {   // the library reads Arrow bits, not slots
+            s.arrow_bits.assign((size_t)((s.length + 7) / 8), 0);
+            for (int64_t r = 0; r < s.length; r++)
+                if (s.data[(size_t)r]) s.arrow_bits[(size_t)(r >> 3)] |= (uint8_t)(1u << (r & 7));
+            c.values = s.arrow_bits.empty() ? nullptr : s.arrow_bits.data();
+        }
         c.validity = s.validity.empty() ? nullptr : s.validity.data();
         c.offset = 0; c.length = s.length; c.null_count = s.NullN();
         c.type = (int32_t)s.typ; c.residency = BOWGPU_HOST;
@@ -314,6 +324,8 @@ inline std::pair<BowPtr, Error> NewBowFromColBasedInterfaces(const std::vector<s
             if (types[c] == Type::Int64) {
                 int64_t x = std::holds_alternative<int64_t>(*v) ? std::get<int64_t>(*v) : GoInt64(std::get<double>(*v));
                 memcpy(&d[r], &x, 8);
+            } else if (types[c] == Type::Boolean) {
+                d[r] = std::holds_alternative<bool>(*v) ? (std::get<bool>(*v) ? 1 : 0) : std::holds_alternative<int64_t>(*v) ? std::get<int64_t>(*v) != 0 : std::get<double>(*v) != 0;
             } else {
                 double x = std::holds_alternative<double>(*v) ? std::get<double>(*v) : (double)std::get<int64_t>(*v);
                 memcpy(&d[r], &x, 8);
@@ -354,6 +366,12 @@ struct OutStore {
         return o;
     }
     Series ToSeries(const std::string &name, const bowgpu_out &o) {
+        if (o.type == BOWGPU_BOOLEAN) {   // a Boolean result arrives bit-packed (ceil(length / 8) bytes): back into 0 / 1 slots
+            const uint8_t *bits = reinterpret_cast<const uint8_t *>(data.data());
+            std::vector<uint64_t> slots((size_t)o.length);
+            for (int64_t r = 0; r < o.length; r++) slots[(size_t)r] = (bits[r >> 3] >> (r & 7)) & 1u;
+            data = std::move(slots);
+        }
         data.resize((size_t)o.length);
         validity.resize((size_t)((o.length + 7) / 8));
         return NewSeriesRaw(name, (Type)o.type, data, validity);
@@ -1021,6 +1039,7 @@ inline RollingPtr Rolling::Aggregate(const std::vector<ColAggregation> &aggrs) c
                     Value v;
                     if (s.IsValid(w)) {
                         if (typ == Type::Int64) { int64_t x; memcpy(&x, &s.data[w], 8); v = Scalar(x); }
+                        else if (typ == Type::Boolean) v = Scalar(s.data[w] != 0);
                         else { double x; memcpy(&x, &s.data[w], 8); v = Scalar(x); }
                     }
                     for (const auto &t : aggrs[i].Transformations()) {
@@ -1032,6 +1051,7 @@ inline RollingPtr Rolling::Aggregate(const std::vector<ColAggregation> &aggrs) c
                     bool valid = v.has_value();
                     if (valid) {
                         if (typ == Type::Int64) { int64_t x = std::holds_alternative<int64_t>(*v) ? std::get<int64_t>(*v) : GoInt64(std::get<double>(*v)); memcpy(&bits, &x, 8); }
+                        else if (typ == Type::Boolean && std::holds_alternative<bool>(*v)) bits = std::get<bool>(*v) ? 1 : 0;
                         else { double x = std::holds_alternative<double>(*v) ? std::get<double>(*v) : (double)std::get<int64_t>(*v); memcpy(&bits, &x, 8); }
                     }
                     s.data[w] = bits;

@@ -48,7 +48,8 @@ enum {
     BOWGPU_UNKNOWN = 0,
     BOWGPU_FLOAT64 = 1,
     BOWGPU_INT64 = 2,
-    BOWGPU_BOOLEAN = 3,            /* not accepted by the device path */
+    BOWGPU_BOOLEAN = 3,            /* Arrow bit-packed values.  Accepted as a VALUE column of bowgpu_rolling_aggregate and
+                                      bowgpu_rolling_aggregate_planned (see there); every other entry point declines it */
     BOWGPU_STRING = 4,             /* not accepted by the device path */
     BOWGPU_INPUT_DEPENDENT = 5,
     BOWGPU_ITERATOR_DEPENDENT = 6
@@ -78,7 +79,7 @@ enum {
     BOWGPU_ERR_ARG = -10,
     BOWGPU_ERR_NO_DEVICE = -11,      /* no HIP device / runtime: the product path has no CPU fallback */
     BOWGPU_ERR_HIP = -12,            /* a HIP call failed; message has the hipError string */
-    BOWGPU_ERR_TS_NULLS = -13,       /* interval column has nulls AND the call has Mode or is sharded (or, Rolling.Interpolate on inclusive
+    BOWGPU_ERR_TS_NULLS = -13,       /* interval column has nulls AND the call has Mode, reads a Boolean column or is sharded (or, Rolling.Interpolate on inclusive
                                         windows: a row on a window start has null timestamps behind it and then an EQUAL timestamp, or sits on
                                         -1): the device path declines (caller keeps the reference path); Aggregate and Interpolate are served
                                         otherwise. */
@@ -91,12 +92,13 @@ enum {
 /* One Arrow array as bow holds it.  Replaces per-element Bow.GetInt64/GetFloat64/GetValue
  * (reference bowgetters.go:155-247) with bulk buffer access. */
 typedef struct bowgpu_col {
-    const void *values;       /* int64 / float64 little-endian, 8-byte aligned */
+    const void *values;       /* int64 / float64 little-endian, 8-byte aligned; BOWGPU_BOOLEAN: the Arrow bit-packed buffer (bit offset + i,
+                                 LSB first), addressed like `validity`: any byte alignment */
     const uint8_t *validity;  /* may be NULL (all valid) */
     int64_t offset;           /* arrow Data.Offset(): slices share buffers (bow.go:279-283) */
     int64_t length;           /* Data.Len() */
     int64_t null_count;       /* Data.NullN(); -1 = unknown (the library counts) */
-    int32_t type;             /* BOWGPU_FLOAT64 | BOWGPU_INT64 */
+    int32_t type;             /* BOWGPU_FLOAT64 | BOWGPU_INT64 | BOWGPU_BOOLEAN (Rolling.Aggregate value columns only) */
     int32_t residency;        /* BOWGPU_HOST | BOWGPU_DEVICE | BOWGPU_HOST_PINNED */
 } bowgpu_col;
 
@@ -104,7 +106,10 @@ typedef struct bowgpu_col {
  * (bowbuffer.go:22-40) would allocate: 8*length value bytes and ceil(length/8) validity
  * bytes.  The call fills both (null slots hold 0, as in the reference) and sets
  * null_count so the shim can wrap them with bow.NewSeries(name, typ, data, validity)
- * (bowseries.go:27-29). */
+ * (bowseries.go:27-29).
+ * A BOOLEAN result (First / Last / Mode over a Boolean column) is bit-packed like its validity: `values` holds ceil(length / 8)
+ * bytes, bit k is slot k's value, null slots hold 0, and the padding bits of the last byte of both buffers are clear.  No byte
+ * past ceil(W / 8) is written in either buffer, whatever the residency or the alignment (device pointers need no alignment). */
 typedef struct bowgpu_out {
     void *values;
     uint8_t *validity;
@@ -303,7 +308,32 @@ int bowgpu_plan_windows_ex(const bowgpu_col *ts, int64_t interval, int64_t offse
  * with Mode the call is BOWGPU_ERR_TS_NULLS.  Cost of such a call: one extra pass over the interval column (16 bytes per row) that
  * writes a forward-filled copy of it (8 bytes per row) and n / 8 bytes per rewritten validity class (up to three per value column on
  * an inclusive iteration); every output goes through a device temporary (W * 8 bytes each) before it reaches the caller's buffer;
- * NumRows is counted as Count over the rows that belong to a window and converted to float64 in a pass of its own. */
+ * NumRows is counted as Count over the rows that belong to a window and converted to float64 in a pass of its own.
+ *
+ * BOOLEAN value columns (bowgpu_col.type == BOWGPU_BOOLEAN; the interval column stays Int64).  `values` is the Arrow bit-packed
+ * buffer - bit offset + i, LSB first - addressed exactly as `validity` is: any byte alignment, any offset, read as aligned 32-bit
+ * words (the 8-byte alignment rule is for 8-byte columns).  The three residencies are served; validity may be NULL, null_count -1.
+ * Result types (rolling/aggregation.go:110-121): Sum / ArithmeticMean / Min / Max, the four time-weighted reducers and NumRows
+ * Float64; Count Int64; First / Last / Mode BOOLEAN (bit-packed outputs: see bowgpu_out).  Values, bit for bit the reference's
+ * with ToFloat64(true) = 1.0: for a window with nv valid rows of which nt are true - Sum float64(nt); ArithmeticMean
+ * float64(nt) / float64(nv); Min 0.0 if a valid false exists, else 1.0; Max 1.0 if a valid true exists, else 0.0; Count nv;
+ * First / Last the first / last valid row's bit; Mode the majority and, on a tie, the negation of the last valid value
+ * (mode.go:18-27: the value whose count reaches the maximum first); all nil at nv == 0 but Sum (0.0) and Count (0).  The
+ * windows are the ones Mode sees (an inclusive call does not change them: Window.UnsetInclusive).  These eight run as ONE pass per
+ * Boolean column over the windows' bit ranges, after the other reducers of the call: integer arithmetic, exact at any window
+ * length, no tolerance and no order question (long_windows is untouched by it; kernel_ms includes it).  Cost: the first-rows
+ * pass Mode uses (8 bytes read per row, 8 written per window, once per call) + 8 bytes read per window + 8 bytes written per
+ * window and Float64 / Int64 output (2 bits per window for a Boolean output); workspace 8 * (W + 1) bytes + the outputs'
+ * bitmaps.  transformation.Factor applies to the Float64 / Int64 results as ever; on a BOOLEAN result it is the reference's
+ * error "factor: invalid type bool": BOWGPU_ERR_UNSUPPORTED, before the device is touched.
+ * The time-weighted reducers over a Boolean column are served by WIDENING: the column is expanded once per call into a
+ * Float64 device temporary of 0.0 / 1.0 (8 bytes of workspace per row, + n / 8 for its validity) and takes the ordinary path as
+ * that Float64 column - exactness, long_windows, strict_order and the stated tolerance are those of a Float64 column holding
+ * the same values.
+ * Declined with a Boolean column (the caller keeps the reference path): an interval column with nulls (BOWGPU_ERR_TS_NULLS, as
+ * Mode); bowgpu_shard_* and bowgpu_rolling_aggregate_sharded (BOWGPU_ERR_UNSUPPORTED); under bowgpu_set_devices such a call is
+ * not fanned out and is served by the caller's device, as a call with Mode is.  Interpolate, the fills,
+ * bowgpu_rolling_interpolate_aggregate, bowgpu_aggregate_whole, the frame operations and the Parquet loader decline Boolean. */
 int bowgpu_rolling_aggregate(const bowgpu_col *cols, int32_t ncols, int32_t ts_col,
                              int64_t interval, const bowgpu_options *opts,
                              const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs,
