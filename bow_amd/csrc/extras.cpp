@@ -458,6 +458,7 @@ static int interp_fill_impl(const bowgpu_col *cols, int32_t ncols, int32_t ts_co
             P.aligned16 = (reinterpret_cast<uintptr_t>(P.ts) & 15) == 0 ? 1 : 0;
             for (int j = 0; j < nb; j++) if (reinterpret_cast<uintptr_t>(P.cols[j].values) & 15) P.aligned16 = 0;
             BG_TRY(launch_interp_tiles(c, P));
+            c->last_kernel_name = interp_takes_wave3(P) ? "interp_wave3_kernel" : "interp_tile_kernel";   // (bowgpu_last_kernel_name: the last launch's)
             if (!interp_takes_wave3(P) && b0 == 0) c->last_slow_rows += n;   // (interp_tile_kernel: 2.2 ms per 1e8 rows where interp_wave3_kernel takes 1.15)
             if (!place) BG_TRY(launch_finish_bitmaps(c, bb));
             // the batch's counts - and, behind the last batch, the status words in front of them: one copy

@@ -245,7 +245,8 @@ int bowgpu_last_kernel_ms(double *ms);
  * its hot path is on a route 2 - 3x slower than the figures the documentation quotes. */
 int bowgpu_last_call_slow_rows(int64_t *rows);
 /* ... and which tile kernel that was ("rolling_tw_kernel", "rolling_wave_kernel", "rolling_agg_kernel", "long_stream_kernel", ...; "" before
- * any call).  rolling_simple_kernel comes with its template arguments, spelled as rocprofv3 prints them
+ * any call; Rolling.Interpolate: "interp_wave3_kernel" or "interp_tile_kernel", the one whose outputs the call returned; the fills:
+ * "fill_kernel").  rolling_simple_kernel comes with its template arguments, spelled as rocprofv3 prints them
  * ("rolling_simple_kernel<0, false, false, false, false, false, false>"): the text up to '<' is the kernel, the whole string the
  * instantiation that ran - what bench.py matches against the committed counter files (profiles/) and the per-kernel code hashes
  * the build leaves next to the library (libbowgpu.kernel_sha.json) */

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from bow_amd import capi
+from interp_model import next_valid, prev_valid
 from oracle import pyoracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -485,9 +486,7 @@ def test_fill_long_null_runs_use_the_block_index():
     for off in (0, 3):
         m = n - off
         v, ok = vals[off:], valid[off:]
-        idx = np.arange(m)
-        prev = np.maximum.accumulate(np.where(ok, idx, -1))
-        nxt = np.minimum.accumulate(np.where(ok, idx, m)[::-1])[::-1]
+        prev, nxt = prev_valid(ok), next_valid(ok)       # (tests/interp_model.py: np.maximum.accumulate / np.minimum.accumulate)
         exp = {"Previous": (np.where(prev >= 0, v[np.maximum(prev, 0)], 0.0), prev >= 0),
                "Next": (np.where(nxt < m, v[np.minimum(nxt, m - 1)], 0.0), nxt < m)}
         both = (prev >= 0) & (nxt < m)
@@ -506,8 +505,7 @@ def test_fill_long_null_runs_use_the_block_index():
     got, _ = capi.fill_linear([capi.Column(ref), capi.Column(vals, bm, capi.FLOAT64, 0, n, -1)], 0, 1)
     gv, gm = got.host_arrays()[0], got.valid_mask()
     idx = np.arange(n)
-    prev = np.maximum.accumulate(np.where(valid, idx, -1))
-    nxt = np.minimum.accumulate(np.where(valid, idx, n)[::-1])[::-1]
+    prev, nxt = prev_valid(valid), next_valid(valid)
     both = (prev >= 0) & (nxt < n)
     assert np.array_equal(gm, both)
     p, q = np.maximum(prev, 0), np.minimum(nxt, n - 1)

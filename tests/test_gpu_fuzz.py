@@ -159,7 +159,9 @@ def test_fuzz_aggregate(seed):
 def test_fuzz_interpolate_and_fills(seed):
     rng = np.random.default_rng(2000 + seed)
     for case in range(40):
-        # (sizes are bounded by the ORACLE: like the reference's GetPrevFloat64s walks it is cubic on all-null columns)
+        # (sizes are bounded by the ORACLE: like the reference's GetPrevFloat64s walks it is cubic on all-null columns.  The sizes at which
+        # the kernels' trips, near walks and neighbour index come into play are tests/test_gpu_interp_fuzz.py's, against the model of
+        # tests/interp_model.py; this test stays as the comparison with the oracle itself)
         n = int(rng.integers(1, 500)) if rng.random() < 0.7 else int([511, 512, 513, 700][int(rng.integers(0, 4))])
         ts = rand_ts(rng, n)
         interval = int([1, 2, 5, 10, 64, 100, 1000][int(rng.integers(0, 7))])
