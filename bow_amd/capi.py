@@ -133,6 +133,18 @@ class SortShardInfo(C.Structure):
                 ("local_sort_ms", C.c_double), ("splitter_ms", C.c_double), ("merge_ms", C.c_double)]
 
 
+class ParquetWriteOptions(C.Structure):
+    """bowgpu_parquet_write_options"""
+    _fields_ = [("row_group_rows", C.c_int64), ("page_rows", C.c_int32), ("statistics", C.c_int32), ("encodings", C.POINTER(C.c_int32)),
+                ("meta_keys", C.POINTER(C.c_char_p)), ("meta_values", C.POINTER(C.c_char_p)), ("n_meta", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ParquetWriteInfo(C.Structure):
+    """bowgpu_parquet_write_info"""
+    _fields_ = [("file_bytes", C.c_int64), ("rows", C.c_int64), ("row_groups", C.c_int64), ("data_pages", C.c_int64),
+                ("level_bytes", C.c_int64), ("value_bytes", C.c_int64)]
+
+
 # every symbol include/bowgpu.h declares (checked by tests/test_abi_symbols.py)
 SYMBOLS = [
     "bowgpu_abi_version", "bowgpu_rolling_interpolate_aggregate", "bowgpu_last_error", "bowgpu_device_count", "bowgpu_set_device", "bowgpu_device_name",
@@ -145,7 +157,7 @@ SYMBOLS = [
     "bowgpu_is_col_sorted", "bowgpu_carry_merge",
     "bowgpu_shard_begin", "bowgpu_shard_pass_begin", "bowgpu_shard_plan", "bowgpu_shard_finish", "bowgpu_gen_dense",
     "bowgpu_gen_sparse", "bowgpu_stream_read_ceiling", "bowgpu_stream_rw_probe", "bowgpu_debug_status", "bowgpu_debug_host_copy", "bowgpu_checksum64", "bowgpu_parquet_open", "bowgpu_parquet_close",
-    "bowgpu_parquet_info", "bowgpu_parquet_column", "bowgpu_parquet_read_column", "bowgpu_parquet_column_check",
+    "bowgpu_parquet_info", "bowgpu_parquet_column", "bowgpu_parquet_read_column", "bowgpu_parquet_column_check", "bowgpu_parquet_write",
     "bowgpu_debug_set_route", "bowgpu_debug_get_route", "bowgpu_checksum64_at",
     "bowgpu_set_devices", "bowgpu_get_devices", "bowgpu_set_fanout_min_rows", "bowgpu_last_call_ranks", "bowgpu_fanout_counts",
     "bowgpu_rolling_aggregate_sharded",
@@ -1224,6 +1236,9 @@ PARQUET_ENC_PLAIN, PARQUET_ENC_PLAIN_DICTIONARY, PARQUET_ENC_DELTA_BINARY_PACKED
 PARQUET_ENC_RLE_DICTIONARY, PARQUET_ENC_BYTE_STREAM_SPLIT = 1 << 8, 1 << 9
 
 
+PARQUET_PLAIN, PARQUET_DELTA_BINARY_PACKED = 0, 5   # Parquet Encoding values bowgpu_parquet_write takes
+
+
 class ParquetFile:
     """Parquet column chunks decoded on the device (bowgpu_parquet_*): the reference's NewBowFromParquet for INT64 / DOUBLE columns"""
 
@@ -1261,6 +1276,26 @@ class ParquetFile:
 
     def __del__(self):
         self.close()
+
+
+def write_parquet(path, cols, names, page_rows=0, row_group_rows=0, encodings=None, statistics=True, metadata=None, reserved=0):
+    """bowgpu_parquet_write: the frame `cols` (Int64 / Float64 Columns of any residency) as the Parquet file `path`, encoded on the
+    device.  encodings: None (PLAIN everywhere) or one Parquet Encoding per column (PARQUET_PLAIN / PARQUET_DELTA_BINARY_PACKED);
+    metadata: a dict (or a list of pairs) for the footer's key_value_metadata.  Returns the ParquetWriteInfo."""
+    o = ParquetWriteOptions()
+    o.row_group_rows, o.page_rows, o.statistics, o.reserved = row_group_rows, page_rows, 1 if statistics else 0, reserved
+    if encodings is not None:
+        enc = (C.c_int32 * max(len(encodings), 1))(*encodings)
+        o.encodings = C.cast(enc, C.POINTER(C.c_int32))
+    pairs = list(metadata.items()) if isinstance(metadata, dict) else list(metadata or [])
+    if pairs:
+        keys = (C.c_char_p * len(pairs))(*[k.encode() if isinstance(k, str) else k for k, _ in pairs])
+        vals = (C.c_char_p * len(pairs))(*[v.encode() if isinstance(v, str) else v for _, v in pairs])
+        o.meta_keys, o.meta_values, o.n_meta = C.cast(keys, C.POINTER(C.c_char_p)), C.cast(vals, C.POINTER(C.c_char_p)), len(pairs)
+    cnames = (C.c_char_p * max(len(names), 1))(*[None if nm is None else nm.encode() for nm in names])
+    info = ParquetWriteInfo()
+    check(lib().bowgpu_parquet_write(os.fsencode(path), _cols(cols), cnames, len(cols), C.byref(o), C.byref(info)))
+    return info
 
 
 def checksum64(devbuf, n_words, index_base=0, word_offset=0):

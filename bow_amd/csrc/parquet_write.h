@@ -1,0 +1,85 @@
+// What parquet_write.cpp (the file assembly: plain C++ over host buffers, no device, no other translation unit of the library)
+// and parquet_encode.hip (the encoding of one column chunk on the device) hand each other.  Included by the stand-alone
+// assembly test as well (tests/cpp/test_parquet_assemble.cpp), so nothing here needs HIP.
+#pragma once
+
+#include <stdint.h>
+
+#include <memory>
+#include <string>
+#include <vector>
+
+namespace bowgpu {
+
+constexpr int32_t kPqEncPlain = 0, kPqEncDelta = 5;   // Parquet Encoding values the writer produces
+constexpr int32_t kPqInt64 = 2, kPqDouble = 5;        // Parquet physical types
+
+// One data page as the assembly takes it: its level BIT bytes (ceil(rows / 8), bit k = row k of the page is valid; read only when
+// 0 < valid < rows) and its encoded values section, both in host memory.
+struct PqwPage {
+    int32_t rows = 0, valid = 0;
+    const uint8_t *level_bits = nullptr;
+    const uint8_t *values = nullptr;
+    int64_t value_bytes = 0;
+};
+// Statistics of one column chunk: min / max are the raw 8-byte payloads of the column's type
+struct PqwStats {
+    bool has_minmax = false;
+    uint64_t min = 0, max = 0;
+    int64_t null_count = 0;
+};
+// A host buffer that only grows and is never cleared: the images of one column chunk after the other land in the same pages
+struct PqHostBytes {
+    std::unique_ptr<uint8_t[]> p;
+    size_t cap = 0;
+    uint8_t *take(size_t n) {
+        if (cap < n) { p.reset(); p.reset(new uint8_t[n]); cap = n; }
+        return p.get();
+    }
+};
+// One column chunk as parquet_encode.hip hands it over: the page table, and the two host images its pages point into
+struct PqEncChunk {
+    std::vector<PqwPage> pages;
+    PqHostBytes levels, values;
+    PqwStats stats;
+};
+struct PqwTotals { int64_t file_bytes = 0, rows = 0, row_groups = 0, data_pages = 0, level_bytes = 0, value_bytes = 0; };
+
+// The file, written front to back under `<path>.tmp` and renamed by finish().  Every method returns 0 or -1 with error() set (an
+// errno text where a system call failed); after a failure, or when the writer goes away before finish(), the temporary is removed.
+// Call order: open, then per row group begin_row_group, add_chunk once per column in column order, end_row_group; finish.
+class PqWriter {
+public:
+    PqWriter() = default;
+    PqWriter(const PqWriter &) = delete;
+    PqWriter &operator=(const PqWriter &) = delete;
+    ~PqWriter();
+    // types: kPqInt64 / kPqDouble per column; statistics: min / max in the chunk metadata and column_orders in the footer
+    int open(const char *path, const char *const *names, const int32_t *types, int32_t ncols, bool statistics, const char *const *meta_keys,
+             const char *const *meta_values, int32_t n_meta);
+    int begin_row_group(int64_t rows);
+    int add_chunk(int32_t encoding, const PqwPage *pages, int64_t npages, const PqwStats &stats);
+    int end_row_group();
+    int finish(PqwTotals *totals);
+    const std::string &error() const { return err_; }
+
+private:
+    struct Chunk { int32_t encoding; int64_t offset, bytes, values; PqwStats stats; };
+    struct Group { int64_t rows, bytes; std::vector<Chunk> chunks; };
+    int put(const void *p, size_t n);
+    int flush();
+    int sys_fail(const char *what);
+    void drop();
+
+    std::string path_, tmp_, err_;
+    int fd_ = -1;
+    bool stats_ = false;
+    std::vector<std::string> names_, meta_k_, meta_v_;
+    std::vector<int32_t> types_;
+    std::vector<Group> groups_;
+    std::vector<uint8_t> buf_;
+    int64_t pos_ = 0;   // bytes handed to put() so far: the file offset of the next one
+    PqwTotals tot_;
+};
+
+}  // namespace bowgpu

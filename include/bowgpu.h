@@ -41,6 +41,8 @@ extern "C" {
  * bowgpu_join added (Bow.InnerJoin / OuterJoin on the device); no existing struct changed. */
 /* 14: bowgpu_sort_by_col_sharded and bowgpu_sort_by_col_sharded_info (with the bowgpu_sort_shard_info struct) added: Bow.SortByCol over
  * row-range shards held on several devices; no existing struct changed. */
+/* (still 14): bowgpu_parquet_write, with the bowgpu_parquet_write_options and bowgpu_parquet_write_info structs, added under the same
+ * version: a new entry point and two new structs, nothing existing changed its layout or meaning. */
 #define BOWGPU_ABI_VERSION 14
 
 /* bow.Type (reference bowtypes.go:17-32) */
@@ -873,6 +875,54 @@ enum {
     BOWGPU_PARQUET_ENC_BYTE_STREAM_SPLIT = 512     /* 1 << 9 */
 };
 int bowgpu_parquet_column_check(const bowgpu_parquet *handle, int32_t i, uint32_t *value_encodings);
+
+/* ---- device column -> Parquet file -------------------------------------------------- */
+
+/* Writes a frame of Int64 / Float64 columns to a Parquet file the way the reference's Bow.WriteParquet lays one out
+ * (bowparquet.go:157-253), minus its codec, with the encoding done on the device: per row group and column the validity bits are
+ * cut into the pages' definition levels, the non-null values are compacted, min / max are reduced and - for
+ * DELTA_BINARY_PACKED - the values are delta-packed by HIP kernels; only the encoded bytes cross the host link, once.
+ *
+ * The file: format version 1; flat schema with root `Schema`; every column OPTIONAL whatever its null count (bowparquet.go:190);
+ * INT64 / DOUBLE; UNCOMPRESSED; data page v1; definition levels as RLE / bit-packed hybrid of bit width 1; created_by names the
+ * library; key_value_metadata from the options.  One row group per row_group_rows rows (the last may be shorter), in it one
+ * column chunk per column in column order, in it one page per page_rows rows (the last may be shorter).
+ * Levels of a page: all rows valid - one RLE run of 1; no row valid - one RLE run of 0; otherwise one bit-packed run whose bytes
+ * are the page's validity bits from bit 0, padded with zero bits to a whole group of 8.
+ * PLAIN: the page's non-null values, 8 bytes each, in row order.
+ * DELTA_BINARY_PACKED (Int64 columns): blocks of 128 in 4 miniblocks of 32 (parquet-mr's layout for INT64) over the page's
+ * non-null values; wrapping differences; the block minimum is the true minimum; each miniblock has its minimal bit width; the
+ * last miniblock that holds values is padded with zero bits; miniblocks behind it have width byte 0 and no body; a page without a
+ * valid row holds the header alone (block size 128, 4 miniblocks, 0 values, first value 0).
+ * Statistics (TYPE_DEFINED_ORDER): null_count always; min_value / max_value with options.statistics - Int64 signed; a NaN takes
+ * no part in a Float64 min / max; both are left out when no valid non-NaN value exists; a zero minimum is written as -0.0, a
+ * zero maximum as +0.0.
+ *
+ * Accepted: Int64 / Float64 columns of the three residencies, any Arrow offset (bit offsets that are no multiple of 8 included),
+ * validity NULL or null_count 0 / -1, 0 rows (a file with a schema and no row group), up to 2^31 - 1 rows.
+ * Declined, with nothing left at `path`: Boolean / String columns, an encoding other than 0 / 5, encoding 5 on a Float64 column
+ * (BOWGPU_ERR_UNSUPPORTED); columns of unequal length, ncols < 1, a NULL or empty name, the same name twice, sizes that break the
+ * rules below, reserved != 0 (BOWGPU_ERR_ARG) - all before any device is touched; no device (BOWGPU_ERR_NO_DEVICE: there is no CPU
+ * fallback).  The file is written as `<path>.tmp` and renamed on success; on any failure the temporary is removed, a failure to
+ * create or write it is BOWGPU_ERR_ARG with the errno text.  The reference's ".parquet" suffix rule is the caller's business.
+ * Device workspace is bounded by row_group_rows. */
+typedef struct {
+    int64_t row_group_rows;       /* 0: 1 << 24.  A multiple of page_rows, at most 1 << 27 */
+    int32_t page_rows;            /* 0: 65536.  A multiple of 64, at most 1 << 20: rows (nulls included) per data page */
+    int32_t statistics;           /* 1: min_value / max_value / null_count per column chunk, and column_orders in the footer; 0: null_count only */
+    const int32_t *encodings;     /* NULL: PLAIN everywhere; else ncols entries, each Parquet Encoding 0 (PLAIN) or 5 (DELTA_BINARY_PACKED, Int64 columns only) */
+    const char *const *meta_keys; /* n_meta key / value pairs for the footer's key_value_metadata (Bow.Metadata) */
+    const char *const *meta_values;
+    int32_t n_meta;
+    int32_t reserved;             /* 0 */
+} bowgpu_parquet_write_options;
+
+/* what was written: the file's size, its rows, row groups and data pages, the bytes of the definition-level sections (each with
+ * its 4-byte length) and of the values sections */
+typedef struct { int64_t file_bytes, rows, row_groups, data_pages, level_bytes, value_bytes; } bowgpu_parquet_write_info;
+
+int bowgpu_parquet_write(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols,
+                         const bowgpu_parquet_write_options *opts /* NULL: defaults */, bowgpu_parquet_write_info *info /* nullable */);
 
 /* ---- row-range sharded Rolling.Aggregate across GPUs: the records the ranks exchange ------------------ */
 
