@@ -14,9 +14,7 @@
 
 #include <algorithm>
 #include <atomic>
-#include <condition_variable>
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "common.h"
@@ -299,7 +297,7 @@ MagicDiv magic_make(uint64_t d) {
     return r;
 }
 
-// ---------------------------------------------------------------- columns on the device
+// ---------------------------------------------------------------- plan
 static int fetch_i64(Ctx *c, const bowgpu_col *col, int64_t row, int64_t *out) {
     const int64_t *p = reinterpret_cast<const int64_t *>(col->values) + col->offset + row;
     if (col->residency == BOWGPU_DEVICE) {
@@ -312,287 +310,6 @@ static int fetch_i64(Ctx *c, const bowgpu_col *col, int64_t row, int64_t *out) {
     return 0;
 }
 
-int fetch_valid(Ctx *c, const bowgpu_col *col, int64_t row, int *valid) {
-    if (!col->validity) { *valid = 1; return 0; }
-    const int64_t bit = col->offset + row;
-    uint8_t byte = 0;
-    if (col->residency == BOWGPU_DEVICE) {
-        if (!c) BG_TRY(ctx_get(&c));
-        BG_HIP(hipMemcpyAsync(&byte, col->validity + (bit >> 3), 1, hipMemcpyDeviceToHost, c->stream));
-        BG_HIP(hipStreamSynchronize(c->stream));
-    } else {
-        byte = col->validity[bit >> 3];
-    }
-    *valid = (byte >> (bit & 7)) & 1;
-    return 0;
-}
-
-int count_nulls_device(Ctx *c, DevCol *dc) {
-    if (!dc->vbits || dc->length == 0) { dc->null_count = 0; return 0; }
-    void *d;
-    BG_TRY(ctx_scratch(c, 4096, &d));
-    uint64_t *dcount = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(d) + 2048);
-    BG_TRY(launch_popcount(c, dc->vbits, dc->vbit0, dc->length, dcount));
-    uint64_t set = 0;
-    BG_HIP(hipMemcpyAsync(&set, dcount, 8, hipMemcpyDeviceToHost, c->stream));
-    BG_HIP(hipStreamSynchronize(c->stream));
-    dc->null_count = dc->length - (int64_t)set;
-    return 0;
-}
-
-// BOWGPU_ROUTE_PINNED_STAGE (A/B switch): pinned input columns are staged through HBM by DMA like pageable ones instead of being read in place
-static bool pinned_as_host() { return (route_mask() & BOWGPU_ROUTE_PINNED_STAGE) != 0; }
-
-int devcol_prepare(Ctx *c, const bowgpu_col *col, DevCol *out, bool need_values, bool need_validity) {
-    if (col->length < 0 || col->offset < 0) return fail(BOWGPU_ERR_ARG, "negative column length/offset");
-    if (col->length > 0 && !col->values) return fail(BOWGPU_ERR_ARG, "column has no values buffer");
-    out->length = col->length;
-    out->type = col->type;
-    out->null_count = col->null_count;
-    const int64_t n = col->length;
-    if (n == 0) { out->null_count = 0; return 0; }
-    const bool has_bitmap = col->validity != nullptr && col->null_count != 0;
-    if (col->residency == BOWGPU_DEVICE) {
-        if (reinterpret_cast<uintptr_t>(col->values) & 7) return fail(BOWGPU_ERR_ARG, "values buffer must be 8-byte aligned");
-        out->values = reinterpret_cast<const char *>(col->values) + 8 * col->offset;
-        if (has_bitmap) {
-            const uintptr_t a = reinterpret_cast<uintptr_t>(col->validity);
-            out->vbits = reinterpret_cast<const uint32_t *>(a & ~(uintptr_t)3);
-            out->vbit0 = (int64_t)(a & 3) * 8 + col->offset;
-            out->vwords = (out->vbit0 + n + 31) >> 5;
-        }
-    } else if (col->residency == BOWGPU_HOST_PINNED && !pinned_as_host()) {
-        // zero-copy: the kernels read the registered host buffers where they lie (coalesced 16-byte loads over PCIe)
-        if (reinterpret_cast<uintptr_t>(col->values) & 7) return fail(BOWGPU_ERR_ARG, "values buffer must be 8-byte aligned");
-        void *dv = nullptr;
-        if (hipHostGetDevicePointer(&dv, const_cast<void *>(col->values), 0) != hipSuccess || !dv) {
-            (void)hipGetLastError();
-            return fail(BOWGPU_ERR_ARG, "BOWGPU_HOST_PINNED: the values buffer is not registered (bowgpu_host_register)");
-        }
-        out->values = reinterpret_cast<const char *>(dv) + 8 * col->offset;
-        if (has_bitmap) {
-            void *db = nullptr;
-            if (hipHostGetDevicePointer(&db, const_cast<uint8_t *>(col->validity), 0) != hipSuccess || !db) {
-                (void)hipGetLastError();
-                return fail(BOWGPU_ERR_ARG, "BOWGPU_HOST_PINNED: the validity buffer is not registered (bowgpu_host_register)");
-            }
-            const uintptr_t a = reinterpret_cast<uintptr_t>(db);
-            out->vbits = reinterpret_cast<const uint32_t *>(a & ~(uintptr_t)3);
-            out->vbit0 = (int64_t)(a & 3) * 8 + col->offset;
-            out->vwords = (out->vbit0 + n + 31) >> 5;
-        }
-    } else if (col->residency == BOWGPU_HOST || col->residency == BOWGPU_HOST_PINNED) {
-        if (need_values) {
-            BG_TRY(out->own_values.alloc((size_t)n * 8 + 16));
-            BG_TRY(copy_h2d(c, out->own_values.p, reinterpret_cast<const char *>(col->values) + 8 * col->offset, (size_t)n * 8,
-                            col->residency == BOWGPU_HOST_PINNED));
-            out->values = out->own_values.p;
-        }
-        if (has_bitmap && need_validity) {
-            const int64_t b0 = col->offset >> 3, b1 = (col->offset + n + 7) >> 3;
-            const size_t nb = (size_t)(b1 - b0);
-            BG_TRY(out->own_validity.alloc(((nb + 3) & ~(size_t)3) + 8));
-            BG_HIP(hipMemsetAsync(out->own_validity.p, 0, out->own_validity.bytes, c->stream));
-            BG_TRY(copy_h2d(c, out->own_validity.p, col->validity + b0, nb, col->residency == BOWGPU_HOST_PINNED));
-            out->vbits = reinterpret_cast<const uint32_t *>(out->own_validity.p);
-            out->vbit0 = col->offset & 7;
-            out->vwords = (out->vbit0 + n + 31) >> 5;
-        }
-    } else {
-        return fail(BOWGPU_ERR_ARG, "unknown residency %d", col->residency);
-    }
-    if (has_bitmap && out->vbits && col->null_count < 0) BG_TRY(count_nulls_device(c, out));
-    if (!has_bitmap) out->null_count = 0;
-    if (out->null_count == 0) { out->vbits = nullptr; }
-    return 0;
-}
-
-int devout_prepare(Ctx *c, bowgpu_out *out, int64_t slots, DevOut *d, int pool_slot) {
-    d->user = out;
-    d->capacity = slots;
-    if (out->length < slots) return fail(BOWGPU_ERR_ARG, "output column has %lld slots, %lld needed", (long long)out->length, (long long)slots);
-    if (slots == 0) return 0;
-    if (!out->values || !out->validity) return fail(BOWGPU_ERR_ARG, "output column lacks a values or validity buffer");
-    const size_t vb = (size_t)((slots + 7) >> 3);
-    if (out->residency == BOWGPU_DEVICE) {
-        if (reinterpret_cast<uintptr_t>(out->values) & 7) return fail(BOWGPU_ERR_ARG, "output values must be 8-byte aligned");
-        d->values = out->values;
-        // The kernels update validity as 32-bit words; a caller buffer of exactly ceil(W/8) bytes may end
-        // mid-word, so always assemble in an aligned temporary and copy the exact byte count back.
-        if (pool_slot >= 0) {
-            void *pp;
-            BG_TRY(ctx_pool(c, pool_slot, ((vb + 3) & ~(size_t)3) + 4, &pp));
-            d->validity = reinterpret_cast<uint8_t *>(pp);
-            d->pool_slot = pool_slot;
-        } else {
-            BG_TRY(d->own_validity.alloc(((vb + 3) & ~(size_t)3) + 4));
-            d->validity = reinterpret_cast<uint8_t *>(d->own_validity.p);
-        }
-    } else {
-        BG_TRY(d->own_values.alloc((size_t)slots * 8));
-        BG_TRY(d->own_validity.alloc(((vb + 3) & ~(size_t)3) + 4));
-        d->values = d->own_values.p;
-        d->validity = reinterpret_cast<uint8_t *>(d->own_validity.p);
-    }
-    return 0;
-}
-
-// Device <-> host copies of PAGEABLE caller buffers go through the context's own pinned staging (two kBouncePiece halves: the
-// DMA of one overlaps the CPU copy of the other) and never hand the caller's pointer to the HIP runtime.  The runtime would pin
-// the caller's pages itself (a userptr mapping, kept in a cache), and that goes wrong in ways the library cannot see: it refuses
-// a range that lies only partly inside a registered one (a small malloc'ed buffer sharing a page with a buffer somebody
-// registered), and on this pool GPU writes through such mappings were seen to die with "write access to a read-only page" on
-// fresh machines.  Small copies (the runtime stages those itself) and BOWGPU_RUNTIME_PINS=1 (A/B switch) keep the direct form.
-constexpr size_t kBouncePiece = 4u << 20;
-constexpr size_t kBounceDirect = 16384;
-static bool runtime_pins() {
-    static const bool on = [] { const char *e = getenv("BOWGPU_RUNTIME_PINS"); return e && e[0] == '1'; }();
-    return on;
-}
-static int bounce_get(Ctx *c, char **half0, char **half1) {
-    if (!c->h_bounce) {
-        BG_HIP(hipHostMalloc(&c->h_bounce, 2 * kBouncePiece, hipHostMallocDefault));   // (its own block: ctx_pinned's must not move)
-        BG_HIP(hipEventCreateWithFlags(&c->bounce_ev[0], hipEventDisableTiming));
-        BG_HIP(hipEventCreateWithFlags(&c->bounce_ev[1], hipEventDisableTiming));
-    }
-    *half0 = reinterpret_cast<char *>(c->h_bounce);
-    *half1 = *half0 + kBouncePiece;
-    return 0;
-}
-// The CPU side of the staging: one core copies at ~12 GB/s, the link takes 55.  Pieces of a megabyte or more are split over a small
-// process-wide pool of helper threads (they only ever call memcpy; created on first use, BOWGPU_COPY_THREADS = 0 .. 8, default 3;
-// the pool object is never destroyed, so no thread can wake up into a torn-down condition variable at exit).
-namespace {
-struct CopyPool {
-    struct Job { char *d; const char *s; size_t n; std::atomic<int> *left; };
-    std::mutex m;
-    std::condition_variable work, done;
-    std::vector<Job> q;
-    int nthreads = 0;
-    void run() {
-        for (;;) {
-            Job j;
-            {
-                std::unique_lock<std::mutex> lk(m);
-                work.wait(lk, [&] { return !q.empty(); });
-                j = q.back();
-                q.pop_back();
-            }
-            memcpy(j.d, j.s, j.n);
-            if (j.left->fetch_sub(1) == 1) {
-                std::lock_guard<std::mutex> lk(m);
-                done.notify_all();
-            }
-        }
-    }
-};
-CopyPool *copy_pool() {
-    static CopyPool *pool = [] {
-        CopyPool *p = new CopyPool();   // (leaked on purpose)
-        const char *e = getenv("BOWGPU_COPY_THREADS");
-        int n = e ? atoi(e) : 3;
-        if (n < 0) n = 0;
-        if (n > 8) n = 8;
-        for (int i = 0; i < n; i++) {
-            try { std::thread([p] { p->run(); }).detach(); p->nthreads++; } catch (...) { break; }
-        }
-        return p;
-    }();
-    return pool;
-}
-void staged_memcpy(void *dst, const void *src, size_t n) {
-    constexpr size_t kMinPart = 256u << 10;
-    CopyPool *p = n >= 4 * kMinPart ? copy_pool() : nullptr;
-    if (!p || p->nthreads == 0) { memcpy(dst, src, n); return; }
-    const int parts = p->nthreads + 1;
-    const size_t part = ((n / parts) + 63) & ~(size_t)63;
-    std::atomic<int> left(0);
-    char *d = reinterpret_cast<char *>(dst);
-    const char *s = reinterpret_cast<const char *>(src);
-    size_t off = part;   // [0, part) is the caller's own share
-    {
-        std::lock_guard<std::mutex> lk(p->m);
-        for (int i = 1; i < parts && off < n; i++, off += part) {
-            const size_t len = off + part < n && i + 1 < parts ? part : n - off;
-            left.fetch_add(1);
-            p->q.push_back({d + off, s + off, len, &left});
-            if (len == n - off) { off = n; break; }
-        }
-    }
-    p->work.notify_all();
-    memcpy(d, s, part < n ? part : n);
-    std::unique_lock<std::mutex> lk(p->m);
-    p->done.wait(lk, [&] { return left.load() == 0; });
-}
-}  // namespace
-
-int copy_d2h(Ctx *c, void *dst, const void *src, size_t bytes, bool registered) {
-    if (bytes == 0) return 0;
-    if (bytes <= kBounceDirect || registered || runtime_pins()) {
-        const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) return 0;
-        (void)hipGetLastError();
-        if (e != hipErrorInvalidValue) return hip_fail(e, "hipMemcpyAsync (device to host)");
-    }
-    char *h[2];
-    BG_TRY(bounce_get(c, &h[0], &h[1]));
-    const size_t pieces = (bytes + kBouncePiece - 1) / kBouncePiece;
-    auto len = [&](size_t k) { return k + 1 < pieces ? kBouncePiece : bytes - k * kBouncePiece; };
-    for (size_t k = 0; k <= pieces; k++) {
-        if (k < pieces) {   // piece k on its way into half k & 1 ...  (behind an earlier upload out of that half: stream order would do, but
-                            // the caller may have switched streams since - bowgpu_set_stream - so wait for the upload's event)
-            if (c->bounce_busy[k & 1]) BG_HIP(hipEventSynchronize(c->bounce_ev[k & 1]));
-            c->bounce_busy[k & 1] = false;
-            BG_HIP(hipMemcpyAsync(h[k & 1], reinterpret_cast<const char *>(src) + k * kBouncePiece, len(k), hipMemcpyDeviceToHost, c->stream));
-            BG_HIP(hipEventRecord(c->bounce_ev[k & 1], c->stream));
-        }
-        if (k > 0) {        // ... while piece k - 1 leaves the other half
-            BG_HIP(hipEventSynchronize(c->bounce_ev[(k - 1) & 1]));
-            staged_memcpy(reinterpret_cast<char *>(dst) + (k - 1) * kBouncePiece, h[(k - 1) & 1], len(k - 1));
-        }
-    }
-    return 0;
-}
-int copy_h2d(Ctx *c, void *dst, const void *src, size_t bytes, bool registered) {
-    if (bytes == 0) return 0;
-    if (bytes <= kBounceDirect || registered || runtime_pins()) {
-        const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) return 0;
-        (void)hipGetLastError();
-        if (e != hipErrorInvalidValue) return hip_fail(e, "hipMemcpyAsync (host to device)");
-    }
-    char *h[2];
-    BG_TRY(bounce_get(c, &h[0], &h[1]));
-    const size_t pieces = (bytes + kBouncePiece - 1) / kBouncePiece;
-    for (size_t k = 0; k < pieces; k++) {
-        const size_t m = k + 1 < pieces ? kBouncePiece : bytes - k * kBouncePiece;
-        if (c->bounce_busy[k & 1]) BG_HIP(hipEventSynchronize(c->bounce_ev[k & 1]));   // the DMA that last read this half is done
-        staged_memcpy(h[k & 1], reinterpret_cast<const char *>(src) + k * kBouncePiece, m);
-        BG_HIP(hipMemcpyAsync(reinterpret_cast<char *>(dst) + k * kBouncePiece, h[k & 1], m, hipMemcpyHostToDevice, c->stream));
-        BG_HIP(hipEventRecord(c->bounce_ev[k & 1], c->stream));
-        c->bounce_busy[k & 1] = true;
-    }
-    return 0;
-}
-
-int devout_finish(Ctx *c, DevOut *d, int64_t slots, int32_t type, int64_t null_count, bool copy_bitmap) {
-    bowgpu_out *out = d->user;
-    out->length = slots;
-    out->type = type;
-    out->null_count = null_count;
-    if (slots == 0) return 0;
-    const size_t vb = (size_t)((slots + 7) >> 3);
-    if (out->residency == BOWGPU_DEVICE) {
-        if (copy_bitmap) BG_HIP(hipMemcpyAsync(out->validity, d->validity, vb, hipMemcpyDeviceToDevice, c->stream));
-    } else {
-        // (registered buffers take the DMA directly; pageable ones go through the staging halves)
-        BG_TRY(copy_d2h(c, out->values, d->values, (size_t)slots * 8, out->residency == BOWGPU_HOST_PINNED));
-        BG_TRY(copy_d2h(c, out->validity, d->validity, vb, out->residency == BOWGPU_HOST_PINNED));
-    }
-    return 0;
-}
-
-// ---------------------------------------------------------------- plan
 static int enforce_interval_and_offset(int64_t interval, int64_t offset, int64_t *out) {
     // reference rolling/rolling.go:114-128
     if (interval <= 0) return fail(BOWGPU_ERR_INTERVAL, "strictly positive interval required");
@@ -1531,8 +1248,7 @@ static int run_modes(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, int32_
         BG_TRY(devout_prepare(c, &outs[i], W, &d, kPoolMode));
         int64_t nulls = 0;
         if (W > 0) {
-            const size_t vb = (size_t)((W + 7) >> 3);
-            BG_HIP(hipMemsetAsync(d.validity, 0, ((vb + 3) & ~(size_t)3) + 4, c->stream));
+            BG_HIP(hipMemsetAsync(d.validity, 0, temp_bits_bytes((size_t)((W + 7) >> 3)), c->stream));
             int64_t n_mid = 0, n_long = 0;
             BG_TRY(launch_mode(c, reinterpret_cast<const int64_t *>(dts.values), reinterpret_cast<const int64_t *>(first_idx.p), n, plan.s0, plan.interval, W,
                                plan.s0 > plan.first_ts ? 1 : 0, call.inclusive, values, vbits, vbit0, cols[col].type == BOWGPU_INT64, &aggs[i], d.values,
@@ -1712,63 +1428,13 @@ static int run_aggregate_null_ts(Ctx *c, const AggCall &call, const bowgpu_agg *
     return 0;
 }
 
-// ---- BOOLEAN value columns (rolling_bool.hip) ---------------------------------------------------------------------------------
-
-// n bits from bit `offset` of an Arrow bitmap - a Boolean column's values or a validity bitmap - as aligned 32-bit words on the
-// device: any byte address, any offset (what devcol_prepare does for validity; the 8-byte rule is for 8-byte values)
-struct DevBits {
-    const uint32_t *words = nullptr;
-    int64_t bit0 = 0;
-    DevBuf own;
-};
-static int devbits_prepare(Ctx *c, const uint8_t *bytes, int64_t offset, int64_t n, int32_t residency, const char *what, DevBits *out) {
-    if (residency == BOWGPU_HOST || (residency == BOWGPU_HOST_PINNED && pinned_as_host())) {
-        const int64_t b0 = offset >> 3, b1 = (offset + n + 7) >> 3;
-        const size_t nb = (size_t)(b1 - b0);
-        BG_TRY(out->own.alloc(((nb + 3) & ~(size_t)3) + 8));
-        BG_HIP(hipMemsetAsync(out->own.p, 0, out->own.bytes, c->stream));
-        BG_TRY(copy_h2d(c, out->own.p, bytes + b0, nb, residency == BOWGPU_HOST_PINNED));
-        out->words = reinterpret_cast<const uint32_t *>(out->own.p);
-        out->bit0 = offset & 7;
-        return 0;
-    }
-    const void *dev = bytes;
-    if (residency == BOWGPU_HOST_PINNED) {
-        void *dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, const_cast<uint8_t *>(bytes), 0) != hipSuccess || !dp) {
-            (void)hipGetLastError();
-            return fail(BOWGPU_ERR_ARG, "BOWGPU_HOST_PINNED: the %s buffer is not registered (bowgpu_host_register)", what);
-        }
-        dev = dp;
-    } else if (residency != BOWGPU_DEVICE) {
-        return fail(BOWGPU_ERR_ARG, "unknown residency %d", residency);
-    }
-    const uintptr_t a = reinterpret_cast<uintptr_t>(dev);
-    out->words = reinterpret_cast<const uint32_t *>(a & ~(uintptr_t)3);
-    out->bit0 = (int64_t)(a & 3) * 8 + offset;
-    return 0;
-}
-// a Boolean column's value bits and - where it has a bitmap to read - its validity bits
-struct DevBoolCol { DevBits t, v; };
-static int devboolcol_prepare(Ctx *c, const bowgpu_col *col, DevBoolCol *out) {
-    if (col->length < 0 || col->offset < 0) return fail(BOWGPU_ERR_ARG, "negative column length/offset");
-    if (col->length == 0) return 0;
-    if (!col->values) return fail(BOWGPU_ERR_ARG, "column has no values buffer");
-    BG_TRY(devbits_prepare(c, reinterpret_cast<const uint8_t *>(col->values), col->offset, col->length, col->residency, "values", &out->t));
-    if (col->validity && col->null_count != 0) BG_TRY(devbits_prepare(c, col->validity, col->offset, col->length, col->residency, "validity", &out->v));
-    return 0;
-}
-
 // The value reducers over Boolean columns (aggs[at[.]]: Sum, ArithmeticMean, Min, Max, Count, First, Last, Mode): per column one
-// launch of bool_windows_kernel over the window row ranges for every reducer asked of it (kBoolMaxOuts outputs a launch).  8-byte
-// outputs go the way of every output (devout_prepare / devout_finish: values in place or through a temporary, validity through a
-// word-aligned working copy); a BOOLEAN output (First / Last / Mode) has ceil(W / 8) bytes of values like its validity, so both are
-// assembled in word-aligned temporaries and exactly those bytes copied on.  *ms: the kernels' bracket.
+// launch of bool_windows_kernel over the window row ranges for every reducer asked of it (kBoolMaxOuts outputs a launch).  Every
+// output goes through devout_prepare / devout_finish; a BOOLEAN one (First / Last / Mode) has bit-packed values.  *ms: the kernels' bracket.
 static int run_bools(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, const std::vector<int> &at, bowgpu_out *outs, WindowRows *wr, double *ms) {
     const bowgpu_col *cols = call.cols;
     const Plan &plan = call.plan;
     const int64_t n = cols[call.ts_col].length, W = plan.W;
-    const size_t vb = (size_t)((W + 7) >> 3), vwords_bytes = ((vb + 3) & ~(size_t)3) + 8;
     DevBuf counter;
     if (W > 0) {
         BG_TRY(window_rows_make(c, call, wr));
@@ -1797,7 +1463,6 @@ static int run_bools(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, const 
             P.nouts = (int32_t)grp.size();
         }
         std::vector<DevOut> douts(grp.size());
-        std::vector<DevBuf> bvals(grp.size()), bvalid(grp.size());
         std::vector<int> types(grp.size());
         for (size_t o = 0; o < grp.size(); o++) {
             const int i = grp[o];
@@ -1808,21 +1473,9 @@ static int run_bools(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, const 
             q.kind = aggs[i].kind;
             q.nfac = aggs[i].n_factors;
             for (int f = 0; f < aggs[i].n_factors; f++) q.fac[f] = aggs[i].factors[f];
-            if (t == BOWGPU_BOOLEAN) {
-                if (outs[i].length < W) return fail(BOWGPU_ERR_ARG, "output column has %lld slots, %lld needed", (long long)outs[i].length, (long long)W);
-                if (W == 0) continue;
-                if (!outs[i].values || !outs[i].validity) return fail(BOWGPU_ERR_ARG, "output column lacks a values or validity buffer");
-                if (outs[i].residency != BOWGPU_HOST && outs[i].residency != BOWGPU_DEVICE && outs[i].residency != BOWGPU_HOST_PINNED)
-                    return fail(BOWGPU_ERR_ARG, "unknown residency %d", outs[i].residency);
-                BG_TRY(bvals[o].alloc(vwords_bytes));
-                BG_TRY(bvalid[o].alloc(vwords_bytes));
-                q.values = bvals[o].p;
-                q.valid = bvalid[o].as<uint32_t>();
-            } else {
-                BG_TRY(devout_prepare(c, &outs[i], W, &douts[o], -1));
-                q.values = douts[o].values;
-                q.valid = reinterpret_cast<uint32_t *>(douts[o].validity);
-            }
+            BG_TRY(devout_prepare(c, &outs[i], W, &douts[o], -1, t == BOWGPU_BOOLEAN));
+            q.values = douts[o].values;
+            q.valid = reinterpret_cast<uint32_t *>(douts[o].validity);
         }
         unsigned long long null_windows = 0;
         if (W > 0) {
@@ -1839,22 +1492,7 @@ static int run_bools(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, const 
         for (size_t o = 0; o < grp.size(); o++) {
             const int i = grp[o];
             const int64_t nulls = kind_never_nil(aggs[i].kind) ? 0 : (int64_t)null_windows;
-            if (types[o] != BOWGPU_BOOLEAN) {
-                BG_TRY(devout_finish(c, &douts[o], W, types[o], nulls));
-                continue;
-            }
-            bowgpu_out *u = &outs[i];
-            u->length = W;
-            u->type = BOWGPU_BOOLEAN;
-            u->null_count = nulls;
-            if (W == 0) continue;
-            if (u->residency == BOWGPU_DEVICE) {
-                BG_HIP(hipMemcpyAsync(u->values, bvals[o].p, vb, hipMemcpyDeviceToDevice, c->stream));
-                BG_HIP(hipMemcpyAsync(u->validity, bvalid[o].p, vb, hipMemcpyDeviceToDevice, c->stream));
-            } else {
-                BG_TRY(copy_d2h(c, u->values, bvals[o].p, vb, u->residency == BOWGPU_HOST_PINNED));
-                BG_TRY(copy_d2h(c, u->validity, bvalid[o].p, vb, u->residency == BOWGPU_HOST_PINNED));
-            }
+            BG_TRY(devout_finish(c, &douts[o], W, types[o], nulls));
         }
         BG_HIP(hipStreamSynchronize(c->stream));   // (the temporaries of this launch go back to the block cache)
     }
@@ -2150,13 +1788,6 @@ int bowgpu_trim(int32_t all_threads, int64_t *bytes_freed) {
 
 // The range is registered as given.  A range that an earlier registration already covers is fine; one it covers only partly is
 // refused (two small buffers inside one page can do that: register the enclosing allocation instead).
-static bool host_range_mapped(const void *p) {
-    void *d = nullptr;
-    const bool ok = hipHostGetDevicePointer(&d, const_cast<void *>(p), 0) == hipSuccess && d;
-    if (!ok) (void)hipGetLastError();
-    return ok;
-}
-
 int bowgpu_host_register(void *ptr, int64_t bytes) {
     if (!ptr || bytes <= 0) return fail(BOWGPU_ERR_ARG, "null buffer / non-positive size");
     Ctx *c;
@@ -2165,7 +1796,7 @@ int bowgpu_host_register(void *ptr, int64_t bytes) {
     if (e == hipSuccess) return 0;
     (void)hipGetLastError();
     if (e == hipErrorHostMemoryAlreadyRegistered) {
-        if (host_range_mapped(ptr) && host_range_mapped(reinterpret_cast<char *>(ptr) + bytes - 1)) return 0;
+        if (host_mapped(ptr, "first byte's") && host_mapped(reinterpret_cast<char *>(ptr) + bytes - 1, "last byte's")) return 0;
         return fail(BOWGPU_ERR_ARG, "bowgpu_host_register: the range overlaps an earlier registration only partly");
     }
     return hip_fail(e, "hipHostRegister");

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/bowgpu.h"
+#include "bit_span.h"
 #include "debug_routes.h"
 
 namespace bowgpu {
@@ -115,9 +116,24 @@ struct DevBuf {
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
-// A column made device-resident: aliases the caller's pointers (BOWGPU_DEVICE) or owns an
-// uploaded copy (BOWGPU_HOST).  values_dev points at element `offset` already; validity is
-// kept as (aligned dword pointer, bit offset).
+// ---------------------------------------------------------------- dev_cols.cpp: caller buffers in and out of the device
+// the device address of registered host memory; nullptr: not registered - the error text says so, naming `what` (BOWGPU_ERR_ARG)
+const void *host_mapped(const void *p, const char *what);
+// n bits from bit `offset` of a caller's byte buffer - a validity bitmap, a Boolean column's values - as aligned 32-bit words on
+// the device, at any byte address and any offset: read in place (device, registered) or uploaded into `own` (pageable)
+struct DevBits {
+    const uint32_t *words = nullptr;   // 4-byte aligned
+    int64_t bit0 = 0;                  // bit index (from words) of row 0
+    int64_t nwords = 0;                // readable 32-bit words at `words`
+    DevBuf own;                        // .p: the bits were staged
+};
+int stage_bits(Ctx *c, const uint8_t *bytes, int64_t offset, int64_t n, int32_t residency, const char *what, DevBits *out);
+// a Boolean column's value bits and - where it has a bitmap to read - its validity bits (the 8-byte rule is for 8-byte values)
+struct DevBoolCol { DevBits t, v; };
+int devboolcol_prepare(Ctx *c, const bowgpu_col *col, DevBoolCol *out);
+
+// A column of 8-byte values made device-resident: aliases the caller's pointers (BOWGPU_DEVICE, BOWGPU_HOST_PINNED) or owns an
+// uploaded copy (BOWGPU_HOST).  values points at element `offset` already; validity is kept as stage_bits gives it.
 struct DevCol {
     const void *values = nullptr;      // element 0 of the logical array
     const uint32_t *vbits = nullptr;   // 4-byte aligned word containing bit `vbit0`
@@ -132,19 +148,21 @@ int devcol_prepare(Ctx *c, const bowgpu_col *col, DevCol *out, bool need_values,
 int count_nulls_device(Ctx *c, DevCol *dc);
 
 // An output column on the device: aliases the caller's buffers or owns temporaries that are
-// copied back by finish().
+// copied back by finish().  The validity is always a word-aligned working copy of temp_bits_bytes(); bit_values: the values are
+// bit-packed too (a BOOLEAN output) and assembled the same way, ceil(slots / 8) bytes of each copied back.
 struct DevOut {
     void *values = nullptr;
     uint8_t *validity = nullptr;
-    int64_t capacity = 0;
-    int pool_slot = -1;   // >= 0: the validity working copy comes from the context pool
+    bool bit_values = false;
     DevBuf own_values, own_validity;
     bowgpu_out *user = nullptr;
 };
 // copies of caller buffers: pageable ones through the context's pinned staging, registered ones (BOWGPU_HOST_PINNED) directly
 int copy_d2h(Ctx *c, void *dst, const void *src, size_t bytes, bool registered = false);
 int copy_h2d(Ctx *c, void *dst, const void *src, size_t bytes, bool registered = false);
-int devout_prepare(Ctx *c, bowgpu_out *out, int64_t slots, DevOut *d, int pool_slot = -1);
+void staged_memcpy(void *dst, const void *src, size_t n);   // the CPU side of those copies: large ones split over the helper threads
+// checks in this order: capacity, empty (nothing else is looked at), buffers, residency, alignment
+int devout_prepare(Ctx *c, bowgpu_out *out, int64_t slots, DevOut *d, int pool_slot = -1, bool bit_values = false);
 int devout_finish(Ctx *c, DevOut *d, int64_t slots, int32_t type, int64_t null_count, bool copy_bitmap = true);
 
 // ---------------------------------------------------------------- frame_cols.cpp: what the frame-level operations share on the host
@@ -158,7 +176,7 @@ struct MoveCols {                     // the columns of one launch, as gather_ke
     int64_t vbit0[kMoveCols];
     uint64_t *out_values[kMoveCols];
     unsigned long long *out_valid[kMoveCols];    // 8-byte aligned, ceil(count / 64) words (the working copy of devout_prepare,
-                                                 // ((ceil(count/8)+3)&~3)+4 bytes, always holds them)
+                                                 // temp_bits_bytes(ceil(count / 8)), always holds them)
 };
 // the context's small scratch block as these operations lay it out
 constexpr size_t kScrHist = 0;                         // Sort: [8][256] digit counts
@@ -219,10 +237,8 @@ int move_group_finish(Ctx *c, MoveGroup *g, const bowgpu_col *cols, int32_t g0, 
 
 // The one size rule of device temporaries that hold rows of a frame.  Values: 8 bytes a row + 16, the margin devcol_prepare's
 // uploads carry too, against the kernels' 16-byte loads (the sites this rule replaced added 0, 8 or 16; none is known to need it).
-// Bitmap: its bytes rounded up to whole 32-bit words + 16: the kernels that fill a frame store whole 32- or 64-bit validity words,
-// and a 64-bit word may begin at the last 32-bit word of the rows and be followed by a reader's look at the word behind it.
+// Bitmap: temp_bits_bytes() of bit_span.h.
 inline size_t temp_values_bytes(int64_t rows) { return (size_t)rows * 8 + 16; }
-inline size_t temp_bits_bytes(size_t bitmap_bytes) { return ((bitmap_bytes + 3) & ~(size_t)3) + 16; }
 // A frame of device temporaries: `rows` slots by ncols columns that live only in HBM, filled by one call (which takes `outs`)
 // and read by the next (which takes as_cols).  A caller whose fill writes bitmaps in place rounds `rows` up itself.
 struct DevFrame {
@@ -518,7 +534,7 @@ struct QuirkFix { int32_t naggs, _pad; QuirkFixAgg a[8]; };
 int launch_ts_quirk_fix(Ctx *c, const int64_t *ts, const uint32_t *tbits, int64_t tbit0, int64_t n, const struct NbrIndex &ix, int64_t s0, int64_t interval,
                         const MagicDiv &magic, int64_t W, const QuirkFix &fx, unsigned long long *d_fixed);
 int launch_count_to_f64(Ctx *c, uint64_t *v, const uint32_t *valid, int64_t n, int n_factors, const double *factors);   // (valid: W bits; the factors go onto the float64)
-int fetch_valid(Ctx *c, const bowgpu_col *col, int64_t row, int *valid);   // (api.cpp) validity bit of one row of a column, wherever it lives
+int fetch_valid(Ctx *c, const bowgpu_col *col, int64_t row, int *valid);   // (dev_cols.cpp) validity bit of one row of a column, wherever it lives
 // Rolling.Interpolate over an interval column with nulls: the kept rows compacted (ts_nulls.hip)
 constexpr int kMaxCompactCols = 16;
 struct CompactCols {

@@ -951,7 +951,7 @@ static int fill_finish(Ctx *c, FillParams &P, int64_t n, const DevCol &dfill, De
     P.n = n;
     P.out_values = reinterpret_cast<uint64_t *>(dout->values);
     // the kernel stores one whole 64-bit validity word per wavefront trip: ceil(n/64)*8 bytes, which the word-aligned working
-    // copy of devout_prepare (((ceil(n/8)+3)&~3)+4 bytes) always holds
+    // copy of devout_prepare (temp_bits_bytes(ceil(n/8))) always holds
     const bowgpu_out *u = dout->user;
     const bool place = n > 0 && u->residency == BOWGPU_DEVICE && (reinterpret_cast<uintptr_t>(u->validity) & 7) == 0 &&
                        ((u->length + 7) >> 3) >= 8 * ((n + 63) >> 6);   // (u->length: still the capacity the caller handed in)

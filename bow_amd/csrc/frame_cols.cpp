@@ -74,12 +74,7 @@ void out_empty(bowgpu_out *out, int32_t type) {
 int aux_in(Ctx *c, const void *p, size_t bytes, int32_t residency, const char *what, const void **dptr, DevBuf *own) {
     *dptr = p;
     if (residency == BOWGPU_HOST_PINNED) {
-        void *dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, const_cast<void *>(p), 0) != hipSuccess || !dp) {
-            (void)hipGetLastError();
-            return fail(BOWGPU_ERR_ARG, "BOWGPU_HOST_PINNED: the %s buffer is not registered (bowgpu_host_register)", what);
-        }
-        *dptr = dp;
+        if (!(*dptr = host_mapped(p, what))) return BOWGPU_ERR_ARG;
     } else if (residency == BOWGPU_HOST) {
         BG_TRY(own->alloc(bytes));
         BG_TRY(copy_h2d(c, own->p, p, bytes));
@@ -201,10 +196,10 @@ int stage_rows(Ctx *c, int dst_dev, int src_dev, const bowgpu_col &sc, int64_t a
     *out = device_col(values->p, b - a, sc.type);
     out->offset = r0 - v0;
     if (has_bitmap(sc)) {
-        const int64_t b0 = r0 >> 3, b1 = (r1 + 7) >> 3;
-        BG_TRY(bits->alloc(temp_bits_bytes((size_t)(b1 - b0))));
+        const BitBytes src = bit_bytes(r0, r1 - r0);   // (stage_bits' upload, but the source may be another device)
+        BG_TRY(bits->alloc(temp_bits_bytes(src.count)));
         BG_HIP(hipMemsetAsync(bits->p, 0, bits->bytes, c->stream));
-        BG_TRY(pull_bytes(c, dst_dev, src_dev, bits->p, sc.validity + b0, (size_t)(b1 - b0), sc.residency));
+        BG_TRY(pull_bytes(c, dst_dev, src_dev, bits->p, sc.validity + src.first, src.count, sc.residency));
         out->validity = bits->as<const uint8_t>();
         out->null_count = -1;
     }

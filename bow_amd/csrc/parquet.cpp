@@ -534,7 +534,7 @@ static int parquet_read_column_impl(bowgpu_parquet *handle, int32_t i, bowgpu_ou
     unsigned long long *dcnt = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(dscr) + 1024);
     BG_HIP(hipMemsetAsync(status, 0, 64, c->stream));
     BG_HIP(hipMemsetAsync(dcnt, 0, 8, c->stream));
-    BG_HIP(hipMemsetAsync(dout.validity, 0, (size_t)(((n + 7) >> 3) + 3) & ~(size_t)3, c->stream));
+    BG_HIP(hipMemsetAsync(dout.validity, 0, temp_bits_bytes((size_t)((n + 7) >> 3)), c->stream));
     void *d_idx = nullptr, *d_exp = nullptr;   // 4 B / 8 B per row of workspace, taken only when a page needs it (a chunk may mix encodings)
     if (walk.kinds & 2u) BG_TRY(ctx_pool(c, kPoolInterp + 3, (size_t)n * 4 + 32, &d_idx));
     if (walk.kinds & (8u | 16u)) BG_TRY(ctx_pool(c, kPoolInterp + 4, (size_t)n * 8 + 32, &d_exp));

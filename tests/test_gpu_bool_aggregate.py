@@ -8,6 +8,7 @@ import pytest
 from bow_amd import capi
 from oracle import pyoracle as orc
 from bool_agg_common import BOOL_RESULT, TIME_AGGS, VALUE_AGGS, bool_cols, compare_exact, pack
+from staging_common import Shifted
 
 pytestmark = pytest.mark.gpu
 
@@ -103,16 +104,6 @@ def test_one_window_of_20000_rows():
         assert outs[0].length == 1
 
 
-class Shifted(capi.DeviceBuffer):
-    """`shift` bytes into a device buffer: a device pointer at an odd byte address"""
-
-    def __init__(self, base, shift):
-        self.base, self.ptr, self.nbytes = base, base.ptr + shift, base.nbytes - shift
-
-    def free(self):
-        self.ptr = None
-
-
 @pytest.mark.parametrize("shift", [1, 3, 6])
 def test_device_pointers_at_odd_byte_addresses(shift):
     rng = np.random.default_rng(7 + shift)
@@ -137,6 +128,11 @@ def guarded_outs(W, count, residency):
         if residency == capi.DEVICE:
             o.values = capi.DeviceBuffer.from_numpy(np.full(W * 8 + 64, 0x5A, np.uint8))
             o.validity = capi.DeviceBuffer.from_numpy(np.full(nb + 64, 0xA5, np.uint8))
+        elif residency == capi.HOST_PINNED:   # (registered here, unregistered when the OutColumn goes)
+            o.values = capi.page_aligned(W + 8, np.uint64, 0x5A5A5A5A5A5A5A5A)
+            o.validity = capi.page_aligned(nb + 64, np.uint8, 0xA5)
+            capi.host_register(o.values)
+            capi.host_register(o.validity)
         else:
             o.values = np.full(W + 8, 0x5A5A5A5A5A5A5A5A, np.uint64)
             o.validity = np.full(nb + 64, 0xA5, np.uint8)
@@ -156,8 +152,8 @@ def check_guards(label, W, outs):
         assert (b[nb:] == 0xA5).all(), (label, i, "validity written past byte %d" % nb)
 
 
-@pytest.mark.parametrize("W", [1, 63, 64, 65, 1000])
-@pytest.mark.parametrize("residency", [capi.HOST, capi.DEVICE])
+@pytest.mark.parametrize("W", [1, 7, 8, 9, 31, 32, 33, 63, 64, 65, 1000])
+@pytest.mark.parametrize("residency", [capi.HOST, capi.DEVICE, capi.HOST_PINNED])
 def test_nothing_past_the_last_byte(W, residency):
     rng = np.random.default_rng(W)
     lens = [int(x) for x in rng.integers(0, 6, W)]
