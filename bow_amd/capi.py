@@ -166,6 +166,7 @@ SYMBOLS = [
     "bowgpu_valid_mask", "bowgpu_drop_nils", "bowgpu_diff", "bowgpu_distinct",
     "bowgpu_append", "bowgpu_find_next",
     "bowgpu_join_rows", "bowgpu_join",
+    "bowgpu_convert",
 ]
 
 _lib = None
@@ -1089,6 +1090,22 @@ def diff(cols, col_idx=None, out_residency=HOST, outs=None, capacity=None):
         oarr[i] = o.c()
     iarr, n_idx = _col_idx(col_idx)
     check(lib().bowgpu_diff(_cols(cols), len(cols), iarr, n_idx, oarr))
+    for i, o in enumerate(outs):
+        o.absorb(oarr[i])
+    return outs
+
+
+def convert(cols, to_types, out_residency=HOST, outs=None):
+    """Bow.Convert (bowgpu_convert) -> list[OutColumn]: outs[i] = cols[i] converted to to_types[i] (INT64 / FLOAT64 / BOOLEAN or
+    their names); the columns need not have equal lengths"""
+    types = [TYPE_NAMES[t] if isinstance(t, str) else t for t in to_types]
+    if outs is None:
+        outs = [OutColumn(c.length, out_residency) for c in cols]
+    oarr = (Out * max(len(outs), 1))()
+    for i, o in enumerate(outs):
+        oarr[i] = o.c()
+    tarr = (C.c_int32 * max(len(types), 1))(*types)
+    check(lib().bowgpu_convert(_cols(cols), tarr, len(cols), oarr))
     for i, o in enumerate(outs):
         o.absorb(oarr[i])
     return outs

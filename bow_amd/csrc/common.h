@@ -835,6 +835,28 @@ int launch_diff(Ctx *c, const DiffArgs &a);
 // s: n keys in non-descending order of Buffer.Less (raw Int64 / Float64 payloads, no NaN); flags the last row of each group of equals
 int launch_distinct_tail(Ctx *c, const uint64_t *s, int64_t n, int is_float, const TileRecords &t);
 
+// convert.hip: Bow.Convert among Int64, Float64 and Boolean (host side: convert_api.cpp).  One launch takes up to kMoveCols columns,
+// each with its own length and its own (source, target) pair.
+constexpr int kConvertShards = 64;       // a column's count of valid rows is added up in this many words: thousands of waves adding
+                                         // into ONE word are served one after the other, ~10 ns each, and that tail outlasts a bitmap copy
+struct ConvertCol {
+    const void *src;                     // row 0 of the 8-byte values; a Boolean source: the aligned words of its value bits
+    int64_t sbit0, swords;               // a Boolean source: bit index (from src) of row 0, readable 32-bit words at src
+    const uint32_t *vbits;               // nullptr: no nulls
+    int64_t vbit0, vwords;
+    void *out_values;                    // 8-byte slots; a Boolean target: ceil(n / 64) 64-bit words, every one stored whole
+    unsigned long long *out_valid;       // ceil(n / 64) words, every one stored whole (the working copy of devout_prepare)
+    int64_t n;
+    int32_t from, to;                    // BOWGPU_INT64 | BOWGPU_FLOAT64 | BOWGPU_BOOLEAN
+};
+struct ConvertArgs {
+    ConvertCol col[kMoveCols];
+    unsigned long long *valid_counts;    // [kMoveCols][kConvertShards], zeroed by the host: valid rows of each column, to be summed
+    int64_t max_n;                       // the longest column of the launch
+    int32_t ncols, _pad;
+};
+int launch_convert(Ctx *c, const ConvertArgs &a);
+
 // append.hip: AppendBows / Bow.Find - the concatenation of the pieces of a frame and the linear search of a column (host side:
 // append_api.cpp)
 struct AppendPiece {                     // one piece of one column, addressed by OUTPUT row

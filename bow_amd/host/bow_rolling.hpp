@@ -2,7 +2,8 @@
 //
 // The reference is Go (no Go toolchain in this image), so the host side above include/bowgpu.h is
 // written in C++ with the SAME names, argument meaning and error strings as the reference:
-//   bow::Bow / Series / Type, AppendBows       <- bow.go, bowseries.go, bowtypes.go, bowappend.go, bowfind.go, bowjoin.go
+//   bow::Bow / Series / Type, AppendBows       <- bow.go, bowseries.go, bowtypes.go, bowappend.go, bowfind.go, bowjoin.go,
+//                                                  bowsetters.go (Filter, Convert)
 //   bow::rolling::IntervalRolling, Rolling, Options, Window, ColAggregation, NewColAggregation,
 //        ColInterpolation, NewColInterpolation  <- rolling/rolling.go, window.go, aggregation.go, interpolation.go
 //   bow::rolling::aggregation::{WindowStart,Sum,ArithmeticMean,Min,Max,Count,First,Last,Mode,IntegralStep,
@@ -284,6 +285,9 @@ class Bow : public std::enable_shared_from_this<Bow> {
     std::pair<BowPtr, Error> DropNils(std::vector<int> colIndices = {}) const;
     std::pair<BowPtr, Error> Diff(std::vector<int> colIndices = {}) const;
     std::pair<BowPtr, Error> Distinct(int colIndex) const;
+    // Convert: bowsetters.go:52-56 (device, among Int64, Float64 and Boolean): the receiver with that column converted, names kept as
+    // Apply keeps them.  A String source or target is an Error that says so: the reference's own loop serves those.
+    std::pair<BowPtr, Error> Convert(int colIndex, Type t) const;
     // Find / FindNext / Contains: bowfind.go:3-32 (device).  nil finds the first null row, whatever rowIndex says, as the reference
     // does; a value boxed as another type than the column's finds nothing, without a device call (bowfind_test.go:31-32).  A failed
     // device call (e.g. no device) finds nothing: the reference's signature has no error to carry it.
@@ -493,7 +497,7 @@ inline RowCmp Bow::MakeFilterValuesV(int colIndex, const std::vector<FilterArg> 
     r.col = colIndex;
     r.typ = ColumnType(colIndex);
     for (const FilterArg &a : values) {
-        const Value v = Convert(r.typ, a);
+        const Value v = bow::Convert(r.typ, a);   // (Type.Convert of one value: the member of the same name is the column's)
         if (!v) { r.match_null = true; continue; }
         uint64_t bits;
         if (r.typ == Type::Int64) { const int64_t x = std::get<int64_t>(*v); memcpy(&bits, &x, 8); }
@@ -607,6 +611,22 @@ inline std::pair<BowPtr, Error> Bow::Distinct(int colIndex) const {
     if (nd == 0) { o.length = 0; o.null_count = 0; o.type = c.type; }   // (nothing was written)
     auto out = std::make_shared<Bow>();
     out->cols.push_back(st.ToSeries(cols[colIndex].Name, o));
+    return {out, Error()};
+}
+
+inline std::pair<BowPtr, Error> Bow::Convert(int colIndex, Type t) const {
+    if (colIndex < 0 || colIndex > NumCols() - 1) return {nullptr, Errorf("no column '" + std::to_string(colIndex) + "'")};
+    if (cols[colIndex].typ == Type::String || t == Type::String)
+        return {nullptr, Errorf("Convert: a String source or target is not served by the device path (" + TypeString(cols[colIndex].typ) + " to " +
+                                TypeString(t) + ")")};
+    const bowgpu_col c = ArrowCol(colIndex);   // (a Boolean series goes in as Arrow bits)
+    const int32_t to = (int32_t)t;
+    detail::OutStore st;
+    bowgpu_out o = st.Make(NumRows());
+    const int rc = bowgpu_convert(&c, &to, 1, &o);
+    if (rc) return {nullptr, detail::AbiError(rc)};
+    auto out = std::make_shared<Bow>(*this);
+    out->cols[colIndex] = st.ToSeries(cols[colIndex].Name, o);
     return {out, Error()};
 }
 

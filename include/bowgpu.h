@@ -43,6 +43,8 @@ extern "C" {
  * row-range shards held on several devices; no existing struct changed. */
 /* (still 14): bowgpu_parquet_write, with the bowgpu_parquet_write_options and bowgpu_parquet_write_info structs, added under the same
  * version: a new entry point and two new structs, nothing existing changed its layout or meaning. */
+/* (still 14): bowgpu_convert (Bow.Convert among Int64, Float64 and Boolean) added under the same version: a new entry point, no struct
+ * added or changed. */
 #define BOWGPU_ABI_VERSION 14
 
 /* bow.Type (reference bowtypes.go:17-32) */
@@ -51,7 +53,8 @@ enum {
     BOWGPU_FLOAT64 = 1,
     BOWGPU_INT64 = 2,
     BOWGPU_BOOLEAN = 3,            /* Arrow bit-packed values.  Accepted as a VALUE column of bowgpu_rolling_aggregate and
-                                      bowgpu_rolling_aggregate_planned (see there); every other entry point declines it */
+                                      bowgpu_rolling_aggregate_planned (see there) and as source or target of bowgpu_convert; every
+                                      other entry point declines it */
     BOWGPU_STRING = 4,             /* not accepted by the device path */
     BOWGPU_INPUT_DEPENDENT = 5,
     BOWGPU_ITERATOR_DEPENDENT = 6
@@ -100,7 +103,7 @@ typedef struct bowgpu_col {
     int64_t offset;           /* arrow Data.Offset(): slices share buffers (bow.go:279-283) */
     int64_t length;           /* Data.Len() */
     int64_t null_count;       /* Data.NullN(); -1 = unknown (the library counts) */
-    int32_t type;             /* BOWGPU_FLOAT64 | BOWGPU_INT64 | BOWGPU_BOOLEAN (Rolling.Aggregate value columns only) */
+    int32_t type;             /* BOWGPU_FLOAT64 | BOWGPU_INT64 | BOWGPU_BOOLEAN (Rolling.Aggregate value columns, bowgpu_convert) */
     int32_t residency;        /* BOWGPU_HOST | BOWGPU_DEVICE | BOWGPU_HOST_PINNED */
 } bowgpu_col;
 
@@ -731,6 +734,38 @@ int bowgpu_diff(const bowgpu_col *cols, int32_t ncols, const int32_t *col_idx, i
  * permutation; then bowgpu_filter_mask's workspace for the flags.  A column in order (sort.IsSorted) and without nulls takes only that
  * last part: it is read twice and nothing is sorted. */
 int bowgpu_distinct(const bowgpu_col *col, bowgpu_out *out, int64_t *n_distinct);
+
+/* ---- Bow.Convert ---------------------------------------------------------------------- */
+
+/* Bow.Convert (bowsetters.go:52-56; Type.Convert, bowtypes.go:64-81; bowconvert.go) for ncols columns in one call:
+ * outs[i] = cols[i] converted to to_types[i].  Source and target type are each BOWGPU_INT64, BOWGPU_FLOAT64 or BOWGPU_BOOLEAN - all nine
+ * pairs, a different pair per column if wanted; this is the entry point that takes a Boolean column from, and brings one to, the
+ * entry points that decline it.  The conventions are those of the other frame entry points: ONE device, any residency per column and
+ * per output (BOWGPU_HOST staged through HBM at most 4 columns at a time, BOWGPU_HOST_PINNED and BOWGPU_DEVICE read where they lie),
+ * per-thread contexts and streams; bowgpu_set_devices does not apply.  Any Arrow offset, bit offsets that are no multiple of 8
+ * included, for the validity and for a Boolean column's value bits; validity NULL, or null_count 0 (the bitmap is not read) or -1.  The
+ * columns need not have equal lengths (Convert has no frame rule); each outs[i].length on entry is a capacity >= cols[i].length.
+ * outs[i] must not overlap cols[i]: an output that overlaps an input is not supported.
+ *   THE RESULT is what Apply builds - NewBuffer, then SetOrDropStrict(i, t.Convert(GetValue(i))) per row.  A null row stays null and
+ * its slot holds 0 (a clear bit), whatever the input's slot held; a valid row stays valid (among these three types Convert cannot
+ * fail): the output's validity is the input's re-based to bit 0, null_count the input's count of nulls (counted in the same pass),
+ * type the target, length the column's.  A BOOLEAN output follows bowgpu_out's rule: ceil(n / 8) bytes of values, padding bits clear
+ * in both buffers, no byte past ceil(n / 8) written.  Per valid row:
+ *     Int64   -> Float64  Go's float64(v): round to nearest, ties to even          Int64 -> Boolean    v != 0
+ *     Float64 -> Int64    Go's int64(v) AS gc/amd64 GIVES IT: truncation toward zero where -2^63 <= v < 2^63; for NaN, +-Inf and
+ *                         everything outside that range 0x8000000000000000 (INT64_MIN).  Go leaves the out-of-range result
+ *                         implementation-defined; the project follows gc on amd64, as it does for -ffp-contract.
+ *     Float64 -> Boolean  v != 0.0: a NaN is true, -0.0 is false                    Boolean -> Int64    1 / 0
+ *     Boolean -> Float64  1.0 / 0.0                                                 same type           the same bits (a NaN keeps its payload)
+ *   ERRORS, all before any device is touched: a source or target of BOWGPU_STRING is BOWGPU_ERR_UNSUPPORTED (the reference's own loop
+ * serves those); any other type code, a null argument with ncols > 0, a negative length or offset, an unknown residency or a
+ * capacity below the column's length is BOWGPU_ERR_ARG.  ncols == 0 returns 0; columns without rows give empty outputs of the target
+ * types without a device; a well-formed call with rows is BOWGPU_ERR_NO_DEVICE on a box without a GPU - no CPU fallback.
+ *   THE METHOD (bow_amd/csrc/convert.hip): one streaming pass, up to 4 columns a launch; 16-byte loads and stores of the 8-byte values,
+ * bits read and written as whole words, the valid rows counted on the way.  No workgroup waits on another; the same call gives the
+ * same bytes.  HBM WORKSPACE: none beyond the staged copies of BOWGPU_HOST columns, the device temporaries of host-resident outputs
+ * and the working copies of the output bitmaps (1/8 byte per row; a Boolean output's values likewise), at most 4 columns at a time. */
+int bowgpu_convert(const bowgpu_col *cols, const int32_t *to_types, int32_t ncols, bowgpu_out *outs);
 
 /* ---- AppendBows / Bow.Find / FindNext / Contains -------------------------------------- */
 
