@@ -167,6 +167,7 @@ SYMBOLS = [
     "bowgpu_append", "bowgpu_find_next",
     "bowgpu_join_rows", "bowgpu_join",
     "bowgpu_convert",
+    "bowgpu_parquet_write_codec",
 ]
 
 _lib = None
@@ -1295,10 +1296,14 @@ class ParquetFile:
         self.close()
 
 
-def write_parquet(path, cols, names, page_rows=0, row_group_rows=0, encodings=None, statistics=True, metadata=None, reserved=0):
+PARQUET_CODEC_UNCOMPRESSED, PARQUET_CODEC_SNAPPY = 0, 1   # Parquet CompressionCodec values bowgpu_parquet_write_codec takes
+
+
+def write_parquet(path, cols, names, page_rows=0, row_group_rows=0, encodings=None, statistics=True, metadata=None, reserved=0, codec=0):
     """bowgpu_parquet_write: the frame `cols` (Int64 / Float64 Columns of any residency) as the Parquet file `path`, encoded on the
     device.  encodings: None (PLAIN everywhere) or one Parquet Encoding per column (PARQUET_PLAIN / PARQUET_DELTA_BINARY_PACKED);
-    metadata: a dict (or a list of pairs) for the footer's key_value_metadata.  Returns the ParquetWriteInfo."""
+    metadata: a dict (or a list of pairs) for the footer's key_value_metadata; codec: 0, or another Parquet CompressionCodec
+    (PARQUET_CODEC_SNAPPY: pages compressed on the device) through bowgpu_parquet_write_codec.  Returns the ParquetWriteInfo."""
     o = ParquetWriteOptions()
     o.row_group_rows, o.page_rows, o.statistics, o.reserved = row_group_rows, page_rows, 1 if statistics else 0, reserved
     if encodings is not None:
@@ -1311,7 +1316,10 @@ def write_parquet(path, cols, names, page_rows=0, row_group_rows=0, encodings=No
         o.meta_keys, o.meta_values, o.n_meta = C.cast(keys, C.POINTER(C.c_char_p)), C.cast(vals, C.POINTER(C.c_char_p)), len(pairs)
     cnames = (C.c_char_p * max(len(names), 1))(*[None if nm is None else nm.encode() for nm in names])
     info = ParquetWriteInfo()
-    check(lib().bowgpu_parquet_write(os.fsencode(path), _cols(cols), cnames, len(cols), C.byref(o), C.byref(info)))
+    if codec == 0:
+        check(lib().bowgpu_parquet_write(os.fsencode(path), _cols(cols), cnames, len(cols), C.byref(o), C.byref(info)))
+    else:
+        check(lib().bowgpu_parquet_write_codec(os.fsencode(path), _cols(cols), cnames, len(cols), C.byref(o), C.c_int32(codec), C.byref(info)))
     return info
 
 

@@ -11,6 +11,7 @@
 //   pq_delta_pages_kernel   one thread per page: where the page's body lies in the values image, its header, its byte count
 //   pq_delta_pack_kernel    one wavefront per block: the block's bytes assembled in LDS - one lane per 32-bit word of a miniblock,
 //                           built from the remainders that overlap it - and stored with aligned 8-byte stores, bytes at the edges
+//   (codec SNAPPY: the values sections stay on the device and snappy_encode.hip compresses them there - pq_snappy_chunk)
 //
 // No atomics, no workgroup waits on another, every byte of the output is a function of the input alone.  Nothing reads or
 // writes global memory unaligned: a block body starts at an arbitrary byte of the image, so its LDS copy is laid out at the same
@@ -302,7 +303,11 @@ int compact_valid(Ctx *c, const DevCol &dk, MaskWork *w, DevBuf *vals, DevBuf *b
 
 }  // namespace
 
-int pq_encode_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, int32_t page_rows, int32_t encoding, bool minmax, PqEncChunk *out) {
+// snappy_encode.hip
+int pq_snappy_chunk(Ctx *c, const uint8_t *image, const std::vector<int64_t> &off, const std::vector<int64_t> &len, PqHostBytes *out,
+                    std::vector<int64_t> *coff, std::vector<int64_t> *clen);
+
+int pq_encode_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, int32_t page_rows, int32_t encoding, int32_t codec, bool minmax, PqEncChunk *out) {
     const int64_t n = b - a, npages = (n + page_rows - 1) / page_rows;
     const size_t page_level_bytes = (size_t)page_rows >> 3;
     const bool is_float = col.type == BOWGPU_FLOAT64;
@@ -366,12 +371,16 @@ int pq_encode_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, int32_t
         BG_TRY(copy_d2h(c, rec.data(), d_rec.p, rec.size() * 8));
     }
 
-    // ---- the values sections
+    // ---- the values sections: brought back as they are, or (kPqSnappy) left on the device for the codec
+    const bool snappy = codec == kPqSnappy;
+    const uint8_t *d_sections = reinterpret_cast<const uint8_t *>(dense);
     std::vector<int64_t> voff((size_t)npages), vlen((size_t)npages);
     DevBuf d_pages, d_min, d_widths, d_bytes, d_sums, d_info, d_image;
     if (encoding == kPqEncPlain) {
-        BG_TRY(copy_d2h(c, out->values.take((size_t)m * 8), dense, (size_t)m * 8));
-        BG_HIP(hipStreamSynchronize(c->stream));
+        if (!snappy) {
+            BG_TRY(copy_d2h(c, out->values.take((size_t)m * 8), dense, (size_t)m * 8));
+            BG_HIP(hipStreamSynchronize(c->stream));
+        }
         int64_t v0 = 0;
         for (int64_t p = 0; p < npages; p++) {
             voff[(size_t)p] = 8 * v0;
@@ -426,9 +435,14 @@ int pq_encode_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, int32_t
             if ((size_t)(voff[(size_t)p] + vlen[(size_t)p]) > used) used = (size_t)(voff[(size_t)p] + vlen[(size_t)p]);
         }
         if (used > image_bytes) return fail(BOWGPU_ERR_HIP, "parquet: a page's values section lies outside the image");
-        BG_TRY(copy_d2h(c, out->values.take(used), d_image.p, used));
-        BG_HIP(hipStreamSynchronize(c->stream));
+        if (!snappy) {
+            BG_TRY(copy_d2h(c, out->values.take(used), d_image.p, used));
+            BG_HIP(hipStreamSynchronize(c->stream));
+        }
+        d_sections = d_image.as<const uint8_t>();
     }
+    std::vector<int64_t> coff, clen;
+    if (snappy) BG_TRY(pq_snappy_chunk(c, d_sections, voff, vlen, &out->comp, &coff, &clen));   // (returns with the stream drained)
 
     if (!rec.empty()) {   // (behind a synchronise in both branches)
         bool any = false;
@@ -461,8 +475,10 @@ int pq_encode_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, int32_t
         pg.rows = (int32_t)(p + 1 < npages ? page_rows : n - p * page_rows);
         pg.valid = (int32_t)counts[(size_t)p];
         pg.level_bits = mixed ? h_levels + (size_t)p * page_level_bytes : nullptr;
-        pg.values = out->values.take(0) + voff[(size_t)p];
+        pg.values = snappy ? nullptr : out->values.take(0) + voff[(size_t)p];
         pg.value_bytes = vlen[(size_t)p];
+        pg.comp = snappy ? out->comp.take(0) + coff[(size_t)p] : nullptr;
+        pg.comp_bytes = snappy ? clen[(size_t)p] : 0;
     }
     return 0;
 }

@@ -5,7 +5,10 @@
 // else of the library; with BOWGPU_PARQUET_ASSEMBLE_ONLY defined this file is that alone (tests/cpp/test_parquet_assemble.cpp).
 //
 // The file: format version 1, root `Schema`, every column OPTIONAL (bowparquet.go:190), INT64 / DOUBLE, UNCOMPRESSED, data page
-// v1, definition levels as RLE / bit-packed hybrid of bit width 1, PLAIN or DELTA_BINARY_PACKED values.
+// v1, definition levels as RLE / bit-packed hybrid of bit width 1, PLAIN or DELTA_BINARY_PACKED values.  With codec SNAPPY
+// (bowgpu_parquet_write_codec; the reference's codec, bowparquet.go:326-338) a page's section is one raw Snappy stream of
+// [4-byte levels length | levels | values]: the preamble and the levels literal are written here, the values' elements come from
+// snappy_encode.hip as they lie.
 #include <errno.h>
 #include <fcntl.h>
 #include <stdio.h>
@@ -147,20 +150,39 @@ int PqWriter::begin_row_group(int64_t rows) {
     return 0;
 }
 
-int PqWriter::add_chunk(int32_t encoding, const PqwPage *pages, int64_t npages, const PqwStats &stats) {
+int PqWriter::add_chunk(int32_t encoding, const PqwPage *pages, int64_t npages, const PqwStats &stats, int32_t codec) {
+    if (codec != kPqUncompressed && codec != kPqSnappy) { err_ = "parquet: the writer has no codec " + std::to_string(codec); drop(); return -1; }
     Group &g = groups_.back();
-    Chunk ch{encoding, pos_, 0, 0, stats};
+    Chunk ch{encoding, codec, pos_, 0, 0, 0, stats};
     std::vector<uint8_t> head;
     for (int64_t p = 0; p < npages; p++) {
         const PqwPage &pg = pages[p];
         std::vector<uint8_t> lv;
         put_levels(&lv, pg);
         const int64_t body = (int64_t)lv.size() + pg.value_bytes;
+        const uint8_t *values = pg.values;
+        int64_t value_bytes = pg.value_bytes;
+        if (codec == kPqSnappy) {   // the preamble and the levels section as a literal in front of it; the values' stream follows
+            TWriter s;
+            s.varint((uint64_t)body);
+            const size_t n = lv.size();   // 4 + a run header + at most 128 KiB of bits: the 3-byte length form at the most
+            if (n - 1 >= (1u << 24)) { err_ = "parquet: a page's levels section of " + std::to_string(n) + " bytes does not fit a literal"; drop(); return -1; }
+            if (n <= 60) s.byte((uint8_t)((n - 1) << 2));
+            else {
+                const int k = n <= 256 ? 1 : n <= 65536 ? 2 : 3;
+                s.byte((uint8_t)((59 + k) << 2));
+                for (int j = 0; j < k; j++) s.byte((uint8_t)((n - 1) >> (8 * j)));
+            }
+            s.b.insert(s.b.end(), lv.begin(), lv.end());
+            lv.swap(s.b);
+            values = pg.comp;
+            value_bytes = pg.comp_bytes;
+        }
         TWriter w;
         w.open_struct();
         w.i32(1, 0);                  // DATA_PAGE
         w.i32(2, (int32_t)body);      // uncompressed_page_size
-        w.i32(3, (int32_t)body);      // compressed_page_size
+        w.i32(3, (int32_t)((int64_t)lv.size() + value_bytes));   // compressed_page_size
         w.open_struct(5);             // DataPageHeader
         w.i32(1, pg.rows);            //   num_values: rows, nulls included
         w.i32(2, encoding);
@@ -169,16 +191,17 @@ int PqWriter::add_chunk(int32_t encoding, const PqwPage *pages, int64_t npages, 
         w.close_struct();
         w.close_struct();
         head = w.b;
+        ch.raw += (int64_t)head.size() + body;
         head.insert(head.end(), lv.begin(), lv.end());
         if (put(head.data(), head.size()) != 0) return -1;
-        if (pg.value_bytes > 0 && put(pg.values, (size_t)pg.value_bytes) != 0) return -1;
+        if (value_bytes > 0 && put(values, (size_t)value_bytes) != 0) return -1;
         ch.values += pg.rows;
-        tot_.level_bytes += (int64_t)lv.size();
+        tot_.level_bytes += body - pg.value_bytes;
         tot_.value_bytes += pg.value_bytes;
     }
     tot_.data_pages += npages;
     ch.bytes = pos_ - ch.offset;
-    g.bytes += ch.bytes;
+    g.bytes += ch.raw;
     g.chunks.push_back(ch);
     return 0;
 }
@@ -224,9 +247,9 @@ int PqWriter::finish(PqwTotals *totals) {
             w.list(3, 8, 1);              //   path_in_schema
             w.varint(names_[i].size());
             w.b.insert(w.b.end(), names_[i].begin(), names_[i].end());
-            w.i32(4, 0);                  //   UNCOMPRESSED
+            w.i32(4, ch.codec);           //   UNCOMPRESSED / SNAPPY
             w.i64(5, ch.values);
-            w.i64(6, ch.bytes);
+            w.i64(6, ch.raw);             //   total_uncompressed_size, total_compressed_size: the page headers count in both
             w.i64(7, ch.bytes);
             w.i64(9, ch.offset);          //   data_page_offset
             w.open_struct(12);            //   Statistics
@@ -286,7 +309,8 @@ int PqWriter::finish(PqwTotals *totals) {
 
 namespace bowgpu {
 // parquet_encode.hip: rows [a, b) of one column as the pages of one column chunk, encoded on the device and brought back once
-int pq_encode_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, int32_t page_rows, int32_t encoding, bool minmax, PqEncChunk *out);
+// (codec kPqSnappy: the values sections stay on the device and their Snappy streams come back instead, snappy_encode.hip)
+int pq_encode_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, int32_t page_rows, int32_t encoding, int32_t codec, bool minmax, PqEncChunk *out);
 }
 
 using namespace bowgpu;
@@ -332,9 +356,12 @@ int write_checks(const char *path, const bowgpu_col *cols, const char *const *na
     return 0;
 }
 
-int write_impl(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols, const bowgpu_parquet_write_options *o, bowgpu_parquet_write_info *info) {
+int write_impl(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols, const bowgpu_parquet_write_options *o, int32_t codec,
+               bowgpu_parquet_write_info *info) {
     WritePlan plan;
     BG_TRY(write_checks(path, cols, names, ncols, o, &plan));
+    if (codec != kPqUncompressed && codec != kPqSnappy)
+        return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: compression codec %d (UNCOMPRESSED = 0 and SNAPPY = 1 are written)", codec);
     Ctx *c;
     BG_TRY(ctx_get(&c));
     PqWriter w;
@@ -345,8 +372,8 @@ int write_impl(const char *path, const bowgpu_col *cols, const char *const *name
         const int64_t b = a + plan.rg_rows < plan.n ? a + plan.rg_rows : plan.n;
         if (w.begin_row_group(b - a) != 0) return fail(BOWGPU_ERR_ARG, "%s", w.error().c_str());
         for (int i = 0; i < ncols; i++) {
-            BG_TRY(synced(c, pq_encode_chunk(c, cols[i], a, b, plan.page_rows, plan.enc[(size_t)i], plan.statistics, &ch)));
-            if (w.add_chunk(plan.enc[(size_t)i], ch.pages.data(), (int64_t)ch.pages.size(), ch.stats) != 0) return fail(BOWGPU_ERR_ARG, "%s", w.error().c_str());
+            BG_TRY(synced(c, pq_encode_chunk(c, cols[i], a, b, plan.page_rows, plan.enc[(size_t)i], codec, plan.statistics, &ch)));
+            if (w.add_chunk(plan.enc[(size_t)i], ch.pages.data(), (int64_t)ch.pages.size(), ch.stats, codec) != 0) return fail(BOWGPU_ERR_ARG, "%s", w.error().c_str());
         }
         if (w.end_row_group() != 0) return fail(BOWGPU_ERR_ARG, "%s", w.error().c_str());
     }
@@ -368,7 +395,14 @@ int write_impl(const char *path, const bowgpu_col *cols, const char *const *name
 extern "C" int bowgpu_parquet_write(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols,
                                     const bowgpu_parquet_write_options *opts, bowgpu_parquet_write_info *info) {
     // (no C++ exception may cross the C ABI; the writer's destructor has removed the temporary by the time one is caught)
-    try { return write_impl(path, cols, names, ncols, opts, info); }
+    try { return write_impl(path, cols, names, ncols, opts, kPqUncompressed, info); }
+    catch (const std::bad_alloc &) { return fail(BOWGPU_ERR_OOM, "parquet: out of host memory while writing '%s'", path); }
+    catch (const std::exception &e) { return fail(BOWGPU_ERR_ARG, "parquet: writing '%s' failed (%s)", path, e.what()); }
+}
+
+extern "C" int bowgpu_parquet_write_codec(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols,
+                                          const bowgpu_parquet_write_options *opts, int32_t codec, bowgpu_parquet_write_info *info) {
+    try { return write_impl(path, cols, names, ncols, opts, codec, info); }
     catch (const std::bad_alloc &) { return fail(BOWGPU_ERR_OOM, "parquet: out of host memory while writing '%s'", path); }
     catch (const std::exception &e) { return fail(BOWGPU_ERR_ARG, "parquet: writing '%s' failed (%s)", path, e.what()); }
 }

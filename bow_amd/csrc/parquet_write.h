@@ -13,14 +13,18 @@ namespace bowgpu {
 
 constexpr int32_t kPqEncPlain = 0, kPqEncDelta = 5;   // Parquet Encoding values the writer produces
 constexpr int32_t kPqInt64 = 2, kPqDouble = 5;        // Parquet physical types
+constexpr int32_t kPqUncompressed = 0, kPqSnappy = 1; // Parquet CompressionCodec values the writer produces
 
 // One data page as the assembly takes it: its level BIT bytes (ceil(rows / 8), bit k = row k of the page is valid; read only when
-// 0 < valid < rows) and its encoded values section, both in host memory.
+// 0 < valid < rows) and its encoded values section, both in host memory.  Under kPqSnappy the section itself stays away: value_bytes
+// is still its size, and comp / comp_bytes is the raw Snappy stream (a sequence of elements, no preamble) that decodes to it.
 struct PqwPage {
     int32_t rows = 0, valid = 0;
     const uint8_t *level_bits = nullptr;
     const uint8_t *values = nullptr;
     int64_t value_bytes = 0;
+    const uint8_t *comp = nullptr;
+    int64_t comp_bytes = 0;
 };
 // Statistics of one column chunk: min / max are the raw 8-byte payloads of the column's type
 struct PqwStats {
@@ -37,10 +41,10 @@ struct PqHostBytes {
         return p.get();
     }
 };
-// One column chunk as parquet_encode.hip hands it over: the page table, and the two host images its pages point into
+// One column chunk as parquet_encode.hip hands it over: the page table, and the host images its pages point into
 struct PqEncChunk {
     std::vector<PqwPage> pages;
-    PqHostBytes levels, values;
+    PqHostBytes levels, values, comp;
     PqwStats stats;
 };
 struct PqwTotals { int64_t file_bytes = 0, rows = 0, row_groups = 0, data_pages = 0, level_bytes = 0, value_bytes = 0; };
@@ -58,14 +62,16 @@ public:
     int open(const char *path, const char *const *names, const int32_t *types, int32_t ncols, bool statistics, const char *const *meta_keys,
              const char *const *meta_values, int32_t n_meta);
     int begin_row_group(int64_t rows);
-    int add_chunk(int32_t encoding, const PqwPage *pages, int64_t npages, const PqwStats &stats);
+    // codec kPqSnappy: a page's compressed section is the preamble (the varint of its uncompressed size), its levels section as
+    // one literal element, and the page's comp stream as it lies
+    int add_chunk(int32_t encoding, const PqwPage *pages, int64_t npages, const PqwStats &stats, int32_t codec = kPqUncompressed);
     int end_row_group();
     int finish(PqwTotals *totals);
     const std::string &error() const { return err_; }
 
 private:
-    struct Chunk { int32_t encoding; int64_t offset, bytes, values; PqwStats stats; };
-    struct Group { int64_t rows, bytes; std::vector<Chunk> chunks; };
+    struct Chunk { int32_t encoding, codec; int64_t offset, bytes, raw, values; PqwStats stats; };   // bytes: as written; raw: uncompressed
+    struct Group { int64_t rows, bytes; std::vector<Chunk> chunks; };                                // bytes: uncompressed
     int put(const void *p, size_t n);
     int flush();
     int sys_fail(const char *what);

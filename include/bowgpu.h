@@ -45,6 +45,8 @@ extern "C" {
  * version: a new entry point and two new structs, nothing existing changed its layout or meaning. */
 /* (still 14): bowgpu_convert (Bow.Convert among Int64, Float64 and Boolean) added under the same version: a new entry point, no struct
  * added or changed. */
+/* (still 14): bowgpu_parquet_write_codec (the writer with a compression codec, SNAPPY compressed on the device) added under the same
+ * version: a new entry point beside bowgpu_parquet_write, whose options struct and behaviour stay as they are. */
 #define BOWGPU_ABI_VERSION 14
 
 /* bow.Type (reference bowtypes.go:17-32) */
@@ -958,6 +960,24 @@ typedef struct { int64_t file_bytes, rows, row_groups, data_pages, level_bytes, 
 
 int bowgpu_parquet_write(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols,
                          const bowgpu_parquet_write_options *opts /* NULL: defaults */, bowgpu_parquet_write_info *info /* nullable */);
+
+/* bowgpu_parquet_write with a compression codec (a Parquet CompressionCodec value): the file the reference's writer produces,
+ * which compresses with SNAPPY (bowparquet.go:326-338).
+ *   0 (UNCOMPRESSED): the file bowgpu_parquet_write writes for the same arguments, byte for byte.
+ *   1 (SNAPPY): every data page's section is one raw Snappy stream of [4-byte levels length | levels | values].  The values are
+ *     compressed on the device, so only the compressed bytes cross the host link: a page's values section is cut into fragments of
+ *     4 KiB, one wavefront compresses one fragment on its own (back-references stay inside the fragment and use the 1- or 2-byte-offset
+ *     copy forms, copies are 4 .. 64 bytes), and the fragments' element sequences follow each other behind the preamble and the
+ *     literal that holds the levels, which the host writes.  The stream is a function of the page's bytes alone; a page's values
+ *     never take more than 32 + n + n / 6 bytes for n bytes.  PageHeader carries uncompressed_page_size and compressed_page_size,
+ *     ColumnMetaData codec = 1 and total_uncompressed_size / total_compressed_size (page headers counted in both).  Levels forms,
+ *     value encodings, statistics, row groups, metadata, the temporary and its removal are those of bowgpu_parquet_write.
+ *   any other value: BOWGPU_ERR_UNSUPPORTED, before any device or the file system is touched, as are all declines of
+ *     bowgpu_parquet_write, which apply unchanged.
+ * info: level_bytes / value_bytes stay the uncompressed section sizes; file_bytes is the file as written. */
+int bowgpu_parquet_write_codec(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols,
+                               const bowgpu_parquet_write_options *opts /* NULL: defaults */, int32_t codec,
+                               bowgpu_parquet_write_info *info /* nullable */);
 
 /* ---- row-range sharded Rolling.Aggregate across GPUs: the records the ranks exchange ------------------ */
 
