@@ -1254,7 +1254,8 @@ PARQUET_ENC_PLAIN, PARQUET_ENC_PLAIN_DICTIONARY, PARQUET_ENC_DELTA_BINARY_PACKED
 PARQUET_ENC_RLE_DICTIONARY, PARQUET_ENC_BYTE_STREAM_SPLIT = 1 << 8, 1 << 9
 
 
-PARQUET_PLAIN, PARQUET_DELTA_BINARY_PACKED = 0, 5   # Parquet Encoding values bowgpu_parquet_write takes
+PARQUET_PLAIN, PARQUET_DELTA_BINARY_PACKED, PARQUET_RLE_DICTIONARY = 0, 5, 8   # Parquet Encoding values bowgpu_parquet_write takes
+PARQUET_DICT_MAX = 65536   # BOWGPU_PARQUET_DICT_MAX: a column chunk with more distinct 64-bit patterns is written PLAIN
 
 
 class ParquetFile:
@@ -1301,7 +1302,10 @@ PARQUET_CODEC_UNCOMPRESSED, PARQUET_CODEC_SNAPPY = 0, 1   # Parquet CompressionC
 
 def write_parquet(path, cols, names, page_rows=0, row_group_rows=0, encodings=None, statistics=True, metadata=None, reserved=0, codec=0):
     """bowgpu_parquet_write: the frame `cols` (Int64 / Float64 Columns of any residency) as the Parquet file `path`, encoded on the
-    device.  encodings: None (PLAIN everywhere) or one Parquet Encoding per column (PARQUET_PLAIN / PARQUET_DELTA_BINARY_PACKED);
+    device.  encodings: None (PLAIN everywhere) or one Parquet Encoding per column (PARQUET_PLAIN / PARQUET_DELTA_BINARY_PACKED /
+    PARQUET_RLE_DICTIONARY: per column chunk a dictionary of its distinct 64-bit patterns, built on the device, and bit-packed
+    indices; a chunk with more than PARQUET_DICT_MAX patterns or without a valid row comes out PLAIN - ParquetFile.check_column on
+    the written file tells);
     metadata: a dict (or a list of pairs) for the footer's key_value_metadata; codec: 0, or another Parquet CompressionCodec
     (PARQUET_CODEC_SNAPPY: pages compressed on the device) through bowgpu_parquet_write_codec.  Returns the ParquetWriteInfo."""
     o = ParquetWriteOptions()

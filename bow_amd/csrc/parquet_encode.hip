@@ -11,6 +11,8 @@
 //   pq_delta_pages_kernel   one thread per page: where the page's body lies in the values image, its header, its byte count
 //   pq_delta_pack_kernel    one wavefront per block: the block's bytes assembled in LDS - one lane per 32-bit word of a miniblock,
 //                           built from the remainders that overlap it - and stored with aligned 8-byte stores, bytes at the edges
+//   (RLE_DICTIONARY: parquet_dict.hip finds the chunk's dictionary and packs the indices - pq_dict_chunk; a chunk without a value
+//    or with more distinct patterns than the cap takes the PLAIN branch here, and PqEncChunk::encoding says which it was)
 //   (codec SNAPPY: the values sections stay on the device and snappy_encode.hip compresses them there - pq_snappy_chunk)
 //
 // No atomics, no workgroup waits on another, every byte of the output is a function of the input alone.  Nothing reads or
@@ -306,6 +308,9 @@ int compact_valid(Ctx *c, const DevCol &dk, MaskWork *w, DevBuf *vals, DevBuf *b
 // snappy_encode.hip
 int pq_snappy_chunk(Ctx *c, const uint8_t *image, const std::vector<int64_t> &off, const std::vector<int64_t> &len, PqHostBytes *out,
                     std::vector<int64_t> *coff, std::vector<int64_t> *clen);
+// parquet_dict.hip
+int pq_dict_chunk(Ctx *c, const uint64_t *dense, int64_t m, const std::vector<uint32_t> &counts, std::vector<uint64_t> *dict, DevBuf *image,
+                  std::vector<int64_t> *off, std::vector<int64_t> *len, bool *fallback);
 
 int pq_encode_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, int32_t page_rows, int32_t encoding, int32_t codec, bool minmax, PqEncChunk *out) {
     const int64_t n = b - a, npages = (n + page_rows - 1) / page_rows;
@@ -376,6 +381,21 @@ int pq_encode_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, int32_t
     const uint8_t *d_sections = reinterpret_cast<const uint8_t *>(dense);
     std::vector<int64_t> voff((size_t)npages), vlen((size_t)npages);
     DevBuf d_pages, d_min, d_widths, d_bytes, d_sums, d_info, d_image;
+    out->dict.clear();
+    if (encoding == kPqEncRleDict) {   // a chunk without a value, or with more distinct patterns than the cap: the PLAIN branch below
+        bool fallback = m == 0;
+        if (!fallback) BG_TRY(pq_dict_chunk(c, dense, m, counts, &out->dict, &d_image, &voff, &vlen, &fallback));
+        if (fallback) {
+            encoding = kPqEncPlain;
+        } else {
+            if (!snappy) {
+                BG_TRY(copy_d2h(c, out->values.take(d_image.bytes), d_image.p, d_image.bytes));
+                BG_HIP(hipStreamSynchronize(c->stream));
+            }
+            d_sections = d_image.as<const uint8_t>();
+        }
+    }
+    out->encoding = encoding;
     if (encoding == kPqEncPlain) {
         if (!snappy) {
             BG_TRY(copy_d2h(c, out->values.take((size_t)m * 8), dense, (size_t)m * 8));
@@ -387,7 +407,7 @@ int pq_encode_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, int32_t
             vlen[(size_t)p] = 8 * (int64_t)counts[(size_t)p];
             v0 += counts[(size_t)p];
         }
-    } else {
+    } else if (encoding == kPqEncDelta) {
         std::vector<PqDevPage> pages((size_t)npages + 1);
         int64_t v0 = 0, nblocks = 0;
         for (int64_t p = 0; p <= npages; p++) {

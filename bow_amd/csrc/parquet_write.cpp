@@ -5,7 +5,8 @@
 // else of the library; with BOWGPU_PARQUET_ASSEMBLE_ONLY defined this file is that alone (tests/cpp/test_parquet_assemble.cpp).
 //
 // The file: format version 1, root `Schema`, every column OPTIONAL (bowparquet.go:190), INT64 / DOUBLE, UNCOMPRESSED, data page
-// v1, definition levels as RLE / bit-packed hybrid of bit width 1, PLAIN or DELTA_BINARY_PACKED values.  With codec SNAPPY
+// v1, definition levels as RLE / bit-packed hybrid of bit width 1, PLAIN, DELTA_BINARY_PACKED or RLE_DICTIONARY values (the last
+// behind the chunk's dictionary page, whose entries parquet_dict.hip finds and the host orders).  With codec SNAPPY
 // (bowgpu_parquet_write_codec; the reference's codec, bowparquet.go:326-338) a page's section is one raw Snappy stream of
 // [4-byte levels length | levels | values]: the preamble and the levels literal are written here, the values' elements come from
 // snappy_encode.hip as they lie.
@@ -150,11 +151,50 @@ int PqWriter::begin_row_group(int64_t rows) {
     return 0;
 }
 
-int PqWriter::add_chunk(int32_t encoding, const PqwPage *pages, int64_t npages, const PqwStats &stats, int32_t codec) {
+int PqWriter::add_chunk(int32_t encoding, const PqwPage *pages, int64_t npages, const PqwStats &stats, int32_t codec, const uint64_t *dict, int64_t ndict) {
     if (codec != kPqUncompressed && codec != kPqSnappy) { err_ = "parquet: the writer has no codec " + std::to_string(codec); drop(); return -1; }
+    if ((encoding == kPqEncRleDict) != (dict != nullptr && ndict > 0) || ndict > ((int64_t)1 << 27)) {
+        err_ = "parquet: a dictionary of " + std::to_string(ndict) + " entries with value encoding " + std::to_string(encoding);
+        drop();
+        return -1;
+    }
     Group &g = groups_.back();
-    Chunk ch{encoding, codec, pos_, 0, 0, 0, stats};
+    Chunk ch{encoding, codec, pos_, pos_, 0, 0, 0, stats};
     std::vector<uint8_t> head;
+    if (encoding == kPqEncRleDict) {   // the dictionary page: PLAIN entries; kPqSnappy: the preamble and literal elements of at most 64 KiB
+        const uint8_t *body = reinterpret_cast<const uint8_t *>(dict);
+        const int64_t raw = 8 * ndict;
+        TWriter s;
+        if (codec == kPqSnappy) {
+            s.varint((uint64_t)raw);
+            for (int64_t at = 0; at < raw; at += 65536) {
+                const size_t n = (size_t)(raw - at < 65536 ? raw - at : 65536);   // a multiple of 8
+                if (n <= 60) s.byte((uint8_t)((n - 1) << 2));
+                else {
+                    const int k = n <= 256 ? 1 : 2;
+                    s.byte((uint8_t)((59 + k) << 2));
+                    for (int j = 0; j < k; j++) s.byte((uint8_t)((n - 1) >> (8 * j)));
+                }
+                s.b.insert(s.b.end(), body + at, body + at + n);
+            }
+        }
+        const int64_t comp = codec == kPqSnappy ? (int64_t)s.b.size() : raw;
+        TWriter w;
+        w.open_struct();
+        w.i32(1, 2);                  // DICTIONARY_PAGE
+        w.i32(2, (int32_t)raw);       // uncompressed_page_size
+        w.i32(3, (int32_t)comp);      // compressed_page_size
+        w.open_struct(7);             // DictionaryPageHeader
+        w.i32(1, (int32_t)ndict);     //   num_values
+        w.i32(2, kPqEncPlain);
+        w.close_struct();
+        w.close_struct();
+        if (put(w.b.data(), w.b.size()) != 0) return -1;
+        if (codec == kPqSnappy ? put(s.b.data(), s.b.size()) != 0 : put(body, (size_t)raw) != 0) return -1;
+        ch.raw += (int64_t)w.b.size() + raw;
+        ch.data_offset = pos_;
+        tot_.value_bytes += raw;
+    }
     for (int64_t p = 0; p < npages; p++) {
         const PqwPage &pg = pages[p];
         std::vector<uint8_t> lv;
@@ -241,8 +281,10 @@ int PqWriter::finish(PqwTotals *totals) {
             w.i64(2, ch.offset);          //   file_offset
             w.open_struct(3);             //   ColumnMetaData
             w.i32(1, types_[i]);
-            w.list(2, 5, 2);              //   encodings: the values', and RLE for the levels
+            const bool dict = ch.encoding == kPqEncRleDict;
+            w.list(2, 5, dict ? 3 : 2);   //   encodings: the values' (and PLAIN for a dictionary page), and RLE for the levels
             w.zigzag(ch.encoding);
+            if (dict) w.zigzag(kPqEncPlain);
             w.zigzag(3);
             w.list(3, 8, 1);              //   path_in_schema
             w.varint(names_[i].size());
@@ -251,7 +293,8 @@ int PqWriter::finish(PqwTotals *totals) {
             w.i64(5, ch.values);
             w.i64(6, ch.raw);             //   total_uncompressed_size, total_compressed_size: the page headers count in both
             w.i64(7, ch.bytes);
-            w.i64(9, ch.offset);          //   data_page_offset
+            w.i64(9, ch.data_offset);     //   data_page_offset
+            if (dict) w.i64(11, ch.offset);   // dictionary_page_offset
             w.open_struct(12);            //   Statistics
             w.i64(3, ch.stats.null_count);
             if (stats_ && ch.stats.has_minmax) {
@@ -347,7 +390,8 @@ int write_checks(const char *path, const bowgpu_col *cols, const char *const *na
         if (!names[i] || !names[i][0]) return fail(BOWGPU_ERR_ARG, "parquet: column %d has no name", i);
         if (!seen.insert(names[i]).second) return fail(BOWGPU_ERR_ARG, "parquet: two columns are named '%s'", names[i]);
         const int32_t e = o && o->encodings ? o->encodings[i] : kPqEncPlain;
-        if (e != kPqEncPlain && e != kPqEncDelta) return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: value encoding %d for column '%s' (PLAIN = 0 and DELTA_BINARY_PACKED = 5 are written)", e, names[i]);
+        if (e != kPqEncPlain && e != kPqEncDelta && e != kPqEncRleDict)
+            return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: value encoding %d for column '%s' (PLAIN = 0, DELTA_BINARY_PACKED = 5 and RLE_DICTIONARY = 8 are written)", e, names[i]);
         if (e == kPqEncDelta && col.type != BOWGPU_INT64) return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: DELTA_BINARY_PACKED on the Float64 column '%s' (it is written for Int64 columns)", names[i]);
         p->enc.push_back(e);
         p->types.push_back(col.type == BOWGPU_INT64 ? kPqInt64 : kPqDouble);
@@ -373,7 +417,9 @@ int write_impl(const char *path, const bowgpu_col *cols, const char *const *name
         if (w.begin_row_group(b - a) != 0) return fail(BOWGPU_ERR_ARG, "%s", w.error().c_str());
         for (int i = 0; i < ncols; i++) {
             BG_TRY(synced(c, pq_encode_chunk(c, cols[i], a, b, plan.page_rows, plan.enc[(size_t)i], codec, plan.statistics, &ch)));
-            if (w.add_chunk(plan.enc[(size_t)i], ch.pages.data(), (int64_t)ch.pages.size(), ch.stats, codec) != 0) return fail(BOWGPU_ERR_ARG, "%s", w.error().c_str());
+            // (ch.encoding: PLAIN where a dictionary was asked for and the chunk fell back)
+            if (w.add_chunk(ch.encoding, ch.pages.data(), (int64_t)ch.pages.size(), ch.stats, codec, ch.dict.empty() ? nullptr : ch.dict.data(), (int64_t)ch.dict.size()) != 0)
+                return fail(BOWGPU_ERR_ARG, "%s", w.error().c_str());
         }
         if (w.end_row_group() != 0) return fail(BOWGPU_ERR_ARG, "%s", w.error().c_str());
     }

@@ -11,7 +11,7 @@
 
 namespace bowgpu {
 
-constexpr int32_t kPqEncPlain = 0, kPqEncDelta = 5;   // Parquet Encoding values the writer produces
+constexpr int32_t kPqEncPlain = 0, kPqEncDelta = 5, kPqEncRleDict = 8;   // Parquet Encoding values the writer produces
 constexpr int32_t kPqInt64 = 2, kPqDouble = 5;        // Parquet physical types
 constexpr int32_t kPqUncompressed = 0, kPqSnappy = 1; // Parquet CompressionCodec values the writer produces
 
@@ -41,11 +41,15 @@ struct PqHostBytes {
         return p.get();
     }
 };
-// One column chunk as parquet_encode.hip hands it over: the page table, and the host images its pages point into
+// One column chunk as parquet_encode.hip hands it over: the page table, and the host images its pages point into.  encoding: what the
+// chunk came out as - kPqEncPlain where kPqEncRleDict was asked for and the chunk has no value or too many distinct ones; dict: the
+// entries of a kPqEncRleDict chunk in the order of the contract, empty otherwise
 struct PqEncChunk {
     std::vector<PqwPage> pages;
     PqHostBytes levels, values, comp;
     PqwStats stats;
+    int32_t encoding = kPqEncPlain;
+    std::vector<uint64_t> dict;
 };
 struct PqwTotals { int64_t file_bytes = 0, rows = 0, row_groups = 0, data_pages = 0, level_bytes = 0, value_bytes = 0; };
 
@@ -63,14 +67,17 @@ public:
              const char *const *meta_values, int32_t n_meta);
     int begin_row_group(int64_t rows);
     // codec kPqSnappy: a page's compressed section is the preamble (the varint of its uncompressed size), its levels section as
-    // one literal element, and the page's comp stream as it lies
-    int add_chunk(int32_t encoding, const PqwPage *pages, int64_t npages, const PqwStats &stats, int32_t codec = kPqUncompressed);
+    // one literal element, and the page's comp stream as it lies.  encoding kPqEncRleDict: dict / ndict (> 0) are the chunk's dictionary
+    // entries, 8 bytes each, written as its dictionary page in front of the data pages (kPqSnappy: as literal elements, here); a page's
+    // values section is then the bit width and its indices as parquet_dict.hip leaves them
+    int add_chunk(int32_t encoding, const PqwPage *pages, int64_t npages, const PqwStats &stats, int32_t codec = kPqUncompressed,
+                  const uint64_t *dict = nullptr, int64_t ndict = 0);
     int end_row_group();
     int finish(PqwTotals *totals);
     const std::string &error() const { return err_; }
 
 private:
-    struct Chunk { int32_t encoding, codec; int64_t offset, bytes, raw, values; PqwStats stats; };   // bytes: as written; raw: uncompressed
+    struct Chunk { int32_t encoding, codec; int64_t offset, data_offset, bytes, raw, values; PqwStats stats; };   // offset: of the chunk (its dictionary page, if any); bytes: as written; raw: uncompressed
     struct Group { int64_t rows, bytes; std::vector<Chunk> chunks; };                                // bytes: uncompressed
     int put(const void *p, size_t n);
     int flush();

@@ -931,23 +931,38 @@ int bowgpu_parquet_column_check(const bowgpu_parquet *handle, int32_t i, uint32_
  * non-null values; wrapping differences; the block minimum is the true minimum; each miniblock has its minimal bit width; the
  * last miniblock that holds values is padded with zero bits; miniblocks behind it have width byte 0 and no body; a page without a
  * valid row holds the header alone (block size 128, 4 miniblocks, 0 values, first value 0).
+ * RLE_DICTIONARY (encoding 8, Int64 / Float64 columns), per column chunk, over the chunk's non-null values:
+ *   the dictionary holds the distinct values by 64-bit pattern (-0.0 and +0.0 are two entries, as are two NaNs of different payload;
+ *   nothing is declined), ascending as unsigned 64-bit integers of the little-endian payload, for both types (negative Int64 values
+ *   come last); at most BOWGPU_PARQUET_DICT_MAX entries.  A chunk with more distinct patterns, or without a valid row, is written
+ *   PLAIN, byte for byte what encoding 0 gives for that chunk: the decision is per chunk, so a column may be dictionary-encoded in
+ *   one row group and PLAIN in the next, and the caller learns what happened from bowgpu_parquet_column_check on the written file
+ *   (its value_encodings mask).  The dictionary page comes first in the chunk (PageHeader.type = DICTIONARY_PAGE,
+ *   DictionaryPageHeader{num_values = entries, encoding = PLAIN}, the entries at 8 bytes each).  The data pages are v1 with encoding 8
+ *   and levels as above; a values section is one byte for the bit width w = max(1, bit_length(entries - 1)) and, where the page has
+ *   k > 0 non-null values, one bit-packed run: varint((ceil(k / 8) << 1) | 1), then the k indices at w bits each, LSB first, padded
+ *   with zero bits to a whole group of 8 values.  A page with k = 0 holds the width byte alone; there are no RLE runs.
+ *   ColumnMetaData: encodings RLE_DICTIONARY, PLAIN, RLE; dictionary_page_offset is the chunk's first byte, data_page_offset the
+ *   first data page; total_uncompressed_size / total_compressed_size include the dictionary page and its header; statistics as
+ *   for every encoding.
  * Statistics (TYPE_DEFINED_ORDER): null_count always; min_value / max_value with options.statistics - Int64 signed; a NaN takes
  * no part in a Float64 min / max; both are left out when no valid non-NaN value exists; a zero minimum is written as -0.0, a
  * zero maximum as +0.0.
  *
  * Accepted: Int64 / Float64 columns of the three residencies, any Arrow offset (bit offsets that are no multiple of 8 included),
  * validity NULL or null_count 0 / -1, 0 rows (a file with a schema and no row group), up to 2^31 - 1 rows.
- * Declined, with nothing left at `path`: Boolean / String columns, an encoding other than 0 / 5, encoding 5 on a Float64 column
- * (BOWGPU_ERR_UNSUPPORTED); columns of unequal length, ncols < 1, a NULL or empty name, the same name twice, sizes that break the
+ * Declined, with nothing left at `path`: Boolean / String columns, an encoding other than 0 / 5 / 8 (2, PLAIN_DICTIONARY, among
+ * them), encoding 5 on a Float64 column (BOWGPU_ERR_UNSUPPORTED); columns of unequal length, ncols < 1, a NULL or empty name, the same name twice, sizes that break the
  * rules below, reserved != 0 (BOWGPU_ERR_ARG) - all before any device is touched; no device (BOWGPU_ERR_NO_DEVICE: there is no CPU
  * fallback).  The file is written as `<path>.tmp` and renamed on success; on any failure the temporary is removed, a failure to
  * create or write it is BOWGPU_ERR_ARG with the errno text.  The reference's ".parquet" suffix rule is the caller's business.
  * Device workspace is bounded by row_group_rows. */
+#define BOWGPU_PARQUET_DICT_MAX 65536   /* entries of one column chunk's dictionary at the most: 512 KiB, index width at most 16 */
 typedef struct {
     int64_t row_group_rows;       /* 0: 1 << 24.  A multiple of page_rows, at most 1 << 27 */
     int32_t page_rows;            /* 0: 65536.  A multiple of 64, at most 1 << 20: rows (nulls included) per data page */
     int32_t statistics;           /* 1: min_value / max_value / null_count per column chunk, and column_orders in the footer; 0: null_count only */
-    const int32_t *encodings;     /* NULL: PLAIN everywhere; else ncols entries, each Parquet Encoding 0 (PLAIN) or 5 (DELTA_BINARY_PACKED, Int64 columns only) */
+    const int32_t *encodings;     /* NULL: PLAIN everywhere; else ncols entries, each Parquet Encoding 0 (PLAIN), 5 (DELTA_BINARY_PACKED, Int64 columns only) or 8 (RLE_DICTIONARY) */
     const char *const *meta_keys; /* n_meta key / value pairs for the footer's key_value_metadata (Bow.Metadata) */
     const char *const *meta_values;
     int32_t n_meta;
@@ -955,7 +970,8 @@ typedef struct {
 } bowgpu_parquet_write_options;
 
 /* what was written: the file's size, its rows, row groups and data pages, the bytes of the definition-level sections (each with
- * its 4-byte length) and of the values sections */
+ * its 4-byte length) and of the values sections.  With RLE_DICTIONARY chunks: data_pages counts data pages only, value_bytes
+ * includes the body of every dictionary page (8 bytes an entry) */
 typedef struct { int64_t file_bytes, rows, row_groups, data_pages, level_bytes, value_bytes; } bowgpu_parquet_write_info;
 
 int bowgpu_parquet_write(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols,
@@ -972,6 +988,8 @@ int bowgpu_parquet_write(const char *path, const bowgpu_col *cols, const char *c
  *     never take more than 32 + n + n / 6 bytes for n bytes.  PageHeader carries uncompressed_page_size and compressed_page_size,
  *     ColumnMetaData codec = 1 and total_uncompressed_size / total_compressed_size (page headers counted in both).  Levels forms,
  *     value encodings, statistics, row groups, metadata, the temporary and its removal are those of bowgpu_parquet_write.
+ *     A dictionary page's body (RLE_DICTIONARY) is a raw Snappy stream of the preamble and literal elements of at most 64 KiB,
+ *     written by the host; the index sections of its data pages are compressed on the device like any other values section.
  *   any other value: BOWGPU_ERR_UNSUPPORTED, before any device or the file system is touched, as are all declines of
  *     bowgpu_parquet_write, which apply unchanged.
  * info: level_bytes / value_bytes stay the uncompressed section sizes; file_bytes is the file as written. */
