@@ -34,8 +34,8 @@ struct PqPage {  // must match parquet_decode.hip
     int32_t dict_in_raw, _pad;
 };
 int launch_parquet_decode(Ctx *c, const uint8_t *chunk, const PqPage *pages, int64_t npages, bool any_compressed, uint8_t *raw,
-                          int optional, uint32_t kinds, uint32_t *indices, uint64_t *expanded, uint64_t *out_values, uint32_t *out_valid,
-                          unsigned long long *valid_count, uint32_t *status);
+                          int optional, uint32_t kinds, uint32_t *indices, uint32_t *idx_counts, uint64_t *expanded, uint64_t *out_values,
+                          uint32_t *out_valid, unsigned long long *valid_count, uint32_t *status);
 
 namespace {
 
@@ -405,6 +405,9 @@ int walk_column(const ParquetFile *pf, int32_t i, PqWalk *w) {
                 (!dict_hdr && (int64_t)h.raw_size > (int64_t)16 * h.num_values + (1 << 20)) ||
                 (dict_hdr && (h.dict_values < 0 || (int64_t)h.dict_values > (int64_t)1 << 27 || (int64_t)h.raw_size != (int64_t)8 * h.dict_values)))
                 return fail(BOWGPU_ERR_ARG, "parquet: implausible page header in column '%s'", sc.name.c_str());
+            // a page that is stored, not compressed, is read in place up to raw_size: that must be what the chunk holds of it
+            if ((cc.codec == 0 || (h.type == 3 && h.v2 && !h.v2_compressed)) && h.raw_size != h.comp_size)
+                return fail(BOWGPU_ERR_ARG, "parquet: a stored page of column '%s' claims %d bytes and holds %d", sc.name.c_str(), h.raw_size, h.comp_size);
             if (h.type == 2) {  // the chunk's dictionary: PLAIN values, decompressed like a page
                 if ((h.dict_encoding != 0 && h.dict_encoding != 2) || dict_off >= 0 || (int64_t)h.raw_size != (int64_t)h.dict_values * 8)
                     return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: dictionary page of column '%s' is not PLAIN 8-byte values", sc.name.c_str());
@@ -536,12 +539,13 @@ static int parquet_read_column_impl(bowgpu_parquet *handle, int32_t i, bowgpu_ou
     BG_HIP(hipMemsetAsync(dcnt, 0, 8, c->stream));
     BG_HIP(hipMemsetAsync(dout.validity, 0, temp_bits_bytes((size_t)((n + 7) >> 3)), c->stream));
     void *d_idx = nullptr, *d_exp = nullptr;   // 4 B / 8 B per row of workspace, taken only when a page needs it (a chunk may mix encodings)
-    if (walk.kinds & 2u) BG_TRY(ctx_pool(c, kPoolInterp + 3, (size_t)n * 4 + 32, &d_idx));
+    // (behind the n index slots: one word per page, the count of indices its stream gave)
+    if (walk.kinds & 2u) BG_TRY(ctx_pool(c, kPoolInterp + 3, ((size_t)n + pages.size()) * 4 + 32, &d_idx));
     if (walk.kinds & (8u | 16u)) BG_TRY(ctx_pool(c, kPoolInterp + 4, (size_t)n * 8 + 32, &d_exp));
     BG_TRY(launch_parquet_decode(c, reinterpret_cast<const uint8_t *>(d_bytes), reinterpret_cast<const PqPage *>(d_pages), (int64_t)pages.size(),
                                  any_comp, reinterpret_cast<uint8_t *>(d_raw), optional, walk.kinds, reinterpret_cast<uint32_t *>(d_idx),
-                                 reinterpret_cast<uint64_t *>(d_exp), reinterpret_cast<uint64_t *>(dout.values),
-                                 reinterpret_cast<uint32_t *>(dout.validity), dcnt, status));
+                                 d_idx ? reinterpret_cast<uint32_t *>(d_idx) + n : nullptr, reinterpret_cast<uint64_t *>(d_exp),
+                                 reinterpret_cast<uint64_t *>(dout.values), reinterpret_cast<uint32_t *>(dout.validity), dcnt, status));
     uint32_t hstat = 0;
     uint64_t hcnt = 0;
     BG_HIP(hipMemcpyAsync(&hstat, status, 4, hipMemcpyDeviceToHost, c->stream));

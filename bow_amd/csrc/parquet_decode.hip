@@ -86,6 +86,7 @@ constexpr uint32_t kStBlockSize = 128u;   // DELTA_BINARY_PACKED: illegal block 
 constexpr uint32_t kStCount = 256u;       // the values section holds more values than the page has rows
 constexpr uint32_t kStLevels = 512u;      // the definition levels ask for more values than the section holds
 constexpr uint32_t kStBssLength = 1024u;  // BYTE_STREAM_SPLIT: a section length that is no multiple of 8
+constexpr uint32_t kStLevelsEnd = 2048u;  // the definition levels end before the page's rows do
 
 // Header of a DELTA_BINARY_PACKED values section at src[*pos .. end).  0, or the status bit of what is wrong with it.
 __device__ __forceinline__ uint32_t delta_header(const uint8_t *src, int64_t *pos, int64_t end, int64_t *vals_per_mini, int64_t *minis,
@@ -175,9 +176,11 @@ __global__ __launch_bounds__(256) void snappy_pages_kernel(const uint8_t *__rest
 // Dictionary-encoded data pages (PLAIN_DICTIONARY / RLE_DICTIONARY): after the definition levels comes one byte = bit width, then
 // the RLE / bit-packed hybrid of dictionary indices, one per non-null value.  One wavefront per page expands it into a dense
 // uint32 array (the lanes share every run: an RLE run is a fill, a bit-packed run one bit-field extraction per value).
+// idx_counts[pg] = how many indices the page's stream gave (at most num_values): page_scatter_kernel looks up no index past it, so a
+// stream that ends early is reported there (kStLevels) and never read from what an earlier call left in the index workspace.
 __global__ __launch_bounds__(256) void dict_indices_kernel(const uint8_t *__restrict__ raw, const uint8_t *__restrict__ chunk,
                                                            const PqPage *__restrict__ pages, int64_t npages,
-                                                           int optional, uint32_t *indices, uint32_t *status) {
+                                                           int optional, uint32_t *indices, uint32_t *idx_counts, uint32_t *status) {
     const int lane = threadIdx.x & 63;
     const int64_t pg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (pg >= npages) return;
@@ -189,9 +192,9 @@ __global__ __launch_bounds__(256) void dict_indices_kernel(const uint8_t *__rest
         const uint32_t lbytes = (uint32_t)src[0] | ((uint32_t)src[1] << 8) | ((uint32_t)src[2] << 16) | ((uint32_t)src[3] << 24);
         pos = 4 + (int64_t)lbytes;
     }
-    if (pos >= P.raw_size) return;  // a page of nulls only carries no index stream
+    if (pos >= P.raw_size) { if (lane == 0) idx_counts[pg] = 0; return; }  // a page of nulls only carries no index stream
     const int bw = src[pos++];
-    if (bw > 32) { if (lane == 0) atomicOr(&status[0], 16u); return; }
+    if (bw > 32) { if (lane == 0) { idx_counts[pg] = 0; atomicOr(&status[0], 16u); } return; }
     const int vbytes = (bw + 7) >> 3;
     uint32_t *dst = indices + P.idx_off;
     int64_t outp = 0;
@@ -201,8 +204,10 @@ __global__ __launch_bounds__(256) void dict_indices_kernel(const uint8_t *__rest
         if (h & 1) {  // bit-packed: (h >> 1) groups of 8 values, bw bits each, LSB first
             const int64_t count = (int64_t)(h >> 1) * 8;
             const int64_t nbytes = (int64_t)(h >> 1) * bw;
-            if (pos + nbytes > P.raw_size + 8) { if (lane == 0) atomicOr(&status[0], 16u); return; }
-            const int64_t take = count < cap - outp ? count : cap - outp;
+            if (pos + nbytes > P.raw_size + 8) { if (lane == 0) atomicOr(&status[0], 16u); break; }
+            int64_t take = count < cap - outp ? count : cap - outp;
+            // a last group may lack its padding bytes (some writers cut it); an index whose own bits lie past the page is not given
+            if (bw) { const int64_t whole = (P.raw_size - pos) * 8 / bw; if (whole < take) take = whole; }
             for (int64_t j = lane; j < take; j += 64) {
                 const int64_t bit = j * bw;
                 const uint8_t *q = src + pos + (bit >> 3);
@@ -214,15 +219,16 @@ __global__ __launch_bounds__(256) void dict_indices_kernel(const uint8_t *__rest
             outp += take;
         } else {  // RLE: (h >> 1) copies of one value stored in ceil(bw / 8) bytes
             const int64_t count = h >> 1;
+            if (count == 0 || pos + vbytes > P.raw_size) break;  // malformed: no progress / the run's value lies past the page
             uint32_t val = 0;
-            for (int b = 0; b < vbytes; b++) val |= (pos + b < P.raw_size ? (uint32_t)src[pos + b] : 0u) << (8 * b);
+            for (int b = 0; b < vbytes; b++) val |= (uint32_t)src[pos + b] << (8 * b);
             pos += vbytes;
             const int64_t take = count < cap - outp ? count : cap - outp;
             for (int64_t j = lane; j < take; j += 64) dst[outp + j] = val;
             outp += take;
-            if (count == 0) break;  // malformed: no progress
         }
     }
+    if (lane == 0) idx_counts[pg] = (uint32_t)outp;
 }
 
 // DELTA_BINARY_PACKED data pages (INT64): <block size> <miniblocks per block> <total value count> <first value (zigzag)>, then per
@@ -327,7 +333,8 @@ __global__ __launch_bounds__(256) void bss_pages_kernel(const uint8_t *__restric
 __global__ __launch_bounds__(256) void page_scatter_kernel(const uint8_t *__restrict__ raw, const uint8_t *__restrict__ chunk,
                                                            const PqPage *__restrict__ pages, int64_t npages,
                                                            int optional, const uint32_t *__restrict__ indices,
-                                                           const uint64_t *__restrict__ expanded, uint64_t *out_values, uint32_t *out_valid,
+                                                           const uint32_t *__restrict__ idx_counts, const uint64_t *__restrict__ expanded,
+                                                           uint64_t *out_values, uint32_t *out_valid,
                                                            unsigned long long *valid_count, uint32_t *status) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t pg = (int64_t)blockIdx.x * 4 + wv;
@@ -362,6 +369,7 @@ __global__ __launch_bounds__(256) void page_scatter_kernel(const uint8_t *__rest
         if (delta_header(src, &hp, P.raw_size, &V, &mpb, &xcount, &first)) xcount = 0;  // (the status bit is delta_pages_kernel's)
     }
     if (xcount > nv) xcount = nv;
+    const int64_t icount = P.kind == 1 ? (int64_t)idx_counts[pg] : 0;  // kind 1: how many indices dict_indices_kernel gave
 
     // the levels arrive as runs; rows are handled 2048 at a time (64 lanes x one 32-row word)
     int64_t lpos = 0;        // read position in the level bytes
@@ -382,10 +390,11 @@ __global__ __launch_bounds__(256) void page_scatter_kernel(const uint8_t *__rest
             const int stop = row + 2048 < nv ? row + 2048 : nv;
             while (pos < stop) {
                 if (run_left == 0) {
-                    if (lpos >= lv_end) break;
+                    if (lpos >= lv_end) { if (lane == 0) atomicOr(&status[0], kStLevelsEnd); break; }  // rows are left, levels are not
                     const uint32_t h = rd_varint(lv, &lpos, lv_end);
                     if (h & 1) { run_kind = 1; run_left = (int)(h >> 1) * 8; run_bits = lpos * 8; lpos += (h >> 1); }  // bit width 1: one byte per group of 8
                     else { run_kind = 0; run_left = (int)(h >> 1); run_val = lpos < lv_end ? (lv[lpos] & 1) : 0; lpos += 1; }
+                    if (lpos > lv_end && lane == 0) atomicOr(&status[0], kStLevelsEnd);  // the run's own bytes lie past the levels
                     if (run_left == 0) continue;
                 }
                 const int take = run_left < stop - pos ? run_left : stop - pos;
@@ -422,8 +431,10 @@ __global__ __launch_bounds__(256) void page_scatter_kernel(const uint8_t *__rest
                 uint64_t v = 0;
                 if ((word >> k) & 1u) {
                     if (P.kind == 1) {  // the vi-th index of the page (expanded by dict_indices_kernel) -> the chunk's dictionary
-                        const uint32_t ix = indices[P.idx_off + vi];
-                        if (ix < (uint32_t)P.dict_count) {
+                        const uint32_t ix = vi < icount ? indices[P.idx_off + vi] : 0u;
+                        if (vi >= icount) {
+                            atomicOr(&status[0], kStLevels);
+                        } else if (ix < (uint32_t)P.dict_count) {
                             const uintptr_t addr = reinterpret_cast<uintptr_t>((P.dict_in_raw ? raw : chunk) + P.dict_off + (int64_t)ix * 8);  // (a stored dictionary sits at any byte offset)
                             const uint64_t *al = reinterpret_cast<const uint64_t *>(addr & ~(uintptr_t)7);
                             const int shb = (int)(addr & 7) * 8;
@@ -463,16 +474,16 @@ __global__ __launch_bounds__(256) void page_scatter_kernel(const uint8_t *__rest
 }
 
 int launch_parquet_decode(Ctx *c, const uint8_t *chunk, const PqPage *pages, int64_t npages, bool any_compressed, uint8_t *raw,
-                          int optional, uint32_t kinds, uint32_t *indices, uint64_t *expanded, uint64_t *out_values, uint32_t *out_valid,
-                          unsigned long long *valid_count, uint32_t *status) {  // kinds: bit k set = some page has PqPage.kind k
+                          int optional, uint32_t kinds, uint32_t *indices, uint32_t *idx_counts, uint64_t *expanded, uint64_t *out_values,
+                          uint32_t *out_valid, unsigned long long *valid_count, uint32_t *status) {  // kinds: bit k set = some page has PqPage.kind k
     if (npages <= 0) return 0;
     const unsigned grid = (unsigned)((npages + 3) / 4);
     if (any_compressed) hipLaunchKernelGGL(snappy_pages_kernel, dim3(grid), dim3(256), 0, c->stream, chunk, pages, npages, raw, status);
-    if (kinds & 2u) hipLaunchKernelGGL(dict_indices_kernel, dim3(grid), dim3(256), 0, c->stream, raw, chunk, pages, npages, optional, indices, status);
+    if (kinds & 2u) hipLaunchKernelGGL(dict_indices_kernel, dim3(grid), dim3(256), 0, c->stream, raw, chunk, pages, npages, optional, indices, idx_counts, status);
     if (kinds & 8u) hipLaunchKernelGGL(delta_pages_kernel, dim3(grid), dim3(256), 0, c->stream, raw, chunk, pages, npages, optional, expanded, status);
     if (kinds & 16u) hipLaunchKernelGGL(bss_pages_kernel, dim3(grid), dim3(256), 0, c->stream, raw, chunk, pages, npages, optional, expanded, status);
-    hipLaunchKernelGGL(page_scatter_kernel, dim3(grid), dim3(256), 0, c->stream, raw, chunk, pages, npages, optional, indices, expanded,
-                       out_values, out_valid, valid_count, status);
+    hipLaunchKernelGGL(page_scatter_kernel, dim3(grid), dim3(256), 0, c->stream, raw, chunk, pages, npages, optional, indices, idx_counts,
+                       expanded, out_values, out_valid, valid_count, status);
     BG_HIP(hipGetLastError());
     return 0;
 }

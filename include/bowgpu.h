@@ -890,7 +890,7 @@ int bowgpu_join(const bowgpu_col *left_cols, int32_t n_left, int32_t left_key, c
  * DOUBLE columns - what the reference writes (bowparquet.go:326-338), what pyarrow / pandas write by default, and what Parquet v2
  * writers (parquet-mr / Spark with writer.version=v2, pyarrow with column_encoding) choose for these two types.  Anything else -
  * other codecs, types and encodings, DELTA_BINARY_PACKED on a DOUBLE column, nested schemas: BOWGPU_ERR_UNSUPPORTED.  Damaged page
- * data: BOWGPU_ERR_ARG. */
+ * data: BOWGPU_ERR_ARG - a dictionary index stream or definition levels that end before the page's values or rows do included. */
 typedef struct bowgpu_parquet bowgpu_parquet;
 int bowgpu_parquet_open(const char *path, bowgpu_parquet **handle);
 int bowgpu_parquet_close(bowgpu_parquet *handle);
