@@ -1,0 +1,713 @@
+// agg_pass.cpp — the pass machinery of Rolling.Aggregate: a built job, its tile pass, the long-window forms, the redo ladder and
+// the fused Interpolate + Aggregate pass.  Every routing constant of a call lives here.
+
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <time.h>
+
+#include "agg_host.h"
+
+namespace bowgpu {
+
+// Up to which window length (rows on average) a call on a NULLABLE column stays on rolling_twc_kernel with its 256 rows of look-ahead
+// instead of taking the streaming form (0: it does not) - from the 1e8-row sweeps of profiles/r05_stdout_midw_sweep.txt, 30 % nulls, kernel
+// ms compacting / streaming at 144 and 192 rows per window: one kind of integral 0.45 / 0.70 and 0.47 / 0.64, First + Last 0.38 / 0.46 and
+// 0.37 / 0.43 (both up to 255 rows); Min + Max 0.47 / 0.61 and 0.49 / 0.52, both kinds of integral 0.63 / 0.73 and 0.69 / 0.65 (up to 176);
+// sums and counts alone: the streaming form (0.41 / 0.37).  Columns without nulls: the streaming form throughout (it has its dense
+// instantiations; the compacting kernel is 10 - 40 % behind there).
+static int64_t compact_long_max_rows(uint32_t need) {
+    if ((need & kNeedTimeWeighted) == kNeedTimeWeighted || (need & kNeedMinMax)) return kCompactLongBothMaxAvgRows;
+    if (need & (kNeedTimeWeighted | kNeedFirstLast)) return kCompactLongMaxAvgRows;
+    return 0;
+}
+// 32-bit window ids counted from the window that starts at slot0, and timestamps that float64 holds exactly: what the compacting kernel,
+// the 32-bit staged times of rolling_tw.hip and the fused kernel ask of a call
+static bool ids_and_times_fit(const Plan &plan, int64_t slot0, int64_t W) {
+    const int64_t lim53 = 1ll << 53;
+    return plan.first_ts > -lim53 && plan.last_ts < lim53 && (uint64_t)plan.last_ts - (uint64_t)slot0 < 0xFFFFFFF0ull && W < 0xFFFFFFF0ll;
+}
+
+// (naggs <= kMaxAggs: run_aggregate batches, shard_check and fused_try bound it)
+int job_build(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs, int64_t wid_base, int64_t W,
+              bool holds_row0, AggJob *job, int nullable_per_pass) {
+    pending_drop(c);
+    const bowgpu_col *cols = call.cols;
+    const int32_t ncols = call.ncols, ts_col = call.ts_col;
+    const Plan &plan = call.plan;
+    const bowgpu_col *tsc = &cols[ts_col];
+    const int64_t n = tsc->length;
+    BG_TRY(front_check(c, cols, ncols, ts_col));
+
+    job->dcols.clear();
+    job->dcols.resize(ncols);
+    job->douts.clear();
+    job->douts.resize(naggs);
+    job->W = W;
+    job->inclusive = call.inclusive;
+    memcpy(job->aggs, aggs, sizeof(bowgpu_agg) * (size_t)naggs);
+    job->naggs = naggs;
+    job->need = need_mask(aggs, naggs);
+    job->plan = plan;
+    job->strict = call.strict;
+    job->check_plan = call.check_plan;
+    std::vector<DevCol> &dcols = job->dcols;
+    AggParams &P = job->P;
+    memset(&P, 0, sizeof P);
+    {
+        bowgpu_col t = *tsc;
+        t.validity = nullptr;
+        t.null_count = 0;
+        BG_TRY(devcol_prepare(c, &t, &job->dts, true, false));
+    }
+    P.ts = reinterpret_cast<const int64_t *>(job->dts.values);
+    P.n = n;
+    P.row_base = 0;
+    P.s0 = plan.s0;
+    P.interval = plan.interval;
+    P.W = W;
+    P.wid_base = wid_base;
+    P.magic = plan.magic;
+    P.fits32 = ((uint64_t)plan.interval >> 32) == 0;
+    if (P.fits32) interp_magic32(plan.interval, &P.m32, &P.sh1_32, &P.sh2_32);
+    P.inclusive = call.inclusive;
+    P.naggs = naggs;
+    P.pre_rows = (n > 0 && holds_row0 && plan.s0 > plan.first_ts) ? 1 : 0;
+
+    // column slots: each distinct input column whose values some reducer reads
+    ColSlots slots(ncols);
+    for (int i = 0; i < naggs; i++) {
+        if (!kind_reads_values(aggs[i].kind)) continue;
+        const int col = aggs[i].col;
+        const bool opens = slots.find(aggs[i], nullable_per_pass) < 0;
+        if (opens && P.ncols >= kMaxCols) return fail(BOWGPU_ERR_UNSUPPORTED, "at most %d value columns per call", kMaxCols);
+        const int s = slots.take(aggs[i], nullable_per_pass);
+        if (opens) {
+            P.ncols++;
+            DevCol &dc = dcols[col];
+            if (dc.values == nullptr && n > 0) {
+                if (col == ts_col) {
+                    dc.values = job->dts.values; dc.length = n; dc.type = BOWGPU_INT64; dc.null_count = 0;
+                } else {
+                    BG_TRY(devcol_prepare(c, &cols[col], &dc, true, true));
+                }
+            }
+            ColDesc &cd = P.cols[s];
+            cd.values = dc.values;
+            cd.vbits = dc.vbits;
+            cd.vbit0 = dc.vbit0;
+            cd.vwords = dc.vwords;
+            cd.type = cols[col].type;
+        }
+        P.aggs[i].slot = s;
+    }
+
+    for (int i = 0; i < naggs; i++) {
+        AggDesc &a = P.aggs[i];
+        a.kind = aggs[i].kind;
+        if (!kind_reads_values(aggs[i].kind)) a.slot = P.ncols > 0 ? 0 : -1;  // rides along with the first column pass
+        int t = kind_type(aggs[i].kind);
+        if (t == BOWGPU_INPUT_DEPENDENT) t = cols[aggs[i].col].type;      // aggregation.go:114-115
+        if (t == BOWGPU_ITERATOR_DEPENDENT) t = tsc->type;                // aggregation.go:116-117
+        a.out_type = t;
+        a.n_factors = aggs[i].n_factors;
+        for (int f = 0; f < a.n_factors; f++) a.factors[f] = aggs[i].factors[f];
+        BG_TRY(devout_prepare(c, &outs[i], W, &job->douts[i], i));
+        a.out_values = job->douts[i].values;
+        a.out_valid = kind_never_nil(aggs[i].kind) ? nullptr : reinterpret_cast<uint32_t *>(job->douts[i].validity);
+    }
+
+    // per-pass summaries
+    P.first_pass_slot = kMaxCols;
+    P.last_val_slot = -1;
+    for (int i = 0; i < naggs; i++) {
+        const AggDesc &d = P.aggs[i];
+        const int k = d.kind;
+        const int idx = d.slot + 1;
+        P.pass_mask[idx] |= 1u << i;
+        uint32_t fl = 0;
+        if (kind_reads_values(k)) fl |= kPassNeedVals;
+        if (k == BOWGPU_AGG_MIN || k == BOWGPU_AGG_MAX) fl |= kPassMinMax;
+        if (k == BOWGPU_AGG_FIRST || k == BOWGPU_AGG_LAST) fl |= kPassFirstLast;
+        if (d.out_valid) fl |= kPassNullable;
+        if (k >= BOWGPU_AGG_INTEGRAL_STEP && k <= BOWGPU_AGG_WAVG_LINEAR && d.slot >= 0) P.cols[d.slot].need_ts = 1;
+        P.pass_flags[idx] |= fl;
+        if (d.slot < P.first_pass_slot) P.first_pass_slot = d.slot;
+        if (kind_reads_values(k) && d.slot > P.last_val_slot) P.last_val_slot = d.slot;
+    }
+    for (int s = 0; s <= kMaxCols; s++) {
+        int nn = 0;
+        for (int i = 0; i < naggs; i++) if ((P.pass_mask[s] >> i) & 1u) nn += P.aggs[i].out_valid != nullptr;
+        if (nn > P.n_nullable_max) P.n_nullable_max = nn;
+    }
+
+    // status words + long-window list
+    // at most one long window per tile (the lean kernels' tile = 512 rows), spread over kLongLists sub-lists
+    const int64_t ntiles = (n + 511) / 512;
+    const int64_t sub_cap = ntiles / kLongLists + 2;
+    job->scratch_bytes = 8192 + (size_t)sub_cap * kLongLists * 16;
+    void *dscr;
+    BG_TRY(ctx_scratch(c, job->scratch_bytes, &dscr));
+    P.status = reinterpret_cast<uint32_t *>(dscr);
+    P.long_list = reinterpret_cast<int64_t *>(reinterpret_cast<char *>(dscr) + 8192);
+    P.long_cap = sub_cap;
+    return 0;
+}
+
+// status words and valid counts live side by side in the device scratch block and come back in ONE copy
+constexpr size_t kCountsOffset = 1024;                       // bytes: counts[kMaxAggs] behind the status words
+constexpr size_t kReadbackBytes = kCountsOffset + 8 * kMaxAggs;
+static_assert(kStatusWords * 4 <= kCountsOffset, "status words overlap the counters");
+
+// preset: the check of a caller's plan against the column rides in the launch
+static void job_bitmaps(const AggJob *job, bool all_ones, bool preset, BitmapBatch *b) {
+    memset(b, 0, sizeof *b);
+    b->n = job->naggs;
+    b->status_words = kStatusWords;
+    b->nbits = job->W > 0 ? job->W : 0;
+    b->status = job->P.status;
+    b->counts = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(job->P.status) + kCountsOffset);
+    for (int i = 0; i < job->naggs; i++) {
+        b->work[i] = reinterpret_cast<uint32_t *>(job->douts[i].validity);
+        const bowgpu_out *u = job->douts[i].user;
+        b->user[i] = (u && u->residency == BOWGPU_DEVICE) ? u->validity : nullptr;
+        // never-nil reducers: all-ones bitmap; nullable ones start all-null (bowbuffer.go:25) - except under the simple kernels,
+        // where every bitmap starts as ones and only the bits of nil results are cleared
+        b->ones[i] = all_ones || kind_never_nil(job->aggs[i].kind);
+        b->count[i] = !kind_never_nil(job->aggs[i].kind);
+    }
+    if (preset && job->check_plan) { b->check_ts = job->P.ts; b->check_n = job->P.n; b->check_first = job->plan.first_ts; b->check_last = job->plan.last_ts; }
+}
+
+// valid counts of the nullable outputs + bitmaps into the caller's buffers (one launch) + copy-back of host-resident outputs,
+// enqueued only (no sync); the counts come back with the status words (job_readback)
+static int job_enqueue_tail(Ctx *c, AggJob *job) {
+    const int64_t W = job->W;
+    if (W > 0) {
+        BitmapBatch b;
+        job_bitmaps(job, false, false, &b);
+        if (W <= kFinishHostBits) {
+            // a small call is a chain of dependent launches and little else: its last launch hands the status words and the counts to
+            // the host itself instead of a copy command doing so behind it
+            BG_TRY(ctx_pinned(c, 16384, reinterpret_cast<void **>(&b.host_block)));
+            job->tail_wrote_host = true;
+        } else if (job->counts_used) BG_HIP(hipMemsetAsync(b.counts, 0, 8 * kMaxAggs, c->stream));
+        BG_TRY(launch_finish_bitmaps(c, b));
+        job->counts_used = true;
+    }
+    for (int i = 0; i < job->naggs; i++) BG_TRY(devout_finish(c, &job->douts[i], W, job->P.aggs[i].out_type, 0, false));
+    return 0;
+}
+
+static int job_readback(Ctx *c, AggJob *job, uint32_t **hstat, uint64_t **hcnt) {
+    char *hp;
+    BG_TRY(ctx_pinned(c, 16384, reinterpret_cast<void **>(&hp)));
+    if (job->tail_wrote_host) job->tail_wrote_host = false;   // (finish_bitmaps_kernel is storing both there)
+    else BG_HIP(hipMemcpyAsync(hp, job->P.status, kReadbackBytes, hipMemcpyDeviceToHost, c->stream));
+    *hstat = reinterpret_cast<uint32_t *>(hp);
+    *hcnt = reinterpret_cast<uint64_t *>(hp + kCountsOffset);
+    return 0;
+}
+
+// The settle step of everything a job has enqueued: [the tail, where the call's outputs are complete with it,] the read-back of the
+// status words and the counts ...
+static int job_settle_enqueue(Ctx *c, AggJob *job, bool tail, uint32_t **hstat, uint64_t **hcnt) {
+    if (tail) BG_TRY(job_enqueue_tail(c, job));
+    return job_readback(c, job, hstat, hcnt);
+}
+// ... and the synchronisation
+static int job_settle(Ctx *c, AggJob *job, bool tail, uint32_t **hstat, uint64_t **hcnt) {
+    BG_TRY(job_settle_enqueue(c, job, tail, hstat, hcnt));
+    BG_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int fail_ts_unsorted() { return fail(BOWGPU_ERR_TS_UNSORTED, "interval column is not ascending: outside the device path"); }
+
+// The Aggregate status words (common.h kAggSt*) that end a call, as its error; `look`: the words this site asks about (a bit per word).
+// kAggStRedo and kAggStFusedDeclines are not errors: job_pass_complete and fused_try act on them.
+constexpr uint32_t kLookPlan = 1u << kAggStPlanMismatch, kLookUnsorted = 1u << kAggStUnsorted, kLookOverflow = 1u << kAggStListOverflow,
+                   kLookStrict = 1u << kAggStStrictTooLong;
+static int agg_status_error(const uint32_t *hstat, uint32_t look) {
+    if ((look & kLookPlan) && hstat[kAggStPlanMismatch])
+        return fail(BOWGPU_ERR_ARG, "the plan was not made for this interval column (its first / last timestamp differ)");
+    if ((look & kLookUnsorted) && hstat[kAggStUnsorted]) return fail_ts_unsorted();
+    if ((look & kLookOverflow) && hstat[kAggStListOverflow]) return fail(BOWGPU_ERR_HIP, "internal: long-window list overflow");
+    if ((look & kLookStrict) && hstat[kAggStStrictTooLong])
+        return fail(BOWGPU_ERR_UNSUPPORTED, "strict_order: some window holds more than 2^20 rows (one lane walks a window in row order: beyond that the call is declined)");
+    return 0;
+}
+
+static void job_null_counts(AggJob *job, const uint64_t *hcnt) {
+    for (int i = 0; i < job->naggs; i++)
+        job->douts[i].user->null_count = (job->W > 0 && !kind_never_nil(job->aggs[i].kind)) ? job->W - (int64_t)hcnt[i] : 0;
+}
+
+// Can the wave-tile kernels (rolling_simple.hip; time_weighted: rolling_tw.hip) take this call?  16-B aligned columns, no rows
+// below s0, interval < 2^32, at most kSimpleMaxAggs outputs; rolling_simple.hip: exclusive windows without time-weighted
+// reducers.  *wide: the rows reach 2^32 or more past output slot 0 (nanosecond timestamps): ids relative to each tile's window.
+static bool simple_applies(const AggJob *job, bool time_weighted, bool *is_int, bool *has_nulls, bool *wide) {
+    const AggParams &P = job->P;
+    const Plan &plan = job->plan;
+    if ((job->inclusive && !time_weighted) || !P.fits32 || job->naggs > kSimpleMaxAggs) return false;
+    if (P.W <= 0) return false;
+
+    // output slot 0 starts at s0 + wid_base * interval (wid_base != 0: a shard; it never lies above the shard's first row).  Rows
+    // below it exist only as the frame's rows below s0 (P.pre_rows: they ride in window 0; the kernels force their ids)
+    const int64_t slot0_start = P.s0 + (int64_t)((uint64_t)P.wid_base * (uint64_t)P.interval);
+    if (plan.first_ts < slot0_start && !(P.pre_rows && P.wid_base == 0)) return false;
+    // rows within 2^32 of slot 0: global 32-bit window ids; else (nanosecond timestamps) ids relative to each tile's first window
+    *wide = (uint64_t)plan.last_ts - (uint64_t)slot0_start >= 0xFFFFFFF0ull || P.W >= 0xFFFFFFF0ll;
+    // (columns that start on an 8-byte but not a 16-byte boundary - Arrow slices with odd offsets - stay here: 8-byte loads)
+    *is_int = true;  // (reducers over the interval column itself)
+    *has_nulls = false;
+    for (int s = 0; s < P.ncols; s++) {
+        *has_nulls = *has_nulls || P.cols[s].vbits != nullptr;
+        *is_int = P.cols[0].type == BOWGPU_INT64;
+    }
+    if ((job->need & kNeedTimeWeighted) && !time_weighted) return false;
+    if (route_mask() & BOWGPU_ROUTE_NO_SIMPLE) return false;
+    return true;
+}
+
+// the descriptor of the wave-tile kernels (rolling_simple.hip, rolling_tw.hip, rolling_fused.hip) from a built job
+static void simple_params_build(const AggJob *job, bool wide, SimpleParams *out) {
+    const AggParams &P = job->P;
+    const bowgpu_agg *aggs = job->aggs;
+    const int32_t naggs = job->naggs;
+    SimpleParams &S = *out;
+    memset(&S, 0, sizeof S);
+    S.ts = P.ts;
+    S.n = P.n; S.interval = P.interval; S.W = P.W;
+    S.wid_base = P.wid_base;
+    S.magic = P.magic;
+    S.s0 = P.s0 + (int64_t)((uint64_t)P.wid_base * (uint64_t)P.interval);
+    S.m32 = P.m32; S.sh1 = P.sh1_32; S.sh2 = P.sh2_32;
+    S.shift_k = 0;
+    if (wide) {  // ids from (ts - tile base) >> k divided by interval >> k, k = trailing zero bits of the interval
+        int k = 0;
+        while (k < 31 && !(((uint64_t)P.interval >> k) & 1ull)) k++;
+        S.shift_k = k;
+        interp_magic32((int64_t)((uint64_t)P.interval >> k), &S.m32, &S.sh1, &S.sh2);
+    }
+    S.naggs = naggs;
+    S.ncols = P.ncols > 0 ? P.ncols : 1;
+    S.values[0] = P.ts;  // only WindowStart / NumRows: any column serves as "the" column
+    for (int s = 0; s < P.ncols; s++) {
+        S.values[s] = P.cols[s].values;
+        S.vbits[s] = P.cols[s].vbits; S.vbit0[s] = P.cols[s].vbit0; S.vwords[s] = P.cols[s].vwords;
+        S.col_is_int[s] = P.cols[s].type == BOWGPU_INT64;
+    }
+    for (int i = 0; i < naggs; i++) {
+        S.kind[i] = aggs[i].kind;
+        S.nfac[i] = aggs[i].n_factors;
+        for (int f = 0; f < aggs[i].n_factors && f < BOWGPU_MAX_FACTORS; f++) S.fac[i][f] = aggs[i].factors[f];
+        S.col[i] = P.aggs[i].slot < 0 ? 0 : P.aggs[i].slot;
+        S.out_values[i] = reinterpret_cast<uint64_t *>(P.aggs[i].out_values);
+        S.out_valid[i] = P.aggs[i].out_valid;
+    }
+    S.need = job->need;
+    for (int i = 0; i < naggs; i++) {
+        const int k = aggs[i].kind;
+        const int cls = (k == BOWGPU_AGG_MIN || k == BOWGPU_AGG_MAX) ? 1 : (k == BOWGPU_AGG_INTEGRAL_STEP || k == BOWGPU_AGG_WAVG_STEP) ? 2
+                        : (k == BOWGPU_AGG_INTEGRAL_TRAPEZOID || k == BOWGPU_AGG_WAVG_LINEAR) ? 3
+                        : (k == BOWGPU_AGG_SUM || k == BOWGPU_AGG_MEAN || k == BOWGPU_AGG_FIRST || k == BOWGPU_AGG_LAST) ? 0 : 4;
+        S.kind_mask[cls] |= 1u << i;
+        S.col_mask[S.col[i]] |= 1u << i;
+    }
+    S.status = P.status; S.long_list = P.long_list; S.long_cap = P.long_cap;
+    S.inclusive = job->inclusive ? 1 : 0;
+    S.pre_rows = P.pre_rows;
+    S.unaligned_mask = (reinterpret_cast<uintptr_t>(P.ts) & 15) ? 0x80000000u : 0u;
+    for (int s = 0; s < S.ncols; s++)
+        if (reinterpret_cast<uintptr_t>(S.values[s]) & 15) S.unaligned_mask |= 1u << s;
+}
+// launch_rolling_simple's own encoding of the statistics it walks for: bit 0 extrema, bit 1 First / Last
+static int simple_launch_need(uint32_t need) { return ((need & kNeedMinMax) ? 1 : 0) | ((need & kNeedFirstLast) ? 2 : 0); }
+
+static int job_launch_tiles(Ctx *c, AggJob *job, TileAttempt attempt, PassState *ps) {
+    AggParams &P = job->P;
+    const Plan &plan = job->plan;
+    const int64_t W = job->W;
+    const bool allow_simple = attempt != kAttemptNoSimple, force_large_list = attempt == kAttemptLargeList;
+    ps->redo_with = kAttemptNone;
+    if (W <= 0) { BG_HIP(hipMemsetAsync(P.status, 0, kReadbackBytes, c->stream)); return 0; }
+    // The lean kernels cover exclusive windows without time-weighted reducers and without rows below s0; everything
+    // else (and BOWGPU_ROUTE_FORCE_GENERAL, used by the tests to cover all of them) takes the general kernel.
+    // (rows below s0 - P.pre_rows - are taken by the wave-tile kernels; the lean wave kernel declines them below)
+    const uint32_t route = route_mask();
+    const bool force = (route & BOWGPU_ROUTE_FORCE_GENERAL) != 0;
+    const bool lean = !job->inclusive && !(job->need & kNeedTimeWeighted) && !force;
+    bool is_int = false, has_nulls = false, wide = false;
+    bool simple = lean && allow_simple && simple_applies(job, false, &is_int, &has_nulls, &wide);
+    // time-weighted reducers / inclusive windows: the same wave-tile structure with ts staged as float64 (rolling_tw.hip)
+    const bool tw = !lean && !force && allow_simple && simple_applies(job, true, &is_int, &has_nulls, &wide);
+    simple = simple || tw;
+    P.bits_preset = simple ? 1 : 0;
+    {
+        BitmapBatch b;
+        job_bitmaps(job, simple, true, &b);
+        BG_TRY(launch_preset_bitmaps(c, b));   // + status words and counters to zero (+ the check of a caller-supplied plan)
+        job->counts_used = false;
+    }
+    // kernel_ms brackets the dominant kernel only, on the stream it runs on
+    BG_HIP(hipEventRecord(c->ev0, c->stream));
+    if (simple) {
+        SimpleParams S;
+        simple_params_build(job, wide, &S);
+        const int64_t avg_rows = P.n / P.W;
+        // 32-bit staged timestamps / the compacting form: exact when float64(s0 of slot 0) + float64(offset) needs no rounding, i.e. every |ts| < 2^53
+        const bool ts32 = !P.pre_rows && ids_and_times_fit(plan, S.s0, P.W) && S.s0 > -(1ll << 53);
+        // a nullable column: the compacting form (rolling_twc.hip) where its 32-bit times and its head list allow; a tile that overflows
+        // the list raises kAggStRedo and the call is redone as kAttemptLargeList, i.e. by rolling_tw.hip / rolling_simple.hip
+        const bool compact_ok = has_nulls && ts32 && !force_large_list && !(route & BOWGPU_ROUTE_TW_ROWS);
+        bool compact;
+        if (tw) {
+            // (BOWGPU_ROUTE_TW_F64: test / A-B switch that keeps the float64 form)
+            compact = compact_ok && !(route & BOWGPU_ROUTE_TW_F64) && avg_rows >= kCompactMinAvgRows;
+        } else if (ps->band_rows) {
+            compact = false;   // (job_run: extrema / First + Last alone on a nullable column in the 129 .. 200 band - rolling_simple.hip + the queue launch)
+        } else {
+            // beyond 128 rows per window the call is here only because job_run kept it off the streaming form (compact_long_max_rows); up to
+            // there: a nullable column whose outputs want sums AND extrema, windows of kCompactValuesMinAvgRows rows and more - the compacting
+            // form walks the valid points once where rolling_simple.hip walks the rows twice (or once under the validity bit) - 1e8
+            // rows, 30 % nulls, Sum + Min + Max: 0.412 against 0.440 ms at 64 rows per window, 0.451 against 0.558 at 128; below
+            // that length, and for every other value set, rolling_simple.hip stays ahead (the A/B of round 5, timing only; the sweep that shows the routed
+            // kernels side by side is profiles/r05_stdout_midw_sweep.txt)
+            compact = compact_ok && ((avg_rows > 128 && avg_rows <= compact_long_max_rows(job->need)) ||
+                                     ((job->need & kNeedSum) && (job->need & kNeedMinMax) && avg_rows >= kCompactValuesMinAvgRows));
+        }
+        if (compact) {
+            BG_TRY(launch_rolling_twc(c, S, avg_rows > 128));   // (windows of 129 .. kCompactLongMaxAvgRows rows on average: 256 rows of look-ahead)
+            ps->redo_with = kAttemptLargeList;
+            c->last_kernel_name = "rolling_twc_kernel";
+        } else if (tw) {
+            BG_TRY(launch_rolling_tw(c, S, is_int, has_nulls, wide, ts32 && !(route & BOWGPU_ROUTE_TW_F64)));
+            ps->redo_with = kAttemptNoSimple;
+            c->last_kernel_name = "rolling_tw_kernel";
+        } else {
+            // (the head list of a tile comes in two sizes - rolling_simple.hip SimpleCap: the small one buys four more resident
+            // wavefronts per CU and serves calls whose windows average >= 5 rows; BOWGPU_ROUTE_SIMPLE_LARGE_LIST / _SMALL_LIST force
+            // either, for tests; a call whose tiles overflow the small list is redone with the large one - job_pass_complete)
+            // (the unpadded instantiation's small list holds 254 heads: windows of 3 rows and more, as before the pads)
+            const int64_t small_list_rows = rolling_simple_plain(S, is_int, has_nulls) ? 3 : 5;
+            const bool dense = force_large_list || ((route & BOWGPU_ROUTE_SIMPLE_LARGE_LIST) ? true : (route & BOWGPU_ROUTE_SIMPLE_SMALL_LIST) ? false : avg_rows < small_list_rows);
+            ps->redo_with = dense ? kAttemptNoSimple : kAttemptLargeList;
+            BG_TRY(launch_rolling_simple(c, S, simple_launch_need(job->need), is_int, has_nulls, wide, dense));   // (sets c->last_kernel_name: the instantiation)
+        }
+    } else if (lean && !P.pre_rows) {
+        BG_TRY(launch_rolling_fast(c, P));
+        c->last_kernel_name = "rolling_wave_kernel";
+    } else {
+        static const bool trace = [] { const char *t = getenv("BOWGPU_TRACE_ROUTE"); return t && t[0] == '1'; }();
+        if (trace && !force && !(route & BOWGPU_ROUTE_NO_SIMPLE) && allow_simple)
+            fprintf(stderr, "bowgpu route: general kernel (n=%lld W=%lld interval=%lld inclusive=%d naggs=%d pre_rows=%lld wid_base=%lld "
+                            "fits32=%d allow_simple=%d plan=%d first_ts=%lld s0=%lld)\n", (long long)P.n, (long long)P.W,
+                    (long long)P.interval, (int)job->inclusive, job->naggs, (long long)P.pre_rows, (long long)P.wid_base, (int)P.fits32,
+                    (int)allow_simple, 1, (long long)plan.first_ts, (long long)P.s0);
+        BG_TRY(launch_rolling_aggregate(c, P));
+        c->last_kernel_name = "rolling_agg_kernel";
+        c->last_slow_rows += P.n;   // (the general kernel: 0.32 of the HBM peak where the wave-tile kernels reach 0.6 - 0.7)
+    }
+    BG_HIP(hipEventRecord(c->ev1, c->stream));
+    return 0;
+}
+
+static int long_workspace(Ctx *c, const AggParams &P, int64_t n_entries, LongWork *w) {
+    const int64_t max_work = n_entries + (P.n + kLongChunkRows - 1) / kLongChunkRows;
+    const int64_t scan_blocks = (n_entries + 2047) / 2048;
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t b_entries = up((size_t)n_entries * long_entry_size());
+    const size_t b_nchunks = up((size_t)n_entries * 4);
+    const size_t b_offsets = up((size_t)(n_entries + 1) * 8);
+    const size_t b_sums = up((size_t)(scan_blocks + 1) * 8);
+    const size_t b_parts = up((size_t)max_work * (size_t)(P.ncols > 0 ? P.ncols : 1) * long_part_size());
+    const size_t b_map = up((size_t)max_work * 4);
+    void *blk;
+    BG_TRY(ctx_pool(c, Ctx::kPoolSlots - 1, b_entries + b_nchunks + b_offsets + b_sums + 256 + b_map + b_parts, &blk));
+    char *q = reinterpret_cast<char *>(blk);
+    w->entries = q; q += b_entries;
+    w->nchunks = reinterpret_cast<int32_t *>(q); q += b_nchunks;
+    w->offsets = reinterpret_cast<int64_t *>(q); q += b_offsets;
+    w->sums = reinterpret_cast<int64_t *>(q); q += b_sums;
+    w->total = reinterpret_cast<int64_t *>(q); q += 256;
+    w->work_entry = reinterpret_cast<int32_t *>(q); q += b_map;
+    w->parts = q;
+    w->max_work = max_work;
+    return 0;
+}
+// hstat == nullptr: the long-only pipeline (every window of the call)
+static int run_long_windows(Ctx *c, const AggParams &P, const uint32_t *hstat, int64_t *n_long_out, bool strict) {
+    LongListStarts starts;
+    starts.start[0] = 0;
+    if (hstat)
+        for (int s = 0; s < kLongLists; s++) starts.start[s + 1] = starts.start[s] + hstat[kLongCountWord + s];
+    const int64_t n_long = hstat ? starts.start[kLongLists] : P.W;
+    *n_long_out = n_long;
+    if (n_long == 0) return 0;
+    LongWork w;
+    BG_TRY(long_workspace(c, P, n_long, &w));
+    return launch_long_windows_v2(c, P, hstat ? &starts : nullptr, w.entries, w.nchunks, w.offsets, w.sums, w.total, w.work_entry, w.parts, w.max_work, strict);
+}
+
+// BOWGPU_CALL_PROFILE=1 (diagnostic): where a call's wall time goes on the host - until the synchronisation, inside it, after it
+double now_us() { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e6 + t.tv_nsec * 1e-3; }
+
+// From how many rows per window (on average) on a tile pass is followed by long_queue_kernel unconditionally: below, windows longer than a
+// tile's look-ahead are the exception and a call pays nothing for them until one shows up (the host then reads the counts and launches the
+// machinery: rounds 1 - 5); from here on they are expected, and the launch (a few microseconds when the queue is empty) replaces a host
+// round trip and eight launches
+constexpr int64_t kQueueMinAvgRows = 64;
+static int job_queue_enqueue(Ctx *c, AggJob *job, PassState *ps) {
+    if (!ps->queue) return 0;
+    const AggParams &P = job->P;
+    BG_TRY(launch_long_queue(c, P, P.long_cap * kLongLists, ps->qw.entries, ps->qw.nchunks, job->strict ? ((int64_t)1 << 20) : kQueueWalkMaxRows, job->strict));
+    BG_HIP(hipEventRecord(c->ev1, c->stream));   // (the bracket of kernel_ms: tile kernel + queue)
+    return 0;
+}
+
+// bowgpu_agg_info.kernel_ms: the bracket of the dominant kernel
+static int job_report_ms(Ctx *c, bool ran, double *kernel_ms) {
+    float ms = 0;
+    if (ran) BG_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->last_kernel_ms = ms;
+    if (kernel_ms) *kernel_ms = ms;
+    return 0;
+}
+
+// the tile pass of a call, enqueued only: bitmap preset, tile kernel, (tail), read-back of the status words - no synchronisation
+int job_pass_enqueue(Ctx *c, AggJob *job, bool finish, PassState *ps) {
+    {
+        const uint32_t route = route_mask();
+        const int64_t avg_rows = job->W > 0 ? job->P.n / job->W : 0;
+        ps->queue = job->W > 0 && !(route & BOWGPU_ROUTE_QUEUE_HOST) && (avg_rows >= kQueueMinAvgRows || (route & BOWGPU_ROUTE_QUEUE_DEVICE));
+        if (ps->queue) BG_TRY(long_workspace(c, job->P, job->P.long_cap * kLongLists, &ps->qw));
+    }
+    BG_TRY(job_launch_tiles(c, job, kAttemptFirst, ps));
+    BG_TRY(job_queue_enqueue(c, job, ps));
+    // status -> host (pinned).  Optimistically enqueue the tail (null counts, copy-back) behind the tile kernel so
+    // the common case needs ONE synchronisation; if windows were queued for the cooperative path, run it and redo the tail.
+    return job_settle_enqueue(c, job, finish, &ps->hstat, &ps->hcnt);
+}
+
+// ... and its completion: the one synchronisation, the redo of a call the wave-tile kernels could not describe, the queued long windows
+int job_pass_complete(Ctx *c, AggJob *job, bool finish, PassState *ps, int64_t *long_windows, double *kernel_ms) {
+    AggParams &P = job->P;
+    uint32_t *hstat = ps->hstat;
+    uint64_t *hcnt = ps->hcnt;
+    c->prof_sync_begin = now_us();
+    BG_HIP(hipStreamSynchronize(c->stream));
+    c->prof_sync_end = now_us();
+    BG_TRY(agg_status_error(hstat, kLookPlan | kLookUnsorted));
+    // the redo ladder: the same kernel with its large list before anything slower is tried, then the general lean kernel; each attempt
+    // is the whole sequence again - launch, queue, tail, read-back, synchronise - and after it only the order of the rows is asked about
+    while (hstat[kAggStRedo] && ps->redo_with != kAttemptNone) {
+        BG_TRY(job_launch_tiles(c, job, ps->redo_with, ps));
+        BG_TRY(job_queue_enqueue(c, job, ps));
+        BG_TRY(job_settle(c, job, finish, &hstat, &hcnt));
+        BG_TRY(agg_status_error(hstat, kLookUnsorted));
+    }
+    BG_TRY(agg_status_error(hstat, kLookOverflow));
+    int64_t n_long = 0;
+    if (ps->queue) {
+        // long_queue_kernel has walked the queued windows of up to kQueueWalkMaxRows rows in row order (exact) behind the tile kernel; the
+        // longer ones are listed for the chunked order-free machinery - usually none, and the call is done with its one synchronisation
+        BG_TRY(agg_status_error(hstat, kLookStrict));
+        const int64_t n_big = (int64_t)hstat[kQueueBigWord];
+        if (n_big > 0) {
+            const LongWork &w = ps->qw;
+            BG_TRY(launch_long_windows_v2(c, P, nullptr, w.entries, w.nchunks, w.offsets, w.sums, w.total, w.work_entry, w.parts, w.max_work, false, n_big));
+            if (finish) BG_TRY(job_settle(c, job, true, &hstat, &hcnt));
+        }
+        n_long = n_big;
+    } else {
+        // (strict_order: the windows a tile could not hold are walked in row order by one lane each - long_strict_kernel - instead of
+        // being reduced as a tree; a window beyond 2^20 rows declines the call)
+        BG_TRY(run_long_windows(c, P, hstat, &n_long, job->strict));
+        if (n_long > 0 && (finish || job->strict)) {
+            BG_TRY(job_settle(c, job, finish, &hstat, &hcnt));
+            BG_TRY(agg_status_error(hstat, kLookStrict));
+        }
+        if (job->strict) n_long = 0;   // (none of them was reduced order-free)
+    }
+    if (finish) job_null_counts(job, hcnt);
+    if (long_windows) *long_windows = n_long;
+    return job_report_ms(c, job->W > 0, kernel_ms);
+}
+
+int job_run(Ctx *c, AggJob *job, int64_t *long_windows, double *kernel_ms, bool finish, bool allow_long_only) {
+    AggParams &P = job->P;
+    const Plan &plan = job->plan;
+    const int64_t W = job->W;
+    const uint32_t need = job->need;
+    const bool strict = job->strict;
+    // Long-only pipeline: when the windows of an unsharded call average thousands of rows, nearly all of them would be queued
+    // for long_windows.hip by a tile kernel that reads every row just to find that out.  Skip it: order check of the interval
+    // column + every window as an entry of the multi-workgroup reduction.  (BOWGPU_ROUTE_NO_LONG_ONLY: test switch.)
+    const uint32_t route = route_mask();
+    const bool nlo = (route & BOWGPU_ROUTE_NO_LONG_ONLY) != 0 || strict;
+    const bool cls = (route & BOWGPU_ROUTE_LONG_CLASSIC) != 0;      // test / A-B switches: only the bisection + per-window chunks form ...
+    const bool sall = (route & BOWGPU_ROUTE_LONG_STREAM_ALL) != 0;  // ... / the streaming form for every reducer set
+    // Which form?  The streaming form - one read of the rows, long_windows.hip long_short_kernel / long_stream_kernel - for every
+    // reducer set from 128 rows per window on average (1e8 rows: 1000-row windows 0.26 - 0.33 ms against 0.44 - 0.72 ms for the
+    // bisection form; 128 .. 256-row windows 0.35 - 0.55 ms dense, 0.40 - 0.76 ms on irregular data with nulls, against 0.35 - 1.0 /
+    // 0.7 - 1.8 ms for the tile kernels, whose lane-per-window walk idles most lanes at that length); the bisection form keeps the
+    // calls of a handful of giant windows (from 4M rows per window: the streaming form's final merge is one workgroup per window).
+    // (round 4: the tile kernels' walks are branch-free and their staged columns padded against LDS bank conflicts - at 128 rows per
+    // window they beat the streaming form for every set but the calls with both kinds of integral (Mean: 0.283 against 0.319 ms dense,
+    // 0.327 against 0.341 with nulls), scratch/midw_sweep.py; from 129 on some window of the call no longer fits a tile's look-ahead and
+    // the cooperative path would have to run as well: the streaming form takes over)
+    const bool both_tw = (need & kNeedTimeWeighted) == kNeedTimeWeighted;
+    const int64_t avg_rows = W > 0 ? P.n / W : 0;
+    // (round 5: with a nullable column the tile kernels compact the valid points first - rolling_twc.hip - and beat the streaming form at 128
+    // rows per window for both kinds of integral too: 0.53 against 0.72 ms per 1e8 rows)
+    bool any_nulls = false;
+    for (int s = 0; s < P.ncols; s++) any_nulls = any_nulls || P.cols[s].vbits != nullptr;
+    // ... and with 256 rows of look-ahead the same kernel keeps the calls of 129 .. 176 / 255 rows per window on a nullable column whose
+    // reducer set the streaming form serves worst (compact_long_max_rows)
+    // Round 6: the windows a tile pass queues are served behind it without the host (long_queue_kernel: a lane per queued window, in row
+    // order), which moves the hand-over to the streaming form for columns WITHOUT nulls from 129 rows per window to where the streaming
+    // form wins on WALL (1e8 rows, dense, wall ms tile route / streaming form at 144, 160, 192, 224 rows per window -
+    // profiles/r06_stdout_midw_band_first.txt): Min + Max 0.407 / 0.547, 0.420 / 0.510, 0.455 / 0.472, 0.504 / 0.448; Sum + Min + Max
+    // 0.445 / 0.549, 0.463 / 0.507, 0.508 / 0.472; First + Last 0.363 / 0.412, 0.368 / 0.396, 0.408 / 0.379; one kind of integral
+    // 0.458 / 0.504, 0.470 / 0.483, 0.511 / 0.454; sums and counts alone and both kinds of integral: the streaming form throughout.
+    // ... and for NULLABLE columns when the set has neither sums nor integrals (the null rows are staged as NaN and never win; no second walk):
+    // 1e8 rows, 30 % nulls, wall ms rolling_simple.hip + queue / what round 5 routed (rolling_twc.hip, from 192 rows the streaming form) at 144,
+    // 160, 192 rows per window: Min + Max 0.448 / 0.575, 0.454 / 0.581, 0.468 / 0.568 (224 rows: 0.562 / 0.543); First + Last 0.419 / 0.466,
+    // 0.422 / 0.466, 0.450 / 0.460; Sum + Min + Max gains nothing (0.594 / 0.608) and keeps round 5's rule (profiles/r06_stdout_nullable_band_ab.txt)
+    const bool no_sum_set = (need & (kNeedMinMax | kNeedFirstLast)) && !(need & (kNeedSum | kNeedTimeWeighted));
+    int64_t tile_band_rows = 0;   // (both kinds of integral; sums and counts alone)
+    if (both_tw) tile_band_rows = 0;
+    else if ((need & kNeedMinMax) && !(need & (kNeedSum | kNeedTimeWeighted))) tile_band_rows = 200;   // (240 was tried once the tile kernel found the extrema of long windows with all its lanes: at 224 rows the queue walk costs more than that saves - 0.498 against 0.453 ms wall, profiles/r06_stdout_midw_band.txt)
+    else if (need & (kNeedMinMax | kNeedFirstLast | kNeedTimeWeighted)) tile_band_rows = 176;
+    // what both ways of keeping a call of 129+ rows per window on the tile kernels ask for; the route bits and the bound differ
+    const bool tiles_fit = !sall && !cls && avg_rows > 128 && P.fits32 && !P.pre_rows && ids_and_times_fit(plan, P.s0, W) &&
+                           job->naggs <= kSimpleMaxAggs && !(route & (BOWGPU_ROUTE_NO_SIMPLE | BOWGPU_ROUTE_FORCE_GENERAL)) && !strict;
+    const bool tile_band = tiles_fit && (!any_nulls || (no_sum_set && !(route & BOWGPU_ROUTE_TW_ROWS))) && avg_rows <= tile_band_rows &&
+                           !(route & BOWGPU_ROUTE_QUEUE_HOST);
+    const bool compact_long = tiles_fit && !tile_band && any_nulls && avg_rows <= compact_long_max_rows(need) &&
+                              !(route & (BOWGPU_ROUTE_TW_ROWS | BOWGPU_ROUTE_TW_F64));
+    const bool stream_ok = !cls && !compact_long && !tile_band &&
+                           avg_rows >= ((sall || (both_tw && !any_nulls)) ? kLongOnlyAvgRows : kLongStreamAnyAvgRows) &&
+                           avg_rows < kLongClassicAvgRows && W < (1ll << 32);
+    const bool classic_ok = avg_rows >= kLongBisectAvgRows;
+    // bowgpu_options.strict_order on a call of long windows: every window by one lane in row order (long_windows.hip
+    // long_strict_kernel) instead of a tile kernel that reads every row only to queue nearly every window
+    const bool strict_long = strict && avg_rows >= kLongStreamAnyAvgRows && !(route & BOWGPU_ROUTE_NO_LONG_ONLY);
+    if (allow_long_only && W > 0 && P.wid_base == 0 && (((stream_ok || classic_ok) && !nlo) || strict_long)) {
+        P.bits_preset = 0;
+        {
+            BitmapBatch b;
+            job_bitmaps(job, false, true, &b);
+            BG_TRY(launch_preset_bitmaps(c, b));
+        }
+        BG_HIP(hipEventRecord(c->ev0, c->stream));
+        int64_t n_all = W;
+        if (strict_long) {
+            BG_TRY(run_long_windows(c, P, nullptr, &n_all, true));
+            n_all = 0;   // (bowgpu_agg_info.long_windows counts the windows reduced order-free: none)
+            c->last_kernel_name = "long_strict_kernel";
+        } else if (!stream_ok) {
+            BG_TRY(run_long_windows(c, P, nullptr, &n_all, false));
+            c->last_kernel_name = "long_partial_kernel";
+        } else {
+            void *w;
+            BG_TRY(ctx_pool(c, Ctx::kPoolSlots - 1, long_stream_workspace(P.n, P.W, P.ncols), &w));
+            BG_TRY(launch_long_stream(c, P, w));
+            c->last_kernel_name = "long_stream_kernel";
+        }
+        BG_HIP(hipEventRecord(c->ev1, c->stream));
+        uint32_t *hs;
+        uint64_t *hc = nullptr;
+        BG_TRY(job_settle(c, job, finish, &hs, &hc));
+        BG_TRY(agg_status_error(hs, kLookPlan | kLookUnsorted | kLookStrict));
+        if (finish) job_null_counts(job, hc);
+        if (long_windows) *long_windows = n_all;
+        return job_report_ms(c, true, kernel_ms);
+    }
+    PassState ps;
+    ps.band_rows = tile_band && any_nulls;
+    BG_TRY(job_pass_enqueue(c, job, finish, &ps));
+    return job_pass_complete(c, job, finish, &ps, long_windows, kernel_ms);
+}
+
+// the tail of a call whose outputs other launches completed (the shard stitch); strict: a window of more than 2^20 rows declines the call
+int job_finish(Ctx *c, AggJob *job, bool strict) {
+    uint32_t *hstat;
+    uint64_t *hcnt = nullptr;
+    BG_TRY(job_settle(c, job, true, &hstat, &hcnt));
+    job_null_counts(job, hcnt);
+    return agg_status_error(hstat, strict ? kLookStrict : 0);
+}
+
+// ---- Rolling.Interpolate(...).Aggregate(...) in ONE pass over the rows (rolling_fused.hip), where the shape allows it.
+// *done = false: the call is outside the fused kernel's domain (or some tile of it was - the kernel said so): the caller makes the two
+// calls through device temporaries instead (bowgpu_rolling_interpolate_aggregate).  The domain: exclusive windows, the reducers of
+// rolling_simple.hip, an interval column without nulls interpolated by WindowStart, value columns under Linear / StepPrevious / None /
+// WindowStart, a frame that starts at or above 0 and spans less than 2^32 from its first window, windows of 4 .. 128 rows on average.
+int fused_try(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t ts_col, const Plan &plan, const bowgpu_options &o, int inclusive,
+              const bowgpu_interp *interps, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs, double *kernel_ms, bool *done) {
+    *done = false;
+    const bowgpu_col *tsc = &cols[ts_col];
+    const int64_t n = tsc->length, W = plan.W;
+    if (route_mask() & (BOWGPU_ROUTE_NO_FUSED | BOWGPU_ROUTE_NO_SIMPLE | BOWGPU_ROUTE_FORCE_GENERAL)) return 0;
+    if (n <= 0 || W <= 0 || inclusive || o.inclusive || naggs > kSimpleMaxAggs) return 0;
+    if (tsc->validity && tsc->null_count != 0) return 0;                      // (an interval column with nulls: extras.cpp interp_null_ts)
+    if (plan.first_ts < plan.s0 || plan.s0 <= -(1ll << 53)) return 0;   // rows below s0; float64(ts) inexact
+    // a window that starts at -1, the reference's "no first value" sentinel (interpolation.go:99-105): such a window never gets a synthetic row
+    if (plan.s0 <= -1 && (uint64_t)(-1 - plan.s0) % (uint64_t)plan.interval == 0 && (int64_t)((uint64_t)(-1 - plan.s0) / (uint64_t)plan.interval) < W) return 0;
+    if (((uint64_t)plan.interval >> 32) != 0 || !ids_and_times_fit(plan, plan.s0, W)) return 0;
+    if (n / W < 4 || n / W > 128) return 0;
+    for (int i = 0; i < ncols; i++) {
+        const int k = interps[i].kind;
+        if (k != BOWGPU_INTERP_WINDOW_START && k != BOWGPU_INTERP_LINEAR && k != BOWGPU_INTERP_STEP_PREVIOUS && k != BOWGPU_INTERP_NONE) return 0;
+    }
+    if (interps[ts_col].kind != BOWGPU_INTERP_WINDOW_START) return 0;           // anything else does not keep the window grid
+    if (need_mask(aggs, naggs) & (kNeedTimeWeighted | kNeedMode)) return 0;
+    {
+        std::vector<int> used(ncols, 0);
+        int distinct = 0;
+        for (int i = 0; i < naggs; i++)
+            if (kind_reads_values(aggs[i].kind) && !used[aggs[i].col]++) distinct++;
+        if (distinct > kMaxCols) return 0;
+    }
+    AggJob job;
+    const AggCall call = {cols, ncols, ts_col, plan, 0, false, false};
+    BG_TRY(job_build(c, call, aggs, naggs, outs, 0, W, true, &job, kMaxAggs));   // (one pass per column whatever its reducers)
+    AggParams &P = job.P;
+    bool is_int = false, has_nulls = false, wide = false;
+    if (P.pre_rows || !simple_applies(&job, false, &is_int, &has_nulls, &wide) || wide) return 0;
+    P.bits_preset = 1;
+    {
+        BitmapBatch b;
+        job_bitmaps(&job, true, true, &b);
+        BG_TRY(launch_preset_bitmaps(c, b));
+        job.counts_used = false;
+    }
+    FusedParams F;
+    memset(&F, 0, sizeof F);
+    simple_params_build(&job, false, &F.s);
+    for (int s = 0; s < kMaxCols; s++) { F.cols[s].kind = BOWGPU_INTERP_NONE; F.cols[s].type = BOWGPU_INT64; }
+    for (int i = 0; i < naggs; i++) {
+        if (!kind_reads_values(aggs[i].kind) || P.aggs[i].slot < 0) continue;
+        const bowgpu_interp &ip = interps[aggs[i].col];
+        FusedCol &fc = F.cols[P.aggs[i].slot];
+        fc.type = cols[aggs[i].col].type; fc.kind = ip.kind;
+        fc.has_prev = ip.has_prev_row; fc.prev_t_valid = ip.prev_t_valid; fc.prev_v_valid = ip.prev_v_valid;
+        fc.const_value = ip.const_value; fc.prev_t = ip.prev_t; fc.prev_v = ip.prev_v; fc.prev_v_i64 = ip.prev_v_i64;
+    }
+    F.inv_interval = (1.0 / (double)plan.interval) * (1.0 + 0x1.0p-40);
+    BG_HIP(hipEventRecord(c->ev0, c->stream));
+    BG_TRY(launch_rolling_fused(c, F, simple_launch_need(job.need), has_nulls));
+    BG_HIP(hipEventRecord(c->ev1, c->stream));
+    uint32_t *hstat;
+    uint64_t *hcnt = nullptr;
+    BG_TRY(job_settle(c, &job, true, &hstat, &hcnt));
+    BG_TRY(agg_status_error(hstat, kLookUnsorted));
+    if (hstat[kAggStRedo] || hstat[kAggStFusedDeclines]) return 0;   // a tile the fused kernel cannot describe (too many heads, a long window, a far neighbour point)
+    job_null_counts(&job, hcnt);
+    *done = true;
+    return job_report_ms(c, true, kernel_ms);
+}
+
+}  // namespace bowgpu

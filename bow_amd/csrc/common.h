@@ -17,7 +17,7 @@ namespace bowgpu {
 // ---------------------------------------------------------------- errors
 void set_error(const char *fmt, ...);
 int fail(int code, const char *fmt, ...);
-int fail_ts_unsorted();   // BOWGPU_ERR_TS_UNSORTED: what every device path says about an interval column that is not ascending (api.cpp)
+int fail_ts_unsorted();   // BOWGPU_ERR_TS_UNSORTED: what every device path says about an interval column that is not ascending (agg_pass.cpp)
 int hip_fail(hipError_t e, const char *what);
 
 #define BG_HIP(expr)                                         \
@@ -83,9 +83,15 @@ struct Ctx {
     // freed through null_ts_cache_free by the fill, bowgpu_trim, bowgpu_set_device and at thread exit
     void *null_ts_cache = nullptr;
     void (*null_ts_cache_free)(void *) = nullptr;
+    double prof_sync_begin = 0, prof_sync_end = 0;   // BOWGPU_CALL_PROFILE: around the one synchronisation of a tile pass (job_pass_complete)
 };
 void ctx_drop_null_ts_cache(Ctx *c);
-int ctx_get(Ctx **out);                       // initialises HIP on first use; fails loudly without a GPU
+int ctx_get(Ctx **out);                       // initialises HIP on first use; fails loudly without a GPU; settles and drops a pass in flight unless an owner calls
+// the pass bowgpu_shard_pass_begin left in flight on the calling thread (runtime.cpp holds the slot, shard_api.cpp knows what is in it)
+void pending_set(void *pass, void (*destroy)(void *));   // (overwrites: the caller has dropped or collected what was there)
+void *pending_get();
+void pending_drop(Ctx *c);                    // synchronises the stream, then destroys
+struct PendingOwnerScope { bool was; PendingOwnerScope(); ~PendingOwnerScope(); };   // the two owners: ctx_get leaves the pass to them
 int ctx_scratch(Ctx *c, size_t bytes, void **dptr);
 int ctx_pinned(Ctx *c, size_t bytes, void **hptr);
 int ctx_params(Ctx *c, void **dptr);
@@ -93,7 +99,7 @@ int ctx_pool(Ctx *c, int slot, size_t bytes, void **dptr);
 
 // ---------------------------------------------------------------- temp device buffers
 // RAII device allocation (stream-ordered free at scope exit after a sync by the caller).
-// Device scratch of one call.  Blocks come from / go back to a small per-thread cache (api.cpp devbuf_*), so a call pays
+// Device scratch of one call.  Blocks come from / go back to a small per-thread cache (runtime.cpp devbuf_*), so a call pays
 // neither hipMalloc nor hipFree (which also synchronises the device) once the sizes have been seen; every entry point
 // synchronises its stream before its DevBufs go out of scope.
 void devbuf_release(void *p, size_t cap);
@@ -295,7 +301,7 @@ int multi_interpolate_aggregate(const bowgpu_col *cols, int32_t ncols, int32_t t
                                 const bowgpu_interp *interps, int32_t ninterps, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs,
                                 bowgpu_agg_info *info, bool *done);
 
-// api.cpp, for bowgpu_rolling_aggregate_sharded (multi.cpp): the checks of bowgpu_rolling_aggregate that need no column data
+// aggregate_api.cpp, for bowgpu_rolling_aggregate_sharded (multi.cpp): the checks of bowgpu_rolling_aggregate that need no column data
 // (interval column type, interval, aggregators) plus the shard protocol's own (Mode, at most 16 aggregators) - host only
 int sharded_validate(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, int64_t interval, const bowgpu_agg *aggs, int32_t naggs);
 // nulls of an interval column (counted on the calling thread's device when the caller said -1)
@@ -421,27 +427,27 @@ int interp_validate(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, const
 
 int launch_rolling_twc(Ctx *c, const SimpleParams &p, bool long_halo = false);   // (long_halo: 256 rows of look-ahead) nullable columns under time-weighted reducers, 32-bit times: the valid points compacted first (rolling_twc.hip)
 constexpr int64_t kCompactLongMaxAvgRows = 255;             // ... and, with 256 rows of look-ahead, up to this many (beyond: the streaming form) - one kind of integral, First / Last
-constexpr int64_t kCompactLongBothMaxAvgRows = 176;         //     both kinds of integral, Min / Max: the streaming form is ahead from 192 rows on (api.cpp compact_long_max_rows)
+constexpr int64_t kCompactLongBothMaxAvgRows = 176;         //     both kinds of integral, Min / Max: the streaming form is ahead from 192 rows on (agg_pass.cpp compact_long_max_rows)
 constexpr int64_t kCompactValuesMinAvgRows = 48;            // value reducers alone: only sums AND extrema on a nullable column, from this window length on
 constexpr int64_t kCompactMinAvgRows = 12;                  // ... for calls whose windows average at least this many rows (its head list: 92 per 640 rows)
 int launch_rolling_aggregate(Ctx *c, const AggParams &p);   // general kernel (rolling_agg.hip)
 int launch_rolling_fast(Ctx *c, const AggParams &p);        // lean kernel for exclusive windows without time-weighted reducers (rolling_fast.hip)
 constexpr int kLongChunkRows = 4096;
 constexpr int kLongStreamRows = 512;  // chunk of the streaming form of the long-window reduction (long_windows.hip)
-constexpr int64_t kLongOnlyAvgRows = 128;   // calls with BOTH kinds of integral whose windows average at least this many rows skip the tile kernels: streaming form (api.cpp job_run)
+constexpr int64_t kLongOnlyAvgRows = 128;   // calls with BOTH kinds of integral whose windows average at least this many rows skip the tile kernels: streaming form (agg_pass.cpp job_run)
 constexpr int64_t kLongStreamAnyAvgRows = 129;   // ... the same for every other reducer set (256 until long_short_kernel took a boundary per 128-row trip; 128 until the tile kernels' walks became branch-free: windows of exactly 128 rows fit a tile's look-ahead and the tile kernels win there)
 constexpr int64_t kLongBisectAvgRows = 512; // ... bisection form where the streaming form does not apply (BOWGPU_ROUTE_LONG_CLASSIC; W >= 2^32)
 constexpr int64_t kLongClassicAvgRows = 1ll << 22;   // ... and from here on the handful of giant windows go by bisection + per-window chunks
 constexpr int kLongLists = 64;      // sub-lists of the long-window queue (agg_device.h push_long_window)
 constexpr int kLongCountWord = 16;  // status[kLongCountWord + s] = entries in sub-list s
 constexpr int kStatusWords = kLongCountWord + kLongLists;
-// the words below kLongCountWord that the Aggregate kernels raise and api.cpp agg_status_error reads (Interpolate keeps a status block
+// the words below kLongCountWord that the Aggregate kernels raise and agg_pass.cpp agg_status_error reads (Interpolate keeps a status block
 // of its own whose words 5 - 7 mean other things: interpolate.hip, extras.cpp).  rolling_agg.hip, rolling_fast.hip and shard.hip spell
 // them by name; the wave-tile kernels, long_windows.hip and agg_device.h still write the numbers (an edit to those files asks for the
 // round's counter files again: tests/test_profiles_fresh.py)
 constexpr int kAggStUnsorted = 0;        // the interval column is not ascending
 constexpr int kAggStListOverflow = 2;    // the long-window list overflowed (agg_device.h push_long_window)
-constexpr int kAggStRedo = 4;            // some tile is beyond what the wave-tile kernel that ran can describe: the call is redone (api.cpp job_pass_complete)
+constexpr int kAggStRedo = 4;            // some tile is beyond what the wave-tile kernel that ran can describe: the call is redone (agg_pass.cpp job_pass_complete)
 constexpr int kAggStFusedDeclines = 5;   // rolling_fused.hip: a far neighbour point - the call takes the two-call form
 constexpr int kAggStPlanMismatch = 6;    // the preset launch: a caller's plan was not made for this interval column
 constexpr int kAggStStrictTooLong = 7;   // strict_order: a window of more than 2^20 rows
@@ -642,7 +648,7 @@ struct InterpParams {
 int64_t interp_tiles(int64_t n);
 bool interp_fast32(const Plan &plan, int64_t kq);
 bool interp_wide32(const Plan &plan, int64_t kq);   // ... without the bound on the frame's span: 32-bit arithmetic relative to each trip
-void interp_magic32(int64_t interval, uint32_t *m, uint32_t *sh1, uint32_t *sh2);   // the 32-bit magic divisor of an interval < 2^32 (also api.cpp: job_build, simple_params_build)
+void interp_magic32(int64_t interval, uint32_t *m, uint32_t *sh1, uint32_t *sh2);   // the 32-bit magic divisor of an interval < 2^32 (also agg_pass.cpp: job_build, simple_params_build)
 constexpr int kInterpSuperRows = 8192;
 constexpr int kInterpEdgeBlocks = 128;   // interp_edge_fix_kernel: workgroups (= partial valid-output counts) per column
 int64_t interp_supers(int64_t n);

@@ -1045,7 +1045,7 @@ int bowgpu_aggregate_whole(const bowgpu_col *cols, int32_t ncols, int32_t ts_col
     for (int i = 0; i < naggs; i++) any_mode |= aggs[i].kind == BOWGPU_AGG_MODE;
     int64_t tfirst = 0, tlast = 0;
     if (general) {
-        int64_t *hp;   // (one small kernel that stores both into the registered block: api.cpp plan_make does the same)
+        int64_t *hp;   // (one small kernel that stores both into the registered block: aggregate_api.cpp plan_make does the same)
         BG_TRY(ctx_pinned(c, 4096, reinterpret_cast<void **>(&hp)));
         hp += 256;
         BG_TRY(launch_fetch_two(c, reinterpret_cast<const int64_t *>(dts.values), 0, n - 1, hp));

@@ -37,7 +37,7 @@
 
 namespace bowgpu {
 
-int current_device_of_thread();   // api.cpp: the device the calling thread's context is (or will be) on
+int current_device_of_thread();   // runtime.cpp: the device the calling thread's context is (or will be) on
 
 namespace {
 

@@ -14,7 +14,7 @@
 // So the tile kernel of rolling_simple.hip - one wavefront per tile of 512 + 128 rows, one lane walks one window in row order -
 // only needs each window's synthetic value fed to the same left-to-right walk: bit-identical to the two-call path by construction.
 //
-// What it does NOT take raises a status flag and the host makes the two calls instead (api.cpp fused_run -> the generic path):
+// What it does NOT take raises a status flag and the host makes the two calls instead (agg_pass.cpp fused_try -> the generic path):
 // windows that run past a tile's look-ahead, tiles denser than the head list, a run of more than 2048 null rows between a window
 // and its neighbour point (the two-call path has the neighbour index for those).  Inclusive windows, time-weighted reducers, wide
 // frames, rows below s0 and interval columns with nulls never get here (the host declines them up front).

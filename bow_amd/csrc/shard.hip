@@ -47,7 +47,7 @@ constexpr int kSeqLimit = 8192;  // longer ranges are merged from 256 contiguous
 // "dead window 0" rule of the tile kernels, here for the window as stitched across shards.
 // strict: bowgpu_options.strict_order - the rows are walked by ONE lane in row order whatever their number (the 256 contiguous partials
 // of a long range change the order of a Sum's additions); a range of more than 2^20 rows raises status[kAggStStrictTooLong] and is left alone (the
-// stated limit of strict_order: api.cpp turns it into BOWGPU_ERR_UNSUPPORTED)
+// stated limit of strict_order: shard_api.cpp turns it into BOWGPU_ERR_UNSUPPORTED)
 __global__ __launch_bounds__(256) void range_state_kernel(const AggParams p, const int mode, const uint64_t wid,
                                                           const bowgpu_carry_state *seeds,
                                                           bowgpu_carry_state *states_out, const bowgpu_next_row *next, const int seed_alive,

@@ -5,7 +5,7 @@
 // BETWEEN two taken rows of one window sits inside the slice - the reducers see its value columns (sum.go:15-22 reads every row
 // of w.Bow) - while the null rows behind a window's last taken row, in front of the next window's first row, belong to no slice.
 // countWindows (rolling.go:143-154) measures from the last VALID timestamp, and HasNext (:162-173) ends the iteration at once
-// when the physically last timestamp is null (api.cpp handles that case: every output slot stays nil).
+// when the physically last timestamp is null (aggregate_api.cpp handles that case: every output slot stays nil).
 //
 // As a statement about rows (ascending valid timestamps; the tile kernels check that): with p(i) / q(i) the nearest row before /
 // after a null row i whose timestamp is valid, i belongs to window w iff wid(ts[p]) == wid(ts[q]) == w.  So the tile kernels can

@@ -1,4 +1,4 @@
-"""Which form for which window length: 1e8 rows, window lengths 64 .. 1e6 rows, three reducer sets, the routes of api.cpp job_run
+"""Which form for which window length: 1e8 rows, window lengths 64 .. 1e6 rows, three reducer sets, the routes of agg_pass.cpp job_run
 (auto / streaming for every set / bisection form / tile kernels + cooperative path).  Prints bracket / wall per call in ms (the bracket of the tile route covers the tile kernel only)."""
 import gc, os, sys, time
 sys.path.insert(0, '.')

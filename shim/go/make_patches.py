@@ -101,7 +101,7 @@ def edit_whole_go(src, path):
 
 
 def error_strings():
-    """the texts of the reference's errors that the shim words itself (the rest come through bowgpu_last_error, which api.cpp words)"""
+    """the texts of the reference's errors that the shim words itself (the rest come through bowgpu_last_error, which the library words)"""
     out = {}
     src = open(os.path.join(REF, "bowfill.go")).read()
     m = re.search(r'fmt\.Errorf\("(refColIndex \'%d\' is empty or not sorted)",', src)

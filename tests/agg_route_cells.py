@@ -11,7 +11,7 @@ import numpy as np
 
 from bow_amd import capi
 
-# both sides of every window-length threshold of common.h and api.cpp job_run
+# both sides of every window-length threshold of common.h and agg_pass.cpp job_run
 ROWS = (2, 3, 5, 11, 12, 16, 17, 47, 48, 63, 64, 127, 128, 129, 176, 177, 200, 201, 255, 256, 511, 512, 1000)
 ROWS_VARIANTS = (4, 12, 64, 128, 144, 192, 256, 1000)   # the lengths that also run under every variant below
 COLUMNS = ("f64", "f64_nulls", "i64")

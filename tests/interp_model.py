@@ -352,7 +352,7 @@ def outside_inclusive_interpolate(ts, interval, offset):
 
 def rows_below_s0_ride(ts, interval, offset):
     """rows below the first window start that window 0 takes along: the interpolated interval column then begins s0, ts[0] < s0, ...
-    and Aggregate declines it (BOWGPU_ERR_TS_UNSORTED, -14: api.cpp fail_ts_unsorted; include/bowgpu.h:465-468, "including their
+    and Aggregate declines it (BOWGPU_ERR_TS_UNSORTED, -14: agg_pass.cpp fail_ts_unsorted; include/bowgpu.h:465-468, "including their
     declines")"""
     s0, W = plan(ts, interval, offset)
     if W == 0 or int(ts[0]) >= s0:

@@ -1,4 +1,4 @@
-"""Seeded cases for the paths that serve an INTERVAL COLUMN WITH NULLS (bow_amd/csrc/ts_nulls.hip, api.cpp run_aggregate_null_ts,
+"""Seeded cases for the paths that serve an INTERVAL COLUMN WITH NULLS (bow_amd/csrc/ts_nulls.hip, aggregate_api.cpp run_aggregate_null_ts,
 extras.cpp interp_null_ts): what tests/test_gpu_null_ts_fuzz.py pushes through the device and tests/test_null_ts_cases_cpu.py checks
 without one.  No GPU is needed to draw a case or to build its oracle columns; Case.ccols() alone touches the device, and only for a
 device-resident case.

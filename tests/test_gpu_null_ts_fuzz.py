@@ -1,4 +1,4 @@
-"""Differential fuzzing of the paths that serve an INTERVAL COLUMN WITH NULLS (bow_amd/csrc/ts_nulls.hip, api.cpp
+"""Differential fuzzing of the paths that serve an INTERVAL COLUMN WITH NULLS (bow_amd/csrc/ts_nulls.hip, aggregate_api.cpp
 run_aggregate_null_ts, extras.cpp interp_null_ts) against the oracle: the seeded cases of tests/null_ts_cases.py - the interval column
 and every value column at an Arrow offset inside longer buffers of random bits, row counts on the edges of the keep words and the
 tiles, null runs past the near walk (2048 bits) and the blocks (4096) of the neighbour index and on its word edges, a null last row,
