@@ -31,7 +31,7 @@ struct AggJob {
     DevCol dts;
     AggParams P;
     int64_t W = 0;
-    size_t scratch_bytes = 0;
+    unsigned long long *counts = nullptr;   // kScrAggCounts of the scratch block (P.status: its kScrStatus)
     int inclusive = 0;
     bool counts_used = false;   // the valid counters hold a previous count (they accumulate): zero them before counting again
     bool tail_wrote_host = false;   // the finish launch stores the status words and the counts into the registered host block itself

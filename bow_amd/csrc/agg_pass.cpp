@@ -145,19 +145,12 @@ int job_build(Ctx *c, const AggCall &call, const bowgpu_agg *aggs, int32_t naggs
     // at most one long window per tile (the lean kernels' tile = 512 rows), spread over kLongLists sub-lists
     const int64_t ntiles = (n + 511) / 512;
     const int64_t sub_cap = ntiles / kLongLists + 2;
-    job->scratch_bytes = 8192 + (size_t)sub_cap * kLongLists * 16;
-    void *dscr;
-    BG_TRY(ctx_scratch(c, job->scratch_bytes, &dscr));
-    P.status = reinterpret_cast<uint32_t *>(dscr);
-    P.long_list = reinterpret_cast<int64_t *>(reinterpret_cast<char *>(dscr) + 8192);
+    BG_TRY(scratch_at(c, scr_long_list((size_t)sub_cap * kLongLists * 16), &P.long_list));   // (first: the one region that can make the block grow)
+    BG_TRY(scratch_at(c, kScrStatus, &P.status));
+    BG_TRY(scratch_at(c, kScrAggCounts, &job->counts));
     P.long_cap = sub_cap;
     return 0;
 }
-
-// status words and valid counts live side by side in the device scratch block and come back in ONE copy
-constexpr size_t kCountsOffset = 1024;                       // bytes: counts[kMaxAggs] behind the status words
-constexpr size_t kReadbackBytes = kCountsOffset + 8 * kMaxAggs;
-static_assert(kStatusWords * 4 <= kCountsOffset, "status words overlap the counters");
 
 // preset: the check of a caller's plan against the column rides in the launch
 static void job_bitmaps(const AggJob *job, bool all_ones, bool preset, BitmapBatch *b) {
@@ -166,7 +159,7 @@ static void job_bitmaps(const AggJob *job, bool all_ones, bool preset, BitmapBat
     b->status_words = kStatusWords;
     b->nbits = job->W > 0 ? job->W : 0;
     b->status = job->P.status;
-    b->counts = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(job->P.status) + kCountsOffset);
+    b->counts = job->counts;
     for (int i = 0; i < job->naggs; i++) {
         b->work[i] = reinterpret_cast<uint32_t *>(job->douts[i].validity);
         const bowgpu_out *u = job->douts[i].user;
@@ -189,9 +182,9 @@ static int job_enqueue_tail(Ctx *c, AggJob *job) {
         if (W <= kFinishHostBits) {
             // a small call is a chain of dependent launches and little else: its last launch hands the status words and the counts to
             // the host itself instead of a copy command doing so behind it
-            BG_TRY(ctx_pinned(c, 16384, reinterpret_cast<void **>(&b.host_block)));
+            BG_TRY(registered_at(c, kRegStatus, &b.host_block));
             job->tail_wrote_host = true;
-        } else if (job->counts_used) BG_HIP(hipMemsetAsync(b.counts, 0, 8 * kMaxAggs, c->stream));
+        } else if (job->counts_used) BG_HIP(hipMemsetAsync(b.counts, 0, kScrAggCounts.size, c->stream));
         BG_TRY(launch_finish_bitmaps(c, b));
         job->counts_used = true;
     }
@@ -200,12 +193,10 @@ static int job_enqueue_tail(Ctx *c, AggJob *job) {
 }
 
 static int job_readback(Ctx *c, AggJob *job, uint32_t **hstat, uint64_t **hcnt) {
-    char *hp;
-    BG_TRY(ctx_pinned(c, 16384, reinterpret_cast<void **>(&hp)));
+    BG_TRY(registered_at(c, kRegStatus, hstat));
+    BG_TRY(registered_at(c, kRegAggCounts, hcnt));
     if (job->tail_wrote_host) job->tail_wrote_host = false;   // (finish_bitmaps_kernel is storing both there)
-    else BG_HIP(hipMemcpyAsync(hp, job->P.status, kReadbackBytes, hipMemcpyDeviceToHost, c->stream));
-    *hstat = reinterpret_cast<uint32_t *>(hp);
-    *hcnt = reinterpret_cast<uint64_t *>(hp + kCountsOffset);
+    else BG_HIP(hipMemcpyAsync(*hstat, job->P.status, kReadbackBytes, hipMemcpyDeviceToHost, c->stream));   // status words and counts: ONE copy
     return 0;
 }
 

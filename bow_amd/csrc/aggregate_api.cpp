@@ -61,8 +61,7 @@ int plan_make(Ctx *c, const bowgpu_col *ts, int64_t interval, int64_t raw_offset
         if (ts->residency == BOWGPU_DEVICE) {
             if (!c) BG_TRY(ctx_get(&c));
             int64_t *hp;
-            BG_TRY(ctx_pinned(c, 4096, reinterpret_cast<void **>(&hp)));
-            hp += 256;  // bytes 2048.. of the pinned block
+            BG_TRY(registered_at(c, kRegTwoTs, &hp));
             BG_TRY(launch_fetch_two(c, base, 0, n - 1, hp));   // (the kernel stores into the registered block)
             BG_HIP(hipStreamSynchronize(c->stream));
             first = hp[0]; last = hp[1];
@@ -207,10 +206,9 @@ static int window_rows_make(Ctx *c, const AggCall &call, WindowRows *wr) {
     t.null_count = 0;
     BG_TRY(devcol_prepare(c, &t, &wr->dts, true, false));
     BG_TRY(wr->first_idx.alloc((size_t)(W + 1) * 8));
-    void *dscr;
-    BG_TRY(ctx_scratch(c, 8192, &dscr));
-    uint32_t *status = reinterpret_cast<uint32_t *>(dscr);
-    BG_HIP(hipMemsetAsync(status, 0, 64, c->stream));
+    uint32_t *status;
+    BG_TRY(scratch_at(c, kScrStatus, &status));
+    BG_HIP(hipMemsetAsync(status, 0, kStatusHeadBytes, c->stream));
     BG_TRY(launch_window_first_rows(c, reinterpret_cast<const int64_t *>(wr->dts.values), n, call.plan, reinterpret_cast<int64_t *>(wr->first_idx.p), status));
     uint32_t hstat[4] = {0, 0, 0, 0};
     BG_HIP(hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, c->stream));

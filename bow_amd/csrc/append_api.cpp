@@ -82,14 +82,15 @@ int append_launch(Ctx *c, const bowgpu_col *const *frames, int32_t nframes, int3
     for (int i = 0; i < gc; i++) a.pieces[i] = reinterpret_cast<const AppendPiece *>(reinterpret_cast<char *>(dt) + t->pieces_offset(i));
     BG_TRY(launch_append(c, a));
     BG_HIP(hipEventRecord(c->ev1, c->stream));
-    uint64_t *d_valid = reinterpret_cast<uint64_t *>(g.scratch + kScrNulls);
+    uint64_t *d_valid;
+    BG_TRY(scratch_at(c, kScrMoveCounts, &d_valid));
     bool counted = false;
     for (int i = 0; i < gc; i++) {
         if (!count_on_device[i]) continue;
         BG_TRY(launch_popcount(c, reinterpret_cast<const uint32_t *>(g.cols.out_valid[i]), 0, total, d_valid + i));
         counted = true;
     }
-    if (counted) BG_HIP(hipMemcpyAsync(valid, d_valid, 8 * kMoveCols, hipMemcpyDeviceToHost, c->stream));
+    if (counted) BG_HIP(hipMemcpyAsync(valid, d_valid, kScrMoveCounts.size, hipMemcpyDeviceToHost, c->stream));
     return 0;
 }
 
@@ -178,11 +179,8 @@ int bowgpu_find_next(const bowgpu_col *col, int64_t row_start, const void *value
     a.vbit0 = dc.vbit0;
     a.vwords = dc.vwords;
     a.n = col->length;
-    void *scr, *back;
-    BG_TRY(synced(c, ctx_scratch(c, kScrBytes, &scr)));
-    BG_TRY(synced(c, ctx_pinned(c, 16384, &back)));   // the context's registered block: the kernel stores the row there itself
-    a.result = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(scr) + kScrFlags);
-    a.host_result = reinterpret_cast<uint32_t *>(back) + 8;
+    BG_TRY(synced(c, scratch_at(c, kScrFlags, &a.result)));
+    BG_TRY(synced(c, registered_at(c, kRegFindRow, &a.host_result)));   // the kernel stores the row there itself
     BG_HIP(hipEventRecord(c->ev0, c->stream));
     BG_TRY(synced(c, launch_find(c, a)));
     BG_HIP(hipEventRecord(c->ev1, c->stream));

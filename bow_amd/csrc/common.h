@@ -46,11 +46,11 @@ struct Ctx {
     bool inited = false;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;  // stream in use (own or external)
-    // small persistent device scratch (status words, long-window list) + pinned host mirror
+    // the scratch block (device) and the registered block (pinned host memory): runtime.cpp owns the fields, ctx_blocks.h the layouts
     void *d_scratch = nullptr;
     size_t d_scratch_bytes = 0;
     void *h_pinned = nullptr;
-    size_t h_pinned_bytes = 0;
+    size_t h_pinned_bytes = 0;     // kRegBytes once allocated
     void *h_bounce = nullptr;   // two halves of pinned staging for copies of pageable caller buffers (copy_d2h / copy_h2d)
     hipEvent_t bounce_ev[2] = {nullptr, nullptr};
     bool bounce_busy[2] = {false, false};
@@ -92,8 +92,8 @@ void pending_set(void *pass, void (*destroy)(void *));   // (overwrites: the cal
 void *pending_get();
 void pending_drop(Ctx *c);                    // synchronises the stream, then destroys
 struct PendingOwnerScope { bool was; PendingOwnerScope(); ~PendingOwnerScope(); };   // the two owners: ctx_get leaves the pass to them
-int ctx_scratch(Ctx *c, size_t bytes, void **dptr);
-int ctx_pinned(Ctx *c, size_t bytes, void **hptr);
+int ctx_scratch(Ctx *c, size_t bytes, void **dptr);   // for scratch_at / registered_at (below) and runtime.cpp alone
+int ctx_pinned(Ctx *c, void **hptr);
 int ctx_params(Ctx *c, void **dptr);
 int ctx_pool(Ctx *c, int slot, size_t bytes, void **dptr);
 
@@ -184,12 +184,6 @@ struct MoveCols {                     // the columns of one launch, as gather_ke
     unsigned long long *out_valid[kMoveCols];    // 8-byte aligned, ceil(count / 64) words (the working copy of devout_prepare,
                                                  // temp_bits_bytes(ceil(count / 8)), always holds them)
 };
-// the context's small scratch block as these operations lay it out
-constexpr size_t kScrHist = 0;                         // Sort: [8][256] digit counts
-constexpr size_t kScrFlags = 8 * 256 * 4;              // four words.  Sort: [0] not ascending, [1] NaN seen, [2] bad index (take); Filter: filter_stats_kernel's
-constexpr size_t kScrNulls = kScrFlags + 16;           // kMoveCols 64-bit counts: the outputs' nulls (gather) / valid rows (scatter)
-constexpr size_t kScrBytes = kScrNulls + 8 * kMoveCols;   // (more than devcol_prepare's null count asks for: the block does not move under a call)
-
 bool movable_type(int32_t t);         // Int64 / Float64
 bool residency_ok(int32_t r);
 // nulls of a column where that is known without the device (host-resident bitmaps are counted here); -1: ask the device
@@ -225,19 +219,18 @@ struct StagedCols {
     }
 };
 // One group of up to kMoveCols columns from frame column g0 on.  prepare: stages the inputs `have` lacks, prepares the outputs for
-// `count` slots, fills cols, and only then takes the scratch block (counting a column's nulls may have replaced it).  The caller
-// launches and reads its counts back.  finish: devout_finish of every output + the group's one synchronise.  Both report a failure
+// `count` slots, fills cols.  The caller launches and reads its counts (kScrMoveCounts of the scratch block) back.  finish:
+// devout_finish of every output + the group's one synchronise.  Both report a failure
 // through synced().  A group's staged inputs and
 // output temporaries go back when the MoveGroup does: before the next group's are taken.
 struct MoveGroup {
     MoveCols cols;
-    char *scratch = nullptr;
     DevCol staged[kMoveCols];
     DevOut douts[kMoveCols];
 };
 int move_group_prepare(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t g0, const StagedCols &have, bowgpu_out *outs, int64_t count, MoveGroup *g);
 // the second half of prepare alone, for a call whose inputs are not one column each (AppendBows: a list of pieces): ncols, the
-// outputs, the scratch block; the caller describes its inputs to its kernel itself
+// outputs; the caller describes its inputs to its kernel itself
 int move_group_outputs(Ctx *c, int32_t ncols, int32_t g0, bowgpu_out *outs, int64_t count, MoveGroup *g);
 int move_group_finish(Ctx *c, MoveGroup *g, const bowgpu_col *cols, int32_t g0, int64_t count, const int64_t *null_counts);
 
@@ -479,7 +472,7 @@ struct BitmapBatch {
     uint32_t *status;              // preset zeroes status[0 .. status_words) and counts[0 .. kMaxAggs)
     unsigned long long *counts;
     char *host_block;              // finish, one workgroup per bitmap (nbits <= kFinishHostBits): registered host memory that receives the status
-                                   // words [0, status_words) and, at byte 1024 + 8 a, bitmap a's count - by the kernel's own stores
+                                   // words [0, status_words) and, in kRegAggCounts, bitmap a's count - by the kernel's own stores
     const int64_t *check_ts;       // preset: a caller-supplied plan is checked against this interval column (nullptr: no check);
     int64_t check_n, check_first, check_last;   // status[kAggStPlanMismatch] = 1 when its first / last row are not the plan's two timestamps
 };
@@ -760,7 +753,7 @@ int launch_gather(Ctx *c, const GatherNoRowArgs &a, const GatherIdx &ix);
 // sort_api.cpp, next to argsort_device: the host side of every gather (Sort, take, Distinct, Join).
 // the launch half of a gather of the columns `cols` (frame columns g0 ..) of `length` rows: the scratch words zeroed, the kernel, ev1
 // recorded behind it (no synchronise)
-int gather_enqueue(Ctx *c, char *scratch, const MoveCols &cols, int32_t g0, int64_t length, const GatherIdx &ix, int64_t n_idx);
+int gather_enqueue(Ctx *c, const MoveCols &cols, int32_t g0, int64_t length, const GatherIdx &ix, int64_t n_idx);
 // ... over a prepared group, then the outputs' null counts and *bad (synchronises)
 int gather_launch(Ctx *c, const MoveGroup &g, int32_t g0, int64_t length, const GatherIdx &ix, int64_t n_idx, int64_t *nulls, bool *bad);
 // the columns of a frame, kMoveCols a launch, gathered through ix into outs.  *bad: an index outside the frame - nothing of that
@@ -996,5 +989,26 @@ int launch_merge_round(Ctx *c, MergeRoundArgs *a, int nruns);  // fills npairs /
 int launch_gen_dense(Ctx *c, int64_t row0, int64_t n, uint64_t seed, int64_t *ts, double *val);
 int launch_gen_sparse(Ctx *c, int64_t row0, int64_t n, uint64_t seed, int64_t *ts, double *val, uint8_t *validity);
 int launch_checksum64(Ctx *c, const void *dev, int64_t n, uint64_t *d_out2, uint64_t index_base = 0);
+
+}  // namespace bowgpu
+
+// ---------------------------------------------------------------- the two per-thread blocks: their layouts, and the way into them
+#include "ctx_blocks.h"
+
+namespace bowgpu {
+
+// *p = region r of the calling thread's scratch block / registered block.  Nothing else hands out a pointer into either
+template <class T> int scratch_at(Ctx *c, Region r, T **p) {
+    void *base;
+    BG_TRY(ctx_scratch(c, r.end(), &base));
+    *p = reinterpret_cast<T *>(static_cast<char *>(base) + r.offset);
+    return 0;
+}
+template <class T> int registered_at(Ctx *c, Region r, T **p) {
+    void *base;
+    BG_TRY(ctx_pinned(c, &base));
+    *p = reinterpret_cast<T *>(static_cast<char *>(base) + r.offset);
+    return 0;
+}
 
 }  // namespace bowgpu

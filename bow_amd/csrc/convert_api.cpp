@@ -78,10 +78,9 @@ int convert_group(Ctx *c, const bowgpu_col *cols, const int32_t *to_types, int32
         q.out_values = g->douts[i].values;
         q.out_valid = reinterpret_cast<unsigned long long *>(g->douts[i].validity);
     }
-    void *scr;
-    BG_TRY(ctx_scratch(c, sizeof(unsigned long long) * kMoveCols * kConvertShards, &scr));   // (this call's own layout of the block)
-    a.valid_counts = reinterpret_cast<unsigned long long *>(scr);
+    BG_TRY(scratch_at(c, kScrConvertCounts, &a.valid_counts));
     unsigned long long valid[kMoveCols][kConvertShards];
+    static_assert(sizeof valid == kScrConvertCounts.size, "a count per column and shard");
     BG_HIP(hipMemsetAsync(a.valid_counts, 0, sizeof valid, c->stream));
     BG_TRY(launch_convert(c, a));
     BG_HIP(hipEventRecord(c->ev1, c->stream));

@@ -34,9 +34,8 @@ int fetch_valid(Ctx *c, const bowgpu_col *col, int64_t row, int *valid) {
 
 int count_nulls_device(Ctx *c, DevCol *dc) {
     if (!dc->vbits || dc->length == 0) { dc->null_count = 0; return 0; }
-    void *d;
-    BG_TRY(ctx_scratch(c, 4096, &d));
-    uint64_t *dcount = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(d) + 2048);
+    uint64_t *dcount;
+    BG_TRY(scratch_at(c, kScrNullCount, &dcount));
     BG_TRY(launch_popcount(c, dc->vbits, dc->vbit0, dc->length, dcount));
     uint64_t set = 0;
     BG_HIP(hipMemcpyAsync(&set, dcount, 8, hipMemcpyDeviceToHost, c->stream));

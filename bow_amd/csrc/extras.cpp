@@ -13,19 +13,6 @@ using namespace bowgpu;
 
 namespace {
 
-// a device-resident output of `slots` rows whose validity is produced as one byte per row and packed
-struct ByteOut {
-    DevOut out;
-    DevBuf bytes;
-};
-
-int copy_or_alias(Ctx *c, void *user, int residency, const void *dev, size_t nbytes) {
-    if (nbytes == 0 || !user) return 0;
-    if (residency == BOWGPU_DEVICE) BG_HIP(hipMemcpyAsync(user, dev, nbytes, hipMemcpyDeviceToDevice, c->stream));
-    else BG_TRY(copy_d2h(c, user, dev, nbytes, residency == BOWGPU_HOST_PINNED));
-    return 0;
-}
-
 int ts_contract(Ctx *c, const bowgpu_col *tsc) {
     if (tsc->validity && tsc->null_count != 0) {
         DevCol probe;
@@ -63,10 +50,9 @@ int bowgpu_window_bounds(const bowgpu_col *ts, int64_t interval, const bowgpu_op
     const int64_t n = ts->length, W = plan.W;
     DevBuf first_idx, d_fi, d_sb, d_se, d_in;
     BG_TRY(first_idx.alloc((size_t)(W + 1) * 8));
-    void *dscr;
-    BG_TRY(ctx_scratch(c, 8192, &dscr));
-    uint32_t *status = reinterpret_cast<uint32_t *>(dscr);
-    BG_HIP(hipMemsetAsync(status, 0, 64, c->stream));
+    uint32_t *status;
+    BG_TRY(scratch_at(c, kScrStatus, &status));
+    BG_HIP(hipMemsetAsync(status, 0, kStatusHeadBytes, c->stream));
     BG_TRY(launch_window_first_rows(c, reinterpret_cast<const int64_t *>(dts.values), n, plan, reinterpret_cast<int64_t *>(first_idx.p), status));
     const bool dev = residency == BOWGPU_DEVICE;
     int64_t *pfi = first_index, *psb = slice_begin, *pse = slice_end;
@@ -232,15 +218,13 @@ static int interp_prepare(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t
     BG_TRY(ctx_pool(c, kPoolInterp + 0, (size_t)ntiles * 4 + 16, &job->tile_local));
     BG_TRY(ctx_pool(c, kPoolInterp + 1, (size_t)(nsuper + 1) * 8, &job->super_before));
     BG_TRY(ctx_pool(c, kPoolInterp + 2, (size_t)nsuper * 4 + 16, &job->super_sum));
-    void *dscr;
-    BG_TRY(ctx_scratch(c, 8192, &dscr));
-    uint32_t *status = reinterpret_cast<uint32_t *>(dscr);
-    BG_HIP(hipMemsetAsync(status, 0, 64, c->stream));
+    uint32_t *status;
+    BG_TRY(scratch_at(c, kScrStatus, &status));
+    BG_HIP(hipMemsetAsync(status, 0, kStatusHeadBytes, c->stream));
     const int64_t *ts = reinterpret_cast<const int64_t *>(job->dts.values);
     int64_t *d_total = reinterpret_cast<int64_t *>(status + 4);
     int64_t *hback;   // the pass' findings arrive in the registered block by the scan kernel's own stores
-    BG_TRY(ctx_pinned(c, 16384, reinterpret_cast<void **>(&hback)));
-    hback += 384;     // bytes 3072.. of it
+    BG_TRY(registered_at(c, kRegInterpCount, &hback));
     BG_TRY(launch_interp_count(c, ts, n, pl, job->kq, job->has_left, job->left_ts, reinterpret_cast<int32_t *>(job->tile_local),
                                reinterpret_cast<int32_t *>(job->super_sum), reinterpret_cast<int64_t *>(job->super_before), d_total, status, hback));
     BG_HIP(hipStreamSynchronize(c->stream));
@@ -363,13 +347,11 @@ static int interp_fill_impl(const bowgpu_col *cols, int32_t ncols, int32_t ts_co
     std::vector<DevOut> douts(ninterps);
     InterpParams P;
     memset(&P, 0, sizeof P);
-    void *dscr;
-    BG_TRY(ctx_scratch(c, 8192, &dscr));
+    BG_TRY(scratch_at(c, kScrStatus, &P.status));
     P.ts = reinterpret_cast<const int64_t *>(job.dts.values);
     P.n = n; P.s0 = job.plan.s0; P.interval = job.plan.interval; P.W = job.plan.W; P.magic = job.plan.magic;
     P.tile_local = reinterpret_cast<const int32_t *>(job.tile_local);
     P.super_before = reinterpret_cast<const int64_t *>(job.super_before);
-    P.status = reinterpret_cast<uint32_t *>(dscr);
     P.kq = job.kq;
     P.kq_empty = job.kq_empty;
     P.inclusive = o.inclusive ? 1 : 0; P.e0 = job.e0;
@@ -403,7 +385,8 @@ static int interp_fill_impl(const bowgpu_col *cols, int32_t ncols, int32_t ts_co
     }
     std::vector<uint64_t> hcnt(ninterps, 0);
     uint32_t hstat[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long *dcnt = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(dscr) + 1024);
+    unsigned long long *dcnt;
+    BG_TRY(scratch_at(c, kScrInterpCounts, &dcnt));
     // The output positions depend on the interval column alone, so the columns go through the kernel kMaxCols at a time (a Bow
     // of any width: interpolation.go:98-161 loops over the interpolators).  Per batch, in place: the kernel + the edge fix (which
     // also sums the counts); through working copies: ONE launch zeroes the batch's bitmaps (and, first batch, the status words), the
@@ -416,13 +399,14 @@ static int interp_fill_impl(const bowgpu_col *cols, int32_t ncols, int32_t ts_co
         const bool place = can_place && interp_takes_wave3(P) && !(route_mask() & BOWGPU_ROUTE_INTERP_COPIES);
         P.in_place = place ? 1 : 0;
         P.trip_valid = place ? trip_valid : nullptr;
-        char *hp;
-        BG_TRY(ctx_pinned(c, 16384, reinterpret_cast<void **>(&hp)));
+        uint32_t *hs;
+        unsigned long long *hc;
+        BG_TRY(registered_at(c, kRegStatus, &hs));
+        BG_TRY(registered_at(c, kRegInterpCounts, &hc));
         // (in place: kInterpEdgeBlocks partial counts per column of the batch, every one of them stored - by interp_edge_fix_kernel, straight
         // into the host's registered block, the status words in front of them: no copy command behind the launches)
-        P.valid_counts = place ? reinterpret_cast<unsigned long long *>(hp + 1024) : dcnt;
-        P.host_status = place ? reinterpret_cast<uint32_t *>(hp) : nullptr;
-        static_assert(1024 + 8 * (size_t)kMaxCols * kInterpEdgeBlocks <= 16384, "the registered block holds the status words and the partial counts");
+        P.valid_counts = place ? hc : dcnt;
+        P.host_status = place ? hs : nullptr;
         for (int b0 = 0; b0 < ncols; b0 += kMaxCols) {
             const int nb = ncols - b0 < kMaxCols ? ncols - b0 : kMaxCols;
             const bool last_batch = b0 + nb == ncols;
@@ -453,7 +437,7 @@ static int interp_fill_impl(const bowgpu_col *cols, int32_t ncols, int32_t ts_co
                 bb.ones[j] = 0;
                 bb.count[j] = 1;
             }
-            if (place) { if (b0 == 0) BG_HIP(hipMemsetAsync(P.status, 0, 64, c->stream)); }   // (the status words; the partial counts are all stored)
+            if (place) { if (b0 == 0) BG_HIP(hipMemsetAsync(P.status, 0, kStatusHeadBytes, c->stream)); }   // (the status words; the partial counts are all stored)
             else BG_TRY(launch_preset_bitmaps(c, bb));
             P.aligned16 = (reinterpret_cast<uintptr_t>(P.ts) & 15) == 0 ? 1 : 0;
             for (int j = 0; j < nb; j++) if (reinterpret_cast<uintptr_t>(P.cols[j].values) & 15) P.aligned16 = 0;
@@ -463,18 +447,17 @@ static int interp_fill_impl(const bowgpu_col *cols, int32_t ncols, int32_t ts_co
             if (!place) BG_TRY(launch_finish_bitmaps(c, bb));
             // the batch's counts - and, behind the last batch, the status words in front of them: one copy
             if (!place) {
-                if (last_batch) BG_HIP(hipMemcpyAsync(hp, P.status, 1024 + 8 * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
-                else BG_HIP(hipMemcpyAsync(hp + 1024, dcnt, 8 * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+                if (last_batch) BG_HIP(hipMemcpyAsync(hs, P.status, kScrInterpCounts.offset + 8 * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+                else BG_HIP(hipMemcpyAsync(hc, dcnt, 8 * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
             }
             BG_HIP(hipStreamSynchronize(c->stream));   // (per batch: the pinned block is read before the next batch's copy lands in it)
-            const unsigned long long *hc = reinterpret_cast<const unsigned long long *>(hp + 1024);
             for (int j = 0; j < nb; j++) {
                 unsigned long long v = 0;
                 if (place) for (int k = 0; k < kInterpEdgeBlocks; k++) v += hc[j * kInterpEdgeBlocks + k];
                 else v = hc[j];
                 hcnt[b0 + j] = v;
             }
-            if (last_batch) memcpy(hstat, hp, sizeof hstat);
+            if (last_batch) memcpy(hstat, hs, sizeof hstat);
         }
         return 0;
     };
@@ -862,9 +845,8 @@ int bowgpu_shard_interp_points(const bowgpu_col *cols, int32_t ncols, int32_t ts
 
 // ---------------------------------------------------------------------------- IsColSorted / FillLinear
 static int col_order_flags(Ctx *c, const DevCol &dc, int32_t type, uint32_t *flags) {
-    void *dscr;
-    BG_TRY(ctx_scratch(c, 8192, &dscr));
-    uint32_t *dflags = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(dscr) + 256);
+    uint32_t *dflags;
+    BG_TRY(scratch_at(c, kScrOrderFlags, &dflags));
     BG_TRY(launch_col_order(c, reinterpret_cast<const uint64_t *>(dc.values), dc.vbits, dc.vbit0, dc.length, type, dflags));
     BG_HIP(hipMemcpyAsync(flags, dflags, 4, hipMemcpyDeviceToHost, c->stream));
     BG_HIP(hipStreamSynchronize(c->stream));
@@ -945,9 +927,8 @@ static int fill_linear_impl(const bowgpu_col *cols, int32_t ncols, int32_t ref_c
 // never needs the index (Interpolate does the same since round 5).  A device-resident output bitmap that can take the kernel's whole
 // 64-bit words - 8-byte aligned, capacity to the end of the word holding row n - 1 - is written in place: no copy behind the kernel.
 static int fill_finish(Ctx *c, FillParams &P, int64_t n, const DevCol &dfill, DevOut *dout, int type) {
-    void *dscr;
-    BG_TRY(ctx_scratch(c, 8192, &dscr));
-    uint64_t *dcnt = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(dscr) + 8);
+    BG_TRY(scratch_at(c, kScrFillFar, &P.far_flag));
+    BG_TRY(scratch_at(c, kScrFillCount, &P.valid_count));
     P.n = n;
     P.out_values = reinterpret_cast<uint64_t *>(dout->values);
     // the kernel stores one whole 64-bit validity word per wavefront trip: ceil(n/64)*8 bytes, which the word-aligned working
@@ -956,8 +937,6 @@ static int fill_finish(Ctx *c, FillParams &P, int64_t n, const DevCol &dfill, De
     const bool place = n > 0 && u->residency == BOWGPU_DEVICE && (reinterpret_cast<uintptr_t>(u->validity) & 7) == 0 &&
                        ((u->length + 7) >> 3) >= 8 * ((n + 63) >> 6);   // (u->length: still the capacity the caller handed in)
     P.out_valid_words = reinterpret_cast<uint32_t *>(place ? u->validity : dout->validity);
-    P.valid_count = reinterpret_cast<unsigned long long *>(dcnt);
-    P.far_flag = reinterpret_cast<uint32_t *>(dscr);
     memset(&P.nbr, 0, sizeof P.nbr);
     struct { uint32_t far, pad; uint64_t cnt; } back = {0, 0, 0};
     for (int attempt = 0; attempt < 2; attempt++) {
@@ -966,11 +945,11 @@ static int fill_finish(Ctx *c, FillParams &P, int64_t n, const DevCol &dfill, De
             BG_TRY(ctx_pool(c, kPoolInterp + 3, nbr_index_bytes(n, dfill.vbit0), &ix));
             BG_TRY(nbr_index_build(c, dfill.vbits, dfill.vbit0, n, ix, &P.nbr));
         }
-        BG_HIP(hipMemsetAsync(dscr, 0, 16, c->stream));
+        BG_HIP(hipMemsetAsync(P.far_flag, 0, span(kScrFillFar, kScrFillCount), c->stream));
         BG_HIP(hipEventRecord(c->ev0, c->stream));
         BG_TRY(fill_run(c, P));
         BG_HIP(hipEventRecord(c->ev1, c->stream));
-        BG_HIP(hipMemcpyAsync(&back, dscr, 16, hipMemcpyDeviceToHost, c->stream));
+        BG_HIP(hipMemcpyAsync(&back, P.far_flag, sizeof back, hipMemcpyDeviceToHost, c->stream));
         BG_HIP(hipStreamSynchronize(c->stream));
         if (!back.far) break;
     }
@@ -1046,20 +1025,19 @@ int bowgpu_aggregate_whole(const bowgpu_col *cols, int32_t ncols, int32_t ts_col
     int64_t tfirst = 0, tlast = 0;
     if (general) {
         int64_t *hp;   // (one small kernel that stores both into the registered block: aggregate_api.cpp plan_make does the same)
-        BG_TRY(ctx_pinned(c, 4096, reinterpret_cast<void **>(&hp)));
-        hp += 256;
+        BG_TRY(registered_at(c, kRegTwoTs, &hp));
         BG_TRY(launch_fetch_two(c, reinterpret_cast<const int64_t *>(dts.values), 0, n - 1, hp));
         BG_HIP(hipStreamSynchronize(c->stream));
         tfirst = hp[0]; tlast = hp[1];
     }
     auto go_i64 = [](double x) -> int64_t { return (!(x >= -9223372036854775808.0 && x < 9223372036854775808.0)) ? INT64_MIN : (int64_t)x; };
     const int64_t first_value = go_i64((double)tfirst), last_value = go_i64((double)tlast);
-    // where the finish launches store what the host reads back: the context's registered block (bytes 8192.. : values, then validity bytes)
-    char *hblock;
-    BG_TRY(ctx_pinned(c, 16384, reinterpret_cast<void **>(&hblock)));
-    uint64_t *host_values = reinterpret_cast<uint64_t *>(hblock + 8192);
-    uint8_t *host_valid = reinterpret_cast<uint8_t *>(hblock + 8192 + 8 * 64);
-    if (naggs > 64) return fail(BOWGPU_ERR_UNSUPPORTED, "whole-frame aggregation: at most 64 aggregators per call");
+    // where the finish launches store what the host reads back: the context's registered block (values, then validity bytes)
+    uint64_t *host_values;
+    uint8_t *host_valid;
+    BG_TRY(registered_at(c, kRegWholeValues, &host_values));
+    BG_TRY(registered_at(c, kRegWholeValid, &host_valid));
+    if (naggs > kWholeMaxAggs) return fail(BOWGPU_ERR_UNSUPPORTED, "whole-frame aggregation: at most %d aggregators per call", kWholeMaxAggs);
 
     int64_t nblocks = (n + 65535) / 65536;
     if (nblocks > 2048) nblocks = 2048;

@@ -82,14 +82,15 @@ int scatter_launch(Ctx *c, const MoveGroup &g, int64_t n, const MaskWork &w, uns
     BG_TRY(launch_filter_scatter(c, a));
     BG_HIP(hipEventRecord(c->ev1, c->stream));
     // null_count = rows - set bits of the finished bitmap (an input column without nulls has none to count)
-    uint64_t *d_valid = reinterpret_cast<uint64_t *>(g.scratch + kScrNulls);
+    uint64_t *d_valid;
+    BG_TRY(scratch_at(c, kScrMoveCounts, &d_valid));
     bool counted = false;
     for (int i = 0; i < g.cols.ncols; i++) {
         if (!g.cols.vbits[i]) continue;
         BG_TRY(launch_popcount(c, reinterpret_cast<const uint32_t *>(g.cols.out_valid[i]), 0, count, d_valid + i));
         counted = true;
     }
-    if (counted) BG_HIP(hipMemcpyAsync(valid, d_valid, 8 * kMoveCols, hipMemcpyDeviceToHost, c->stream));
+    if (counted) BG_HIP(hipMemcpyAsync(valid, d_valid, kScrMoveCounts.size, hipMemcpyDeviceToHost, c->stream));
     return 0;
 }
 
@@ -99,21 +100,16 @@ namespace bowgpu {
 
 int mask_work_prepare(Ctx *c, int64_t n, MaskWork *w, TileRecords *t) {
     const int64_t ntiles = (n + kFilterTileRows - 1) / kFilterTileRows;
-    void *scr;
-    BG_TRY(ctx_scratch(c, kScrBytes, &scr));
-    char *s = reinterpret_cast<char *>(scr);
+    BG_TRY(scratch_at(c, kScrFlags, &t->stats));
+    BG_TRY(registered_at(c, kRegFilterStats, &t->host_stats));   // filter_stats_kernel stores the three numbers there itself
     BG_TRY(w->mask.alloc((size_t)ntiles * (kFilterTileRows / 8)));
     BG_TRY(w->tiles.alloc((size_t)ntiles * 4));
     BG_TRY(w->spans.alloc((size_t)ntiles * 4));
     t->mask = w->mask.as<unsigned long long>();
     t->tile_counts = w->tiles.as<uint32_t>();
     t->tile_spans = w->spans.as<uint32_t>();
-    t->stats = reinterpret_cast<uint32_t *>(s + kScrFlags);
-    void *back;   // the context's registered block: filter_stats_kernel stores the three numbers there itself
-    BG_TRY(ctx_pinned(c, 16384, &back));
-    t->host_stats = reinterpret_cast<uint32_t *>(back);
     w->back = t->host_stats;
-    BG_HIP(hipMemsetAsync(s + kScrFlags, 0, 16, c->stream));
+    BG_HIP(hipMemsetAsync(t->stats, 0, kScrFlags.size, c->stream));
     return 0;
 }
 

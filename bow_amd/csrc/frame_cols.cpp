@@ -137,10 +137,7 @@ int move_group_outputs(Ctx *c, int32_t ncols, int32_t g0, bowgpu_out *outs, int6
         m.out_values[i] = reinterpret_cast<uint64_t *>(g->douts[i].values);
         m.out_valid[i] = reinterpret_cast<unsigned long long *>(g->douts[i].validity);
     }
-    void *scr = nullptr;
-    const int rc = ctx_scratch(c, kScrBytes, &scr);
-    g->scratch = reinterpret_cast<char *>(scr);
-    return synced(c, rc);
+    return 0;
 }
 
 int move_group_finish(Ctx *c, MoveGroup *g, const bowgpu_col *cols, int32_t g0, int64_t count, const int64_t *null_counts) {
@@ -207,9 +204,8 @@ int stage_rows(Ctx *c, int dst_dev, int src_dev, const bowgpu_col &sc, int64_t a
 }
 
 int recount_nulls(Ctx *c, const void *bits, int64_t n, int64_t *nulls) {
-    void *scr;
-    BG_TRY(ctx_scratch(c, 8192, &scr));
-    uint64_t *d_count = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(scr) + 1024);
+    uint64_t *d_count;
+    BG_TRY(scratch_at(c, kScrOneCount, &d_count));
     uint64_t set = 0;
     BG_TRY(launch_popcount(c, reinterpret_cast<const uint32_t *>(bits), 0, n, d_count));
     BG_HIP(hipMemcpyAsync(&set, d_count, 8, hipMemcpyDeviceToHost, c->stream));

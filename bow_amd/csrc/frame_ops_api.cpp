@@ -86,9 +86,10 @@ int diff_launch(Ctx *c, const MoveGroup &g, const bowgpu_col *scols, int32_t g0,
         if (scols[g0 + i].type == BOWGPU_FLOAT64) a.float_mask |= 1u << i;
     BG_TRY(launch_diff(c, a));
     BG_HIP(hipEventRecord(c->ev1, c->stream));
-    uint64_t *d_valid = reinterpret_cast<uint64_t *>(g.scratch + kScrNulls);
+    uint64_t *d_valid;
+    BG_TRY(scratch_at(c, kScrMoveCounts, &d_valid));
     for (int i = 0; i < g.cols.ncols; i++) BG_TRY(launch_popcount(c, reinterpret_cast<const uint32_t *>(g.cols.out_valid[i]), 0, n, d_valid + i));
-    BG_HIP(hipMemcpyAsync(valid, d_valid, 8 * kMoveCols, hipMemcpyDeviceToHost, c->stream));
+    BG_HIP(hipMemcpyAsync(valid, d_valid, kScrMoveCounts.size, hipMemcpyDeviceToHost, c->stream));
     return 0;
 }
 
@@ -117,8 +118,6 @@ int compact_valid_device(Ctx *c, const DevCol &dk, MaskWork *w, DevBuf *vals, De
 int gather_keys_device(Ctx *c, const uint64_t *keys, int64_t m, const uint32_t *perm, DevBuf *vals, DevBuf *bits) {
     BG_TRY(vals->alloc((size_t)m * 8));
     BG_TRY(bits->alloc((size_t)((m + 63) >> 6) * 8));
-    void *scr;
-    BG_TRY(ctx_scratch(c, kScrBytes, &scr));
     MoveCols cols = MoveCols();
     cols.ncols = 1;
     cols.values[0] = keys;
@@ -126,7 +125,7 @@ int gather_keys_device(Ctx *c, const uint64_t *keys, int64_t m, const uint32_t *
     cols.out_valid[0] = bits->as<unsigned long long>();
     GatherIdx ix;
     ix.u32 = perm;
-    return gather_enqueue(c, reinterpret_cast<char *>(scr), cols, 0, m, ix, m);
+    return gather_enqueue(c, cols, 0, m, ix, m);
 }
 
 int distinct_device(Ctx *c, const bowgpu_col *col, bowgpu_out *out, int64_t *n_distinct) {

@@ -448,9 +448,7 @@ int sharded_tail(Ctx *c, ShardedCall *sc, int r, const bowgpu_shard_decision &d)
         }
     }
     if (a.n > 0) {
-        char *hp;
-        BG_TRY(ctx_pinned(c, 16384, reinterpret_cast<void **>(&hp)));
-        a.report = reinterpret_cast<uint8_t *>(hp + 12288);   // (bytes 12288.. of the context's pinned block: free once the finish has returned)
+        BG_TRY(registered_at(c, kRegTailReport, &a.report));
         a.slot = s;
         BG_TRY(launch_shard_tail(c, a));
         BG_HIP(hipStreamSynchronize(c->stream));

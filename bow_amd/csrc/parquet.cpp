@@ -531,12 +531,12 @@ static int parquet_read_column_impl(bowgpu_parquet *handle, int32_t i, bowgpu_ou
     for (const PqSpan &sp : spans)
         BG_TRY(copy_h2d(c, reinterpret_cast<char *>(d_bytes) + sp.dev_off, pf->map + sp.file_off, (size_t)sp.len));
     BG_HIP(hipMemcpyAsync(d_pages, pages.data(), pages.size() * sizeof(PqPage), hipMemcpyHostToDevice, c->stream));
-    void *dscr;
-    BG_TRY(ctx_scratch(c, 8192, &dscr));
-    uint32_t *status = reinterpret_cast<uint32_t *>(dscr);
-    unsigned long long *dcnt = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(dscr) + 1024);
-    BG_HIP(hipMemsetAsync(status, 0, 64, c->stream));
-    BG_HIP(hipMemsetAsync(dcnt, 0, 8, c->stream));
+    uint32_t *status;
+    unsigned long long *dcnt;
+    BG_TRY(scratch_at(c, kScrStatus, &status));
+    BG_TRY(scratch_at(c, kScrOneCount, &dcnt));
+    BG_HIP(hipMemsetAsync(status, 0, kStatusHeadBytes, c->stream));
+    BG_HIP(hipMemsetAsync(dcnt, 0, kScrOneCount.size, c->stream));
     BG_HIP(hipMemsetAsync(dout.validity, 0, temp_bits_bytes((size_t)((n + 7) >> 3)), c->stream));
     void *d_idx = nullptr, *d_exp = nullptr;   // 4 B / 8 B per row of workspace, taken only when a page needs it (a chunk may mix encodings)
     // (behind the n index slots: one word per page, the count of indices its stream gave)

@@ -518,10 +518,10 @@ __global__ __launch_bounds__(256) void finish_bitmaps_kernel(const BitmapBatch b
         __syncthreads();
         if (threadIdx.x == 0) {
             const unsigned long long t = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
-            if (b.host_block) reinterpret_cast<unsigned long long *>(b.host_block + 1024)[a] = t;   // (the only workgroup of this bitmap)
+            if (b.host_block) reinterpret_cast<unsigned long long *>(b.host_block + kAggCountsFromStatus)[a] = t;   // (the only workgroup of this bitmap)
             else if (t) atomicAdd(&b.counts[a], t);
         }
-    } else if (b.host_block && threadIdx.x == 0) reinterpret_cast<unsigned long long *>(b.host_block + 1024)[a] = 0;
+    } else if (b.host_block && threadIdx.x == 0) reinterpret_cast<unsigned long long *>(b.host_block + kAggCountsFromStatus)[a] = 0;
     // the status words of the launches in front of this one, straight into the host's block: no copy command behind the call's last launch
     if (b.host_block && a == 0 && blockIdx.x == 0)
         for (int t = threadIdx.x; t < b.status_words; t += blockDim.x) reinterpret_cast<uint32_t *>(b.host_block)[t] = b.status[t];

@@ -212,6 +212,7 @@ void ctx_drop_null_ts_cache(Ctx *c) {
 }
 
 int ctx_scratch(Ctx *c, size_t bytes, void **dptr) {
+    if (bytes < kScrFixedBytes) bytes = kScrFixedBytes;   // (ctx_blocks.h: only a tile pass' long-window list asks for more)
     if (c->d_scratch_bytes < bytes) {
         if (c->d_scratch) (void)hipFree(c->d_scratch);
         c->d_scratch = nullptr;
@@ -223,14 +224,10 @@ int ctx_scratch(Ctx *c, size_t bytes, void **dptr) {
     return 0;
 }
 
-int ctx_pinned(Ctx *c, size_t bytes, void **hptr) {
-    if (bytes < 16384) bytes = 16384;  // one block for every small user (status words, null counts, seeds): it never moves under them
-    if (c->h_pinned_bytes < bytes) {
-        if (c->h_pinned) (void)hipHostFree(c->h_pinned);
-        c->h_pinned = nullptr;
-        c->h_pinned_bytes = 0;
-        BG_HIP(hipHostMalloc(&c->h_pinned, bytes, hipHostMallocDefault));
-        c->h_pinned_bytes = bytes;
+int ctx_pinned(Ctx *c, void **hptr) {
+    if (!c->h_pinned) {   // one block for every small user: it never moves under them
+        BG_HIP(hipHostMalloc(&c->h_pinned, kRegBytes, hipHostMallocDefault));
+        c->h_pinned_bytes = kRegBytes;
     }
     *hptr = c->h_pinned;
     return 0;
@@ -564,9 +561,8 @@ int bowgpu_stream_read_ceiling(const void *dev_a, const void *dev_b, int64_t byt
     if ((reinterpret_cast<uintptr_t>(dev_a) | reinterpret_cast<uintptr_t>(dev_b)) & 15) return fail(BOWGPU_ERR_ARG, "buffers must be 16-byte aligned");
     Ctx *c;
     BG_TRY(ctx_get(&c));
-    void *d;
-    BG_TRY(ctx_scratch(c, 4096, &d));
-    uint64_t *dout = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(d) + 3072);
+    uint64_t *dout;
+    BG_TRY(scratch_at(c, kScrProbe, &dout));
     double best = 0.0;
     const int shapes[][2] = {{0, 8}, {0, 16}, {0, 32}, {1, 0}};  // {mode, workgroups per CU}
     for (const auto &sh : shapes) {
@@ -610,10 +606,13 @@ int bowgpu_debug_host_copy(void *dst, const void *src, int64_t bytes) {
 int bowgpu_debug_status(int32_t first, int32_t n, uint32_t *out, int32_t zero_after) {
     Ctx *c;
     BG_TRY(ctx_get(&c));
-    if (!out || first < 0 || n <= 0 || (size_t)(first + n) * 4 > 8192 || !c->d_scratch) return fail(BOWGPU_ERR_ARG, "bad status range");
-    BG_TRY(copy_d2h(c, out, reinterpret_cast<uint32_t *>(c->d_scratch) + first, (size_t)n * 4));
+    // (a thread that has made no call yet has no status block to show)
+    if (!out || first < 0 || n <= 0 || (size_t)(first + n) * 4 > kScrDiag.size || !c->d_scratch) return fail(BOWGPU_ERR_ARG, "bad status range");
+    uint32_t *words;
+    BG_TRY(scratch_at(c, kScrDiag, &words));
+    BG_TRY(copy_d2h(c, out, words + first, (size_t)n * 4));
     BG_HIP(hipStreamSynchronize(c->stream));
-    if (zero_after) BG_HIP(hipMemsetAsync(reinterpret_cast<uint32_t *>(c->d_scratch) + first, 0, (size_t)n * 4, c->stream));
+    if (zero_after) BG_HIP(hipMemsetAsync(words + first, 0, (size_t)n * 4, c->stream));
     return 0;
 }
 
@@ -624,9 +623,8 @@ int bowgpu_checksum64(const void *dev, int64_t n_words, uint64_t *xor_out, uint6
 int bowgpu_checksum64_at(const void *dev, int64_t n_words, int64_t index_base, uint64_t *xor_out, uint64_t *sum_out) {
     Ctx *c;
     BG_TRY(ctx_get(&c));
-    void *d;
-    BG_TRY(ctx_scratch(c, 4096, &d));
-    uint64_t *dout = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(d) + 3072);
+    uint64_t *dout;
+    BG_TRY(scratch_at(c, kScrProbe, &dout));
     BG_TRY(launch_checksum64(c, dev, n_words, dout, (uint64_t)index_base));
     uint64_t h[2] = {0, 0};
     BG_HIP(hipMemcpyAsync(h, dout, 16, hipMemcpyDeviceToHost, c->stream));

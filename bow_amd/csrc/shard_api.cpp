@@ -404,9 +404,8 @@ int bowgpu_shard_finish(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, i
             }
             // (the records were built by the caller's all_gather: pageable memory, so stage through the pinned block)
             bowgpu_carry_state *hseed;
-            static_assert(4096 + sizeof seeds <= 16384, "pinned block");
-            BG_TRY(ctx_pinned(c, 16384, reinterpret_cast<void **>(&hseed)));
-            hseed = reinterpret_cast<bowgpu_carry_state *>(reinterpret_cast<char *>(hseed) + 4096);
+            static_assert(sizeof seeds == kRegSeeds.size, "the registered block's seeds");
+            BG_TRY(registered_at(c, kRegSeeds, &hseed));
             memcpy(hseed, seeds, sizeof(bowgpu_carry_state) * naggs);
             BG_HIP(hipMemcpyAsync(dseed, hseed, sizeof(bowgpu_carry_state) * naggs, hipMemcpyHostToDevice, c->stream));
             // the window may also be the rank's last one: then the next rank's first row can be its inclusive row

@@ -34,18 +34,18 @@ namespace bowgpu {
 int argsort_device(Ctx *c, const bowgpu_col *key, const DevCol &dk, SortWork *w, int32_t *sorted) {
     const int64_t n = dk.length;
     const int is_float = key->type == BOWGPU_FLOAT64;
-    void *scr;
-    BG_TRY(ctx_scratch(c, kScrBytes, &scr));
-    char *s = reinterpret_cast<char *>(scr);
-    uint32_t *d_hist = reinterpret_cast<uint32_t *>(s + kScrHist), *d_flags = reinterpret_cast<uint32_t *>(s + kScrFlags);
+    uint32_t *d_hist, *d_flags;   // (the flags lie right behind the histogram: one memset and one copy for both)
+    BG_TRY(scratch_at(c, kScrHist, &d_hist));
+    BG_TRY(scratch_at(c, kScrFlags, &d_flags));
     const uint64_t *raw = reinterpret_cast<const uint64_t *>(dk.values);
     // a key read in place over the host link leaves its images in HBM during that one read
     const bool in_place_host = key->residency == BOWGPU_HOST_PINNED && !dk.own_values.p;
     if (in_place_host) BG_TRY(w->keys[1].alloc((size_t)n * 8));
-    BG_HIP(hipMemsetAsync(s, 0, kScrFlags + 16, c->stream));
+    BG_HIP(hipMemsetAsync(d_hist, 0, span(kScrHist, kScrFlags), c->stream));
     BG_TRY(launch_sort_hist(c, raw, n, is_float, d_hist, d_flags, in_place_host ? w->keys[1].as<uint64_t>() : nullptr));
     uint32_t back[8 * 256 + 4];
-    BG_HIP(hipMemcpyAsync(back, s, sizeof back, hipMemcpyDeviceToHost, c->stream));
+    static_assert(sizeof back == span(kScrHist, kScrFlags), "histogram and flags");
+    BG_HIP(hipMemcpyAsync(back, d_hist, sizeof back, hipMemcpyDeviceToHost, c->stream));
     BG_HIP(hipStreamSynchronize(c->stream));
     const uint32_t *flags = back + 8 * 256;
     if (flags[1]) return fail(BOWGPU_ERR_UNSUPPORTED, "column to sort by holds a NaN: Less is not an order there (the caller keeps the reference path)");
@@ -84,14 +84,16 @@ int argsort_device(Ctx *c, const bowgpu_col *key, const DevCol &dk, SortWork *w,
 }
 
 // ---------------------------------------------------------------- the gather's host side
-int gather_enqueue(Ctx *c, char *scratch, const MoveCols &cols, int32_t g0, int64_t length, const GatherIdx &ix, int64_t n_idx) {
+int gather_enqueue(Ctx *c, const MoveCols &cols, int32_t g0, int64_t length, const GatherIdx &ix, int64_t n_idx) {
     GatherNoRowArgs a;
     memset(&a, 0, sizeof a);
     a.cols = cols;
     a.n_idx = n_idx;
     a.length = length;
-    a.null_counts = reinterpret_cast<unsigned long long *>(scratch + kScrNulls);
-    a.bad = reinterpret_cast<uint32_t *>(scratch + kScrFlags) + 2;
+    uint32_t *flags;
+    BG_TRY(scratch_at(c, kScrFlags, &flags));
+    BG_TRY(scratch_at(c, kScrMoveCounts, &a.null_counts));
+    a.bad = flags + 2;
     a.key_slot = ix.key_col >= g0 && ix.key_col < g0 + kMoveCols ? ix.key_col - g0 : -1;
     if (a.key_slot >= 0) {
         a.idx2 = ix.i32_2;
@@ -99,16 +101,19 @@ int gather_enqueue(Ctx *c, char *scratch, const MoveCols &cols, int32_t g0, int6
         a.vbits2 = ix.key2->vbits;
         a.vbit02 = ix.key2->vbit0;
     }
-    BG_HIP(hipMemsetAsync(scratch + kScrFlags, 0, 16 + 8 * kMoveCols, c->stream));
+    BG_HIP(hipMemsetAsync(flags, 0, span(kScrFlags, kScrMoveCounts), c->stream));
     BG_TRY(launch_gather(c, a, ix));
     BG_HIP(hipEventRecord(c->ev1, c->stream));
     return 0;
 }
 
 int gather_launch(Ctx *c, const MoveGroup &g, int32_t g0, int64_t length, const GatherIdx &ix, int64_t n_idx, int64_t *nulls, bool *bad) {
-    BG_TRY(gather_enqueue(c, g.scratch, g.cols, g0, length, ix, n_idx));
+    BG_TRY(gather_enqueue(c, g.cols, g0, length, ix, n_idx));
     struct { uint32_t flags[4]; unsigned long long nulls[kMoveCols]; } back;
-    BG_HIP(hipMemcpyAsync(&back, g.scratch + kScrFlags, sizeof back, hipMemcpyDeviceToHost, c->stream));
+    static_assert(sizeof back == span(kScrFlags, kScrMoveCounts), "flags and counts");
+    const uint32_t *flags;
+    BG_TRY(scratch_at(c, kScrFlags, &flags));
+    BG_HIP(hipMemcpyAsync(&back, flags, sizeof back, hipMemcpyDeviceToHost, c->stream));
     BG_HIP(hipStreamSynchronize(c->stream));
     *bad = back.flags[2] != 0;
     for (int i = 0; i < kMoveCols; i++) nulls[i] = (int64_t)back.nulls[i];

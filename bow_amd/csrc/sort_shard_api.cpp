@@ -68,15 +68,14 @@ struct ShardSort {
 };
 
 int read_images(Ctx *c, const RankState &me, const uint32_t *pos, int npos, uint64_t *out) {
-    void *scr;
-    BG_TRY(ctx_scratch(c, kScrBytes, &scr));
     ImageAtArgs a;
     memset(&a, 0, sizeof a);
     a.keys = me.skeys; a.mode = me.smode; a.npos = npos;
     memcpy(a.pos, pos, sizeof(uint32_t) * (size_t)npos);
-    a.out = reinterpret_cast<uint64_t *>(scr);
+    static_assert(sizeof(uint64_t) * (sizeof a.pos / sizeof a.pos[0]) == kScrImages.size, "an image per position");
+    BG_TRY(scratch_at(c, kScrImages, &a.out));
     BG_TRY(launch_image_at(c, a));
-    BG_HIP(hipMemcpyAsync(out, scr, sizeof(uint64_t) * (size_t)npos, hipMemcpyDeviceToHost, c->stream));
+    BG_HIP(hipMemcpyAsync(out, a.out, sizeof(uint64_t) * (size_t)npos, hipMemcpyDeviceToHost, c->stream));
     BG_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -144,7 +143,6 @@ bool splitters(Ctx *c, ShardSort *ss, int r, int *rc_out) {
         if (ss->T[d] >= ss->total) { for (int s = 0; s < world; s++) cut(s, d) = ss->ranks[s].n; }   // trailing empty ranks: everything lies below
         else if (ss->T[d] > 0) open.push_back({d, lo0, hi0});                                           // (T[d] = 0: nothing does)
     }
-    void *scr = nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     for (int round = 0; !open.empty(); round++) {
         int rc = 0;
@@ -157,10 +155,10 @@ bool splitters(Ctx *c, ShardSort *ss, int r, int *rc_out) {
             memset(&a, 0, sizeof a);
             a.keys = me.skeys; a.n = me.n; a.mode = me.smode; a.ncand = ncand;
             for (int j = 0; j < ncand; j++) a.cand[j] = open[j].lo + ((open[j].hi - open[j].lo) >> 1);
-            rc = ctx_scratch(c, kScrBytes, &scr);
-            a.out = reinterpret_cast<uint32_t *>(scr);
+            static_assert(sizeof(uint32_t) * 2 * (sizeof a.cand / sizeof a.cand[0]) == kScrSplitBounds.size, "two counts per candidate");
+            rc = scratch_at(c, kScrSplitBounds, &a.out);
             if (rc == 0) rc = launch_split_bounds(c, a);
-            if (rc == 0 && hipMemcpyAsync(mine, scr, sizeof(uint32_t) * 2 * (size_t)ncand, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+            if (rc == 0 && hipMemcpyAsync(mine, a.out, sizeof(uint32_t) * 2 * (size_t)ncand, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
                 rc = hip_fail(hipGetLastError(), "hipMemcpyAsync (splitter bounds)");
             if (rc == 0 && hipStreamSynchronize(c->stream) != hipSuccess) rc = hip_fail(hipGetLastError(), "hipStreamSynchronize");
         } else if (rc == 0) {
