@@ -862,7 +862,7 @@ def shard_interpolate(cols, ts_col, interval, interps, global_s0, rank, all_poin
 
 def fill_linear(cols, ref_col, fill_col, out_residency=HOST, capacity=None, ref_checked=False):
     """capacity: rows the output buffers can hold (default: exactly the column's) - a device-resident bitmap that reaches the end of its
-    last 64-bit word and is 8-byte aligned is written in place (bow_amd/csrc/extras.cpp fill_finish)"""
+    last 64-bit word and is 8-byte aligned is written in place (bow_amd/csrc/fill_api.cpp fill_finish)"""
     out = OutColumn(cols[fill_col].length if capacity is None else capacity, out_residency)
     o = out.c()
     unchanged = C.c_int32(0)

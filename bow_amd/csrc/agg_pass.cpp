@@ -643,7 +643,7 @@ int fused_try(Ctx *c, const bowgpu_col *cols, int32_t ncols, int32_t ts_col, con
     const int64_t n = tsc->length, W = plan.W;
     if (route_mask() & (BOWGPU_ROUTE_NO_FUSED | BOWGPU_ROUTE_NO_SIMPLE | BOWGPU_ROUTE_FORCE_GENERAL)) return 0;
     if (n <= 0 || W <= 0 || inclusive || o.inclusive || naggs > kSimpleMaxAggs) return 0;
-    if (tsc->validity && tsc->null_count != 0) return 0;                      // (an interval column with nulls: extras.cpp interp_null_ts)
+    if (tsc->validity && tsc->null_count != 0) return 0;                      // (an interval column with nulls: interp_null_ts.cpp)
     if (plan.first_ts < plan.s0 || plan.s0 <= -(1ll << 53)) return 0;   // rows below s0; float64(ts) inexact
     // a window that starts at -1, the reference's "no first value" sentinel (interpolation.go:99-105): such a window never gets a synthetic row
     if (plan.s0 <= -1 && (uint64_t)(-1 - plan.s0) % (uint64_t)plan.interval == 0 && (int64_t)((uint64_t)(-1 - plan.s0) / (uint64_t)plan.interval) < W) return 0;

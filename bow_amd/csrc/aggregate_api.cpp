@@ -1,5 +1,6 @@
 // aggregate_api.cpp — the unsharded Rolling.Aggregate call: window planning, argument validation mirroring the reference's
-// drivers, the paths for Mode, Boolean columns and an interval column with nulls, and the bowgpu_rolling_* / bowgpu_plan_windows* entry points.
+// drivers, the paths for Mode, Boolean columns and an interval column with nulls, and the bowgpu_rolling_* / bowgpu_plan_windows* /
+// bowgpu_window_bounds entry points.
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -44,8 +45,7 @@ int64_t first_window_start(int64_t first, int64_t interval, int64_t offset_norm)
 int plan_make(Ctx *c, const bowgpu_col *ts, int64_t interval, int64_t raw_offset, Plan *p) {
     // reference rolling/rolling.go:69-112 and :143-154
     if (ts->type != BOWGPU_INT64)
-        return fail(BOWGPU_ERR_TS_TYPE, "impossible to create a new intervalRolling on column of type %s",
-                    ts->type == BOWGPU_FLOAT64 ? "float64" : ts->type == BOWGPU_BOOLEAN ? "bool" : ts->type == BOWGPU_STRING ? "utf8" : "undefined");
+        return fail(BOWGPU_ERR_TS_TYPE, "impossible to create a new intervalRolling on column of type %s", arrow_type_name(ts->type));
     BG_TRY(enforce_interval_and_offset(interval, raw_offset, &p->offset));
     p->interval = interval;
     p->magic = magic_make((uint64_t)interval);
@@ -631,8 +631,7 @@ int sharded_validate(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, int6
     // plan_make's order (newIntervalRolling first), then validateAggregation's, then the protocol's own limits
     const int t = cols[ts_col].type;
     if (t != BOWGPU_INT64)
-        return fail(BOWGPU_ERR_TS_TYPE, "impossible to create a new intervalRolling on column of type %s",
-                    t == BOWGPU_FLOAT64 ? "float64" : t == BOWGPU_BOOLEAN ? "bool" : t == BOWGPU_STRING ? "utf8" : "undefined");
+        return fail(BOWGPU_ERR_TS_TYPE, "impossible to create a new intervalRolling on column of type %s", arrow_type_name(t));
     int64_t off;
     BG_TRY(enforce_interval_and_offset(interval, 0, &off));
     int inclusive = 0, nic = -1;
@@ -649,6 +648,22 @@ int ts_null_rows(Ctx *c, const bowgpu_col *ts, int64_t *nulls) {
     *nulls = probe.null_count;
     BG_HIP(hipStreamSynchronize(c->stream));   // (before the probe's blocks go back to the cache)
     return 0;
+}
+
+int ts_contract(Ctx *c, const bowgpu_col *tsc) {
+    if (tsc->validity && tsc->null_count != 0) {
+        DevCol probe;
+        BG_TRY(devcol_prepare(c, tsc, &probe, false, true));
+        if (probe.null_count > 0) return fail(BOWGPU_ERR_TS_NULLS, "interval column has %lld nulls: outside the device path", (long long)probe.null_count);
+    }
+    return 0;
+}
+
+int ts_device(Ctx *c, const bowgpu_col *tsc, DevCol *dts) {
+    bowgpu_col t = *tsc;
+    t.validity = nullptr;
+    t.null_count = 0;
+    return devcol_prepare(c, &t, dts, true, false);
 }
 
 }  // namespace bowgpu
@@ -669,6 +684,50 @@ int bowgpu_plan_windows(const bowgpu_col *ts, int64_t interval, int64_t offset, 
     BG_TRY(plan_make(nullptr, ts, interval, offset, &p));
     *s0 = p.s0;
     *num_windows = p.W;
+    return 0;
+}
+
+// the plan materialised: every window's first row, slice and inclusive flag (the iterator)
+int bowgpu_window_bounds(const bowgpu_col *ts, int64_t interval, const bowgpu_options *opts, int64_t *first_index,
+                         int64_t *slice_begin, int64_t *slice_end, uint8_t *is_inclusive, int32_t residency) {
+    if (!ts) return fail(BOWGPU_ERR_ARG, "null argument");
+    const bowgpu_options o = options_or(opts);
+    Plan plan;
+    BG_TRY(plan_make(nullptr, ts, interval, o.offset, &plan));
+    if (plan.W == 0) return 0;
+    Ctx *c;
+    BG_TRY(ctx_get(&c));
+    BG_TRY(ts_contract(c, ts));
+    DevCol dts;
+    BG_TRY(ts_device(c, ts, &dts));
+    const int64_t n = ts->length, W = plan.W;
+    DevBuf first_idx, d_fi, d_sb, d_se, d_in;
+    BG_TRY(first_idx.alloc((size_t)(W + 1) * 8));
+    uint32_t *status;
+    BG_TRY(scratch_at(c, kScrStatus, &status));
+    BG_HIP(hipMemsetAsync(status, 0, kStatusHeadBytes, c->stream));
+    BG_TRY(launch_window_first_rows(c, reinterpret_cast<const int64_t *>(dts.values), n, plan, reinterpret_cast<int64_t *>(first_idx.p), status));
+    const bool dev = residency == BOWGPU_DEVICE;
+    int64_t *pfi = first_index, *psb = slice_begin, *pse = slice_end;
+    uint8_t *pin = is_inclusive;
+    if (!dev) {
+        if (first_index) { BG_TRY(d_fi.alloc((size_t)W * 8)); pfi = reinterpret_cast<int64_t *>(d_fi.p); }
+        if (slice_begin) { BG_TRY(d_sb.alloc((size_t)W * 8)); psb = reinterpret_cast<int64_t *>(d_sb.p); }
+        if (slice_end) { BG_TRY(d_se.alloc((size_t)W * 8)); pse = reinterpret_cast<int64_t *>(d_se.p); }
+        if (is_inclusive) { BG_TRY(d_in.alloc((size_t)W)); pin = reinterpret_cast<uint8_t *>(d_in.p); }
+    }
+    BG_TRY(launch_window_bounds(c, reinterpret_cast<const int64_t *>(dts.values), n, plan, o.inclusive ? 1 : 0,
+                                plan.s0 > plan.first_ts ? 1 : 0, reinterpret_cast<const int64_t *>(first_idx.p), pfi, psb, pse, pin));
+    uint32_t hstat[4] = {0, 0, 0, 0};
+    BG_HIP(hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, c->stream));
+    if (!dev) {
+        if (first_index) BG_TRY(copy_d2h(c, first_index, pfi, (size_t)W * 8));
+        if (slice_begin) BG_TRY(copy_d2h(c, slice_begin, psb, (size_t)W * 8));
+        if (slice_end) BG_TRY(copy_d2h(c, slice_end, pse, (size_t)W * 8));
+        if (is_inclusive) BG_TRY(copy_d2h(c, is_inclusive, pin, (size_t)W));
+    }
+    BG_HIP(hipStreamSynchronize(c->stream));
+    if (hstat[0]) return fail_ts_unsorted();
     return 0;
 }
 
@@ -722,8 +781,7 @@ int bowgpu_rolling_aggregate(const bowgpu_col *cols, int32_t ncols, int32_t ts_c
                              bowgpu_out *outs, bowgpu_agg_info *info) {
     if (!cols || ncols <= 0) return fail(BOWGPU_ERR_ARG, "no columns");
     if (ts_col < 0 || ts_col >= ncols) return fail(BOWGPU_ERR_BAD_COL, "no interval column with index %d", ts_col);
-    bowgpu_options o = {0, 0, 0};
-    if (opts) o = *opts;
+    const bowgpu_options o = options_or(opts);
     // reference order: the Rolling exists first (newIntervalRolling errors), then Aggregate validates
     Plan plan;
     BG_TRY(plan_make(nullptr, &cols[ts_col], interval, o.offset, &plan));
@@ -739,8 +797,7 @@ int bowgpu_rolling_interpolate_aggregate(const bowgpu_col *cols, int32_t ncols, 
     if (!cols || ncols <= 0) return fail(BOWGPU_ERR_ARG, "no columns");
     if (ts_col < 0 || ts_col >= ncols) return fail(BOWGPU_ERR_BAD_COL, "no interval column with index %d", ts_col);
     if (!interps) return fail(BOWGPU_ERR_ARG, "null argument");
-    bowgpu_options o = {0, 0, 0};
-    if (opts) o = *opts;
+    const bowgpu_options o = options_or(opts);
     // the reference's order: the Rolling exists first (newIntervalRolling), Interpolate validates its interpolators, then Aggregate
     // validates its aggregators against the interpolated Bow - which has the input's columns and types (interpolation.go:139-155)
     Plan plan;

@@ -15,10 +15,6 @@ namespace {
 constexpr int64_t kAppendMaxRows = (int64_t)1 << 31;   // rows inside the kernels are 32 bits wide
 constexpr int32_t kAppendMaxPieces = 1 << 18;          // the piece table of a launch group: 100 bytes a piece
 
-const char *type_name(int32_t t) {   // bowtypes.go:89-96 (arrow type names)
-    return t == BOWGPU_FLOAT64 ? "float64" : t == BOWGPU_INT64 ? "int64" : t == BOWGPU_BOOLEAN ? "bool" : t == BOWGPU_STRING ? "utf8" : "undefined";
-}
-
 // everything that can be said about the pieces without reading a column; *total: rows of the result
 int pieces_checks(const bowgpu_col *const *frames, int32_t nframes, int32_t ncols, int64_t *total) {
     if (nframes < 1) return fail(BOWGPU_ERR_ARG, "no frame to append (%d)", nframes);
@@ -33,7 +29,7 @@ int pieces_checks(const bowgpu_col *const *frames, int32_t nframes, int32_t ncol
         BG_TRY(frame_cols_checks(frames[f], ncols, n, true));
         for (int i = 0; i < ncols; i++)
             if (frames[f][i].type != frames[0][i].type)   // bowappend.go:40-42
-                return fail(BOWGPU_ERR_TYPE, "incompatible types '%s' and '%s'", type_name(frames[0][i].type), type_name(frames[f][i].type));
+                return fail(BOWGPU_ERR_TYPE, "incompatible types '%s' and '%s'", arrow_type_name(frames[0][i].type), arrow_type_name(frames[f][i].type));
         *total += n;
         if (*total >= kAppendMaxRows)
             return fail(BOWGPU_ERR_UNSUPPORTED, "the frames have %lld rows and more: the device path serves fewer than 2^31 = 2147483648 rows",

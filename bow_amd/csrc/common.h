@@ -19,6 +19,12 @@ void set_error(const char *fmt, ...);
 int fail(int code, const char *fmt, ...);
 int fail_ts_unsorted();   // BOWGPU_ERR_TS_UNSORTED: what every device path says about an interval column that is not ascending (agg_pass.cpp)
 int hip_fail(hipError_t e, const char *what);
+// the Arrow name of a column type as the reference's error texts spell it (bowtypes.go:89-96)
+inline const char *arrow_type_name(int t) {
+    return t == BOWGPU_FLOAT64 ? "float64" : t == BOWGPU_INT64 ? "int64" : t == BOWGPU_BOOLEAN ? "bool" : t == BOWGPU_STRING ? "utf8" : "undefined";
+}
+// a call's options: the caller's, or the defaults when it passed none
+inline bowgpu_options options_or(const bowgpu_options *opts) { return opts ? *opts : bowgpu_options{0, 0, 0}; }
 
 #define BG_HIP(expr)                                         \
     do {                                                     \
@@ -65,7 +71,7 @@ struct Ctx {
     size_t pool_bytes[kPoolSlots] = {};
     uint64_t pool_gen[kPoolSlots] = {};     // bumped on every ctx_pool() of the slot: lets a cached result notice that its block was handed out again
     // what bowgpu_rolling_interpolate_count leaves for the _fill call that follows it on the same (unchanged) columns: the
-    // per-trip prefix of exact window heads, so that the interval column is not scanned a second time (extras.cpp)
+    // per-trip prefix of exact window heads, so that the interval column is not scanned a second time (interpolate_api.cpp)
     struct InterpCache {
         bool valid = false;
         const void *ts_values = nullptr;
@@ -75,11 +81,16 @@ struct Ctx {
         int has_left = 0;
         uint64_t gen = 0, gen0 = 0;         // pool_gen of the two prefix blocks when they were written
         uint64_t epoch = 0;                 // device_write_epoch() when it was written: any write / free through the library since then drops it
-        int64_t s0 = 0, W = 0, first_ts = 0, last_ts = 0, offset_norm = 0, kq = -1, drop = 0, M = 0, wbase = 0;
-        int kq_empty = 0, inclusive = 0, e0 = 0;
+        // What pass 1 found (interpolate_api.cpp interp_prepare): the plan's pieces, then InterpParams' kq / drop / wbase / kq_empty /
+        // e0 and M = output rows - input rows.  An InterpJob holds the same struct: count -> fill hands it over in one assignment.
+        // (inclusive is a KEY field of the cache, not a finding: it sits here because the members keep their places)
+        struct Found {
+            int64_t s0 = 0, W = 0, first_ts = 0, last_ts = 0, offset_norm = 0, kq = -1, drop = 0, M = 0, wbase = 0;
+            int kq_empty = 0, inclusive = 0, e0 = 0;
+        } found;
     } interp_cache;
     void *d_params = nullptr;      // 4 KB device block holding the kernels' descriptor struct
-    // what an Interpolate _count over an interval column WITH NULLS leaves for its _fill (extras.cpp NullTsState: device temporaries);
+    // what an Interpolate _count over an interval column WITH NULLS leaves for its _fill (interp_null_ts.cpp NullTsState: device temporaries);
     // freed through null_ts_cache_free by the fill, bowgpu_trim, bowgpu_set_device and at thread exit
     void *null_ts_cache = nullptr;
     void (*null_ts_cache_free)(void *) = nullptr;
@@ -203,6 +214,9 @@ int aux_in(Ctx *c, const void *p, size_t bytes, int32_t residency, const char *w
 bowgpu_col device_col(const void *values, int64_t n, int32_t type);
 bool any_device_out(const bowgpu_out *outs, int32_t n);   // some output column is device-resident (the write epoch moves with the call)
 void out_empty(bowgpu_out *out, int32_t type);            // an output column of a result without rows
+template <class TypeOf> void outs_empty(bowgpu_out *outs, int32_t n, TypeOf type_of) {   // ... n of them, column i of type type_of(i)
+    for (int32_t i = 0; i < n; i++) out_empty(&outs[i], type_of(i));
+}
 // a result buffer handed to the caller: dst in device memory is src itself or gets a device-to-device copy (and the write epoch moves)
 int aux_out(Ctx *c, void *dst, const void *src, size_t bytes, int32_t residency);
 int synced(Ctx *c, int rc);            // rc - a failure only after the stream has drained: the call's kernels may still be running on its work buffers
@@ -299,6 +313,9 @@ int multi_interpolate_aggregate(const bowgpu_col *cols, int32_t ncols, int32_t t
 int sharded_validate(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, int64_t interval, const bowgpu_agg *aggs, int32_t naggs);
 // nulls of an interval column (counted on the calling thread's device when the caller said -1)
 int ts_null_rows(Ctx *c, const bowgpu_col *ts, int64_t *nulls);
+// the callers that take no null in the interval column: BOWGPU_ERR_TS_NULLS when it has one; the column on the device, its bitmap left out
+int ts_contract(Ctx *c, const bowgpu_col *tsc);
+int ts_device(Ctx *c, const bowgpu_col *tsc, DevCol *dts);
 
 // shard.hip: the tail of a rank of bowgpu_rolling_aggregate_sharded that does not own its last output slot (one lane per output)
 struct ShardTailArgs {
@@ -415,7 +432,7 @@ struct FusedParams {
     double inv_interval;           // (1 / interval) * (1 + 2^-40): floor(x * inv_interval) == x / interval for every x < 2^32 (rolling_fused.hip fdiv32)
 };
 int launch_rolling_fused(Ctx *c, const FusedParams &fp, int need, bool has_nulls);
-// Interpolate + validateInterpolation (extras.cpp; reference rolling/interpolation.go:30-96)
+// Interpolate + validateInterpolation (interpolate_api.cpp; reference rolling/interpolation.go:30-96)
 int interp_validate(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, const bowgpu_options *o, const bowgpu_interp *interps, int32_t ninterps);
 
 int launch_rolling_twc(Ctx *c, const SimpleParams &p, bool long_halo = false);   // (long_halo: 256 rows of look-ahead) nullable columns under time-weighted reducers, 32-bit times: the valid points compacted first (rolling_twc.hip)
@@ -435,7 +452,7 @@ constexpr int kLongLists = 64;      // sub-lists of the long-window queue (agg_d
 constexpr int kLongCountWord = 16;  // status[kLongCountWord + s] = entries in sub-list s
 constexpr int kStatusWords = kLongCountWord + kLongLists;
 // the words below kLongCountWord that the Aggregate kernels raise and agg_pass.cpp agg_status_error reads (Interpolate keeps a status block
-// of its own whose words 5 - 7 mean other things: interpolate.hip, extras.cpp).  rolling_agg.hip, rolling_fast.hip and shard.hip spell
+// of its own whose words 5 - 7 mean other things: interpolate.hip, interpolate_api.cpp).  rolling_agg.hip, rolling_fast.hip and shard.hip spell
 // them by name; the wave-tile kernels, long_windows.hip and agg_device.h still write the numbers (an edit to those files asks for the
 // round's counter files again: tests/test_profiles_fresh.py)
 constexpr int kAggStUnsorted = 0;        // the interval column is not ascending
@@ -596,7 +613,7 @@ static_assert(kPoolAppend > kPoolWhole && kPoolAppend < Ctx::kPoolSlots - 1, "co
 static_assert(kPoolMode != kPoolColOrder && kPoolColOrder != kPoolShard && kPoolMode != kPoolShard && kPoolMode > 15 && kPoolShard < kPoolInterp &&
               kPoolInterp + 10 < kPoolInterpEdge && kPoolInterpEdge < kPoolGaps && kPoolGaps < kPoolWhole && kPoolWhole < Ctx::kPoolSlots - 1,
               "context pool slots must be distinct");
-// kernel parameter blocks of interp_fill.hip (filled by extras.cpp, passed by value)
+// kernel parameter blocks of interp_fill.hip (filled by interpolate_api.cpp, fill_api.cpp and whole_api.cpp, passed by value)
 struct InterpCol {
     const uint64_t *values;
     const uint32_t *vbits;

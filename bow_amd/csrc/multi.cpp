@@ -841,8 +841,7 @@ int bowgpu_rolling_aggregate_sharded(const bowgpu_col *const *cols_by_rank, cons
                             (long long)cols_by_rank[r][ts_col].length);
         }
     BG_TRY(sharded_validate(cols_by_rank[0], ncols, ts_col, interval, aggs, naggs));
-    bowgpu_options o = {0, 0, 0};
-    if (opts) o = *opts;
+    const bowgpu_options o = options_or(opts);
 
     ShardedCall sc;
     sc.cols_by_rank = cols_by_rank; sc.ids = device_ids; sc.world = world; sc.ncols = ncols; sc.ts_col = ts_col; sc.interval = interval;

@@ -125,8 +125,7 @@ int bowgpu_shard_begin(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, in
                        const bowgpu_agg *aggs, int32_t naggs, const int64_t *global_s0, bowgpu_shard_record *rec) {
     if (!cols || ncols <= 0 || !rec || !aggs) return fail(BOWGPU_ERR_ARG, "null argument");
     if (ts_col < 0 || ts_col >= ncols) return fail(BOWGPU_ERR_BAD_COL, "no interval column with index %d", ts_col);
-    bowgpu_options o = {0, 0, 0};
-    if (opts) o = *opts;
+    const bowgpu_options o = options_or(opts);
     int inclusive = o.inclusive ? 1 : 0, nic = -1;
     BG_TRY(validate_aggs(cols, ncols, ts_col, aggs, naggs, &inclusive, &nic));
     BG_TRY(shard_check(cols, aggs, naggs));
@@ -185,8 +184,7 @@ int bowgpu_shard_pass_begin(const bowgpu_col *cols, int32_t ncols, int32_t ts_co
                             const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs, const bowgpu_shard_record *me) {
     if (!cols || ncols <= 0 || !outs || !me || !aggs) return fail(BOWGPU_ERR_ARG, "null argument");
     if (ts_col < 0 || ts_col >= ncols) return fail(BOWGPU_ERR_BAD_COL, "no interval column with index %d", ts_col);
-    bowgpu_options o = {0, 0, 0};
-    if (opts) o = *opts;
+    const bowgpu_options o = options_or(opts);
     int inclusive = o.inclusive ? 1 : 0, nic = -1;
     BG_TRY(validate_aggs(cols, ncols, ts_col, aggs, naggs, &inclusive, &nic));
     BG_TRY(shard_check(cols, aggs, naggs));
@@ -295,8 +293,7 @@ int bowgpu_shard_finish(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, i
     if (!cols || ncols <= 0 || !outs || !recs || !aggs) return fail(BOWGPU_ERR_ARG, "null argument");
     if (ts_col < 0 || ts_col >= ncols) return fail(BOWGPU_ERR_BAD_COL, "no interval column with index %d", ts_col);
     PendingOwnerScope owner;   // (the pass in flight is this call's to collect or drop)
-    bowgpu_options o = {0, 0, 0};
-    if (opts) o = *opts;
+    const bowgpu_options o = options_or(opts);
     int inclusive = o.inclusive ? 1 : 0, nic = -1;
     BG_TRY(validate_aggs(cols, ncols, ts_col, aggs, naggs, &inclusive, &nic));
     BG_TRY(shard_check(cols, aggs, naggs));

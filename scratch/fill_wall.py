@@ -3,7 +3,7 @@
 import sys, time, ctypes as C
 sys.path.insert(0, '.')
 from bow_amd import capi
-n = 100_000_000
+n = int(float(sys.argv[1])) if len(sys.argv) > 1 else 100_000_000
 ts, val = capi.gen_sparse(0, n, seed=42)
 L = capi.lib()
 out = capi.OutColumn(n, capi.DEVICE)

@@ -326,9 +326,9 @@ def trip_figures(ts, s0, interval):
 def outside_inclusive_interpolate(ts, interval, offset):
     """None, or why inclusive Interpolate declines this frame (BOWGPU_ERR_UNSUPPORTED, -9).  From the inputs alone:
       * rows below s0, a window that starts at the reference's -1 sentinel, an interval of 2^31 and more, timestamps beyond 2^53:
-        bow_amd/csrc/extras.cpp:260-261 (interp_fast32 / interp_wide32, interpolate.hip:991-1001, and drop != 0)
+        bow_amd/csrc/interpolate_api.cpp interp_prepare (interp_fast32 / interp_wide32, interpolate.hip:991-1001, and drop != 0)
       * a 512-row trip that spans 2^31 - 1 or more from the start of its first row's window, or that crosses 2^22 - 1 windows and more
-        in one step, or whose outputs do not fit the 16-bit position table: extras.cpp:505-507 (interpolate.hip:515, :522, :577, :606)
+        in one step, or whose outputs do not fit the 16-bit position table: interpolate_api.cpp interp_fill_impl (interpolate.hip:515, :522, :577, :606)
     "Fewer than two rows per window on average" is no condition of today's code - interp_wave3_kernel<true> lists up to 512 runs per
     trip (interpolate.hip:922), as many as a trip has rows - so it is not one here: such a frame has to be served."""
     s0, W = plan(ts, interval, offset)
@@ -385,7 +385,7 @@ def longest_null_run(valid):
 
 def fill_needs_the_index(valid):
     """a null run so long that some 512-row trip inside it cannot see its end within the near walk (64 words of 32 bits, less than a
-    word lost to alignment): extras.cpp fill_finish repeats the kernel with the neighbour index built"""
+    word lost to alignment): fill_api.cpp fill_finish repeats the kernel with the neighbour index built"""
     return longest_null_run(valid) >= NEAR_BITS + TRIP + 64
 
 

@@ -1,5 +1,5 @@
 """Seeded cases for the paths that serve an INTERVAL COLUMN WITH NULLS (bow_amd/csrc/ts_nulls.hip, aggregate_api.cpp run_aggregate_null_ts,
-extras.cpp interp_null_ts): what tests/test_gpu_null_ts_fuzz.py pushes through the device and tests/test_null_ts_cases_cpu.py checks
+interp_null_ts.cpp): what tests/test_gpu_null_ts_fuzz.py pushes through the device and tests/test_null_ts_cases_cpu.py checks
 without one.  No GPU is needed to draw a case or to build its oracle columns; Case.ccols() alone touches the device, and only for a
 device-resident case.
 
@@ -55,7 +55,7 @@ def rows_on_a_start_with_a_null_behind(ts, tvalid, s0, interval):
 
 
 def outside_inclusive_interpolate(ts, tvalid, s0, interval):
-    """the two shapes inclusive Interpolate over an interval column with nulls leaves to the reference (BOWGPU_ERR_TS_NULLS, extras.cpp
+    """the two shapes inclusive Interpolate over an interval column with nulls leaves to the reference (BOWGPU_ERR_TS_NULLS, interp_null_ts.cpp
     interp_null_ts): a row as above that sits on -1 - interpolateWindow's "no first value", interpolation.go:119-127 - or whose next
     valid timestamp equals its own (the next window then has its start and adds no row)"""
     n = len(ts)
@@ -254,7 +254,7 @@ def _interpolate_case(rng, seed, case, tag):
         ts = np.cumsum(rng.integers(1, 4, n)).astype(np.int64)
         interval, inclusive = int(rng.integers(1, 4)), True
     if inclusive:
-        # the domain extras.cpp states for inclusive Interpolate: non-negative timestamps, 0 <= offset < interval, 0 <= s0 <= ts[0],
+        # the domain interp_null_ts.cpp states for inclusive Interpolate: non-negative timestamps, 0 <= offset < interval, 0 <= s0 <= ts[0],
         # a span far below 2^31
         offset = int(rng.integers(0, interval))
         ts = ts - min(int(ts[0]), 0) + int(rng.integers(0, 50))

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from bow_amd import capi
-from interp_model import next_valid, prev_valid
+from interp_model import TRIP, next_valid, plan as model_plan, prev_valid, trip_figures
 from oracle import pyoracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -120,7 +120,7 @@ def test_interpolate_in_one_pass_without_a_count(vtype):
     """bowgpu_rolling_interpolate_fill on its own, without a preceding _count: the caller sizes the buffers (rows + windows at most), the
     call sets their length.  Inclusive windows take ONE pass over the rows (n_out = n + W - e0 needs no count; the fill kernel checks
     the order of the interval column itself); exclusive windows make their own count pass first (a look-back inside the fill kernel
-    was measured slower: extras.cpp).  Equal to the oracle bit for bit; a buffer that is too small is an error that names the
+    was measured slower: interpolate_api.cpp).  Equal to the oracle bit for bit; a buffer that is too small is an error that names the
     size, never a write past its end; an unsorted column is declined."""
     rng = np.random.default_rng(2604)
     typ = capi.FLOAT64 if vtype == "f64" else capi.INT64
@@ -853,6 +853,44 @@ def test_interpolate_count_to_fill_reuse_is_dropped_when_the_column_changes():
     cmp_out("after the tampering, ts", outs[0], want_a[0]); cmp_out("after the tampering, val", outs[1], want_a[1])
 
 
+def test_interpolate_redo_behind_a_reused_count():
+    """A _fill that reuses its _count's pass 1 (device-resident columns, the ordinary pair of calls) and then meets a 512-row trip
+    interp_wave3_kernel declines - here one that spans more than 2^31 from the start of its first row's window (interp_model.py
+    trip_figures / outside_inclusive_interpolate) - makes pass 1 its own again before the workgroup kernel takes the call.  Exclusive
+    windows: the oracle's rows, from interp_tile_kernel; the same frame without the gap: interp_wave3_kernel.  Inclusive windows have
+    no second kernel: declined, behind a count and as one call alike."""
+    rng = np.random.default_rng(31)
+    n, interval, gap_row = 3_000, 10_000_000, 1_300          # (the gap lies inside trip 2: rows 1024 .. 1535)
+    step = rng.integers(1, 200_000, n)
+    vals = np.round(rng.standard_normal(n) * 100, 2)
+    bm = np.packbits(rng.random(n) >= 0.3, bitorder="little")
+    ip = [{"kind": "WindowStart", "col": 0}, {"kind": "Linear", "col": 1}]
+
+    def frame(with_gap):
+        st = step.copy()
+        if with_gap:
+            st[gap_row] = 3_000_000_000
+        ts = np.cumsum(st).astype(np.int64)
+        span, crossed = trip_figures(ts, model_plan(ts, interval, 0)[0], interval)
+        declined = (span >= 2 ** 31 - 1) | (crossed >= 0xFFFF - TRIP - 1)
+        assert list(np.flatnonzero(declined)) == ([gap_row // TRIP] if with_gap else [])
+        dcols = [capi.Column(ts, None, capi.INT64).to_device(), capi.Column(vals, bm, capi.FLOAT64, 0, n, -1).to_device()]
+        return ts, dcols
+
+    for with_gap, kernel in ((True, "interp_tile_kernel"), (False, "interp_wave3_kernel")):
+        ts, dcols = frame(with_gap)
+        got = capi.rolling_interpolate(dcols, 0, interval, ip, out_residency=capi.DEVICE, padded=True)
+        assert capi.last_kernel_name() == kernel, (with_gap, capi.last_kernel_name())
+        want = orc.interpolate([orc.Column(ts, None, orc.INT64), orc.Column(vals, bm, orc.FLOAT64)], 0, interval, ip)
+        cmp_out("gap=%s ts" % with_gap, got[0], want[0])
+        cmp_out("gap=%s val" % with_gap, got[1], want[1])
+    ts, dcols = frame(True)
+    for call in (capi.rolling_interpolate, capi.rolling_interpolate_onepass):
+        with pytest.raises(capi.BowGpuError) as ei:
+            call(dcols, 0, interval, ip, inclusive=True, out_residency=capi.DEVICE)
+        assert ei.value.code == -9   # BOWGPU_ERR_UNSUPPORTED
+
+
 @pytest.mark.parametrize("device", [False, True])
 def test_interpolate_over_an_interval_column_with_nulls_more_than_sixteen_columns(device):
     """Round 6 (VERDICT r05 missing 5): a Bow of 21 columns over an interval column with nulls - BOWGPU_ERR_UNSUPPORTED until round 5 - goes
@@ -888,7 +926,7 @@ def test_interpolate_over_an_interval_column_with_nulls_more_than_sixteen_column
 
 def test_null_ts_fill_uses_what_its_count_built_and_notices_what_came_between():
     """Round 6 (ADVICE r04 / VERDICT r05 weak 10): over an interval column with nulls the _count's compaction of the kept rows stays for the
-    _fill that follows it on the same DEVICE-resident columns (extras.cpp NullTsState) instead of being built a second time.  The fill is
+    _fill that follows it on the same DEVICE-resident columns (interp_null_ts.cpp NullTsState) instead of being built a second time.  The fill is
     right - against the oracle - when it follows its count, when a write through the library came between (the state is dropped), when
     ANOTHER frame's count came between, when it runs without a count, and when the interpolators differ from the count's."""
     import ctypes as C

@@ -1,5 +1,5 @@
 """Differential fuzzing of Rolling.Interpolate, Interpolate(...).Aggregate(...) as one call and Bow.FillPrevious / FillNext / FillMean /
-FillLinear (interpolate.hip, interp_fill.hip, rolling_fused.hip and their drivers in extras.cpp) against the MODEL of tests/interp_model.py
+FillLinear (interpolate.hip, interp_fill.hip, rolling_fused.hip and their drivers in interpolate_api.cpp and fill_api.cpp) against the MODEL of tests/interp_model.py
 - the oracle walks every null run again from every window, so tests/test_gpu_fuzz.py::test_fuzz_interpolate_and_fills, which compares
 with the oracle itself, stops at 700 rows.  The model costs O(n log n); tests/test_interp_model_cpu.py proves it against the oracle
 and the reference's vectors, asserts what the cases cover and that they tell eight wrong models from the right one.  Here: row counts

@@ -1,5 +1,5 @@
 """Differential fuzzing of the paths that serve an INTERVAL COLUMN WITH NULLS (bow_amd/csrc/ts_nulls.hip, aggregate_api.cpp
-run_aggregate_null_ts, extras.cpp interp_null_ts) against the oracle: the seeded cases of tests/null_ts_cases.py - the interval column
+run_aggregate_null_ts, interp_null_ts.cpp) against the oracle: the seeded cases of tests/null_ts_cases.py - the interval column
 and every value column at an Arrow offset inside longer buffers of random bits, row counts on the edges of the keep words and the
 tiles, null runs past the near walk (2048 bits) and the blocks (4096) of the neighbour index and on its word edges, a null last row,
 arbitrary bits in the timestamps of null rows, Int64 / Float64 value columns with and without validity, every reducer with Factor
@@ -90,7 +90,7 @@ def test_fuzz_interpolate_null_interval_column(seed):
         kw = dict(offset=c.offset, inclusive=c.inclusive)
         _inclusive["drawn"] += c.inclusive
         forms = [("count + fill", lambda: both_interp_kernels(lambda: capi.rolling_interpolate(ccols, 0, c.interval, c.interps, **kw)))]
-        if c.device:     # a fill without a count: nothing of a count's compaction to reuse (extras.cpp NullTsState)
+        if c.device:     # a fill without a count: nothing of a count's compaction to reuse (interp_null_ts.cpp NullTsState)
             forms.append(("one pass", lambda: capi.rolling_interpolate_onepass(ccols, 0, c.interval, c.interps, out_residency=capi.DEVICE, **kw)))
         want = None
         for form, run in forms:

@@ -1,6 +1,6 @@
 """The HOST side of libbowgpu.so under AddressSanitizer + UndefinedBehaviorSanitizer (GPU ASan is not available on this pool, so
 the device code is covered by parity tests only; the host code is plain C++ and runs here).  The sanitized build
-(make -C bow_amd/csrc asan) holds api.cpp / extras.cpp / parquet.cpp compiled with g++ and stubs for everything that lives in the
+(make -C bow_amd/csrc asan) holds aggregate_api.cpp / interpolate_api.cpp / parquet.cpp compiled with g++ and stubs for everything that lives in the
 .hip files; a child process preloads the sanitizer runtime, loads it through BOWGPU_LIB and drives every entry point that works
 without a GPU: plans and ctor errors on host-resident columns, aggregation / interpolation validation (which runs before any device
 is touched), the shard plan on thousands of random layouts, carry merges, the Parquet footer and page-header parser on the

@@ -174,7 +174,7 @@ def test_the_inclusive_rewrite_gives_the_oracles_answer():
 
 
 def test_interpolate_on_the_kept_rows_plus_a_marker_column_gives_the_oracles_answer():
-    """Rolling.Interpolate over an interval column with nulls (exclusive iteration) as extras.cpp interp_null_ts makes it: the kept
+    """Rolling.Interpolate over an interval column with nulls (exclusive iteration) as interp_null_ts.cpp makes it: the kept
     rows compacted (timestamps forward-filled, value validity ANDed with the interval column's), one more Int64 column under
     interpolation.None that is valid exactly in the null-timestamp rows and holds their row number; in the output, wherever that
     column is valid the row is a copy of such a row: its timestamp becomes null, its value gets its own validity back."""
@@ -242,7 +242,7 @@ def _synth(kind, sk, pp, np_, prevrow):
 
 
 def test_inclusive_interpolate_on_the_kept_rows_gives_the_oracles_answer():
-    """Rolling.Interpolate over an interval column with nulls after an INCLUSIVE iteration, as extras.cpp interp_null_ts makes it: the
+    """Rolling.Interpolate over an interval column with nulls after an INCLUSIVE iteration, as interp_null_ts.cpp makes it: the
     kept rows - the inclusive keep rule, the rows on a window start with a null timestamp behind them included - compacted, the
     marker column valid in the null-timestamp rows AND in those rows; the ordinary inclusive call then copies such a row twice (the
     end of its window, the start of the next); the second copy stands where the reference has the next window's synthetic start row
