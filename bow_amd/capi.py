@@ -31,6 +31,8 @@ FILTER_MAX_PREDS = 8
 CARRY_MAX_AGGS = 16
 JOIN_INNER, JOIN_OUTER = 0, 1
 MERGE_TILE_ROWS = 2048  # bow_amd/csrc/common.h kMergeTileRows: output rows per workgroup of merge_runs_kernel (bowgpu_sort_by_col_sharded)
+WHOLE_MAX_AGGS = 64      # bow_amd/csrc/ctx_blocks.h kWholeMaxAggs: reducers per bowgpu_aggregate_whole call
+WHOLE_STEP_ROWS = 512    # interp_fill.hip whole_value_kernel: rows a wavefront takes per step (four 128-row chunks, two rows a lane each)
 ABI_VERSION = 14  # include/bowgpu.h BOWGPU_ABI_VERSION (asserted when the library is loaded)
 
 ERR_NAMES = {
@@ -721,8 +723,18 @@ def window_bounds(ts, interval, offset=0, inclusive=False):
     return s0, W, arrs[0][:W], arrs[1][:W], arrs[2][:W], inc[:W].astype(bool)
 
 
-def aggregate_whole(cols, ts_col, aggs):
-    outs = [OutColumn(1) for _ in aggs]
+def whole_layout(n):
+    """(nblocks, chunk) of a whole-frame call over n > 0 rows, as whole_api.cpp lays them out: workgroup b reduces rows [b * chunk,
+    (b + 1) * chunk), each of its four wavefronts a contiguous quarter of ceil(steps / 4) steps of WHOLE_STEP_ROWS rows; thread t of the
+    finish / merge launch folds records [t * per, (t + 1) * per) with per = ceil(nblocks / 256).  Workgroups past the last row exist
+    once the 2048 cap holds and chunk is rounded up."""
+    nblocks = min(2048, (n + 65535) // 65536)
+    chunk = ((n + nblocks - 1) // nblocks + WHOLE_STEP_ROWS - 1) // WHOLE_STEP_ROWS * WHOLE_STEP_ROWS
+    return nblocks, chunk
+
+
+def aggregate_whole(cols, ts_col, aggs, out_residency=HOST):
+    outs = [OutColumn(1, out_residency) for _ in aggs]
     oarr = (Out * max(len(aggs), 1))()
     for i, o in enumerate(outs):
         oarr[i] = o.c()

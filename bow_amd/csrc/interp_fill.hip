@@ -618,7 +618,8 @@ __global__ __launch_bounds__(256) void col_order_join_kernel(const TripEdge *in,
 // merging the lanes' states with an ORDER-PRESERVING shuffle tree (stats_merge is concatenation: First / Last, the NaN-seed
 // rule of Min / Max and the integrals' adjacency survive), then the step into the wavefront's running state.  Level 2: one
 // thread merges the workgroup partials in order.  Fixed shape => deterministic; Sum / Mean / Integral are not in strict
-// row order (1e-12 rel).
+// row order: THE STATED TOLERANCE of one window of n rows (include/bowgpu.h at bowgpu_aggregate_whole) - a bound on sum |T_i|,
+// not a relative error.
 struct WholeParams {
     const int64_t *ts;
     const uint64_t *values;
@@ -697,7 +698,7 @@ __global__ __launch_bounds__(256) void whole_partial_kernel(const WholeParams p)
 // is merged across lanes per step.  The kernel above spends ~600 of its ~850 instructions per 512-row step on the six-round shuffle tree
 // over the 14-field state (0.56 ms per 1e8 rows, 0.18 of peak); none of these reducers needs the adjacency that tree preserves - what
 // depends on ROW ORDER is positional and reduces by row index:
-//   Sum, Count       per lane over all its steps, added up at the end (whole-frame sums never were in row order: 1e-12 rel, see above)
+//   Sum, Count       per lane over all its steps, added up at the end (whole-frame sums never were in row order: the stated tolerance, see above)
 //   First / Last     the lane's lowest / highest valid row and its bits; the lowest / highest index wins
 //   Min / Max        minmax.go:16-28 over the concatenation = the first valid value if that is a NaN (a NaN seed sticks), else the
 //                    extremum of the non-NaN values, the EARLIEST of equal ones (+0 / -0): (value, row) pairs, ties to the lower row
@@ -707,7 +708,7 @@ __global__ __launch_bounds__(256) void whole_partial_kernel(const WholeParams p)
 // terms with its NEXT valid point.  Inside a 128-row chunk that point is the lane's own second row or the first point of the next lane
 // that has one (ballot, lowest set bit above the lane, four ds_bpermute - long_short_kernel's neighbour search); a chunk's first
 // point closes the pair with the last point so far (uniform: carried from chunk to chunk, step to step); the terms are summed per
-// lane, their order is free like the sums' (1e-12 rel).  The range's first and last point go into the Stats record: stats_merge
+// lane, their order is free like the sums' (the stated tolerance).  The range's first and last point go into the Stats record: stats_merge
 // stitches the ranges.
 // (launch bounds: four wavefronts per SIMD - the time-weighted form then fits 128 vector registers with three of them parked in scratch;
 // with nulls as well it would park seventeen and ran 0.46 ms on one box, 0.58 on the next: three wavefronts, 141 registers, none parked)

@@ -362,7 +362,17 @@ int bowgpu_window_bounds(const bowgpu_col *ts, int64_t interval, const bowgpu_op
                          uint8_t *is_inclusive, int32_t residency);
 
 /* aggregation.Aggregate (whole frame) — reference rolling/aggregation/whole.go:12-93.
- * outs[i].length is 1 (0 for an empty Bow). */
+ * outs[i].length is 1 (0 for an empty Bow).  At most 64 reducers per call (BOWGPU_ERR_UNSUPPORTED beyond); an Int64 interval
+ * column without nulls, Int64 / Float64 value columns.
+ * Bit-exact: type, length, validity and null_count of every output (SetOrDropStrict: WindowStart naming a Float64 column is nil,
+ * a nil slot holds zero); WindowStart, NumRows, Count; Min / Max (float64(v); a NaN seed sticks, the earliest of equal extremes);
+ * First / Last / Mode (the row's own 8 bytes: an Int64 beyond 2^53 is not carried through a double); a Factor chain on these.
+ * Sum, ArithmeticMean, IntegralStep / IntegralTrapezoid and WeightedAverageStep / WeightedAverageLinear are summed ORDER-FREE -
+ * per lane, wavefront, workgroup, then a fixed tree over the workgroups' records: equal inputs give equal bits, and they differ
+ * from the reference's left-to-right loop by at most THE STATED TOLERANCE (bowgpu_agg_info.long_windows above) of ONE window of
+ * n = all the frame's rows.  Where every term is an integer and SUM|T_i| < 2^53 (2^52 for the trapezoid terms, multiples of one
+ * half) every partial sum is exact and the result is the reference's, bit for bit.  tests/whole_model.py,
+ * tests/test_gpu_whole_fuzz.py assert all of this. */
 int bowgpu_aggregate_whole(const bowgpu_col *cols, int32_t ncols, int32_t ts_col,
                            const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs);
 

@@ -4,6 +4,7 @@ Aggregate — golden vectors of the reference's tests plus seeded comparisons wi
 import numpy as np
 import pytest
 
+import whole_model as wm
 from bow_amd import capi
 from interp_model import TRIP, next_valid, plan as model_plan, prev_valid, trip_figures
 from oracle import pyoracle as orc
@@ -631,6 +632,26 @@ def test_golden_whole(golden):
             same_list(o.to_list(), exp)
 
 
+def whole_within_the_stated_bound(label, aggs, got, ts, vals, valid, typ):
+    """Sum / ArithmeticMean / the time-weighted reducers of one whole-frame call against tests/whole_model.py: bit for bit where every
+    partial sum is exact, else |got - exact| within THE STATED TOLERANCE of one window of n rows (include/bowgpu.h, tests/tolerance.py)"""
+    n = len(ts)
+    want = wm.M.aggregate([wm.MCol(ts, np.ones(n, bool), wm.INT64), wm.MCol(vals, np.ones(n, bool) if valid is None else valid, typ)], 0, aggs)
+    for a, g, w in zip(aggs, got, want):
+        if a[0] not in wm.ORDER_SENSITIVE:
+            continue
+        assert g.null_count == (0 if w.valid else 1), (label, a)
+        if not w.valid:
+            continue
+        x = float(g.host_arrays()[0].view(np.float64)[0])
+        if not (np.isfinite(x) and np.isfinite(w.exact)):
+            assert (np.isnan(x) and np.isnan(w.exact)) or x == w.exact, (label, a, x, w.exact)
+        elif w.int_exact:
+            assert x == w.as_float(), (label, a, x, w.as_float())
+        else:
+            assert abs(x - w.exact) <= wm.bound(w, a[0], []), (label, a, x, w.exact, wm.bound(w, a[0], []))
+
+
 def test_whole_random_vs_oracle():
     rng = np.random.default_rng(23)
     n = 500_000
@@ -647,6 +668,7 @@ def test_whole_random_vs_oracle():
     for mask in (0, capi.ROUTE_FORCE_GENERAL):
         with capi.route(mask):
             got = capi.aggregate_whole([capi.Column(ts), capi.Column(vals, bm, capi.FLOAT64, 0, n, -1)], 0, aggs)
+        whole_within_the_stated_bound("random route=%d" % mask, aggs, got, ts, vals, valid, capi.FLOAT64)
         for k, g, w in zip(kinds, got, want):
             gl, wl = g.to_list(), w.to_list()
             assert len(gl) == len(wl) == 1 and (gl[0] is None) == (wl[0] is None), k
@@ -678,6 +700,7 @@ def test_whole_time_weighted_sparse_points():
                 for mask in (0, capi.ROUTE_FORCE_GENERAL):
                     with capi.route(mask):
                         got = capi.aggregate_whole([capi.Column(ts, None, capi.INT64, off, n, 0), capi.Column(vals, bm, typ, off, n, -1)], 0, aggs)
+                    whole_within_the_stated_bound((n, off, typ_name, mask), aggs, got, ts[off:off + n], vals[off:off + n], valid[off:off + n], typ)
                     for k, g, w in zip(kinds, got, want):
                         gl, wl = g.to_list(), w.to_list()
                         assert (gl[0] is None) == (wl[0] is None), (k, n, off, typ_name, mask, gl, wl)
@@ -722,6 +745,7 @@ def test_whole_value_reducers_by_row_index(vtype):
                 typ = capi.FLOAT64 if vtype == "f64" else capi.INT64
                 got = capi.aggregate_whole([capi.Column(ts, None, capi.INT64, off, n, 0), capi.Column(vals, bm, typ, off, n, -1 if bm is not None else 0)], 0, aggs)
                 want = orc.aggregate_whole([orc.Column(ts, None, orc.INT64, offset=off, length=n), orc.Column(vals, bm, typ, offset=off, length=n)], 0, aggs)
+                whole_within_the_stated_bound((n, off, plant), aggs, got, ts[off:off + n], vals[off:off + n], None if bm is None else valid[off:off + n], typ)
                 for k, g, w in zip(kinds, got, want):
                     label = (k, n, off, plant)
                     w_null = w.to_list()[0] is None

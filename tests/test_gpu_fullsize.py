@@ -476,3 +476,17 @@ def test_mode_at_scale():
         want, _ = orc.aggregate(oc, 0, interval, aggs, offset=3)
         for (k, _), g, w in zip(aggs, got, want):
             compare("Mode at scale I=%d %s" % (interval, k), g, w)
+
+
+def test_whole_frame_at_the_workgroup_cap():
+    """aggregation.Aggregate over 2048 * 65536 + 1 rows: the workgroup count is capped at 2048, so chunk = 66 048 rows (129 steps, quarters
+    of 33 / 33 / 33 / 30 steps), thread t of the finish launch folds 8 records, and workgroups 2033 .. 2047 have no rows and must write
+    the identity state.  Integer data built on the host once (tests/test_gpu_whole_fuzz.py's planted frame): every result - Sum, Mean,
+    Min, Max, First, Last, Count and the four time-weighted reducers, Float64 and Int64, dense, 30 % nulls around a workgroup without a
+    point, and points in workgroups 0, 296, 298 and the last only, both routes - equals int64 numpy arithmetic bit for bit.  3.3 s on an
+    MI355X, the columns' construction on the host included."""
+    from test_gpu_whole_fuzz import run_planted
+    n = 2048 * 65536 + 1
+    nblocks, chunk = capi.whole_layout(n)
+    assert (nblocks, chunk) == (2048, 66_048) and (n - 1) // chunk == 2032
+    run_planted(n)

@@ -74,20 +74,23 @@ def order_free_bounds(ocols, ts_col, interval, aggs, offset=0, inclusive=False, 
         cnt = np.maximum(mags[where[("Count", col)]].values[:W].astype(np.float64), 1.0)
         r = np.zeros(W) if ref is None else np.where(ref[i].valid_mask(), np.abs(ref[i].values[:W].astype(np.float64)), 0.0)
         r = np.where(np.isfinite(r), r, 0.0)
-        c = 2.0 if _MAG_KIND[k] == "Sum" else 4.0
-        b = c * (n + 2.0) * U * S
-        if k == "ArithmeticMean":
-            b = b / cnt
-        elif k in ("WeightedAverageStep", "WeightedAverageLinear"):
-            b = b / float(interval)
-        factors = list(a[2]) if len(a) > 2 and a[2] else []
-        scale = float(np.prod(np.abs(factors))) if factors else 1.0
-        if k in ("ArithmeticMean", "WeightedAverageStep", "WeightedAverageLinear") or factors:
-            b = b * scale + (2.0 + len(factors)) * U * r
-        else:
-            b = b * scale
-        out.append(b)
+        out.append(window_bound(k, n, S, cnt, float(interval), list(a[2]) if len(a) > 2 and a[2] else [], r))
     return out
+
+
+def window_bound(k, n, S, cnt, width, factors, r):
+    """the formulas above for reducer kind k of windows of n rows: S = sum_i |T_i|, cnt = valid rows (at least 1), width =
+    float64(LastValue - FirstValue), r = |ref| (0 where it is not finite).  Scalars or arrays, one entry per window."""
+    c = 2.0 if _MAG_KIND[k] == "Sum" else 4.0
+    b = c * (n + 2.0) * U * S
+    if k == "ArithmeticMean":
+        b = b / cnt
+    elif k in ("WeightedAverageStep", "WeightedAverageLinear"):
+        b = b / width
+    scale = float(np.prod(np.abs(factors))) if factors else 1.0
+    if k in ("ArithmeticMean", "WeightedAverageStep", "WeightedAverageLinear") or factors:
+        return b * scale + (2.0 + len(factors)) * U * r
+    return b * scale
 
 
 def assert_within(name, g, w, bound):
