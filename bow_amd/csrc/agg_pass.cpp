@@ -539,7 +539,7 @@ int job_run(Ctx *c, AggJob *job, int64_t *long_windows, double *kernel_ms, bool 
     const bool nlo = (route & BOWGPU_ROUTE_NO_LONG_ONLY) != 0 || strict;
     const bool cls = (route & BOWGPU_ROUTE_LONG_CLASSIC) != 0;      // test / A-B switches: only the bisection + per-window chunks form ...
     const bool sall = (route & BOWGPU_ROUTE_LONG_STREAM_ALL) != 0;  // ... / the streaming form for every reducer set
-    // Which form?  The streaming form - one read of the rows, long_windows.hip long_short_kernel / long_stream_kernel - for every
+    // Which form?  The streaming form - one read of the rows, long_stream.hip long_short_kernel / long_stream_kernel - for every
     // reducer set from 128 rows per window on average (1e8 rows: 1000-row windows 0.26 - 0.33 ms against 0.44 - 0.72 ms for the
     // bisection form; 128 .. 256-row windows 0.35 - 0.55 ms dense, 0.40 - 0.76 ms on irregular data with nulls, against 0.35 - 1.0 /
     // 0.7 - 1.8 ms for the tile kernels, whose lane-per-window walk idles most lanes at that length); the bisection form keeps the

@@ -443,7 +443,7 @@ constexpr int64_t kCompactMinAvgRows = 12;                  // ... for calls who
 int launch_rolling_aggregate(Ctx *c, const AggParams &p);   // general kernel (rolling_agg.hip)
 int launch_rolling_fast(Ctx *c, const AggParams &p);        // lean kernel for exclusive windows without time-weighted reducers (rolling_fast.hip)
 constexpr int kLongChunkRows = 4096;
-constexpr int kLongStreamRows = 512;  // chunk of the streaming form of the long-window reduction (long_windows.hip)
+constexpr int kLongStreamRows = 512;  // chunk of the streaming form of the long-window reduction (long_stream.hip)
 constexpr int64_t kLongOnlyAvgRows = 128;   // calls with BOTH kinds of integral whose windows average at least this many rows skip the tile kernels: streaming form (agg_pass.cpp job_run)
 constexpr int64_t kLongStreamAnyAvgRows = 129;   // ... the same for every other reducer set (256 until long_short_kernel took a boundary per 128-row trip; 128 until the tile kernels' walks became branch-free: windows of exactly 128 rows fit a tile's look-ahead and the tile kernels win there)
 constexpr int64_t kLongBisectAvgRows = 512; // ... bisection form where the streaming form does not apply (BOWGPU_ROUTE_LONG_CLASSIC; W >= 2^32)
@@ -453,7 +453,7 @@ constexpr int kLongCountWord = 16;  // status[kLongCountWord + s] = entries in s
 constexpr int kStatusWords = kLongCountWord + kLongLists;
 // the words below kLongCountWord that the Aggregate kernels raise and agg_pass.cpp agg_status_error reads (Interpolate keeps a status block
 // of its own whose words 5 - 7 mean other things: interpolate.hip, interpolate_api.cpp).  rolling_agg.hip, rolling_fast.hip and shard.hip spell
-// them by name; the wave-tile kernels, long_windows.hip and agg_device.h still write the numbers (an edit to those files asks for the
+// them by name; the wave-tile kernels, long_windows.hip, long_stream.hip, long_device.h and agg_device.h still write the numbers (an edit to those files asks for the
 // round's counter files again: tests/test_profiles_fresh.py)
 constexpr int kAggStUnsorted = 0;        // the interval column is not ascending
 constexpr int kAggStListOverflow = 2;    // the long-window list overflowed (agg_device.h push_long_window)
@@ -476,7 +476,10 @@ int launch_long_queue(Ctx *c, const AggParams &p, int64_t capacity, void *big_en
 constexpr int kQueueBigWord = 8;          // status word: windows long_queue_kernel left to the chunked machinery
 constexpr int64_t kQueueWalkMaxRows = 1024;   // ... those longer than this
 size_t long_stream_workspace(int64_t n, int64_t W, int ncols);
-int launch_long_stream(Ctx *c, const AggParams &p, void *workspace);   // every window of the call, one read of the rows
+int launch_long_stream(Ctx *c, const AggParams &p, void *workspace);   // every window of the call, one read of the rows (long_stream.hip)
+// its last step while windows span a few chunks: stream_final_kernel, then long_final_block_kernel for what it leaves (both compiled in long_windows.hip)
+int launch_stream_final(Ctx *c, const AggParams &p, int64_t nchunks, const void *meta, const void *parts, const void *recs, const void *wparts,
+                        void *entries, int64_t *off0, int64_t *off1, unsigned long long *n_leftover, int lite);
 int launch_fix_tail_bits(Ctx *c, uint8_t *bitmap, int64_t nbits);
 // every output bitmap of one call in one launch (rolling_agg.hip)
 struct BitmapBatch {

@@ -17,6 +17,7 @@
 #include "common.h"
 #include "bitmap_device.h"
 #include "bitmap_word.h"
+#include "wave_ops.h"
 
 namespace bowgpu {
 
@@ -27,8 +28,6 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kChunks = 4;                  // chunks of 128 rows a wave takes per trip
 constexpr int kTripRows = 128 * kChunks;
 constexpr int kMaxBlocks = 2048;            // per column: 8 workgroups a CU
-
-typedef unsigned long long u64x2c_t __attribute__((ext_vector_type(2)));
 
 // Go's int64(v) as gc compiles it for amd64 (CVTTSD2SQ): truncation toward zero inside [-2^63, 2^63), the "integer indefinite"
 // 0x8000000000000000 for NaN, +-Inf and everything outside.  The range test is written out: (long long)double outside the range is
@@ -61,7 +60,7 @@ __device__ __forceinline__ unsigned convert_trip(const ConvertCol &q, const int6
         for (int k = 0; k < kChunks; k++) {
             const int r = 128 * k + 2 * lane;
             if (vin && (kFull || r + 1 < left)) {
-                const u64x2c_t x = __builtin_nontemporal_load(reinterpret_cast<const u64x2c_t *>(src + r));
+                const u64x2_t x = __builtin_nontemporal_load(reinterpret_cast<const u64x2_t *>(src + r));
                 a[k] = x.x; b[k] = x.y;
             } else {
                 a[k] = (kFull || r < left) ? __builtin_nontemporal_load(src + r) : 0;
@@ -106,9 +105,9 @@ __device__ __forceinline__ unsigned convert_trip(const ConvertCol &q, const int6
         } else {
             uint64_t *dst = reinterpret_cast<uint64_t *>(q.out_values) + base;
             if (vout && (kFull || r + 1 < left)) {
-                u64x2c_t x;
+                u64x2_t x;
                 x.x = oa; x.y = ob;
-                __builtin_nontemporal_store(x, reinterpret_cast<u64x2c_t *>(dst + r));
+                __builtin_nontemporal_store(x, reinterpret_cast<u64x2_t *>(dst + r));
             } else {
                 if (kFull || r < left) __builtin_nontemporal_store(oa, dst + r);
                 if (kFull || r + 1 < left) __builtin_nontemporal_store(ob, dst + r + 1);

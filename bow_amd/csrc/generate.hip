@@ -9,6 +9,7 @@
 // [1,19], value = U{0..9}+0.5, 30 % nulls).
 
 #include "common.h"
+#include "wave_ops.h"
 
 namespace bowgpu {
 
@@ -152,7 +153,6 @@ template <bool kNt>
 __global__ __launch_bounds__(64) void stream_rw_kernel(const ulonglong2 *__restrict__ a, const ulonglong2 *__restrict__ b, uint64_t *__restrict__ o0,
                                                        uint64_t *__restrict__ o1, const int64_t ntiles, const int64_t tiles_per_xcd,
                                                        const int64_t rows_per_slot, const int64_t nslots) {
-    typedef unsigned long long v2 __attribute__((ext_vector_type(2)));
     const int64_t w = blockIdx.x;
     const int64_t tile = (w & 7) * tiles_per_xcd + (w >> 3);
     if (tile >= ntiles) return;
@@ -162,8 +162,8 @@ __global__ __launch_bounds__(64) void stream_rw_kernel(const ulonglong2 *__restr
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         if (kNt) {
-            const v2 u = __builtin_nontemporal_load(reinterpret_cast<const v2 *>(pa + 64 * j));
-            const v2 v = __builtin_nontemporal_load(reinterpret_cast<const v2 *>(pb + 64 * j));
+            const u64x2_t u = __builtin_nontemporal_load(reinterpret_cast<const u64x2_t *>(pa + 64 * j));
+            const u64x2_t v = __builtin_nontemporal_load(reinterpret_cast<const u64x2_t *>(pb + 64 * j));
             x ^= u.x ^ u.y; y ^= v.x ^ v.y;
         } else {
             const ulonglong2 u = pa[64 * j], v = pb[64 * j];

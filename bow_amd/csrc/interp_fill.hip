@@ -5,6 +5,7 @@
 //   * the whole-frame aggregation.Aggregate (reference rolling/aggregation/whole.go:12-93).
 // All are streaming, HBM-bound passes over Arrow value / validity buffers; none is a contraction.
 #include "bitmap_device.h"
+#include "wave_ops.h"
 
 namespace bowgpu {
 
@@ -568,13 +569,12 @@ __global__ __launch_bounds__(256) void col_order_dense_kernel(const uint64_t *va
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const int r = 128 * k + 2 * lane;
-            const uint32_t llo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)b[k], 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-            const uint32_t lhi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(b[k] >> 32), 0x138, 0xf, 0xf, false);
+            const uint32_t llo = left_u32((uint32_t)b[k], 0);
+            const uint32_t lhi = left_u32((uint32_t)(b[k] >> 32), 0);
             const uint64_t left = lane == 0 ? carry : ((uint64_t)lhi << 32) | llo;
             if ((lane > 0 || has_carry) && r < left_trip) f |= order_cmp<kInt>(left, a[k]);
             if (r + 1 < left_trip) f |= order_cmp<kInt>(a[k], b[k]);
-            carry = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b[k], 63) |
-                    (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b[k] >> 32), 63) << 32;
+            carry = readlane_u64(b[k], 63);
             has_carry = true;
         }
     }
@@ -804,6 +804,7 @@ __global__ __launch_bounds__(256, (kNulls && kTs) ? 3 : 4) void whole_value_kern
                 if ((okx || oky) && above) { trap += (l_v + a_v) / 2 * (a_t - l_t); step += l_v * (a_t - l_t); }
                 // (uniform) the chunk's first point closes the pair with the last point so far; its last point is the new one
                 const int lf = __ffsll((long long)hasm) - 1, ll = 63 - __clzll((long long)hasm);
+                // (wave_ops.h readlane_f64 written out, four times: through the helper the compiler commutes the operands of this kernel's additions)
                 const double q_t = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(o_t), lf), __builtin_amdgcn_readlane(__double2loint(o_t), lf));
                 const double q_v = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(o_v), lf), __builtin_amdgcn_readlane(__double2loint(o_v), lf));
                 if (c_has) {

@@ -19,6 +19,7 @@
 
 #include "bitmap_device.h"
 #include "interp_device.h"
+#include "wave_ops.h"
 
 namespace bowgpu {
 
@@ -399,24 +400,6 @@ __global__ __launch_bounds__(kIThreads) void interp_tile_kernel(const InterpPara
 // (rounds 1 - 2 had two more kernels here, interp_wave_kernel and interp_wave2_kernel: interp_wave3_kernel below replaced both, 1.6 - 2.9x
 // faster; they are gone from the library since round 4.  interp_tile_kernel above stays as the kernel for the shapes wave3 does not
 // take - 64-bit window ids, dropped rows, the -1 sentinel window, a trip whose lists overflow - and as the second opinion of the tests.)
-__device__ __forceinline__ void wave_lds_order() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// inclusive wave scan of one unsigned per lane: Hillis-Steele inside the 16-lane rows (row_shr 1, 2, 4, 8), then the row totals
-// across (row_bcast 15 into rows 1 and 3, row_bcast 31 into rows 2 and 3): six DPP moves + adds, no LDS
-__device__ __forceinline__ uint32_t wave_scan_u32(uint32_t x) {
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, true);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, true);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, true);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, true);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);
-    return x;
-}
-
 // In-kernel stamps (diagnostic build -DBOWGPU_STAMPS only; cdna_hip_programming.md section 7): cycles per phase, summed over the
 // wavefronts into status[32 + 2 * phase] (64-bit), read back with bowgpu_debug_status.  Never in the product build.
 #ifdef BOWGPU_STAMPS
@@ -488,8 +471,7 @@ __device__ __forceinline__ void wave3_trip(const InterpParams &p, const int64_t 
         const int r = 128 * k + 2 * lane;
         const uint64_t *src = col + base;
         if (full && (kFull || (reinterpret_cast<uintptr_t>(col) & 15) == 0)) {   // (kFull: the host found every column 16-byte aligned)
-            typedef unsigned long long u64x2i_t __attribute__((ext_vector_type(2)));
-            const u64x2i_t v = __builtin_nontemporal_load(reinterpret_cast<const u64x2i_t *>(src + r));   // (streamed once)
+            const u64x2_t v = __builtin_nontemporal_load(reinterpret_cast<const u64x2_t *>(src + r));   // (streamed once)
             *a = v.x; *bb = v.y;
         } else { *a = r < left_trip ? src[r] : 0; *bb = r + 1 < left_trip ? src[r + 1] : 0; }
     };
@@ -544,17 +526,18 @@ __device__ __forceinline__ void wave3_trip(const InterpParams &p, const int64_t 
             if (kIncl) {
                 // (exclusive windows: every fill follows a count pass - its own or the _count call's, whose reuse is guarded by the
                 // row-count check below - and interp_count_kernel checks the order; 14 vector instructions per chunk not spent twice)
-                const uint32_t plo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)tb[k], 0x138, 0xf, 0xf, false);
-                const uint32_t phi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(tb[k] >> 32), 0x138, 0xf, 0xf, false);
+                const uint32_t plo = left_u32((uint32_t)tb[k], 0);
+                const uint32_t phi = left_u32((uint32_t)(tb[k] >> 32), 0);
                 const int64_t tl = lane == 0 ? (int64_t)tb_prev : (int64_t)(((uint64_t)phi << 32) | plo);
                 unsorted |= (in0 && !first && tl > (int64_t)ta[k]) || (in1 && (int64_t)ta[k] > (int64_t)tb[k]);
-                tb_prev = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(tb[k] >> 32), 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)tb[k], 63);
+                tb_prev = readlane_u64(tb[k], 63);
             }
             const uint32_t wa = mdiv32(ra, m32), wb = mdiv32(rb, m32);
             // the left neighbour's window: the lane below computed it as its wb (a DPP move, not a third division); lane 0 takes the
             // previous chunk's last - or, the trip's first row: its window is local id 0 by construction, the row before it lies gap0
             // windows further back (ids are unsigned and wrap, the differences below come out right)
-            uint32_t wl = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)wb, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+            // (the two v_readlane of this chunk loop stay written out: through wave_ops.h readlane_u32 interp_wave3_kernel<false> comes out in another order)
+            uint32_t wl = left_u32(wb, 0);
             if (lane == 0) wl = k == 0 ? 0u - (uint32_t)gap0 : (uint32_t)__builtin_amdgcn_readlane((int)wb_prev, 63);
             wb_prev = wb;
             const bool head0 = in0 && (first || wa != wl), head1 = in1 && wb != wa;
@@ -871,7 +854,7 @@ __device__ __forceinline__ void wave3_trip(const InterpParams &p, const int64_t 
                     const uint32_t e0 = 128u * (uint32_t)(k2 + u) + 2u * (uint32_t)lane;
                     const bool lo_ok = e0 - e_lo < tot, hi_ok = e0 + 1u - e_lo < tot;   // (unsigned: also false below e_lo)
                     const ulonglong2 x = fx[u];
-                    if (lo_ok && hi_ok) { typedef unsigned long long u64x2o_t __attribute__((ext_vector_type(2))); u64x2o_t v; v.x = x.x; v.y = x.y; __builtin_nontemporal_store(v, reinterpret_cast<u64x2o_t *>(outA + e0)); }   // (never read back)
+                    if (lo_ok && hi_ok) { u64x2_t v; v.x = x.x; v.y = x.y; __builtin_nontemporal_store(v, reinterpret_cast<u64x2_t *>(outA + e0)); }   // (never read back)
                     else if (lo_ok) outA[e0] = x.x;
                     else if (hi_ok) outA[e0 + 1] = x.y;
                 }

@@ -77,21 +77,24 @@ def _pretty(symbol):
     return "%s<%s>" % (name, ", ".join(args))
 
 
-def kernel_identities(path, kernel, arch="gfx950"):
-    """{instantiation as rocprofv3 prints it: {sha, code_bytes, symbol}} for every instantiation of `kernel` in the object"""
+def _kernel_blobs(path, arch, want):
+    """({symbol: machine code}, {symbol: kernel descriptor}) of the object's kernels whose symbol `want` accepts"""
     with open(path, "rb") as fh:
         co = _device_code_object(fh.read(), arch)
     secs = _sections(co)
-    symtab = [s for s in secs if s["name"] == ".symtab"][0]
-    strs = secs[symtab["link"]]
+    symtabs = [s for s in secs if s["name"] == ".symtab"]
     code, kd = {}, {}
+    if not symtabs:   # (an object without device code)
+        return code, kd
+    symtab = symtabs[0]
+    strs = secs[symtab["link"]]
     for i in range(symtab["size"] // 24):
         name, info, other, shndx, value, size = struct.unpack_from("<IBBHQQ", co, symtab["off"] + 24 * i)
         if shndx in (0, 0xFFF1) or size == 0:
             continue
         a = strs["off"] + name
         nm = co[a:co.index(b"\0", a)].decode()
-        if kernel not in nm:
+        if not want(nm):
             continue
         sec = secs[shndx]
         blob = co[sec["off"] + value - sec["addr"]: sec["off"] + value - sec["addr"] + size]
@@ -99,20 +102,37 @@ def kernel_identities(path, kernel, arch="gfx950"):
             kd[nm[:-3]] = blob
         else:
             code[nm] = blob
+    return code, kd
+
+
+def _identity(text, descriptor):
+    d = bytearray(descriptor)
+    d[16:24] = bytes(8)   # kernel_code_entry_byte_offset: where the code lies relative to the descriptor - moves when ANOTHER kernel of the object grows
+    h = hashlib.sha256()
+    h.update(text)
+    h.update(bytes(d))
+    return h.hexdigest()[:16]
+
+
+def kernel_identities(path, kernel, arch="gfx950"):
+    """{instantiation as rocprofv3 prints it: {sha, code_bytes, symbol}} for every instantiation of `kernel` in the object"""
+    code, kd = _kernel_blobs(path, arch, lambda nm: kernel in nm)
     out = {}
     for sym, text in code.items():
         pretty = _pretty(sym)
         if pretty is None or sym not in kd or not pretty.startswith(kernel):
             continue
-        d = bytearray(kd[sym])
-        d[16:24] = bytes(8)   # kernel_code_entry_byte_offset: where the code lies relative to the descriptor - moves when ANOTHER kernel of the object grows
-        h = hashlib.sha256()
-        h.update(text)
-        h.update(bytes(d))
-        out[pretty] = {"sha": h.hexdigest()[:16], "code_bytes": len(text), "symbol": sym}
+        out[pretty] = {"sha": _identity(text, kd[sym]), "code_bytes": len(text), "symbol": sym}
     if not out:
         raise SystemExit("no instantiation of %s in %s" % (kernel, path))
     return out
+
+
+def all_kernel_identities(path, arch="gfx950"):
+    """{mangled symbol: {sha, code_bytes}} for EVERY kernel of the object (a function symbol with a descriptor `<symbol>.kd`), the ones
+    whose names _pretty cannot spell included (type template arguments, anonymous namespaces); {} for an object without device code"""
+    code, kd = _kernel_blobs(path, arch, lambda nm: True)
+    return {sym: {"sha": _identity(text, kd[sym]), "code_bytes": len(text)} for sym, text in code.items() if sym in kd}
 
 
 if __name__ == "__main__":

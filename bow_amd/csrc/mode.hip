@@ -27,6 +27,7 @@
 #include "agg_device.h"
 #include "bitmap_device.h"
 #include "window_rows.h"
+#include "wave_ops.h"
 
 namespace bowgpu {
 
@@ -169,13 +170,8 @@ __global__ __launch_bounds__(256) void mode_wave_kernel(ModeParams p, const int6
     const bool is_int = p.is_int != 0;
     constexpr uint64_t kEmpty = ~0ull;
     constexpr uint32_t kFlag = 0x80000000u;
-    auto wave_sync = []() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
     for (int i = lane; i < kWaveSlots; i += 64) { keys[i] = kEmpty; cnt[i] = 0; }
-    wave_sync();
+    wave_lds_order();
     // the lane's rows: lane, lane + 64, ... (at most four)
     uint64_t key[4];
     bool use[4];
@@ -216,7 +212,7 @@ __global__ __launch_bounds__(256) void mode_wave_kernel(ModeParams p, const int6
 #pragma unroll
     for (int j = 0; j < 4; j++)
         if (use[j]) { slot[j] = slot_of(key[j], true); atomicAdd(&cnt[slot[j]], 1u); }
-    wave_sync();
+    wave_lds_order();
     auto wave_max = [&](uint32_t x) { for (int o = 32; o > 0; o >>= 1) { const uint32_t y = __shfl_xor((int)x, o); x = y > x ? y : x; } return x; };
     auto wave_min = [&](uint32_t x) { for (int o = 32; o > 0; o >>= 1) { const uint32_t y = __shfl_xor((int)x, o); x = y < x ? y : x; } return x; };
     auto wave_sum = [&](uint32_t x) { for (int o = 32; o > 0; o >>= 1) x += (uint32_t)__shfl_xor((int)x, o); return x; };
@@ -233,9 +229,9 @@ __global__ __launch_bounds__(256) void mode_wave_kernel(ModeParams p, const int6
         }
         return;
     }
-    wave_sync();
+    wave_lds_order();
     for (int i = lane; i < kWaveSlots; i += 64) cnt[i] = cnt[i] == M ? kFlag : 0u;
-    wave_sync();
+    wave_lds_order();
     uint32_t spec_last = 0;
 #pragma unroll
     for (int j = 0; j < 4; j++) {
@@ -243,7 +239,7 @@ __global__ __launch_bounds__(256) void mode_wave_kernel(ModeParams p, const int6
         if (use[j]) { if (cnt[slot[j]] & kFlag) atomicMax(&cnt[slot[j]], kFlag | r); }
         else if (spec_total == M && (int)r < n && is_int && row_valid(p, a + r) && p.values[a + r] == kEmpty) spec_last = r;  // (rows ascend with j)
     }
-    wave_sync();
+    wave_lds_order();
     uint32_t best = 0xFFFFFFFFu;
     for (int i = lane; i < kWaveSlots; i += 64)
         if (cnt[i] & kFlag) { const uint32_t last = cnt[i] & ~kFlag; best = last < best ? last : best; }

@@ -27,6 +27,7 @@
 #include "agg_device.h"
 #include "bitmap_device.h"
 #include "window_rows.h"
+#include "wave_ops.h"
 
 namespace bowgpu {
 
@@ -59,19 +60,6 @@ __device__ __forceinline__ void acc_chunk(const BoolParams &p, int64_t row, int 
     if (s.first < 0) { s.first = rel + lo; s.fbit = (T >> lo) & 1u; }
     s.last = rel + hi;
     s.lbit = (T >> hi) & 1u;
-}
-
-__device__ __forceinline__ int64_t wave_sum64(int64_t x) {
-    for (int o = 32; o > 0; o >>= 1) x += (int64_t)__shfl_xor((long long)x, o);
-    return x;
-}
-__device__ __forceinline__ int64_t wave_min64(int64_t x) {
-    for (int o = 32; o > 0; o >>= 1) { const int64_t y = (int64_t)__shfl_xor((long long)x, o); x = y < x ? y : x; }
-    return x;
-}
-__device__ __forceinline__ int64_t wave_max64(int64_t x) {
-    for (int o = 32; o > 0; o >>= 1) { const int64_t y = (int64_t)__shfl_xor((long long)x, o); x = y > x ? y : x; }
-    return x;
 }
 
 // the two halves of a wavefront's 64-window word: words[2 g], words[2 g + 1]; the second only when it holds a window

@@ -26,6 +26,7 @@
 #include <stdlib.h>
 
 #include "agg_device.h"
+#include "wave_ops.h"
 
 namespace bowgpu {
 
@@ -48,35 +49,6 @@ struct WaveShared {
     uint32_t vbits[kRowsW / 32 + 2];
     uint32_t obits[kMaxNullableW][kSpanWordsW + 1];
 };
-
-__device__ __forceinline__ uint32_t magic_div32(uint32_t n, uint32_t m, uint32_t sh1, uint32_t sh2) {
-    const uint32_t t = __umulhi(m, n);
-    return (t + ((n - t) >> sh1)) >> sh2;
-}
-
-// value of lane-1 (wave shift right by one lane); lane 0 receives `lane0`
-__device__ __forceinline__ uint32_t from_left32(uint32_t x, uint32_t lane0) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)lane0, (int)x, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-}
-__device__ __forceinline__ uint64_t from_left64(uint64_t x, uint64_t lane0) {
-    const uint32_t lo = from_left32((uint32_t)x, (uint32_t)lane0);
-    const uint32_t hi = from_left32((uint32_t)(x >> 32), (uint32_t)(lane0 >> 32));
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t readlane64(uint64_t x, int l) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), l);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-// One wave only: LDS operations of a wave execute in order, so a write phase followed by reads from
-// other lanes needs neither s_barrier nor a wait - only that the compiler keeps the program order.
-// (__syncthreads() would also drain vmcnt(0), i.e. the next tile's prefetch.)
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // ---- the walk of one window, specialised at compile time
 template <bool kNulls, bool kInt, bool kMinMax, bool kFirstLast>
@@ -227,7 +199,7 @@ __global__ __launch_bounds__(kWave, kPersist ? 4 : 5) void rolling_wave_kernel(c
     const int64_t ts_last = p.ts[base + nloc - 1];
 
     // scalar: the tile's first window (one exact 64-bit division on the SALU)
-    const int64_t ts_first = (int64_t)readlane64(ta[0], 0);
+    const int64_t ts_first = (int64_t)readlane_u64(ta[0], 0);
     const uint64_t w0 = magic_div((uint64_t)ts_first - (uint64_t)p.s0, p.magic);
     const int64_t ws0 = p.s0 + (int64_t)(w0 * (uint64_t)p.interval);
     const bool fast32 = p.fits32 && ts_last >= ts_first && (uint64_t)(ts_last - ws0) < 0xFFFFFFF0ull;
@@ -241,35 +213,35 @@ __global__ __launch_bounds__(kWave, kPersist ? 4 : 5) void rolling_wave_kernel(c
     uint32_t left_lw = 0xFFFFFFFEu;  // an id no row of the tile has: the first row of the frame, or a left row in an earlier window
     uint64_t left_w = ~0ull;
     if (left0 != INT64_MIN) {
-        if (fast32) { if (left0 >= ws0) left_lw = magic_div32((uint32_t)left0 - base_lo, p.m32, p.sh1_32, p.sh2_32); }
+        if (fast32) { if (left0 >= ws0) left_lw = mdiv32((uint32_t)left0 - base_lo, p.m32, p.sh1_32, p.sh2_32); }
         else left_w = magic_div((uint64_t)left0 - (uint64_t)p.s0, p.magic);
     }
     // no local window id saturates its 16-bit slot => wid = w0 + id without a per-lane fallback test
-    const bool no_sat = fast32 && magic_div32((uint32_t)ts_last - base_lo, p.m32, p.sh1_32, p.sh2_32) < kSat16;
+    const bool no_sat = fast32 && mdiv32((uint32_t)ts_last - base_lo, p.m32, p.sh1_32, p.sh2_32) < kSat16;
 #pragma unroll
     for (int j = 0; j < kChunksW; j++) {
         const int l = j * 128 + 2 * lane;
         const bool pa = l < nloc, pb = l + 1 < nloc;
         const int64_t tsa = (int64_t)ta[j], tsb = (int64_t)tb[j];
-        const int64_t prev_ts = (int64_t)from_left64((uint64_t)tb[j], (uint64_t)left_ts);
+        const int64_t prev_ts = (int64_t)left_u64((uint64_t)tb[j], (uint64_t)left_ts);
         if (pa && prev_ts > tsa) unsorted = true;
         if (pb && tsa > tsb) unsorted = true;
         bool ha, hb;
         uint32_t la, lb;
         if (fast32) {
-            la = magic_div32((uint32_t)tsa - base_lo, p.m32, p.sh1_32, p.sh2_32);
-            lb = magic_div32((uint32_t)tsb - base_lo, p.m32, p.sh1_32, p.sh2_32);
-            const uint32_t lprev = from_left32(lb, left_lw);
+            la = mdiv32((uint32_t)tsa - base_lo, p.m32, p.sh1_32, p.sh2_32);
+            lb = mdiv32((uint32_t)tsb - base_lo, p.m32, p.sh1_32, p.sh2_32);
+            const uint32_t lprev = left_u32(lb, left_lw);
             ha = pa && (la != lprev);
             hb = pb && (lb != la);
-            left_lw = (uint32_t)__builtin_amdgcn_readlane((int)lb, 63);
+            left_lw = readlane_u32(lb, 63);
         } else {
             const uint64_t wa = magic_div((uint64_t)tsa - (uint64_t)p.s0, p.magic);
             const uint64_t wb = magic_div((uint64_t)tsb - (uint64_t)p.s0, p.magic);
-            const uint64_t wprev = from_left64(wb, left_w);
+            const uint64_t wprev = left_u64(wb, left_w);
             ha = pa && (wa != wprev);
             hb = pb && (wb != wa);
-            left_w = readlane64(wb, 63);
+            left_w = readlane_u64(wb, 63);
             const uint64_t da = wa - w0, db = wb - w0;
             la = da >= kSat16 ? kSat16 : (uint32_t)da;
             lb = db >= kSat16 ? kSat16 : (uint32_t)db;
@@ -282,7 +254,7 @@ __global__ __launch_bounds__(kWave, kPersist ? 4 : 5) void rolling_wave_kernel(c
         if (hb) { sh.seg[pos] = (uint32_t)(l + 1) | ((lb >= kSat16 ? kSat16 : lb) << 16); }
         nseg_total += __popcll(ma) + __popcll(mb);
         if (j == kChunksW - 2) nseg_owned = nseg_total;  // heads inside the 512 owned rows
-        left_ts = (int64_t)readlane64(tb[j], 63);         // last row of this chunk = left neighbour of the next
+        left_ts = (int64_t)readlane_u64(tb[j], 63);         // last row of this chunk = left neighbour of the next
     }
     if (unsorted) atomicOr(&p.status[kAggStUnsorted], 1u);
     if (prefetch_next) load_ts(next_tile, true);  // this tile's ts registers are dead
@@ -312,7 +284,7 @@ __global__ __launch_bounds__(kWave, kPersist ? 4 : 5) void rolling_wave_kernel(c
         const int col_type = cd ? cd->type : BOWGPU_INT64;
         const int variant = (has_nulls ? 1 : 0) | (col_type == BOWGPU_INT64 ? 2 : 0) | (need_mm ? 4 : 0) | (need_fl ? 8 : 0);
 
-        wave_lds_fence();  // previous pass finished with sh.val / sh.vbits / sh.obits
+        wave_lds_order();  // previous pass finished with sh.val / sh.vbits / sh.obits
         if (cd && need_vals) {
             if (staged_slot != slot) {
                 const uint64_t *vp = reinterpret_cast<const uint64_t *>(cd->values);
@@ -337,7 +309,7 @@ __global__ __launch_bounds__(kWave, kPersist ? 4 : 5) void rolling_wave_kernel(c
             (&sh.obits[0][0])[lane] = 0u;  // 4 x 19 words: two stores per lane at most
             if (lane < kMaxNullableW * (kSpanWordsW + 1) - kWave) (&sh.obits[0][0])[kWave + lane] = 0u;
         }
-        wave_lds_fence();
+        wave_lds_order();
 
         const uint64_t wid_first = nseg_owned > 0 ? wid_at(0) : 0;
         const int64_t slot_first = (int64_t)(wid_first - (uint64_t)p.wid_base);
@@ -403,7 +375,7 @@ __global__ __launch_bounds__(kWave, kPersist ? 4 : 5) void rolling_wave_kernel(c
                 }
             }
         }
-        wave_lds_fence();
+        wave_lds_order();
 
         // ---- big gaps (sparse data): the whole wave writes the empty windows, coalesced
         if (__ballot(any_big_gap)) {
@@ -462,7 +434,7 @@ __global__ __launch_bounds__(kWave, kPersist ? 4 : 5) void rolling_wave_kernel(c
         first_pass = false;
     }
     if (prefetch_next && last_val_slot < 0) load_v0(next_tile, true);
-    wave_lds_fence();
+    wave_lds_order();
     if (!kPersist) break;  // one tile per wave: no loop for the compiler to carry registers around
   }  // tiles of this wave
 }

@@ -24,6 +24,7 @@
 
 #include "bitmap_device.h"
 #include "interp_device.h"
+#include "wave_ops.h"
 
 namespace bowgpu {
 
@@ -70,7 +71,7 @@ __device__ __forceinline__ uint32_t mulhi32(uint32_t m, uint32_t n) {
     asm("v_mul_hi_u32 %0, %1, %2" : "=v"(t) : "s"(m), "v"(n));
     return t;
 }
-__device__ __forceinline__ uint32_t mdiv32(uint32_t n, uint32_t m, uint32_t sh1, uint32_t sh2) {
+__device__ __forceinline__ uint32_t mdiv32_asm(uint32_t n, uint32_t m, uint32_t sh1, uint32_t sh2) {   // (wave_ops.h mdiv32 with that multiplication)
     const uint32_t t = mulhi32(m, n);
     return (t + ((n - t) >> sh1)) >> sh2;
 }
@@ -83,19 +84,6 @@ __device__ __forceinline__ uint32_t mdiv32(uint32_t n, uint32_t m, uint32_t sh1,
 // q (d + e) < 2^32 / interval * 2^-39: the truncating conversion gives floor(q).  Three full-rate instructions where the magic-number
 // form takes a quarter-rate multiplication and four more (A/B: -DBOWGPU_FUSED_FDIV=0; every n x interval pair of tests/test_gpu_fused.py's sweep)
 __device__ __forceinline__ uint32_t fdiv32(uint32_t n, double inv) { return (uint32_t)((double)n * inv); }
-__device__ __forceinline__ uint32_t left32(uint32_t x, uint32_t lane0) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)lane0, (int)x, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-}
-typedef unsigned long long u64x2_f __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ ulonglong2 load16_nt(const ulonglong2 *q) {
-    const u64x2_f v = __builtin_nontemporal_load(reinterpret_cast<const u64x2_f *>(q));
-    return make_ulonglong2(v.x, v.y);
-}
-__device__ __forceinline__ void lds_order() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // rows fv .. lv of the staged column behind an optional synthetic first row of value xs (seeded), in row order: sum.go:16-22,
 // arithmeticmean.go:17-24, minmax.go:16-28 over [x_s, x_fv, ..., x_lv].  The same loops and the same settling of v_min_f64 / v_max_f64
@@ -215,7 +203,7 @@ __global__ __launch_bounds__(kWave, kMulti ? 4 : 6) void rolling_fused_kernel(co
     const uint32_t s0_lo = (uint32_t)ws0;
     const uint32_t ik = (uint32_t)p.interval;
     const double inv_ik = fp.inv_interval;
-    auto wdiv = [&](uint32_t x) -> uint32_t { return BOWGPU_FUSED_FDIV ? fdiv32(x, inv_ik) : mdiv32(x, p.m32, p.sh1, p.sh2); };
+    auto wdiv = [&](uint32_t x) -> uint32_t { return BOWGPU_FUSED_FDIV ? fdiv32(x, inv_ik) : mdiv32_asm(x, p.m32, p.sh1, p.sh2); };
 
     // ---- window ids (32-bit, global: the host sends frames whose rows lie within 2^32 of s0), head flags, compaction with a running
     // scalar count; every row's time goes to LDS as its offset from s0
@@ -234,14 +222,14 @@ __global__ __launch_bounds__(kWave, kMulti ? 4 : 6) void rolling_fused_kernel(co
         const int l = j * 128 + 2 * lane;
         const bool pa = kFull || l < nloc, pb = kFull || l + 1 < nloc;
         const int64_t tsa = (int64_t)ta[j], tsb = (int64_t)tb[j];
-        const uint32_t plo = left32((uint32_t)tb[j], (uint32_t)left_ts);
-        const uint32_t phi = left32((uint32_t)(tb[j] >> 32), (uint32_t)((uint64_t)left_ts >> 32));
+        const uint32_t plo = left_u32((uint32_t)tb[j], (uint32_t)left_ts);   // (left_u64 spelled out: through the helper the compiler orders this pass differently)
+        const uint32_t phi = left_u32((uint32_t)(tb[j] >> 32), (uint32_t)((uint64_t)left_ts >> 32));
         const int64_t prev_ts = (int64_t)(((uint64_t)phi << 32) | plo);
         unsorted |= (pa && prev_ts > tsa) || (pb && tsa > tsb);
         const uint32_t ra = (uint32_t)tsa - s0_lo, rb = (uint32_t)tsb - s0_lo;
         const uint32_t wa = wdiv(ra);
         const uint32_t wb = wdiv(rb);
-        const uint32_t wprev = left32(wb, left_w);
+        const uint32_t wprev = left_u32(wb, left_w);
         const bool ha = pa && (wa != wprev);
         const bool hb = pb && (wb != wa);
         const unsigned long long ma = __ballot(ha), mb = __ballot(hb);
@@ -254,9 +242,8 @@ __global__ __launch_bounds__(kWave, kMulti ? 4 : 6) void rolling_fused_kernel(co
         *reinterpret_cast<uint2 *>(&sh.tsx[l]) = make_uint2(ra, rb);   // (l is even: one 8-byte LDS write)
         nseg_total += __popcll(ma) + __popcll(mb);
         if (j == kChunksF - 2) nseg_owned = nseg_total;
-        left_w = (uint32_t)__builtin_amdgcn_readlane((int)wb, 63);
-        left_ts = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(tb[j] >> 32), 63) << 32) |
-                            (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)tb[j], 63));
+        left_w = readlane_u32(wb, 63);
+        left_ts = (int64_t)readlane_u64(tb[j], 63);
     }
     };
     if (BOWGPU_FUSED_INTERIOR && interior) flag_pass(std::true_type{});
@@ -275,7 +262,7 @@ __global__ __launch_bounds__(kWave, kMulti ? 4 : 6) void rolling_fused_kernel(co
     // ---- which windows this wavefront outputs: those that start in its 512 rows, with the slot-aligned hand-over of rolling_simple.hip
     int q_start = 0, q_end = nseg_owned;
     {
-        lds_order();
+        wave_lds_order();
         auto wid_at = [&](int q) -> uint32_t { return wdiv(sh.tsx[sh.seg[q]]); };
         auto handover = [&](int qf, int qlim) -> int {
             if (qf >= qlim) return qf;
@@ -308,10 +295,10 @@ __global__ __launch_bounds__(kWave, kMulti ? 4 : 6) void rolling_fused_kernel(co
         const FusedCol fc = fp.cols[c];
         const uint64_t *__restrict__ src = reinterpret_cast<const uint64_t *>(p.values[c]);
         const uint32_t *cbits = p.vbits[c];
-        lds_order();  // the previous pass is done with sh.val / sh.vbits
+        wave_lds_order();  // the previous pass is done with sh.val / sh.vbits
         if (kNulls) {
             if (lane < kRowsF / 32) sh.vbits[lane] = vword;
-            lds_order();
+            wave_lds_order();
         }
         bool snan = false;
         {
@@ -342,7 +329,7 @@ __global__ __launch_bounds__(kWave, kMulti ? 4 : 6) void rolling_fused_kernel(co
                 if (kNulls) vword = load_vword(c + 1);
             }
         }
-        lds_order();
+        wave_lds_order();
         const bool exact_mm = (kNeed & 1) && __ballot(snan) != 0ull;
 
         // the two neighbour points of a window whose FirstIndex is local row a (0 <= a <= nloc): the nearest valid row of the column
@@ -406,14 +393,14 @@ __global__ __launch_bounds__(kWave, kMulti ? 4 : 6) void rolling_fused_kernel(co
         const bool pred_walk = kNulls && (kNeed & 1) && need_sum && !two_phase;   // one walk, extrema under the validity bit
         for (int phase = two_phase ? 1 : 0; phase <= (two_phase ? 2 : 0); phase++) {
             if (phase == 2) {
-                lds_order();
+                wave_lds_order();
 #pragma unroll
                 for (int j = 0; j < kChunksF; j++) {
                     const uint32_t two = sh.vbits[j * 4 + (lane >> 4)] >> ((2 * lane) & 31);
                     if (!(two & 1u)) sh.val[swz<kSwzF>(j * 128 + 2 * lane)] = kNullAsNaN;
                     if (!(two & 2u)) sh.val[swz<kSwzF>(j * 128 + 2 * lane) + 1] = kNullAsNaN;
                 }
-                lds_order();
+                wave_lds_order();
             }
             const bool do_sum = need_sum && phase != 2;
             const bool do_mm = (kNeed & 1) && phase != 1;

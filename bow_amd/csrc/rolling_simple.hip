@@ -17,6 +17,7 @@
 #include <stddef.h>
 
 #include "agg_device.h"
+#include "wave_ops.h"
 
 namespace bowgpu {
 
@@ -55,30 +56,6 @@ struct SimpleShared {
 static_assert(sizeof(SimpleShared<false, false, true>) <= 6144 && sizeof(SimpleShared<true, false, true>) <= 6144 &&
               sizeof(SimpleShared<false, false, false>) <= 6144, "LDS of the small-list forms: 6 KB (26 wavefronts per CU)");
 
-__device__ __forceinline__ uint32_t mdiv32(uint32_t n, uint32_t m, uint32_t sh1, uint32_t sh2) {
-    const uint32_t t = __umulhi(m, n);
-    return (t + ((n - t) >> sh1)) >> sh2;
-}
-__device__ __forceinline__ uint32_t left32(uint32_t x, uint32_t lane0) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)lane0, (int)x, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-}
-// 16-byte loads / 8-byte stores with the non-temporal hint: rows 128..511 of a tile are read by this wavefront only, so their
-// lines should be the first to leave the XCD's L2; the first and the last chunk are shared with the neighbouring tiles (the
-// look-ahead) and stay plain.  Measured on the benched shape (scratch/headline_ab.hip, 1e9 rows): -2 % kernel time for the
-// loads, another -1.5 % with the outputs stored non-temporal (they are never read back by this kernel).
-typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ ulonglong2 load16_nt(const ulonglong2 *q) {
-    const u64x2_t v = __builtin_nontemporal_load(reinterpret_cast<const u64x2_t *>(q));
-    return make_ulonglong2(v.x, v.y);
-}
-__device__ __forceinline__ void store8_nt(uint64_t *p, uint64_t v) { __builtin_nontemporal_store(v, p); }
-// the double that the lane kCtrl names holds (row_shr:N inside a row of 16 lanes); a lane without such a neighbour keeps its own
-template <int kCtrl>
-__device__ __forceinline__ double row_dpp64(double x) {
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(x), __double2loint(x), kCtrl, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(x), __double2hiint(x), kCtrl, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
 // Tiles of FEW windows (at most kCoopMaxHeads heads in the tile's 640 rows: windows of ~92 rows and more; ~128 when the window's lane walks
 // its rows for a sum anyway - the extrema then ride along at 2 instructions per row): the extrema of the tile's windows
 // are found by ALL 64 lanes - 16 lanes per window, four windows per pass, each lane over a contiguous piece of its window - instead of
@@ -94,11 +71,6 @@ __device__ __forceinline__ double row_dpp64(double x) {
 #endif
 constexpr int kCoopMaxHeads = BOWGPU_COOP_MAX_HEADS;
 constexpr int kCoopMaxHeadsSum = BOWGPU_COOP_MAX_HEADS < 5 ? BOWGPU_COOP_MAX_HEADS : 5;
-__device__ __forceinline__ void lds_order() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 }  // namespace
 
@@ -124,6 +96,10 @@ __global__ __launch_bounds__(kWave, 6) void rolling_simple_kernel(const SimplePa
     const int nloc = interior ? kRowsS : (int)(n - base);
 
     // ---- loads: ts, then the first value column right behind it
+    // 16-byte loads with the non-temporal hint (load16_nt): rows 128..511 of a tile are read by this wavefront only, so their
+    // lines should be the first to leave the XCD's L2; the first and the last chunk are shared with the neighbouring tiles (the
+    // look-ahead) and stay plain.  Measured on the benched shape (scratch/headline_ab.hip, 1e9 rows): -2 % kernel time for the
+    // loads, another -1.5 % with the outputs stored non-temporal (they are never read back by this kernel).
     uint64_t ta[kChunksS], tb[kChunksS], va[kChunksS], vb[kChunksS];
     const uint64_t *__restrict__ ts = reinterpret_cast<const uint64_t *>(p.ts);
     // a column whose first row is only 8-byte aligned (an Arrow slice with an odd offset) is read with two 8-byte loads per lane and
@@ -205,15 +181,15 @@ __global__ __launch_bounds__(kWave, 6) void rolling_simple_kernel(const SimplePa
         const int l = j * 128 + 2 * lane;
         const bool pa = l < nloc, pb = l + 1 < nloc;
         const int64_t tsa = (int64_t)ta[j], tsb = (int64_t)tb[j];
-        const uint32_t plo = left32((uint32_t)tb[j], (uint32_t)left_ts);
-        const uint32_t phi = left32((uint32_t)(tb[j] >> 32), (uint32_t)((uint64_t)left_ts >> 32));
+        const uint32_t plo = left_u32((uint32_t)tb[j], (uint32_t)left_ts);   // (left_u64 spelled out: through the helper the compiler orders this pass differently)
+        const uint32_t phi = left_u32((uint32_t)(tb[j] >> 32), (uint32_t)((uint64_t)left_ts >> 32));
         const int64_t prev_ts = (int64_t)(((uint64_t)phi << 32) | plo);
         unsorted |= (pa && prev_ts > tsa) || (pb && tsa > tsb);
         const uint32_t ra = rel32(tsa), rb = rel32(tsb);
         uint32_t wa = mdiv32(ra, p.m32, p.sh1, p.sh2);
         uint32_t wb = mdiv32(rb, p.m32, p.sh1, p.sh2);
         if (pre) { if (tsa < ws0) wa = 0u; if (tsb < ws0) wb = 0u; }
-        const uint32_t wprev = left32(wb, left_w);
+        const uint32_t wprev = left_u32(wb, left_w);
         const bool ha = pa && (wa != wprev);
         const bool hb = pb && (wb != wa);
         const uint32_t la = wa - w_first, lb = wb - w_first;
@@ -227,9 +203,8 @@ __global__ __launch_bounds__(kWave, 6) void rolling_simple_kernel(const SimplePa
         if (hb && pos < kSegCapS) sh.seg[pos] = (uint32_t)(l + 1) | (lb << 16);
         nseg_total += __popcll(ma) + __popcll(mb);
         if (j == kChunksS - 2) nseg_owned = nseg_total;
-        left_w = (uint32_t)__builtin_amdgcn_readlane((int)wb, 63);
-        left_ts = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(tb[j] >> 32), 63) << 32) |
-                            (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)tb[j], 63));
+        left_w = readlane_u32(wb, 63);
+        left_ts = (int64_t)readlane_u64(tb[j], 63);
         // single column: its values go to LDS now (their registers die here)
         if (!kMulti && !kNulls && !kInt) {
             *reinterpret_cast<ulonglong2 *>(&sh.val[swz<kSwzS>(l)]) = make_ulonglong2(va[j], vb[j]);
@@ -256,7 +231,7 @@ __global__ __launch_bounds__(kWave, 6) void rolling_simple_kernel(const SimplePa
     // when the head that CLOSES the handed-over windows lies inside those rows; otherwise each tile keeps its own.
     int q_start = 0, q_end = nseg_owned;
     {
-        lds_order();                                // the segment list is complete
+        wave_lds_order();                                // the segment list is complete
         const uint32_t slot_lo = (uint32_t)w0;      // output slot = w0 + id: its low bits are the same whichever tile computes them
         // heads are in id order and ids grow by at least one per head: the heads below the aligned id are among the first kAlignS
         auto handover = [&](int qf, int qlim) -> int {   // qf: first head of a tile; qlim: heads inside the shared 128 rows end here
@@ -313,10 +288,10 @@ __global__ __launch_bounds__(kWave, 6) void rolling_simple_kernel(const SimplePa
         const bool cint = kMulti ? (p.col_is_int[c] != 0) : kInt;  // mixed column types: per pass (uniform)
         constexpr bool kStageHere = kMulti || kNulls || kInt;
         if (kStageHere) {
-            lds_order();  // the previous pass is done with sh.val / sh.vbits
+            wave_lds_order();  // the previous pass is done with sh.val / sh.vbits
             if (kNulls) {
                 if (lane < kRowsS / 32) sh.vbits[lane] = vword;
-                lds_order();
+                wave_lds_order();
             }
             const uint64_t fill = need_sum ? 0ull : kNullAsNaN;
             snan = false;
@@ -340,7 +315,7 @@ __global__ __launch_bounds__(kWave, 6) void rolling_simple_kernel(const SimplePa
                 if (kNulls) vword = load_vword(c + 1);
             }
         }
-        lds_order();
+        wave_lds_order();
         const bool exact_mm = (kNeed & 1) && __ballot(snan) != 0ull;
         // a nullable column whose outputs want sums AND extrema is walked twice: phase 1 with +0.0 in the null rows (everything but
         // Min / Max), then the null rows are overwritten with NaN and phase 2 walks the extrema.  Every other shape: phase 0, one walk.
@@ -348,14 +323,14 @@ __global__ __launch_bounds__(kWave, 6) void rolling_simple_kernel(const SimplePa
         const bool pred_walk = kNulls && (kNeed & 1) && need_sum && !two_phase;   // one walk, extrema under the validity bit
         for (int phase = two_phase ? 1 : 0; phase <= (two_phase ? 2 : 0); phase++) {
             if (phase == 2) {
-                lds_order();
+                wave_lds_order();
 #pragma unroll
                 for (int j = 0; j < kChunksS; j++) {
                     const uint32_t two = sh.vbits[j * 4 + (lane >> 4)] >> ((2 * lane) & 31);
                     if (!(two & 1u)) sh.val[swz<kSwzS>(j * 128 + 2 * lane)] = kNullAsNaN;
                     if (!(two & 2u)) sh.val[swz<kSwzS>(j * 128 + 2 * lane) + 1] = kNullAsNaN;
                 }
-                lds_order();
+                wave_lds_order();
             }
             const bool do_sum = need_sum && phase != 2;
             const bool do_mm = (kNeed & 1) && phase != 1;
@@ -386,7 +361,7 @@ __global__ __launch_bounds__(kWave, 6) void rolling_simple_kernel(const SimplePa
                     // ordered inclusive scan over the row's 16 lanes: what the earlier lanes hold stays unless this lane's is strictly better
 #define BG_COOP_STEP(CTRL, DIST)                                            \
                     {                                                        \
-                        const double en = row_dpp64<CTRL>(mnl), ex = row_dpp64<CTRL>(mxl);  \
+                        const double en = dpp_keep_f64<CTRL, 0xf>(mnl), ex = dpp_keep_f64<CTRL, 0xf>(mxl);  \
                         if (sub >= DIST) { if (!(mnl < en)) mnl = en; if (!(mxl > ex)) mxl = ex; } \
                     }
                     BG_COOP_STEP(0x111, 1) BG_COOP_STEP(0x112, 2) BG_COOP_STEP(0x114, 4) BG_COOP_STEP(0x118, 8)

@@ -29,6 +29,7 @@
 #include <stddef.h>
 
 #include "agg_device.h"
+#include "wave_ops.h"
 
 namespace bowgpu {
 
@@ -69,37 +70,6 @@ struct TwShared {
 static_assert(sizeof(TwShared<false, true, false>) <= 8192 && sizeof(TwShared<true, true, false>) <= 8192, "LDS of the 32-bit forms: 8 KB");
 static_assert(sizeof(TwShared<false, false, false>) <= 11264 && sizeof(TwShared<true, false, false>) <= 11264, "LDS of the 64-bit forms: 11 KB");
 static_assert(sizeof(TwShared<false, true, true>) <= 6144 && sizeof(TwShared<false, false, true>) <= 6144, "LDS of the lean forms: 6 KB");
-
-__device__ __forceinline__ uint32_t mdiv32(uint32_t n, uint32_t m, uint32_t sh1, uint32_t sh2) {
-    const uint32_t t = __umulhi(m, n);
-    return (t + ((n - t) >> sh1)) >> sh2;
-}
-__device__ __forceinline__ uint32_t left32(uint32_t x, uint32_t lane0) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)lane0, (int)x, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-}
-// the value lane - 1 holds (lane 0: `lane0`)
-__device__ __forceinline__ double left64(double x, double lane0) {
-    const uint64_t b = (uint64_t)__double_as_longlong(x), f = (uint64_t)__double_as_longlong(lane0);
-    const uint32_t lo = left32((uint32_t)b, (uint32_t)f), hi = left32((uint32_t)(b >> 32), (uint32_t)(f >> 32));
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-__device__ __forceinline__ double lane63(double x) {
-    const uint64_t b = (uint64_t)__double_as_longlong(x);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, 63), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), 63);
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-// non-temporal 16-byte loads / 8-byte stores: see rolling_simple.hip (rows 128..511 of a tile are read by this wavefront only;
-// outputs are never read back)
-typedef unsigned long long u64x2_tw __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ ulonglong2 load16_nt(const ulonglong2 *q) {
-    const u64x2_tw v = __builtin_nontemporal_load(reinterpret_cast<const u64x2_tw *>(q));
-    return make_ulonglong2(v.x, v.y);
-}
-__device__ __forceinline__ void lds_order() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 }  // namespace
 
@@ -245,15 +215,15 @@ __global__ __launch_bounds__(kWave, (kShort || kLean || (!kNulls && kTs32 && (!k
         const int l = j * 128 + 2 * lane;
         const bool pa = l < nloc, pb = l + 1 < nloc;
         const int64_t tsa = (int64_t)ta[j], tsb = (int64_t)tb[j];
-        const uint32_t plo = left32((uint32_t)tb[j], (uint32_t)left_ts);
-        const uint32_t phi = left32((uint32_t)(tb[j] >> 32), (uint32_t)((uint64_t)left_ts >> 32));
+        const uint32_t plo = left_u32((uint32_t)tb[j], (uint32_t)left_ts);   // (left_u64 spelled out: through the helper the compiler orders this pass differently)
+        const uint32_t phi = left_u32((uint32_t)(tb[j] >> 32), (uint32_t)((uint64_t)left_ts >> 32));
         const int64_t prev_ts = (int64_t)(((uint64_t)phi << 32) | plo);
         unsorted |= (pa && prev_ts > tsa) || (pb && tsa > tsb);
         const uint32_t ra = rel32(tsa), rb = rel32(tsb);
         uint32_t wa = mdiv32(ra, p.m32, p.sh1, p.sh2);
         uint32_t wb = mdiv32(rb, p.m32, p.sh1, p.sh2);
         if (pre) { if (tsa < ws0) wa = 0u; if (tsb < ws0) wb = 0u; }
-        const uint32_t wprev = left32(wb, left_w);
+        const uint32_t wprev = left_u32(wb, left_w);
         const bool ha = pa && (wa != wprev);
         const bool hb = pb && (wb != wa);
         hmask |= (ha ? 1u : 0u) << (2 * j) | (hb ? 2u : 0u) << (2 * j);
@@ -282,9 +252,8 @@ __global__ __launch_bounds__(kWave, (kShort || kLean || (!kNulls && kTs32 && (!k
         }
         nseg_total += __popcll(ma) + __popcll(mb);
         if (j == kChunksT - 2) nseg_owned = nseg_total;
-        left_w = (uint32_t)__builtin_amdgcn_readlane((int)wb, 63);
-        left_ts = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(tb[j] >> 32), 63) << 32) |
-                            (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)tb[j], 63));
+        left_w = readlane_u32(wb, 63);
+        left_ts = (int64_t)readlane_u64(tb[j], 63);
         // the rows' times, for the term passes (float64(ts) and the window id are both recomputed from them there)
         if (!kLean) {
             if (kTs32) *reinterpret_cast<uint2 *>(&sh.tsx[l]) = make_uint2(ra, rb);   // (l is even: one 8-byte LDS write)
@@ -293,8 +262,8 @@ __global__ __launch_bounds__(kWave, (kShort || kLean || (!kNulls && kTs32 && (!k
         if (early_terms) {   // (see the term pass below for what a slot holds)
             const double xa = cint0 ? (double)(int64_t)va[j] : __longlong_as_double((long long)va[j]);
             const double xb = cint0 ? (double)(int64_t)vb[j] : __longlong_as_double((long long)vb[j]);
-            const double xp = left64(xb, early_carry_x);
-            early_carry_x = lane63(xb);
+            const double xp = left_f64(xb, early_carry_x);
+            early_carry_x = readlane_f64(xb, 63);
             // float64(t1) - float64(t0): the 32-bit difference converted (exact: both times are, and they are less than 2^32 apart), else as written
             const double dta = kTs32 ? (double)(uint32_t)((uint32_t)tsa - (uint32_t)prev_ts) : (double)tsa - (double)prev_ts;
             const double dtb = kTs32 ? (double)(uint32_t)((uint32_t)tsb - (uint32_t)tsa) : (double)tsb - (double)tsa;
@@ -357,7 +326,7 @@ __global__ __launch_bounds__(kWave, (kShort || kLean || (!kNulls && kTs32 && (!k
         next_wid = W32;
         return reaches_end ? 0 : 1;
     };
-    lds_order();   // the head list and the staged times are complete
+    wave_lds_order();   // the head list and the staged times are complete
     int g_r0 = 0, g_r1 = 0, g_state = 2;
     uint32_t g_wid = 0, g_next = 0, g_e1 = 0;
     if (lane < nseg_owned) g_state = geometry(lane, g_r0, g_r1, g_wid, g_next, g_e1);
@@ -368,11 +337,11 @@ __global__ __launch_bounds__(kWave, (kShort || kLean || (!kNulls && kTs32 && (!k
         const bool cint = p.col_is_int[c] != 0;  // mixed column types: per pass (uniform)
         // ---- stage the values (converted to float64, nulls replaced: rolling_simple.hip) - the gather source of the term pass for a
         // nullable column, and what the value reducers walk
-        lds_order();  // the previous pass is done with sh.val / sh.vbits
+        wave_lds_order();  // the previous pass is done with sh.val / sh.vbits
         const bool early = early_terms && c == 0;   // its first kind of terms is in sh.val already (flag pass)
         if (kNulls) {
             if (lane < kRowsT / 32) sh.vbits[lane] = vword;
-            lds_order();
+            wave_lds_order();
         }
         // ---- stage the column: float64(v) (Int64 columns are converted here: bowgetters.go:224-229), null rows replaced as in
         // rolling_simple.hip.  It is what the value reducers walk and what the term pass reads.
@@ -402,7 +371,7 @@ __global__ __launch_bounds__(kWave, (kShort || kLean || (!kNulls && kTs32 && (!k
             load_col(reinterpret_cast<const uint64_t *>(p.values[c + 1]), va, vb, !((p.unaligned_mask >> (c + 1)) & 1u));
             if (kNulls) vword = load_vword(c + 1);
         }
-        lds_order();
+        wave_lds_order();
         // ---- the term pass: the terms of this lane's ten rows from the staged values and times.  `first` (step terms when the call
         // has them, else trapezoid terms) replaces the staged values in LDS - chunk by chunk for a column without nulls (a row's
         // previous point is the previous row: read before the chunk is written, the row in front of the NEXT chunk saved first), and
@@ -455,7 +424,7 @@ __global__ __launch_bounds__(kWave, (kShort || kLean || (!kNulls && kTs32 && (!k
                         qb = (xa + xb) / 2 * dtb;
                     }
                     if (j + 1 < kChunksT) carry_x = __longlong_as_double((long long)sh.val[swz<kSwzT>(j * 128 + 127)]);
-                    lds_order();   // every lane has read this chunk's values
+                    wave_lds_order();   // every lane has read this chunk's values
                     const double oa = first_is_step ? sa : qa, ob = first_is_step ? sb : qb;
                     *reinterpret_cast<ulonglong2 *>(&sh.val[swz<kSwzT>(l)]) = make_ulonglong2((uint64_t)__double_as_longlong(oa), (uint64_t)__double_as_longlong(ob));
                 } else {
@@ -490,7 +459,7 @@ __global__ __launch_bounds__(kWave, (kShort || kLean || (!kNulls && kTs32 && (!k
                         if (a_ok && has_p && (ha || same_a)) qa = (xp + xa) / 2 * dta;
                         if (b_ok && has_p2 && (hb || same_b)) qb = (xp2 + xb) / 2 * dtb;
                     }
-                    lds_order();   // every lane has gathered for this chunk
+                    wave_lds_order();   // every lane has gathered for this chunk
                     const double oa = first_is_step ? sa : qa, ob = first_is_step ? sb : qb;
                     *reinterpret_cast<ulonglong2 *>(&sh.val[swz<kSwzT>(l)]) = make_ulonglong2((uint64_t)__double_as_longlong(oa), (uint64_t)__double_as_longlong(ob));
                 }
@@ -519,7 +488,7 @@ __global__ __launch_bounds__(kWave, (kShort || kLean || (!kNulls && kTs32 && (!k
             if (phase == 3 && !need_step) continue;
             if (phase == 4 && !need_trap) continue;
             if (phase == 2) {
-                lds_order();
+                wave_lds_order();
 #pragma unroll
                 for (int j = 0; j < kChunksT; j++) {
                     const int l = j * 128 + 2 * lane;
@@ -527,10 +496,10 @@ __global__ __launch_bounds__(kWave, (kShort || kLean || (!kNulls && kTs32 && (!k
                     if (!(two & 1u)) sh.val[swz<kSwzT>(l)] = kNullAsNaN;
                     if (!(two & 2u)) sh.val[swz<kSwzT>(l + 1)] = kNullAsNaN;
                 }
-                lds_order();
+                wave_lds_order();
             }
             if (phase >= 3) {
-                lds_order();   // the walks of the phase before are done with sh.val
+                wave_lds_order();   // the walks of the phase before are done with sh.val
                 if (phase == 3 || !need_step) { if (!early) term_pass(); }
                 else if (kKeep) {
 #pragma unroll
@@ -538,7 +507,7 @@ __global__ __launch_bounds__(kWave, (kShort || kLean || (!kNulls && kTs32 && (!k
                         *reinterpret_cast<ulonglong2 *>(&sh.val[swz<kSwzT>(j * 128 + 2 * lane)]) = make_ulonglong2(
                             (uint64_t)__double_as_longlong(keep_a[kKeep ? j : 0]), (uint64_t)__double_as_longlong(keep_b[kKeep ? j : 0]));
                 }
-                lds_order();
+                wave_lds_order();
             }
             const bool do_sum = need_sum && phase <= 1;
             const bool do_mm = need_mm && (phase == 0 || phase == 2);

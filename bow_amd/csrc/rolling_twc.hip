@@ -23,6 +23,7 @@
 #include <stddef.h>
 
 #include "agg_device.h"
+#include "wave_ops.h"
 
 namespace bowgpu {
 
@@ -47,34 +48,6 @@ struct TwcShared {
 };
 static_assert(sizeof(TwcShared<128>) <= 8192, "LDS of the compacting form: 8 KB (20 wavefronts per CU)");
 static_assert(sizeof(TwcShared<256>) <= 10240, "LDS of the compacting form with the long look-ahead: 10 KB (16 wavefronts per CU)");
-
-__device__ __forceinline__ uint32_t mdiv32(uint32_t n, uint32_t m, uint32_t sh1, uint32_t sh2) {
-    const uint32_t t = __umulhi(m, n);
-    return (t + ((n - t) >> sh1)) >> sh2;
-}
-__device__ __forceinline__ uint32_t left32(uint32_t x, uint32_t lane0) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)lane0, (int)x, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-}
-typedef unsigned long long u64x2_c __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ ulonglong2 load16_nt(const ulonglong2 *q) {
-    const u64x2_c v = __builtin_nontemporal_load(reinterpret_cast<const u64x2_c *>(q));
-    return make_ulonglong2(v.x, v.y);
-}
-__device__ __forceinline__ void lds_order() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// inclusive wave scan (row_shr 1 / 2 / 4 / 8 inside the 16-lane rows, row_bcast 15 / 31 across): six DPP moves + adds, no LDS
-__device__ __forceinline__ uint32_t wave_scan_u32(uint32_t x) {
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, true);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, true);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, true);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, true);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);
-    return x;
-}
 
 }  // namespace
 
@@ -184,7 +157,7 @@ __global__ __launch_bounds__(kWave, (kMulti && kBoth) ? 3 : (kMulti || kHalo != 
         if (two & 2u) { const int s2 = slot + (int)(two & 1u); sh.val[s2] = xb; sh.ctx[s2] = tb32; }
     };
     stage_validity(vword);
-    lds_order();
+    wave_lds_order();
     bool snan0 = false;
     const bool cint0 = p.col_is_int[0] != 0;
 
@@ -200,8 +173,8 @@ __global__ __launch_bounds__(kWave, (kMulti && kBoth) ? 3 : (kMulti || kHalo != 
         const int l = j * 128 + 2 * lane;
         const bool pa = l < nloc, pb = l + 1 < nloc;
         const int64_t tsa = (int64_t)ta[j], tsb = (int64_t)tb[j];
-        const uint32_t plo = left32((uint32_t)tb[j], (uint32_t)left_ts);
-        const uint32_t phi = left32((uint32_t)(tb[j] >> 32), (uint32_t)((uint64_t)left_ts >> 32));
+        const uint32_t plo = left_u32((uint32_t)tb[j], (uint32_t)left_ts);   // (left_u64 spelled out: through the helper the compiler orders this pass differently)
+        const uint32_t phi = left_u32((uint32_t)(tb[j] >> 32), (uint32_t)((uint64_t)left_ts >> 32));
         const int64_t prev_ts = (int64_t)(((uint64_t)phi << 32) | plo);
         unsorted |= (pa && prev_ts > tsa) || (pb && tsa > tsb);
         const uint32_t ra_j = (uint32_t)tsa - s0_lo, rb_j = (uint32_t)tsb - s0_lo;
@@ -209,7 +182,7 @@ __global__ __launch_bounds__(kWave, (kMulti && kBoth) ? 3 : (kMulti || kHalo != 
         compact_chunk(j, va[j], vb[j], ra_j, rb_j, cint0, snan0);
         const uint32_t wa = mdiv32(ra_j, p.m32, p.sh1, p.sh2);
         const uint32_t wb = mdiv32(rb_j, p.m32, p.sh1, p.sh2);
-        const uint32_t wprev = left32(wb, left_w);
+        const uint32_t wprev = left_u32(wb, left_w);
         const bool ha = pa && (wa != wprev);
         const bool hb = pb && (wb != wa);
         const uint32_t la = wa - w_first, lb = wb - w_first;
@@ -225,9 +198,8 @@ __global__ __launch_bounds__(kWave, (kMulti && kBoth) ? 3 : (kMulti || kHalo != 
         if (hb && pos < kCapC) sh.seg[pos] = (uint32_t)(l + 1) | sb | (lb << 11);
         nseg_total += __popcll(ma) + __popcll(mb);
         if (j == kTileC / 128 - 1) nseg_owned = nseg_total;   // (the heads inside the tile's own 512 rows)
-        left_w = (uint32_t)__builtin_amdgcn_readlane((int)wb, 63);
-        left_ts = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(tb[j] >> 32), 63) << 32) |
-                            (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)tb[j], 63));
+        left_w = readlane_u32(wb, 63);
+        left_ts = (int64_t)readlane_u64(tb[j], 63);
     }
     if (__ballot(unsorted)) {  // the call fails with BOWGPU_ERR_TS_UNSORTED
         if (lane == 0) atomicOr(&p.status[0], 1u);
@@ -262,7 +234,7 @@ __global__ __launch_bounds__(kWave, (kMulti && kBoth) ? 3 : (kMulti || kHalo != 
         next_wid = W32;
         return reaches_end ? 0 : 1;
     };
-    lds_order();   // the head list is complete
+    wave_lds_order();   // the head list is complete
     int g_r0 = 0, g_r1 = 0, g_state = 2;
     uint32_t g_wid = 0, g_next = 0, g_e1 = 0;
     if (lane < nseg_owned) g_state = geometry(lane, g_r0, g_r1, g_wid, g_next, g_e1);
@@ -279,9 +251,9 @@ __global__ __launch_bounds__(kWave, (kMulti && kBoth) ? 3 : (kMulti || kHalo != 
         const uint64_t *__restrict__ src = reinterpret_cast<const uint64_t *>(p.values[c]);
         bool snan = snan0;
         if (kMulti && c > 0) {
-            lds_order();  // the previous pass is done with sh.val / sh.ctx / sh.vbits
+            wave_lds_order();  // the previous pass is done with sh.val / sh.ctx / sh.vbits
             stage_validity(vword);
-            lds_order();
+            wave_lds_order();
             snan = false;
 #pragma unroll
             for (int j = 0; j < kChunksC; j++) compact_chunk(j, va[j], vb[j], ra[kMulti ? j : 0], rb[kMulti ? j : 0], cint, snan);
@@ -291,7 +263,7 @@ __global__ __launch_bounds__(kWave, (kMulti && kBoth) ? 3 : (kMulti || kHalo != 
             load_col(reinterpret_cast<const uint64_t *>(p.values[c + 1]), va, vb, !((p.unaligned_mask >> (c + 1)) & 1u));
             vword = load_vword(c + 1);
         }
-        lds_order();
+        wave_lds_order();
         const int total = __builtin_amdgcn_readfirstlane((int)sh.wpre[kWordsC]);   // (the same in every lane: a scalar)
         const bool exact_mm = need_mm && __ballot(snan) != 0ull;
         // ---- this lane's first window in slot space: [ka, kb); its last point, which the step integral's closing term needs, is read
@@ -329,7 +301,7 @@ __global__ __launch_bounds__(kWave, (kMulti && kBoth) ? 3 : (kMulti || kHalo != 
                     if (need_step) { sa = xp * dta; sb = xa * dtb; }
                     if (need_trap) { qa = (xp + xa) / 2 * dta; qb = (xa + xb) / 2 * dtb; }
                     if (j + 1 < kChunksC) carry_x = __longlong_as_double((long long)sh.val[j * 128 + 127]);
-                    lds_order();   // every lane has read this chunk's values
+                    wave_lds_order();   // every lane has read this chunk's values
                     const double oa = need_step ? sa : qa, ob = need_step ? sb : qb;
                     *reinterpret_cast<ulonglong2 *>(&sh.val[k]) = make_ulonglong2((uint64_t)__double_as_longlong(oa), (uint64_t)__double_as_longlong(ob));
                     if (kBoth) { keep_a[kBoth ? j : 0] = qa; keep_b[kBoth ? j : 0] = qb; }
@@ -346,7 +318,7 @@ __global__ __launch_bounds__(kWave, (kMulti && kBoth) ? 3 : (kMulti || kHalo != 
             if (phase == 3 && !need_step) continue;
             if (phase == 4 && !need_trap) continue;
             if (phase >= 3) {
-                lds_order();   // the walks of the phase before are done with sh.val
+                wave_lds_order();   // the walks of the phase before are done with sh.val
                 if (phase == 3 || !need_step) term_pass();
                 else if (kBoth) {
 #pragma unroll
@@ -355,7 +327,7 @@ __global__ __launch_bounds__(kWave, (kMulti && kBoth) ? 3 : (kMulti || kHalo != 
                             *reinterpret_cast<ulonglong2 *>(&sh.val[j * 128 + 2 * lane]) = make_ulonglong2(
                                 (uint64_t)__double_as_longlong(keep_a[kBoth ? j : 0]), (uint64_t)__double_as_longlong(keep_b[kBoth ? j : 0]));
                 }
-                lds_order();
+                wave_lds_order();
             }
             uint32_t out_mask = phase == 0 ? (p.kind_mask[0] | p.kind_mask[1]) : phase == 3 ? p.kind_mask[2] : p.kind_mask[3];
             if (phase == phase1) out_mask |= p.kind_mask[4];

@@ -1,4 +1,5 @@
 // Wave64 scans shared by the radix sort (sort.hip), the filter's compaction (filter.hip) and the join's row lists (join.hip).
+// (The DPP scan and reductions of the Aggregate / Interpolate kernels - other instructions - live in wave_ops.h.)
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -92,13 +92,13 @@ def test_every_profile_file_of_the_round_is_described_and_every_described_file_e
 # which device sources a counter file of the round speaks about (host code - agg_pass.cpp, interpolate_api.cpp, multi.cpp - routes calls; it does not change
 # what a kernel's counters say)
 COUNTER_FILES = {
-    "r06_pmc_rolling_fused.txt": ["rolling_fused.hip", "rolling_simple.hip", "agg_device.h", "interp_device.h", "bitmap_device.h"],
-    "r06_pmc_long_strict.txt": ["long_windows.hip", "agg_device.h"],
-    "r06_pmc_band.txt": ["long_windows.hip", "rolling_simple.hip", "agg_device.h"],
-    "r06_pmc_callers.txt": ["interp_fill.hip", "agg_device.h", "bitmap_device.h"],
-    "r06_pmc_mid_windows.txt": ["rolling_tw.hip", "rolling_twc.hip", "rolling_simple.hip", "agg_device.h"],
-    "r06_pmc_interp_wave3_1e8.txt": ["interpolate.hip", "interp_device.h", "agg_device.h"],
-    "r06_pmc_long_short_tw.txt": ["long_windows.hip", "agg_device.h"],
+    "r06_pmc_rolling_fused.txt": ["rolling_fused.hip", "rolling_simple.hip", "agg_device.h", "interp_device.h", "bitmap_device.h", "wave_ops.h"],
+    "r06_pmc_long_strict.txt": ["long_windows.hip", "long_stream.hip", "long_device.h", "wave_ops.h", "agg_device.h"],
+    "r06_pmc_band.txt": ["long_windows.hip", "long_stream.hip", "long_device.h", "wave_ops.h", "rolling_simple.hip", "agg_device.h"],
+    "r06_pmc_callers.txt": ["interp_fill.hip", "agg_device.h", "bitmap_device.h", "wave_ops.h"],
+    "r06_pmc_mid_windows.txt": ["rolling_tw.hip", "rolling_twc.hip", "rolling_simple.hip", "agg_device.h", "wave_ops.h"],
+    "r06_pmc_interp_wave3_1e8.txt": ["interpolate.hip", "interp_device.h", "agg_device.h", "wave_ops.h"],
+    "r06_pmc_long_short_tw.txt": ["long_windows.hip", "long_stream.hip", "long_device.h", "wave_ops.h", "agg_device.h"],
 }
 
 
