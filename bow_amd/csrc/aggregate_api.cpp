@@ -738,7 +738,7 @@ static int aggregate_with_plan(const bowgpu_col *cols, int32_t ncols, int32_t ts
     int inclusive = opt_inclusive ? 1 : 0, nic = -1;
     BG_TRY(validate_aggs(cols, ncols, ts_col, aggs, naggs, &inclusive, &nic));
     if (!outs) return fail(BOWGPU_ERR_ARG, "no output columns");
-    {   // bowgpu_set_devices: the call cut into row ranges over the listed devices (multi.cpp); not taken -> the one-device path below
+    {   // bowgpu_set_devices: the call cut into row ranges over the listed devices (fan_call.cpp); not taken -> the one-device path below
         bool fanned = false;
         BG_TRY(multi_aggregate(cols, ncols, ts_col, plan, opt_inclusive, strict, aggs, naggs, outs, info, &fanned));
         if (fanned) return 0;
@@ -809,7 +809,7 @@ int bowgpu_rolling_interpolate_aggregate(const bowgpu_col *cols, int32_t ncols, 
         if (cols[aggs[i].col].type == BOWGPU_BOOLEAN)
             return fail(BOWGPU_ERR_UNSUPPORTED, "aggregation %d: Interpolate does not take a Boolean column on the device, so neither does Interpolate + Aggregate", i);
     if (!outs) return fail(BOWGPU_ERR_ARG, "no output columns");
-    {   // bowgpu_set_devices: every rank interpolates and aggregates its own row range (multi.cpp); not taken -> one device, below
+    {   // bowgpu_set_devices: every rank interpolates and aggregates its own row range (fan_call.cpp); not taken -> one device, below
         bool fanned = false;
         BG_TRY(multi_interpolate_aggregate(cols, ncols, ts_col, plan, o.inclusive, strict_wanted(&o), interps, ninterps, aggs, naggs, outs, info, &fanned));
         if (fanned) return 0;

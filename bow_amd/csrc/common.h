@@ -301,14 +301,14 @@ int kind_type(int kind);
 bool kind_never_nil(int kind);
 bool kind_reads_values(int kind);
 
-// multi.cpp: one Rolling.Aggregate over the devices of bowgpu_set_devices (*done = false: not a call for it, nothing was touched)
+// fan_call.cpp: one Rolling.Aggregate over the devices of bowgpu_set_devices (*done = false: not a call for it, nothing was touched)
 int multi_aggregate(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, const Plan &plan, int opt_inclusive, bool strict,
                     const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs, bowgpu_agg_info *info, bool *done);
 int multi_interpolate_aggregate(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, const Plan &plan, int opt_inclusive, bool strict,
                                 const bowgpu_interp *interps, int32_t ninterps, const bowgpu_agg *aggs, int32_t naggs, bowgpu_out *outs,
                                 bowgpu_agg_info *info, bool *done);
 
-// aggregate_api.cpp, for bowgpu_rolling_aggregate_sharded (multi.cpp): the checks of bowgpu_rolling_aggregate that need no column data
+// aggregate_api.cpp, for bowgpu_rolling_aggregate_sharded (sharded_call.cpp): the checks of bowgpu_rolling_aggregate that need no column data
 // (interval column type, interval, aggregators) plus the shard protocol's own (Mode, at most 16 aggregators) - host only
 int sharded_validate(const bowgpu_col *cols, int32_t ncols, int32_t ts_col, int64_t interval, const bowgpu_agg *aggs, int32_t naggs);
 // nulls of an interval column (counted on the calling thread's device when the caller said -1)

@@ -1,6 +1,6 @@
-// What the calls over several devices share (multi.cpp: the fan-out of bowgpu_set_devices and bowgpu_rolling_aggregate_sharded;
-// sort_shard_api.cpp: bowgpu_sort_by_col_sharded): one persistent library thread per rank, the dispatch of one function over them,
-// a barrier among the ranks of one call.  Defined in multi.cpp.
+// What the calls over several devices share (fan_call.cpp: the fan-out of bowgpu_set_devices; sharded_call.cpp:
+// bowgpu_rolling_aggregate_sharded; sort_shard_api.cpp: bowgpu_sort_by_col_sharded): one persistent library thread per rank, the
+// dispatch of one function over them, a barrier among the ranks of one call (fanout.cpp), the staging of a rank's rows (fan_call.cpp).
 #pragma once
 
 #include <condition_variable>
@@ -35,6 +35,36 @@ struct Fanout {
 
 // runs fn(rank) on worker `rank` for rank in [0, world) and waits for all of them
 void fan_run(Fanout *f, int world, const std::function<void(int)> &fn);
+
+// One call's view of the fan-out of bowgpu_set_devices (fanout.cpp owns the list, the pool and the counters).  Constructed: the list
+// and the row threshold as they are now (environment defaults applied), the calling thread's bowgpu_last_call_ranks back to 1, the
+// call counted as listed when two or more devices are.  start(): call_mu taken for the session's lifetime (one fanned-out call per
+// process at a time), the workers restarted when the list has changed.  served(): the call counted, its ranks remembered.
+struct FanSession {
+    std::vector<int> ids;
+    int64_t min_rows = 0;
+    Fanout *f = nullptr;
+    std::unique_lock<std::mutex> call_lock;
+    FanSession();
+    void start();
+    void served(int world);
+};
+
+// A rank's rows of a call's columns as the record protocol sees them.  Pageable columns are staged ONCE (the record pass and the
+// rank's pass both read the staged copy: each row crosses the host link once), values from an 8-row boundary so that one offset
+// serves values and bits; the others are the caller's buffers at the rank's offset.  rank_stage synchronises the stream.
+struct RankRows {
+    std::vector<bowgpu_col> cols;
+    std::vector<DevBuf> staged_bufs;   // [2 * ncols]: the values and the bits of column i
+    bool staged = false;
+    void release_rows() { staged_bufs.clear(); staged = false; }   // on the rank's own thread: the blocks go back to THAT thread's (device's) cache
+};
+struct StageArgs {   // what rank_stage reads of a call
+    const bowgpu_col *cols; int32_t ncols, ts_col;
+    const bowgpu_agg *aggs; int32_t naggs;
+    bool all_used;   // every column is staged, not only the interval column and the aggregators' (Interpolate rewrites them all)
+};
+int rank_stage(Ctx *c, const StageArgs &a, int64_t row0, int64_t nrows, RankRows *rk);
 
 // the workers of the calls over the CALLER's shards (not the fan-out's): one pool, one call at a time (call_mu), grown to the
 // largest world seen; a worker moves to the device its rank names

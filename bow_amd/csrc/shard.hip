@@ -200,7 +200,7 @@ int launch_fill_empty(Ctx *c, const AggParams &p, int64_t slot0, int64_t slot1) 
     return 0;
 }
 
-// bowgpu_rolling_aggregate_sharded (multi.cpp): a rank whose last output slot holds a window that continues on the next non-empty rank
+// bowgpu_rolling_aggregate_sharded (sharded_call.cpp): a rank whose last output slot holds a window that continues on the next non-empty rank
 // does not own it.  That slot is the last one the finish wrote, so its byte is the last validity byte written.  One lane per output:
 // the slot's value -> 0, its validity bit and every bit above it in that byte -> 0, whether the bit was set -> report[i] (a
 // host-mapped block the host reads after the rank's one synchronisation, to take the slot out of null_count)

@@ -1,5 +1,5 @@
 // sort_shard_api.cpp — bowgpu_sort_by_col_sharded: Bow.SortByCol (reference bowsort.go:10-41) over a frame the caller holds as
-// row-range shards, one per device.  One library thread per rank (the workers of multi.cpp) runs: the local sort of the rank's key
+// row-range shards, one per device.  One library thread per rank (the workers of fanout.cpp) runs: the local sort of the rank's key
 // (argsort_device), the exact splitter search across ranks (split_bounds_kernel, bisected by the host), the rank's rows into sorted
 // order (the gather), the exchange (every destination pulls its pieces), their concatenation (the append kernel) and, where the
 // pulled runs interleave, their stable merge (sort_shard.hip) and one more gather.  No key is compared and no row is moved on the CPU.

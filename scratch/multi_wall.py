@@ -1,4 +1,4 @@
-"""ONE bowgpu_rolling_aggregate call over the device list (bowgpu_set_devices; bow_amd/csrc/multi.cpp) at 1e8 rows, interval 10, WindowStart +
+"""ONE bowgpu_rolling_aggregate call over the device list (bowgpu_set_devices; bow_amd/csrc/fan_call.cpp) at 1e8 rows, interval 10, WindowStart +
 ArithmeticMean: wall per call by residency and by number of ranks.  On a one-GPU box device 0 is listed N times - the ranks share ONE host
 link and ONE device, so this shows what the fan-out COSTS (threads, records, staging, the stitch into the caller's buffers), not what
 eight links buy; on a node with several GPUs the list names them (argv[1] = "all")."""

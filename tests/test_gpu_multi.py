@@ -1,4 +1,4 @@
-"""ONE Rolling.Aggregate call over N devices behind the C ABI (bowgpu_set_devices, bow_amd/csrc/multi.cpp; reference
+"""ONE Rolling.Aggregate call over N devices behind the C ABI (bowgpu_set_devices, bow_amd/csrc/fan_call.cpp; reference
 rolling/aggregation.go:123-145 - the user makes one call).  On a one-GPU box the same device is listed N times: N library threads, N
 contexts and streams, N row ranges, the records exchanged in host memory, every rank putting its own windows into the caller's buffers.
 Checked against the oracle AND against the one-device call of the same inputs (bit for bit wherever no window took an order-free form)."""

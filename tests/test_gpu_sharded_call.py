@@ -1,5 +1,5 @@
 """ONE Rolling.Aggregate over a frame the CALLER holds as row-range shards, one per device (bowgpu_rolling_aggregate_sharded,
-bow_amd/csrc/multi.cpp).  On a one-GPU box the same device id is listed k times: k library threads, k contexts and streams, the
+bow_amd/csrc/sharded_call.cpp).  On a one-GPU box the same device id is listed k times: k library threads, k contexts and streams, the
 records exchanged in host memory, every rank writing its own output buffers.  The owned slots, concatenated in rank order, are checked
 against the oracle, against the one-device call of the whole frame (bit for bit wherever no window took an order-free form) and against
 the shard protocol driven by hand over the same per-rank columns (sharded.run_local)."""

@@ -1,5 +1,5 @@
 """configs[4] at its size through ONE call: 8 ranks x 1e9 dense rows, each rank in HBM allocations of its own, aggregated by
-bowgpu_rolling_aggregate_sharded (bow_amd/csrc/multi.cpp) with every rank listed on device 0 - the same rows, the same protocol as
+bowgpu_rolling_aggregate_sharded (bow_amd/csrc/sharded_call.cpp) with every rank listed on device 0 - the same rows, the same protocol as
 tests/test_gpu_fullsize.py's config-4 test drives by hand, behind one C ABI call."""
 import ctypes as C
 

@@ -89,7 +89,7 @@ def test_every_profile_file_of_the_round_is_described_and_every_described_file_e
         assert not missing, "%s quotes evidence that is not under profiles/: %s" % (os.path.relpath(path, ROOT), missing)
 
 
-# which device sources a counter file of the round speaks about (host code - agg_pass.cpp, interpolate_api.cpp, multi.cpp - routes calls; it does not change
+# which device sources a counter file of the round speaks about (host code - agg_pass.cpp, interpolate_api.cpp, fan_call.cpp - routes calls; it does not change
 # what a kernel's counters say)
 COUNTER_FILES = {
     "r06_pmc_rolling_fused.txt": ["rolling_fused.hip", "rolling_simple.hip", "agg_device.h", "interp_device.h", "bitmap_device.h", "wave_ops.h"],
