@@ -30,6 +30,7 @@ FILTER_MAX_VALUES = 32
 FILTER_MAX_PREDS = 8
 CARRY_MAX_AGGS = 16
 JOIN_INNER, JOIN_OUTER = 0, 1
+JOIN_MAX_KEYS = 8
 MERGE_TILE_ROWS = 2048  # bow_amd/csrc/common.h kMergeTileRows: output rows per workgroup of merge_runs_kernel (bowgpu_sort_by_col_sharded)
 WHOLE_MAX_AGGS = 64      # bow_amd/csrc/ctx_blocks.h kWholeMaxAggs: reducers per bowgpu_aggregate_whole call
 WHOLE_STEP_ROWS = 512    # interp_fill.hip whole_value_kernel: rows a wavefront takes per step (four 128-row chunks, two rows a lane each)
@@ -167,7 +168,7 @@ SYMBOLS = [
     "bowgpu_filter_mask", "bowgpu_compact", "bowgpu_filter",
     "bowgpu_valid_mask", "bowgpu_drop_nils", "bowgpu_diff", "bowgpu_distinct",
     "bowgpu_append", "bowgpu_find_next",
-    "bowgpu_join_rows", "bowgpu_join",
+    "bowgpu_join_rows", "bowgpu_join", "bowgpu_join_keys_rows", "bowgpu_join_keys",
     "bowgpu_convert",
     "bowgpu_parquet_write_codec",
 ]
@@ -1219,6 +1220,59 @@ def join(left, left_key, right, right_key, kind, out_residency=HOST, outs=None, 
         oarr[i] = o.c()
     rows = C.c_int64(0)
     check(lib().bowgpu_join(_cols(left), len(left), left_key, _cols(right), len(right), right_key, kind, oarr, C.byref(rows)))
+    for i, o in enumerate(outs):
+        o.absorb(oarr[i])
+    return outs, rows.value
+
+
+def join_keys_rows(left_keys, right_keys, kind, out_residency=HOST, capacity=None, count_only=False):
+    """bowgpu_join_keys_rows -> (l_idx, r_idx, rows, pairs): join_rows on several key pairs - left_keys[k] joins right_keys[k], two lists
+    of Columns of one length (no key: the no-common-column call of join_rows; one: join_rows itself).  A row pair is common when EVERY
+    key pair is equal.  Indices, capacity and count_only as for join_rows"""
+    if len(left_keys) != len(right_keys):
+        raise ValueError("%d left keys, %d right keys" % (len(left_keys), len(right_keys)))
+    n_keys = len(left_keys)
+    lp, rp = _cols(left_keys), _cols(right_keys)
+    rows, pairs = C.c_int64(0), C.c_int64(0)
+    if count_only or capacity is None:
+        check(lib().bowgpu_join_keys_rows(lp, rp, n_keys, kind, None, None, C.c_int64(0), HOST, C.byref(rows), C.byref(pairs)))
+        if count_only:
+            return None, None, rows.value, pairs.value
+        capacity = rows.value
+    if out_residency == DEVICE:
+        bl, br = DeviceBuffer(max(capacity, 1) * 8), DeviceBuffer(max(capacity, 1) * 8)
+        pl, pr = C.c_void_p(bl.ptr), C.c_void_p(br.ptr)
+    else:
+        bl, br = np.full(max(capacity, 1), -7, dtype=np.int64), np.full(max(capacity, 1), -7, dtype=np.int64)
+        pl, pr = bl.ctypes.data_as(C.c_void_p), br.ctypes.data_as(C.c_void_p)
+    check(lib().bowgpu_join_keys_rows(lp, rp, n_keys, kind, pl, pr, C.c_int64(capacity), out_residency, C.byref(rows), C.byref(pairs)))
+    return bl, br, rows.value, pairs.value
+
+
+def join_keys(left, left_keys, right, right_keys, kind, out_residency=HOST, outs=None, capacity=None):
+    """Bow.InnerJoin / OuterJoin on several common columns (bowgpu_join_keys) -> (list[OutColumn], rows): left_keys / right_keys are two
+    lists of column indices of one length, key pair k joining left[left_keys[k]] with right[right_keys[k]]; every left column, then
+    every right column that is no right key.  outs / capacity as for join: by default the count call (join_keys_rows) sizes them"""
+    if len(left_keys) != len(right_keys):
+        raise ValueError("%d left keys, %d right keys" % (len(left_keys), len(right_keys)))
+    n_keys = len(left_keys)
+    n_outs = len(left) + len(right) - n_keys
+    if outs is None:
+        if capacity is None:
+            in_range = all(0 <= k < len(left) for k in left_keys) and all(0 <= k < len(right) for k in right_keys)
+            if n_keys == 0:
+                capacity = (left[0].length if left else 0) + (right[0].length if right else 0) if kind == JOIN_OUTER else 0
+            elif in_range:
+                capacity = join_keys_rows([left[k] for k in left_keys], [right[k] for k in right_keys], kind, count_only=True)[2]
+            else:
+                capacity = 0      # a key index outside its frame: bowgpu_join_keys says so
+        outs = [OutColumn(capacity, out_residency) for _ in range(max(n_outs, 0))]
+    oarr = (Out * max(len(outs), 1))()
+    for i, o in enumerate(outs):
+        oarr[i] = o.c()
+    rows = C.c_int64(0)
+    lk, rk = (C.c_int32 * max(n_keys, 1))(*left_keys), (C.c_int32 * max(n_keys, 1))(*right_keys)
+    check(lib().bowgpu_join_keys(_cols(left), len(left), lk, _cols(right), len(right), rk, n_keys, kind, oarr, C.byref(rows)))
     for i, o in enumerate(outs):
         o.absorb(oarr[i])
     return outs, rows.value

@@ -6,53 +6,44 @@
 #include <vector>
 
 #include "common.h"
+#include "join_host.h"
 
 using namespace bowgpu;
 
-namespace {
+namespace bowgpu {
 
-constexpr int64_t kJoinMaxRows = (int64_t)1 << 31;   // rows inside the kernels are 32 bits wide
-
-// everything a call keeps on the device between its count and its gather
-struct JoinWork {
-    DevCol rk;                 // the right key
-    StagedCols left;           // the left key, by left frame column (moved with its group)
-    const DevCol *lk = nullptr;
-    MaskWork vw, uw;           // the right key's validity; the right-only rows
-    SortWork sw;
-    DevBuf vrows, ckeys, index, simg, first, count, starts, sums, head, stats, ubits, urows, out_l, out_r;
-    int64_t n_left = 0, n_right = 0, rn = 0, rv = 0, rows_left = 0, tail = 0;
-    bool probed = false;       // false: no pair list (an empty side, no common column) - identity rows
-};
-
-int side_limit(int64_t n, const char *side) {
+int join_side_limit(int64_t n, const char *side) {
     if (n >= kJoinMaxRows)
         return fail(BOWGPU_ERR_UNSUPPORTED, "the %s frame has %lld rows: the device join serves fewer than 2^31 = 2147483648 rows", side, (long long)n);
     return 0;
 }
 
-int key_checks(const bowgpu_col *k, const char *side) {
+int join_key_checks(const bowgpu_col *k, const char *side) {
     if (!movable_type(k->type)) return fail(BOWGPU_ERR_UNSUPPORTED, "%s join column is of unsupported type (Int64 / Float64 only)", side);
     if (k->length < 0 || k->offset < 0) return fail(BOWGPU_ERR_ARG, "negative column length/offset");
     if (!residency_ok(k->residency)) return fail(BOWGPU_ERR_ARG, "unknown residency %d", k->residency);
-    return side_limit(k->length, side);
+    return join_side_limit(k->length, side);
 }
 
-int kind_check(int32_t kind) {
+int join_kind_check(int32_t kind) {
     if (kind != BOWGPU_JOIN_INNER && kind != BOWGPU_JOIN_OUTER) return fail(BOWGPU_ERR_ARG, "unknown join kind %d", kind);
     return 0;
 }
 
-int types_check(const bowgpu_col *l, const bowgpu_col *r) {   // bowjoin.go:135-139, up to the column name
+int join_types_check(const bowgpu_col *l, const bowgpu_col *r) {   // bowjoin.go:135-139, up to the column name
     if (l->type != r->type) return fail(BOWGPU_ERR_TYPE, "left and right bow on join columns are of incompatible types");
     return 0;
 }
 
-int rows_limit(int64_t rows) {
+int join_rows_limit(int64_t rows) {
     if (rows >= kJoinMaxRows)
         return fail(BOWGPU_ERR_UNSUPPORTED, "the join has %lld rows: the device join serves fewer than 2^31 = 2147483648 rows", (long long)rows);
     return 0;
 }
+
+}  // namespace bowgpu
+
+namespace {
 
 // the right side: [rows with a null key, row order | rows with a value, key order, ties in row order] and the sorted images
 int right_side(Ctx *c, const bowgpu_col *rkey, JoinWork *w) {
@@ -111,6 +102,10 @@ const uint64_t *sorted_images(const JoinWork &w) {
     return w.simg.p ? w.simg.as<const uint64_t>() : w.sw.keys[w.sw.cur].as<const uint64_t>();
 }
 
+}  // namespace
+
+namespace bowgpu {
+
 // the count: the right side, the probe, the right-only rows.  *rows / *pairs; nothing of the caller's is written.  Synchronises
 int join_count_device(Ctx *c, const bowgpu_col *lkey, int32_t lkey_col, const bowgpu_col *rkey, int32_t kind, JoinWork *w, int64_t *rows, int64_t *pairs) {
     const int64_t n_left = lkey->length, n_right = rkey->length;
@@ -155,7 +150,7 @@ int join_count_device(Ctx *c, const bowgpu_col *lkey, int32_t lkey_col, const bo
                                             "reference path)");
     *pairs = (int64_t)st.pairs;
     w->rows_left = outer ? (int64_t)(st.pairs + ((unsigned long long)n_left - st.matched_left)) : (int64_t)st.pairs;
-    BG_TRY(rows_limit(w->rows_left));
+    BG_TRY(join_rows_limit(w->rows_left));
     w->tail = 0;
     if (outer) {   // one bit per right ROW that occurs in no pair, then the mask pass that counts them per tile
         BG_TRY(w->ubits.alloc((size_t)((n_right + 31) >> 5) * 4 + 8));
@@ -171,7 +166,7 @@ int join_count_device(Ctx *c, const bowgpu_col *lkey, int32_t lkey_col, const bo
         w->tail = w->uw.selected;
     }
     *rows = w->rows_left + w->tail;
-    return rows_limit(*rows);
+    return join_rows_limit(*rows);
 }
 
 // the index pairs of the `rows` output rows, as 32-bit rows in the workspace (no synchronise)
@@ -206,20 +201,20 @@ int join_expand_device(Ctx *c, int32_t kind, JoinWork *w, int64_t rows) {
     return launch_join_expand(c, e);
 }
 
-}  // namespace
+}  // namespace bowgpu
 
 extern "C" {
 
 int bowgpu_join_rows(const bowgpu_col *left_key, const bowgpu_col *right_key, int32_t kind, int64_t *l_idx, int64_t *r_idx, int64_t idx_capacity,
                      int32_t idx_residency, int64_t *rows, int64_t *pairs) {
     if (!rows || !pairs) return fail(BOWGPU_ERR_ARG, "null argument");
-    BG_TRY(kind_check(kind));
+    BG_TRY(join_kind_check(kind));
     if ((left_key == nullptr) != (right_key == nullptr))   // the other frame's length cannot be known: no partial answer
         return fail(BOWGPU_ERR_ARG, "one join column is NULL: give both, or neither for frames without a common column");
     if (left_key) {
-        BG_TRY(key_checks(left_key, "left"));
-        BG_TRY(key_checks(right_key, "right"));
-        BG_TRY(types_check(left_key, right_key));
+        BG_TRY(join_key_checks(left_key, "left"));
+        BG_TRY(join_key_checks(right_key, "right"));
+        BG_TRY(join_types_check(left_key, right_key));
     }
     const bool fill = l_idx != nullptr || r_idx != nullptr;
     if (fill) {
@@ -236,7 +231,7 @@ int bowgpu_join_rows(const bowgpu_col *left_key, const bowgpu_col *right_key, in
     Ctx *c = nullptr;
     if (!probe) {   // no pair list: known without the device
         const int64_t total = outer ? n_left + n_right : 0;
-        BG_TRY(rows_limit(total));
+        BG_TRY(join_rows_limit(total));
         *rows = total;
         if (!fill || total == 0) return 0;
         if (idx_capacity < total) return fail(BOWGPU_ERR_ARG, "index buffers have %lld slots, %lld needed", (long long)idx_capacity, (long long)total);
@@ -287,7 +282,7 @@ int bowgpu_join(const bowgpu_col *left_cols, int32_t n_left_cols, int32_t left_k
     if (!rows) return fail(BOWGPU_ERR_ARG, "null argument");
     if (n_left_cols < 0 || n_right_cols < 0) return fail(BOWGPU_ERR_ARG, "negative column count");
     if ((n_left_cols > 0 && !left_cols) || (n_right_cols > 0 && !right_cols)) return fail(BOWGPU_ERR_ARG, "null argument");
-    BG_TRY(kind_check(kind));
+    BG_TRY(join_kind_check(kind));
     const int64_t n_left = n_left_cols > 0 ? left_cols[0].length : 0, n_right = n_right_cols > 0 ? right_cols[0].length : 0;
     BG_TRY(frame_cols_checks(left_cols, n_left_cols, n_left, true));
     BG_TRY(frame_cols_checks(right_cols, n_right_cols, n_right, true));
@@ -295,10 +290,10 @@ int bowgpu_join(const bowgpu_col *left_cols, int32_t n_left_cols, int32_t left_k
     if (keyed) {
         if (left_key < 0 || left_key > n_left_cols - 1) return fail(BOWGPU_ERR_BAD_COL, "no column '%d' in the left frame", left_key);
         if (right_key < 0 || right_key > n_right_cols - 1) return fail(BOWGPU_ERR_BAD_COL, "no column '%d' in the right frame", right_key);
-        BG_TRY(types_check(&left_cols[left_key], &right_cols[right_key]));
+        BG_TRY(join_types_check(&left_cols[left_key], &right_cols[right_key]));
     }
-    BG_TRY(side_limit(n_left, "left"));
-    BG_TRY(side_limit(n_right, "right"));
+    BG_TRY(join_side_limit(n_left, "left"));
+    BG_TRY(join_side_limit(n_right, "right"));
     // the right columns without the key, as the frame the outputs behind the left columns come from
     std::vector<bowgpu_col> rcols;
     for (int i = 0; i < n_right_cols; i++)
@@ -313,7 +308,7 @@ int bowgpu_join(const bowgpu_col *left_cols, int32_t n_left_cols, int32_t left_k
     int64_t total = 0, npairs = 0;
     if (!probe) {   // no pair list: the row count is known without the device
         total = outer ? n_left + n_right : 0;
-        BG_TRY(rows_limit(total));
+        BG_TRY(join_rows_limit(total));
     } else {
         BG_TRY(ctx_get(&c));
         BG_HIP(hipEventRecord(c->ev0, c->stream));

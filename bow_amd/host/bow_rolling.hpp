@@ -22,6 +22,7 @@
 
 #include <errno.h>
 
+#include <algorithm>
 #include <cctype>
 #include <cmath>
 #include <cstdlib>
@@ -297,13 +298,20 @@ class Bow : public std::enable_shared_from_this<Bow> {
     // InnerJoin: bowjoin.go:12-62 ; OuterJoin: bowjoin.go:66-125 (device).  The common columns are found by name as getCommonCols does
     // (bowjoin.go:128-155); none: no pair, an OuterJoin is all left rows then all right rows.  Where the reference panics - a name twice in
     // the right bow, common columns of different types - this returns an Error with the reference's text.  More than one common column
-    // is an Error too: the device join takes one key per side.  (This mirror models no Arrow metadata.)
+    // is an Error too: these two take one key per side (InnerJoinAll / OuterJoinAll below join on all).  (This mirror models no Arrow
+    // metadata.)
     std::pair<BowPtr, Error> InnerJoin(const BowPtr &other) const { return join(other, BOWGPU_JOIN_INNER); }
     std::pair<BowPtr, Error> OuterJoin(const BowPtr &other) const { return join(other, BOWGPU_JOIN_OUTER); }
+    // InnerJoinAll / OuterJoinAll: the reference's join as it stands - on EVERY common column (getCommonCols collects them all,
+    // getCommonRows bowjoin.go:161-186 calls a row pair common when it agrees on all of them; each key column of a right-only row takes
+    // its own right partner's value, bowjoin.go:383-400), through bowgpu_join_keys.  The same Errors; with no or one common column
+    // exactly what InnerJoin / OuterJoin return.
+    std::pair<BowPtr, Error> InnerJoinAll(const BowPtr &other) const { return join(other, BOWGPU_JOIN_INNER, true); }
+    std::pair<BowPtr, Error> OuterJoinAll(const BowPtr &other) const { return join(other, BOWGPU_JOIN_OUTER, true); }
 
 private:
     std::pair<BowPtr, Error> fill(int method, const std::vector<int> &colIndices) const;
-    std::pair<BowPtr, Error> join(const BowPtr &other, int32_t kind) const;
+    std::pair<BowPtr, Error> join(const BowPtr &other, int32_t kind, bool all_common = false) const;
 };
 
 // NewBow: bow.go:109-116 (all series must have the same length)
@@ -683,12 +691,13 @@ inline std::pair<BowPtr, Error> AppendBows(const std::vector<BowPtr> &bows) {
     return {out, Error()};
 }
 
-inline std::pair<BowPtr, Error> Bow::join(const BowPtr &other, int32_t kind) const {
+inline std::pair<BowPtr, Error> Bow::join(const BowPtr &other, int32_t kind, bool all_common) const {
     if (!other) return {nullptr, Errorf("non bow object passed as argument")};
     const Bow &right = *other;
     if (kind == BOWGPU_JOIN_INNER && (NumCols() == 0 || right.NumCols() == 0))   // bowjoin.go:19-29
         return {NumCols() == 0 && right.NumCols() > 0 ? right.NewEmptySlice() : NewEmptySlice(), Error()};
     int lk = -1, rk = -1, common = 0;
+    std::vector<int32_t> lks, rks;   // every common column, in the left bow's order
     for (int i = 0; i < NumCols(); i++) {   // getCommonCols: bowjoin.go:128-155
         int found = -1, n = 0;
         for (int j = 0; j < right.NumCols(); j++)
@@ -698,11 +707,40 @@ inline std::pair<BowPtr, Error> Bow::join(const BowPtr &other, int32_t kind) con
         if (right.cols[found].typ != cols[i].typ)
             return {nullptr, Errorf("left and right bow on join columns are of incompatible types: " + cols[i].Name)};
         if (common++ == 0) { lk = i; rk = found; }
+        lks.push_back(i);
+        rks.push_back(found);
     }
-    if (common > 1) return {nullptr, Errorf("bow.Join: " + std::to_string(common) + " common columns, the device join takes one")};
+    if (common > 1 && !all_common)
+        return {nullptr, Errorf("bow.Join: " + std::to_string(common) + " common columns, the device join takes one")};
     std::vector<bowgpu_col> lc, rc;
     for (int i = 0; i < NumCols(); i++) lc.push_back(ArrowCol(i));
     for (int i = 0; i < right.NumCols(); i++) rc.push_back(right.ArrowCol(i));
+    if (common > 1) {   // several keys: the count call sizes the outputs, as below
+        if (common > BOWGPU_JOIN_MAX_KEYS)
+            return {nullptr, Errorf("bow.Join: " + std::to_string(common) + " common columns, the device join takes at most " +
+                                    std::to_string(BOWGPU_JOIN_MAX_KEYS))};
+        std::vector<bowgpu_col> lkc, rkc;
+        for (int k = 0; k < common; k++) {
+            lkc.push_back(lc[(size_t)lks[(size_t)k]]);
+            rkc.push_back(rc[(size_t)rks[(size_t)k]]);
+        }
+        int64_t rows = 0, pairs = 0;
+        if (int rcode = bowgpu_join_keys_rows(lkc.data(), rkc.data(), common, kind, nullptr, nullptr, 0, BOWGPU_HOST, &rows, &pairs))
+            return {nullptr, detail::AbiError(rcode)};
+        std::vector<std::string> names;
+        for (int i = 0; i < NumCols(); i++) names.push_back(cols[i].Name);
+        for (int i = 0; i < right.NumCols(); i++)
+            if (std::find(rks.begin(), rks.end(), i) == rks.end()) names.push_back(right.cols[i].Name);
+        std::vector<detail::OutStore> st(names.size());
+        std::vector<bowgpu_out> o(names.size() + 1);
+        for (size_t i = 0; i < names.size(); i++) o[i] = st[i].Make(rows);
+        int64_t got = 0;
+        const int rcode = bowgpu_join_keys(lc.data(), NumCols(), lks.data(), rc.data(), right.NumCols(), rks.data(), common, kind, o.data(), &got);
+        if (rcode) return {nullptr, detail::AbiError(rcode)};
+        auto out = std::make_shared<Bow>();
+        for (size_t i = 0; i < names.size(); i++) out->cols.push_back(st[i].ToSeries(names[i], o[i]));
+        return {out, Error()};
+    }
     int64_t rows = 0, pairs = 0;   // no input size bounds a join's rows: the count call sizes the outputs
     if (common == 0) rows = kind == BOWGPU_JOIN_OUTER ? (int64_t)NumRows() + right.NumRows() : 0;
     else if (int rcode = bowgpu_join_rows(&lc[(size_t)lk], &rc[(size_t)rk], kind, nullptr, nullptr, 0, BOWGPU_HOST, &rows, &pairs))

@@ -47,6 +47,8 @@ extern "C" {
  * added or changed. */
 /* (still 14): bowgpu_parquet_write_codec (the writer with a compression codec, SNAPPY compressed on the device) added under the same
  * version: a new entry point beside bowgpu_parquet_write, whose options struct and behaviour stay as they are. */
+/* (still 14): bowgpu_join_keys_rows / bowgpu_join_keys and BOWGPU_JOIN_MAX_KEYS (the join on several common columns) added under the same
+ * version: two new entry points beside bowgpu_join_rows / bowgpu_join, no struct added or changed. */
 #define BOWGPU_ABI_VERSION 14
 
 /* bow.Type (reference bowtypes.go:17-32) */
@@ -851,7 +853,7 @@ int bowgpu_find_next(const bowgpu_col *col, int64_t row_start, const void *value
  * row's value; on a right-only row it takes the RIGHT key's value and validity (bowjoin.go:397: a right-only row with a null key keeps a
  * null key).  NO COMMON COLUMN (left_key == right_key == -1; bowjoin_test.go:363-396 and :581-604): the pair list is empty, InnerJoin has
  * zero rows, OuterJoin is all left rows then all right rows, and the result has all left columns then ALL right columns.  MORE THAN ONE
- * COMMON COLUMN is not expressible - one key per side - and not offered: the caller keeps the reference path.
+ * COMMON COLUMN is not expressible here - one key per side: it is bowgpu_join_keys_rows / bowgpu_join_keys below.
  *   OUTPUTS are what Buffer.SetOrDropStrict leaves and what bowgpu_take leaves: values moved as raw 64-bit payloads (a NaN's bits in a
  * VALUE column survive), validity bit and null_count set, length / type set, null slots 0, the padding bits of the last validity byte
  * clear, nothing written past the slots produced.  CAPACITY is Filter's rule: bowgpu_out.length on entry; too small is BOWGPU_ERR_ARG
@@ -889,6 +891,50 @@ int bowgpu_join_rows(const bowgpu_col *left_key, const bowgpu_col *right_key, in
  * stay in the workspace as 32-bit rows. */
 int bowgpu_join(const bowgpu_col *left_cols, int32_t n_left, int32_t left_key, const bowgpu_col *right_cols, int32_t n_right,
                 int32_t right_key, int32_t kind, bowgpu_out *outs, int64_t *rows);
+
+/* The join on SEVERAL common columns, as the reference joins on EVERY column name two bows share (getCommonCols bowjoin.go:128-155;
+ * getCommonRows :161-186 calls a row pair common when it agrees on all of them).  Key pair k joins left_keys[k] with right_keys[k]:
+ * column indices into the two frames for bowgpu_join_keys, the columns themselves for bowgpu_join_keys_rows.  Everything above holds
+ * with "the key" read as "the tuple of keys":
+ *   THE PAIR LIST is every (l, r) for which EVERY key pair is equal, ordered by l, then by r.  Equality per column is the one-key join's:
+ * Int64 exactly, Float64 by IEEE == (-0.0 equals +0.0), a null equals a null and never a value, per column - rows that are nil in every
+ * common column on both sides pair up ("outer advanced", bowjoin_test.go:247-298).  A Float64 key with a NaN among its valid rows, on
+ * either side, is BOWGPU_ERR_UNSUPPORTED; the message names the side and the key pair.  A NaN payload under a null is not a key.
+ *   ROW ORDER AND COUNT are bowgpu_join's.  INNER: one output row per pair, in pair order.  OUTER: every left row in left order - a left
+ * row with m matches becomes m rows in ascending right row - then the right rows that occur in no pair, in right row order.
+ *   COLUMNS of the result: every left column in order, then every right column that is NOT one of the right keys, in order:
+ * n_left + n_right - n_keys outputs.  EACH key column holds the left row's value; on a right-only row it takes the value and validity of
+ * ITS OWN right key column (bowjoin.go:383-400 runs per common column).  Key columns may sit at different positions in the two frames.
+ *   n_keys == 0 is the no-common-column join: exactly bowgpu_join with -1 / -1 (bowgpu_join_rows with NULL keys).  n_keys == 1 is
+ * bowgpu_join / bowgpu_join_rows itself: the same code, bytes, *rows / *pairs and workspace.
+ *   ERRORS, all raised before the device is touched when the arguments are host-resident: n_keys < 0 is BOWGPU_ERR_ARG; n_keys >
+ * BOWGPU_JOIN_MAX_KEYS is BOWGPU_ERR_UNSUPPORTED naming the limit; a key index outside its frame BOWGPU_ERR_BAD_COL; a column listed
+ * twice among one side's keys BOWGPU_ERR_ARG; key pair types that differ BOWGPU_ERR_TYPE with the one-key join's text; Boolean / String
+ * anywhere BOWGPU_ERR_UNSUPPORTED; unequal lengths within a frame (for bowgpu_join_keys_rows: among one side's keys) BOWGPU_ERR_ARG.
+ *   ROW LIMITS: each side and the result hold fewer than 2^31 rows, as for the one-key join.  For n_keys >= 2 also L + R < 2^31: the
+ * surrogate pass sorts both sides as one column and the argsort is 31-bit.  More is BOWGPU_ERR_UNSUPPORTED naming the limit.
+ *   CAPACITY, NO DEVICE and FAILURE are the one-key join's rules unchanged: bowgpu_out.length on entry, too small names the size needed
+ * and writes nothing; the NULL-buffer call of bowgpu_join_keys_rows is the count; no device is needed when both frames are empty, for an
+ * INNER with an empty side and for the COUNT of an OUTER with an empty side; outputs are untouched on every failure; the same call gives
+ * the same bytes.  bowgpu_set_devices does not apply.
+ *   THE METHOD for n_keys >= 2 (bow_amd/csrc/join_keys.hip): the key tuples of both sides are reduced to ONE Int64 surrogate column per
+ * side - equal exactly when the tuples are, without nulls or NaN - and the one-key join above runs on those as it stands.  Nothing is
+ * hashed; every step is an integer count.  Per key pair the left then the right key are written into one column of L + R slots (raw bits,
+ * 0 under a null), bowgpu_argsort's sort runs over it (digit skipping and the "already in order" answer apply), the heads of the groups
+ * of equal images are marked over the sorted order and scanned, and every original row receives 1 + its dense rank, a row with a null key
+ * rank 0.  Two keys: the surrogate is rank_0 << 32 | rank_1.  More: the packed pair is ranked again the same way and packed with the next
+ * rank - n_keys + (n_keys - 2) argsorts of L + R rows in front of the one-key join's own sort of R rows.
+ *   HBM WORKSPACE for n_keys >= 2, on top of the one-key join's own, per row of L + R: 8 bytes for the concatenated column, the argsort's
+ * 24 (none when the column is in order), 4 for the marks, two live rank arrays of 4 each, 8 for the packed column - the buffers of one key
+ * pair go back before the next one's are taken.  + the staged copies of BOWGPU_HOST key columns (values and bitmap) of both sides, held for
+ * the whole call: bowgpu_join_keys_rows lets them go before the join proper, bowgpu_join_keys keeps them for the gather. */
+#define BOWGPU_JOIN_MAX_KEYS 8
+
+int bowgpu_join_keys_rows(const bowgpu_col *left_keys, const bowgpu_col *right_keys, int32_t n_keys, int32_t kind, int64_t *l_idx,
+                          int64_t *r_idx, int64_t idx_capacity, int32_t idx_residency, int64_t *rows, int64_t *pairs);
+
+int bowgpu_join_keys(const bowgpu_col *left_cols, int32_t n_left, const int32_t *left_keys, const bowgpu_col *right_cols, int32_t n_right,
+                     const int32_t *right_keys, int32_t n_keys, int32_t kind, bowgpu_out *outs, int64_t *rows);
 
 /* ---- Parquet column chunk -> device column --------------------------- */
 
