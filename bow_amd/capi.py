@@ -31,6 +31,8 @@ FILTER_MAX_PREDS = 8
 CARRY_MAX_AGGS = 16
 JOIN_INNER, JOIN_OUTER = 0, 1
 JOIN_MAX_KEYS = 8
+EQUAL_GO, EQUAL_BITS = 0, 1   # BOWGPU_EQUAL_*: reflect.DeepEqual on the boxed values / the 64-bit patterns
+VALID_ROW_MAX_COLS = 8
 MERGE_TILE_ROWS = 2048  # bow_amd/csrc/common.h kMergeTileRows: output rows per workgroup of merge_runs_kernel (bowgpu_sort_by_col_sharded)
 WHOLE_MAX_AGGS = 64      # bow_amd/csrc/ctx_blocks.h kWholeMaxAggs: reducers per bowgpu_aggregate_whole call
 WHOLE_STEP_ROWS = 512    # interp_fill.hip whole_value_kernel: rows a wavefront takes per step (four 128-row chunks, two rows a lane each)
@@ -136,6 +138,11 @@ class SortShardInfo(C.Structure):
                 ("local_sort_ms", C.c_double), ("splitter_ms", C.c_double), ("merge_ms", C.c_double)]
 
 
+class EqualInfo(C.Structure):
+    """bowgpu_equal_info"""
+    _fields_ = [("equal", C.c_int32), ("first_col", C.c_int32), ("first_row", C.c_int64)]
+
+
 class ParquetWriteOptions(C.Structure):
     """bowgpu_parquet_write_options"""
     _fields_ = [("row_group_rows", C.c_int64), ("page_rows", C.c_int32), ("statistics", C.c_int32), ("encodings", C.POINTER(C.c_int32)),
@@ -171,6 +178,7 @@ SYMBOLS = [
     "bowgpu_join_rows", "bowgpu_join", "bowgpu_join_keys_rows", "bowgpu_join_keys",
     "bowgpu_convert",
     "bowgpu_parquet_write_codec",
+    "bowgpu_equal", "bowgpu_valid_row", "bowgpu_is_col_empty",
 ]
 
 _lib = None
@@ -1172,6 +1180,30 @@ def find_next(col, value, row_start=0):
         ptr = v.ctypes.data_as(C.c_void_p)
     check(lib().bowgpu_find_next(C.byref(c), C.c_int64(row_start), ptr, C.byref(row)))
     return row.value
+
+
+def equal(left, right, mode=EQUAL_GO):
+    """the per-row half of Bow.Equal (bowgpu_equal) -> (equal, first_row, first_col); left / right: lists of Columns (Int64, Float64,
+    Boolean), column i against column i.  mode: EQUAL_GO (a NaN differs from itself, -0.0 equals +0.0) or EQUAL_BITS"""
+    assert len(left) == len(right)
+    info = EqualInfo()
+    check(lib().bowgpu_equal(_cols(left), _cols(right), len(left), mode, C.byref(info)))
+    return bool(info.equal), info.first_row, info.first_col
+
+
+def valid_row(cols, row_start, direction):
+    """bowgpu_valid_row -> the nearest row <= row_start (direction -1) or >= row_start (+1) at which every column is valid, -1: none"""
+    row = C.c_int64(0)
+    check(lib().bowgpu_valid_row(_cols(cols), len(cols), C.c_int64(row_start), direction, C.byref(row)))
+    return row.value
+
+
+def is_col_empty(col):
+    """IsColEmpty (bowgpu_is_col_empty): NullN() == Len()"""
+    c = col.c()
+    empty = C.c_int32(0)
+    check(lib().bowgpu_is_col_empty(C.byref(c), C.byref(empty)))
+    return bool(empty.value)
 
 
 def join_rows(left_key, right_key, kind, out_residency=HOST, capacity=None, count_only=False):

@@ -922,6 +922,37 @@ struct FindArgs {
 };
 int launch_find(Ctx *c, const FindArgs &a);   // presets *result, searches, hands the word to host_result
 
+// equal.hip: the per-row half of Bow.Equal and the Prev / Next valid-row getters (host side: equal_api.cpp)
+struct BitsAt {                          // n bits read where they lie, as stage_bits gives them
+    const uint32_t *words;               // nullptr: nothing to read
+    int64_t bit0, nwords;
+};
+enum : int32_t { kEqualBits = 0, kEqualIeee = 1, kEqualBool = 2 };
+struct EqualCol {                        // one column of both frames: [0] left, [1] right
+    const uint64_t *values[2];           // 8-byte values (kEqualBits / kEqualIeee)
+    BitsAt truth[2];                     // kEqualBool: the value bits
+    BitsAt valid[2];                     // words == nullptr: no nulls to look at
+    int32_t kind, col;                   // how valid rows compare; the column's index in the frame
+};
+constexpr uint64_t kEqualNone = ~0ull;
+struct EqualArgs {
+    int32_t ncols, _pad;
+    int64_t n;
+    unsigned long long *result;          // device word, kEqualNone on entry of the CALL: lowered to (row << 32) | column of the first difference
+    EqualCol col[kMoveCols];
+};
+int launch_equal_preset(Ctx *c, unsigned long long *result);
+int launch_equal(Ctx *c, const EqualArgs &a);   // one group of columns; the word is kept
+int launch_equal_result(Ctx *c, const unsigned long long *result, unsigned long long *host_result);
+struct ValidRowArgs {
+    int32_t ncols, direction;            // +1: the first row >= row_start, -1: the last row <= row_start, where every bitmap has its bit set
+    int64_t n, row_start;                // 0 <= row_start < n
+    BitsAt valid[BOWGPU_VALID_ROW_MAX_COLS];
+    uint32_t *result;                    // device word, kFindNone (-1 as a signed row) on entry
+    uint32_t *host_result;               // registered host memory
+};
+int launch_valid_row(Ctx *c, const ValidRowArgs &a);   // presets *result, searches, hands the word to host_result
+
 // join.hip: Bow.InnerJoin / OuterJoin - the left-ordered lookup join on one key (host side: join_api.cpp)
 struct JoinStats {                       // one device block of a call, zeroed by the host
     unsigned long long pairs;            // length of the reference's commonRows

@@ -43,6 +43,7 @@ constexpr Region kScrProbe = {3072, 16};                           // stream pro
 constexpr Region kScrConvertCounts = {0, 8 * (size_t)kMoveCols * kConvertShards};   // Convert: valid rows per column and shard; one group
 constexpr Region kScrHist = {0, 8 * 256 * 4};                      // Sort: [8][256] digit counts; inside argsort_device (read back before it returns)
 constexpr Region kScrFlags = {8192, 16};                           // four words.  Sort: [0] not ascending, [1] NaN seen, [2] bad index (take); Filter: filter_stats_kernel's; Find: the row
+constexpr Region kScrEqualWord = {8192, 8};                         // Equal: (row << 32) | column of the first difference, kept across the launch groups of a call (lies in kScrFlags: one call at a time)
 constexpr Region kScrMoveCounts = {8208, 8 * (size_t)kMoveCols};   // a move group: the outputs' nulls (gather) / valid rows (scatter, append, diff); one group
 constexpr Region kScrImages = {0, 8 * (2 * (size_t)kShardMaxWorld + 2)};   // sharded Sort read_images: one image per position; inside the helper
 constexpr Region kScrSplitBounds = {0, 4 * 2 * (size_t)kShardMaxWorld};    // sharded Sort splitters: two row counts per candidate; one round
@@ -70,9 +71,10 @@ static_assert(all_apart(kScrConvertCounts, kScrNullCount), "Convert");
 // The Sort histogram is NOT in this set: argsort_device has read it back before the first column of a group is staged, and the null
 // count lies inside it
 static_assert(all_apart(kScrFlags, kScrMoveCounts, kScrNullCount), "move group");
+static_assert(kScrEqualWord.offset % 8 == 0 && all_apart(kScrEqualWord, kScrNullCount), "Equal: a 64-bit atomic word");
 static_assert(kScrFlags.offset == kScrHist.end() && kScrMoveCounts.offset == kScrFlags.end(), "one memset / one copy over histogram + flags, over flags + counts");
 static_assert(inside(kScrFixedBytes, kScrStatus, kScrAggCounts, kScrInterpCounts, kScrOneCount, kScrOrderFlags, kScrFillFar, kScrFillCount, kScrNullCount,
-                     kScrProbe, kScrConvertCounts, kScrHist, kScrFlags, kScrMoveCounts, kScrImages, kScrSplitBounds, kScrDiag), "inside the fixed part");
+                     kScrProbe, kScrConvertCounts, kScrHist, kScrFlags, kScrEqualWord, kScrMoveCounts, kScrImages, kScrSplitBounds, kScrDiag), "inside the fixed part");
 
 // ================================================================ the registered block (host)
 constexpr size_t kRegBytes = 16384;                                // allocated once per thread, never moved
@@ -82,6 +84,7 @@ constexpr Region kRegStatus = {0, 4 * (size_t)kStatusWords};       // tile pass:
 constexpr Region kRegAggCounts = {1024, 8 * (size_t)kMaxAggs};     // tile pass: valid bits per output bitmap, by the same store / copy
 constexpr Region kRegFilterStats = {0, 12};                        // Filter: selected rows, first, last - filter_stats_kernel's stores; mask pass
 constexpr Region kRegFindRow = {32, 4};                            // Find: the row, find_result_kernel's store; one call
+constexpr Region kRegEqualWord = {40, 8};                          // Equal: the word, equal_result_kernel's store; one call
 constexpr Region kRegTwoTs = {2048, 16};                           // plan_make - a HELPER of every windowed call - and whole-frame Aggregate's second implementation: first / last timestamp; inside the helper
 constexpr Region kRegInterpCount = {3072, 24};                     // Interpolate count pass: total, two packed status pairs; inside interp_prepare
 constexpr Region kRegInterpCounts = {1024, 8 * (size_t)kMaxCols * kInterpEdgeBlocks};   // Interpolate fill in place: partial valid counts, interp_edge_fix_kernel's stores; one batch
@@ -101,7 +104,7 @@ static_assert(all_apart(kRegStatus, kRegInterpCounts), "Interpolate fill");
 static_assert(kRegInterpCounts.offset == kScrInterpCounts.offset, "status words and counts arrive in one copy where they are not stored in place");
 // ... whole-frame Aggregate
 static_assert(all_apart(kRegTwoTs, kRegWholeValues, kRegWholeValid), "whole-frame Aggregate");
-static_assert(inside(kRegBytes, kRegStatus, kRegAggCounts, kRegFilterStats, kRegFindRow, kRegTwoTs, kRegInterpCount, kRegInterpCounts, kRegSeeds,
+static_assert(inside(kRegBytes, kRegStatus, kRegAggCounts, kRegFilterStats, kRegFindRow, kRegEqualWord, kRegTwoTs, kRegInterpCount, kRegInterpCounts, kRegSeeds,
                      kRegWholeValues, kRegWholeValid, kRegTailReport), "inside the block");
 
 // the tile pass' read-back: status words and counts in ONE copy, or stored by finish_bitmaps_kernel, which is handed kRegStatus alone

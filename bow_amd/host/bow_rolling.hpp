@@ -31,6 +31,7 @@
 #include <optional>
 #include <sstream>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <variant>
 #include <vector>
@@ -295,6 +296,31 @@ class Bow : public std::enable_shared_from_this<Bow> {
     int Find(int colIndex, const Value &value) const { return FindNext(colIndex, 0, value); }
     int FindNext(int colIndex, int rowIndex, const Value &value) const;
     bool Contains(int colIndex, const Value &value) const { return Find(colIndex, value) != -1; }
+    // Equal on the device: the number of columns, names and types are compared here (this mirror models no Arrow metadata), the rows by
+    // bowgpu_equal.  mode BOWGPU_EQUAL_GO is what Equal above computes; BOWGPU_EQUAL_BITS compares the 64-bit patterns.
+    std::pair<bool, Error> EqualOnDevice(const Bow &o, int mode = BOWGPU_EQUAL_GO) const;
+    // IsColEmpty: bowassertion.go:84-86 ; GetPrevRowIndex / GetNextRowIndex / GetPrevValue(s) / GetNextValue(s): bowgetters.go:65-151
+    // (device: bowgpu_is_col_empty, bowgpu_valid_row; the value(s) at the row found come from GetValue).  A failed device call (e.g. no
+    // device) finds nothing: the reference's signatures have no error to carry it.
+    bool IsColEmpty(int colIndex) const;
+    int GetPrevRowIndex(int colIndex, int rowIndex) const { return validRow({colIndex}, rowIndex, -1); }
+    int GetNextRowIndex(int colIndex, int rowIndex) const { return validRow({colIndex}, rowIndex, +1); }
+    std::pair<Value, int> GetPrevValue(int colIndex, int rowIndex) const {
+        const int r = validRow({colIndex}, rowIndex, -1);
+        return {r < 0 ? Nil() : GetValue(colIndex, r), r};
+    }
+    std::pair<Value, int> GetNextValue(int colIndex, int rowIndex) const {
+        const int r = validRow({colIndex}, rowIndex, +1);
+        return {r < 0 ? Nil() : GetValue(colIndex, r), r};
+    }
+    std::tuple<Value, Value, int> GetPrevValues(int colIndex1, int colIndex2, int rowIndex) const {
+        const int r = validRow({colIndex1, colIndex2}, rowIndex, -1);
+        return {r < 0 ? Nil() : GetValue(colIndex1, r), r < 0 ? Nil() : GetValue(colIndex2, r), r};
+    }
+    std::tuple<Value, Value, int> GetNextValues(int colIndex1, int colIndex2, int rowIndex) const {
+        const int r = validRow({colIndex1, colIndex2}, rowIndex, +1);
+        return {r < 0 ? Nil() : GetValue(colIndex1, r), r < 0 ? Nil() : GetValue(colIndex2, r), r};
+    }
     // InnerJoin: bowjoin.go:12-62 ; OuterJoin: bowjoin.go:66-125 (device).  The common columns are found by name as getCommonCols does
     // (bowjoin.go:128-155); none: no pair, an OuterJoin is all left rows then all right rows.  Where the reference panics - a name twice in
     // the right bow, common columns of different types - this returns an Error with the reference's text.  More than one common column
@@ -312,6 +338,7 @@ class Bow : public std::enable_shared_from_this<Bow> {
 private:
     std::pair<BowPtr, Error> fill(int method, const std::vector<int> &colIndices) const;
     std::pair<BowPtr, Error> join(const BowPtr &other, int32_t kind, bool all_common = false) const;
+    int validRow(const std::vector<int> &colIndices, int rowIndex, int direction) const;
 };
 
 // NewBow: bow.go:109-116 (all series must have the same length)
@@ -650,6 +677,38 @@ inline int Bow::FindNext(int colIndex, int rowIndex, const Value &value) const {
     const bowgpu_col c = ArrowCol(colIndex);
     int64_t row = -1;
     if (bowgpu_find_next(&c, rowIndex, value ? &bits : nullptr, &row)) return -1;
+    return (int)row;
+}
+
+inline std::pair<bool, Error> Bow::EqualOnDevice(const Bow &o, int mode) const {
+    if (NumCols() != o.NumCols()) return {false, Error()};
+    std::vector<bowgpu_col> l, r;
+    for (int i = 0; i < NumCols(); i++) {
+        if (cols[i].Name != o.cols[i].Name || cols[i].typ != o.cols[i].typ) return {false, Error()};
+        l.push_back(ArrowCol(i));
+        r.push_back(o.ArrowCol(i));
+    }
+    bowgpu_equal_info info;
+    const int rc = bowgpu_equal(l.data(), r.data(), NumCols(), mode, &info);
+    if (rc) return {false, detail::AbiError(rc)};
+    return {info.equal != 0, Error()};
+}
+
+inline bool Bow::IsColEmpty(int colIndex) const {
+    const bowgpu_col c = ArrowCol(colIndex);
+    int32_t empty = 0;
+    if (bowgpu_is_col_empty(&c, &empty)) return false;
+    return empty != 0;
+}
+
+inline int Bow::validRow(const std::vector<int> &colIndices, int rowIndex, int direction) const {
+    std::vector<bowgpu_col> c;
+    for (int ci : colIndices) {
+        if (ci < 0 || ci > NumCols() - 1) return -1;
+        c.push_back(ArrowCol(ci));
+    }
+    int64_t row = -1;
+    if (bowgpu_valid_row(c.data(), (int32_t)c.size(), rowIndex, direction, &row)) return -1;
     return (int)row;
 }
 

@@ -49,6 +49,8 @@ extern "C" {
  * version: a new entry point beside bowgpu_parquet_write, whose options struct and behaviour stay as they are. */
 /* (still 14): bowgpu_join_keys_rows / bowgpu_join_keys and BOWGPU_JOIN_MAX_KEYS (the join on several common columns) added under the same
  * version: two new entry points beside bowgpu_join_rows / bowgpu_join, no struct added or changed. */
+/* (still 14): bowgpu_equal (with the bowgpu_equal_info struct), bowgpu_valid_row and bowgpu_is_col_empty (Bow.Equal's rows, the Prev / Next
+ * valid-row getters, IsColEmpty) added under the same version: three new entry points and one new struct, nothing existing changed. */
 #define BOWGPU_ABI_VERSION 14
 
 /* bow.Type (reference bowtypes.go:17-32) */
@@ -57,8 +59,9 @@ enum {
     BOWGPU_FLOAT64 = 1,
     BOWGPU_INT64 = 2,
     BOWGPU_BOOLEAN = 3,            /* Arrow bit-packed values.  Accepted as a VALUE column of bowgpu_rolling_aggregate and
-                                      bowgpu_rolling_aggregate_planned (see there) and as source or target of bowgpu_convert; every
-                                      other entry point declines it */
+                                      bowgpu_rolling_aggregate_planned (see there), as source or target of bowgpu_convert and as a
+                                      column of bowgpu_equal (bowgpu_valid_row / bowgpu_is_col_empty read bitmaps alone); every other
+                                      entry point declines it */
     BOWGPU_STRING = 4,             /* not accepted by the device path */
     BOWGPU_INPUT_DEPENDENT = 5,
     BOWGPU_ITERATOR_DEPENDENT = 6
@@ -827,6 +830,71 @@ int bowgpu_append(const bowgpu_col *const *frames, int32_t nframes, int32_t ncol
  *   No device is needed for zero rows, a row_start past the end, a NaN value, and nil on a column with no nulls to look at.
  *   HBM WORKSPACE: none beyond the staged copy of a BOWGPU_HOST column (for nil: of its bitmap alone). */
 int bowgpu_find_next(const bowgpu_col *col, int64_t row_start, const void *value, int64_t *row);
+
+/* ---- Bow.Equal, the Prev / Next valid-row getters, IsColEmpty --------------------------- */
+
+/* Asking whether two frames are the same, and where the nearest valid row is, where the data lies: the per-row half of Bow.Equal
+ * (bow.go:227-275), the search of GetPrevRowIndex / GetNextRowIndex / GetPrevValue(s) / GetNextValue(s) (bowgetters.go:65-151) and
+ * IsColEmpty (bowassertion.go:84-86).  The conventions are those of the append / find block above: ONE device, any residency per column
+ * (BOWGPU_HOST staged through HBM - for bowgpu_equal at most 4 column pairs at a time -, BOWGPU_HOST_PINNED and BOWGPU_DEVICE read where
+ * they lie), any Arrow offset (bit offsets that are no multiple of 8 included), per-thread contexts and streams; bowgpu_set_devices does
+ * not apply.  A COLUMN HAS NO NULLS TO LOOK AT when its validity is NULL or its null_count is stated as 0.  Fewer than 2^31 rows; more is
+ * BOWGPU_ERR_UNSUPPORTED naming the limit.  For host-resident arguments every decision that needs no data is made before the device is
+ * touched; a well-formed call that has rows to look at is BOWGPU_ERR_NO_DEVICE on a box without a GPU - no CPU fallback.
+ *   THE METHOD (bow_amd/csrc/equal.hip): a wave compares 64 rows of a column pair at a time - both sides' validity words (and a Boolean
+ * column's value words) funnel-shifted onto row alignment, each with its own bit offset, the values by plain coalesced loads - into one
+ * 64-bit "differs" word, and the lowest set bit lowers ONE device word by an unsigned 64-bit atomic min of (row << 32) | column; a wave
+ * whose rows lie above that word leaves without loading.  The valid-row search ANDs the 64-row words of its columns and lowers (raises)
+ * one word the same way, starting at the tile of row_start and moving away from it.  Nothing is written but those words; the same call
+ * gives the same answer. */
+
+/* how valid rows compare in bowgpu_equal */
+enum {
+    BOWGPU_EQUAL_GO = 0,     /* the reference's rule, reflect.DeepEqual on the boxed values of GetRow (bow.go:269): Int64 exactly; Float64 by
+                                IEEE == (-0.0 equals +0.0, a NaN differs from everything, ITSELF INCLUDED: a frame with a valid NaN is not
+                                equal to itself, also when both sides are the same pointers); Boolean by the bit */
+    BOWGPU_EQUAL_BITS = 1    /* "bit for bit": valid rows compare by their 64-bit pattern (a NaN equals a NaN of the same payload, -0.0
+                                differs from +0.0); Boolean by the bit */
+};
+typedef struct {
+    int32_t equal;           /* 1: no row differs (first_col = -1, first_row = -1) */
+    int32_t first_col;       /* the lowest column that differs at first_row; for a type mismatch: the lowest column whose types differ */
+    int64_t first_row;       /* the lowest row at which any column differs; -1 for a type or a length mismatch */
+} bowgpu_equal_info;
+
+/* The per-row half of Bow.Equal: column i of `left` against column i of `right`, ncols columns each.  Names and metadata are the
+ * caller's to compare; the ABI has neither.  Column types: Int64, Float64, Boolean (`values` is the Arrow bit-packed buffer, read at bit
+ * offset + i).  Row r of column c DIFFERS when exactly one side is valid there, or when both are valid and the values differ under
+ * `mode`.  A null row's slot is never compared: garbage under a null differs from nothing.  Bits of a bitmap or of a Boolean buffer
+ * outside [offset, offset + length) do not count.  A column with a bitmap of all ones equals one without a bitmap.
+ *   ANSWERED WITHOUT A DEVICE: ncols == 0: equal.  Column c of different types on the two sides (the reference's Schema().Equal):
+ * equal = 0, first_col = the lowest such c, first_row = -1.  Frames of different lengths: equal = 0, first_col = -1, first_row = -1.
+ * Zero rows on both sides, types matching: equal.
+ *   ERRORS: columns of unequal length within one frame, an unknown mode, ncols < 0, a NULL info: BOWGPU_ERR_ARG.  A String column (or any
+ * other type than the three) on either side: BOWGPU_ERR_UNSUPPORTED.  2^31 rows or more: BOWGPU_ERR_UNSUPPORTED.
+ *   No output.  HBM WORKSPACE: none beyond the staged copies of BOWGPU_HOST columns (at most 4 column pairs at a time) and one word. */
+int bowgpu_equal(const bowgpu_col *left, const bowgpu_col *right, int32_t ncols, int32_t mode, bowgpu_equal_info *info);
+
+/* The nearest row at which EVERY one of the ncols columns is valid: for direction == -1 the largest r <= row_start, for direction == +1
+ * the smallest r >= row_start; *row = -1 when there is none.  Only bitmaps are read, so every column type is accepted, Boolean and String
+ * included; the caller fetches the value(s) at the returned row itself (device-resident: one bowgpu_memcpy_d2h).
+ *   ncols = 1 is GetPrevRowIndex / GetNextRowIndex (bowgetters.go:127-151), the row half of GetPrevValue / GetNextValue (:67-91).
+ *   ncols = 2 is GetPrevValues / GetNextValues (:95-123).  Why: GetPrevValues' loop holds a row index i (<= the start).  Each turn moves
+ * i down to p1 = the largest row <= i where column 1 is valid, then finds p2 = the largest row <= p1 where column 2 is valid; p2 == p1
+ * ends it, otherwise i = p1 - 1.  No row in (p1, i] is valid in column 1, and p1 itself is rejected only when column 2 is null there, so
+ * the loop never steps over a row where both are valid and ends on the first such row it meets going down: the largest row <= the start
+ * where both are valid - or -1 when column 1 runs out (p1 = -1 makes p2 = -1: "equal") or i falls below row 0.  GetNextValues mirrors it.
+ *   row_start outside [0, length) gives -1 without a device: the guard of the reference's loops; a negative start is no error here.
+ * Columns with no nulls to look at drop out; if none is left the answer is row_start, without a device.
+ *   ERRORS: ncols < 1, ncols > BOWGPU_VALID_ROW_MAX_COLS (the message names the limit), a direction other than +1 / -1, columns of unequal
+ * length: BOWGPU_ERR_ARG.  2^31 rows or more: BOWGPU_ERR_UNSUPPORTED.
+ *   HBM WORKSPACE: the staged bitmaps of BOWGPU_HOST columns (all of the call's at once: 1/8 byte per row and column) and one word. */
+#define BOWGPU_VALID_ROW_MAX_COLS 8
+int bowgpu_valid_row(const bowgpu_col *cols, int32_t ncols, int64_t row_start, int32_t direction, int64_t *row);
+
+/* IsColEmpty: *empty = (NullN() == Len()); zero rows is empty (0 == 0).  A stated null_count (or no bitmap) answers without a device;
+ * null_count = -1 with a bitmap: the bitmap is counted on the device.  Any column type. */
+int bowgpu_is_col_empty(const bowgpu_col *col, int32_t *empty);
 
 /* ---- Bow.InnerJoin / Bow.OuterJoin ----------------------------------------------------- */
 
