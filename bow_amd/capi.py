@@ -177,7 +177,7 @@ SYMBOLS = [
     "bowgpu_append", "bowgpu_find_next",
     "bowgpu_join_rows", "bowgpu_join", "bowgpu_join_keys_rows", "bowgpu_join_keys",
     "bowgpu_convert",
-    "bowgpu_parquet_write_codec",
+    "bowgpu_parquet_write_codec", "bowgpu_parquet_read_bool_column", "bowgpu_parquet_bool_column_check",
     "bowgpu_equal", "bowgpu_valid_row", "bowgpu_is_col_empty",
 ]
 
@@ -1351,6 +1351,7 @@ def stream_rw_probe(buf_a, buf_b, bytes_each, out_a, out_b, rows_per_slot):
 # bits of ParquetFile.check_column's mask: 1 << (Parquet Encoding value), as in include/bowgpu.h (BOWGPU_PARQUET_ENC_*)
 PARQUET_ENC_PLAIN, PARQUET_ENC_PLAIN_DICTIONARY, PARQUET_ENC_DELTA_BINARY_PACKED = 1 << 0, 1 << 2, 1 << 5
 PARQUET_ENC_RLE_DICTIONARY, PARQUET_ENC_BYTE_STREAM_SPLIT = 1 << 8, 1 << 9
+PARQUET_ENC_RLE = 1 << 3   # BOOLEAN columns (ParquetFile.check_bool_column)
 
 
 PARQUET_PLAIN, PARQUET_DELTA_BINARY_PACKED, PARQUET_RLE_DICTIONARY = 0, 5, 8   # Parquet Encoding values bowgpu_parquet_write takes
@@ -1358,7 +1359,8 @@ PARQUET_DICT_MAX = 65536   # BOWGPU_PARQUET_DICT_MAX: a column chunk with more d
 
 
 class ParquetFile:
-    """Parquet column chunks decoded on the device (bowgpu_parquet_*): the reference's NewBowFromParquet for INT64 / DOUBLE columns"""
+    """Parquet column chunks decoded on the device (bowgpu_parquet_*): the reference's NewBowFromParquet for INT64 / DOUBLE columns
+    (read_column) and BOOLEAN ones (read_bool_column); self.columns holds (name, type, optional) to dispatch on"""
 
     def __init__(self, path):
         self.h = C.c_void_p()
@@ -1385,6 +1387,21 @@ class ParquetFile:
         device; returns the mask of value encodings found on its data pages (PARQUET_ENC_*)"""
         m = C.c_uint32(0)
         check(lib().bowgpu_parquet_column_check(self.h, i, C.byref(m)))
+        return m.value
+
+    def read_bool_column(self, i, out_residency=HOST):
+        """bowgpu_parquet_read_bool_column: a BOOLEAN column (type BOOLEAN in self.columns) as a bit-packed Boolean OutColumn"""
+        out = OutColumn(self.num_rows, out_residency)
+        o = out.c()
+        check(lib().bowgpu_parquet_read_bool_column(self.h, i, C.byref(o)))
+        out.absorb(o)
+        return out
+
+    def check_bool_column(self, i):
+        """bowgpu_parquet_bool_column_check: raises what read_bool_column(i) would raise about the column's structure, without
+        touching a device; returns the mask of value encodings found on its data pages (PARQUET_ENC_PLAIN, PARQUET_ENC_RLE)"""
+        m = C.c_uint32(0)
+        check(lib().bowgpu_parquet_bool_column_check(self.h, i, C.byref(m)))
         return m.value
 
     def close(self):

@@ -7,6 +7,8 @@
 // of OPTIONAL columns) and what pyarrow / pandas write by default (a dictionary page per column chunk, RLE_DICTIONARY data
 // pages, PLAIN fall-back pages, data page v2 when asked for), plus what Parquet v2 writers choose for these types:
 // DELTA_BINARY_PACKED on INT64 and BYTE_STREAM_SPLIT on INT64 / DOUBLE; INT64 and DOUBLE columns (the device path's types).
+// BOOLEAN columns (PLAIN bits or RLE) have entry points of their own beside those - bowgpu_parquet_read_bool_column and its check -
+// over the same walk, with a bit-packed Boolean output.
 // Other codecs / encodings and nested schemas are declined with BOWGPU_ERR_UNSUPPORTED.
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -36,6 +38,8 @@ struct PqPage {  // must match parquet_decode.hip
 int launch_parquet_decode(Ctx *c, const uint8_t *chunk, const PqPage *pages, int64_t npages, bool any_compressed, uint8_t *raw,
                           int optional, uint32_t kinds, uint32_t *indices, uint32_t *idx_counts, uint64_t *expanded, uint64_t *out_values,
                           uint32_t *out_valid, unsigned long long *valid_count, uint32_t *status);
+int launch_parquet_bool_decode(Ctx *c, const uint8_t *chunk, const PqPage *pages, int64_t npages, bool any_compressed, uint8_t *raw,
+                               int optional, uint32_t *out_bits, uint32_t *out_valid, unsigned long long *valid_count, uint32_t *status);
 
 namespace {
 
@@ -278,11 +282,19 @@ struct PqWalk {
     uint32_t encodings = 0;   // bit e: some data page has Parquet Encoding e
 };
 
-// the checks that need no page: index, schema shape, physical type
-int check_column_type(const ParquetFile *pf, int32_t i) {
+// the checks that need no page: index, schema shape, physical type.  boolean: the gate of bowgpu_parquet_read_bool_column
+// (physical type BOOLEAN), else that of bowgpu_parquet_read_column (INT64 / DOUBLE)
+int check_column_type(const ParquetFile *pf, int32_t i, bool boolean = false) {
     if (i < 0 || i >= (int32_t)pf->cols.size()) return fail(BOWGPU_ERR_BAD_COL, "parquet: no column with index %d", i);
-    if (!pf->flat) return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: nested / repeated schema is outside the loader");
     const PqSchemaCol &sc = pf->cols[i];
+    if (boolean) {
+        if (!pf->flat) return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: nested / repeated schema is outside the loader (column '%s')", sc.name.c_str());
+        if (sc.type != 0)
+            return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: column '%s' is not BOOLEAN (physical type %d; bowgpu_parquet_read_column reads INT64 / DOUBLE)",
+                        sc.name.c_str(), sc.type);
+        return 0;
+    }
+    if (!pf->flat) return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: nested / repeated schema is outside the loader");
     if (sc.type != 2 && sc.type != 5) return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: column '%s' is not INT64 / DOUBLE (physical type %d)", sc.name.c_str(), sc.type);
     return 0;
 }
@@ -368,9 +380,28 @@ int bowgpu_parquet_column(const bowgpu_parquet *handle, int32_t i, char *name, i
 namespace bowgpu {
 namespace {
 
+// A page of a BOOLEAN column that is stored, not compressed, lies in the mapped file as the kernel will see it (body: pg.raw_size
+// bytes): what bool_pages_kernel would report about its values section without counting levels is found here.  The rest - a
+// compressed page, how many values an OPTIONAL page's levels ask for - is the kernel's.
+int check_stored_bool_page(const uint8_t *body, const PqPage &pg, int optional, const char *name) {
+    auto le32 = [](const uint8_t *q) { return (int64_t)((uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24)); };
+    int64_t vpos = 0;
+    if (optional && !pg.v2) {   // 4-byte length + definition levels in front of the values
+        if (pg.raw_size < 4 || le32(body) + 4 > pg.raw_size) return fail(BOWGPU_ERR_ARG, "parquet: the definition levels of a page of column '%s' run past the page", name);
+        vpos = 4 + le32(body);
+    }
+    const int64_t section = pg.raw_size - vpos;
+    if (pg.kind == 6 && section >= 4 && le32(body + vpos) + 4 > section)
+        return fail(BOWGPU_ERR_ARG, "parquet: the RLE length prefix of a page of column '%s' runs past the page", name);
+    if (pg.kind == 5 && !optional && section < ((int64_t)pg.num_values + 7) / 8)
+        return fail(BOWGPU_ERR_ARG, "parquet: a PLAIN page of column '%s' holds %lld bytes for %d values", name, (long long)section, pg.num_values);
+    return 0;
+}
+
 int walk_column(const ParquetFile *pf, int32_t i, PqWalk *w) {
     const PqSchemaCol &sc = pf->cols[i];
     const int optional = sc.repetition == 1 ? 1 : 0;
+    const bool boolean = sc.type == 0;   // the accepted value encodings go by physical type: PLAIN and RLE bits, no dictionary
     std::vector<PqSpan> &spans = w->spans;
     std::vector<PqPage> &pages = w->pages;
     int64_t row0 = 0;
@@ -408,6 +439,8 @@ int walk_column(const ParquetFile *pf, int32_t i, PqWalk *w) {
             // a page that is stored, not compressed, is read in place up to raw_size: that must be what the chunk holds of it
             if ((cc.codec == 0 || (h.type == 3 && h.v2 && !h.v2_compressed)) && h.raw_size != h.comp_size)
                 return fail(BOWGPU_ERR_ARG, "parquet: a stored page of column '%s' claims %d bytes and holds %d", sc.name.c_str(), h.raw_size, h.comp_size);
+            if (h.type == 2 && boolean)
+                return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: dictionary page in the BOOLEAN column '%s' (PLAIN and RLE values are read)", sc.name.c_str());
             if (h.type == 2) {  // the chunk's dictionary: PLAIN values, decompressed like a page
                 if ((h.dict_encoding != 0 && h.dict_encoding != 2) || dict_off >= 0 || (int64_t)h.raw_size != (int64_t)h.dict_values * 8)
                     return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: dictionary page of column '%s' is not PLAIN 8-byte values", sc.name.c_str());
@@ -432,9 +465,11 @@ int walk_column(const ParquetFile *pf, int32_t i, PqWalk *w) {
             } else if (h.type == 0 || (h.type == 3 && h.v2)) {
                 const bool dict_page = h.encoding == 2 || h.encoding == 8;
                 if (h.encoding >= 0 && h.encoding < 32) w->encodings |= 1u << h.encoding;
+                if (boolean && h.encoding != 0 && h.encoding != 3)
+                    return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: value encoding %d in the BOOLEAN column '%s' (PLAIN and RLE are read)", h.encoding, sc.name.c_str());
                 if (h.encoding == 5 && sc.type != 2)
                     return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: value encoding %d (DELTA_BINARY_PACKED) on the DOUBLE column '%s' (it is read on INT64 columns)", h.encoding, sc.name.c_str());
-                if (h.encoding != 0 && h.encoding != 5 && h.encoding != 9 && !dict_page)
+                if (!boolean && h.encoding != 0 && h.encoding != 5 && h.encoding != 9 && !dict_page)
                     return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: value encoding %d in column '%s' (PLAIN, dictionary, DELTA_BINARY_PACKED and BYTE_STREAM_SPLIT are read)", h.encoding, sc.name.c_str());
                 if (dict_page && dict_off < 0) return fail(BOWGPU_ERR_ARG, "parquet: column '%s' has dictionary-encoded pages but no dictionary", sc.name.c_str());
                 if (optional && !h.v2 && h.def_encoding != 3) return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: definition-level encoding %d in column '%s' (RLE is read)", h.def_encoding, sc.name.c_str());
@@ -443,7 +478,7 @@ int walk_column(const ParquetFile *pf, int32_t i, PqWalk *w) {
                     return fail(BOWGPU_ERR_ARG, "parquet: implausible level sizes in a v2 page of column '%s'", sc.name.c_str());
                 PqPage pg;
                 memset(&pg, 0, sizeof pg);
-                pg.kind = dict_page ? 1 : h.encoding == 5 ? 3 : h.encoding == 9 ? 4 : 0;
+                pg.kind = boolean ? (h.encoding == 3 ? 6 : 5) : dict_page ? 1 : h.encoding == 5 ? 3 : h.encoding == 9 ? 4 : 0;
                 pg.v2 = h.v2 ? 1 : 0;
                 pg.lv_off = base + (int64_t)p + h.rep_len;
                 pg.lv_len = h.def_len;
@@ -460,6 +495,7 @@ int walk_column(const ParquetFile *pf, int32_t i, PqWalk *w) {
                 pg.row0 = row0 + vals;
                 pg.raw_off = pg.compressed ? raw_total : pg.src_off;
                 if (pg.compressed) { raw_total += ((int64_t)h.raw_size + 15) & ~(int64_t)15; any_comp = true; }
+                if (boolean && !pg.compressed) BG_TRY(check_stored_bool_page(chunk + p + lv_bytes, pg, optional, sc.name.c_str()));
                 pages.push_back(pg);
                 vals += h.num_values;
             } else if (h.type == 3) {
@@ -476,10 +512,61 @@ int walk_column(const ParquetFile *pf, int32_t i, PqWalk *w) {
     return 0;
 }
 
+// What a walked column is on the device, for either read entry point: its chunks' bytes as they lie in the file, the page table,
+// the scratch of the Snappy pass, the cleared status word and valid-row count
+struct PqDevice {
+    const uint8_t *bytes = nullptr;
+    const PqPage *pages = nullptr;
+    uint8_t *raw = nullptr;
+    uint32_t *status = nullptr;
+    unsigned long long *count = nullptr;
+};
+
+// uploads the column and clears the status, the count and the output's validity working copy (n rows)
+int upload_column(Ctx *c, const ParquetFile *pf, const PqWalk &walk, uint8_t *validity, int64_t n, PqDevice *d) {
+    void *d_bytes, *d_pages, *d_raw = nullptr;
+    BG_TRY(ctx_pool(c, kPoolInterp + 0, (size_t)walk.dev_total + 32, &d_bytes));
+    BG_TRY(ctx_pool(c, kPoolInterp + 1, walk.pages.size() * sizeof(PqPage) + 32, &d_pages));
+    if (walk.any_comp) BG_TRY(ctx_pool(c, kPoolInterp + 2, (size_t)walk.raw_total + 32, &d_raw));
+    for (const PqSpan &sp : walk.spans)
+        BG_TRY(copy_h2d(c, reinterpret_cast<char *>(d_bytes) + sp.dev_off, pf->map + sp.file_off, (size_t)sp.len));
+    BG_HIP(hipMemcpyAsync(d_pages, walk.pages.data(), walk.pages.size() * sizeof(PqPage), hipMemcpyHostToDevice, c->stream));
+    BG_TRY(scratch_at(c, kScrStatus, &d->status));
+    BG_TRY(scratch_at(c, kScrOneCount, &d->count));
+    BG_HIP(hipMemsetAsync(d->status, 0, kStatusHeadBytes, c->stream));
+    BG_HIP(hipMemsetAsync(d->count, 0, kScrOneCount.size, c->stream));
+    BG_HIP(hipMemsetAsync(validity, 0, temp_bits_bytes((size_t)((n + 7) >> 3)), c->stream));
+    d->bytes = reinterpret_cast<const uint8_t *>(d_bytes);
+    d->pages = reinterpret_cast<const PqPage *>(d_pages);
+    d->raw = reinterpret_cast<uint8_t *>(d_raw);
+    return 0;
+}
+
+// behind the decode kernels: the status word decides, then the column goes to the caller with its exact null count
+int finish_column(Ctx *c, const PqDevice &d, const PqSchemaCol &sc, DevOut *dout, int64_t n, int32_t otype) {
+    uint32_t hstat = 0;
+    uint64_t hcnt = 0;
+    BG_HIP(hipMemcpyAsync(&hstat, d.status, 4, hipMemcpyDeviceToHost, c->stream));
+    BG_HIP(hipMemcpyAsync(&hcnt, d.count, 8, hipMemcpyDeviceToHost, c->stream));
+    BG_HIP(hipStreamSynchronize(c->stream));
+    if (hstat) return fail(BOWGPU_ERR_ARG, "parquet: malformed page data in column '%s' (status %u)", sc.name.c_str(), hstat);
+    BG_TRY(devout_finish(c, dout, n, otype, n - (int64_t)hcnt));
+    BG_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 }  // namespace
 }  // namespace bowgpu
 
 extern "C" {
+
+static int parquet_read_bool_column_impl(bowgpu_parquet *handle, int32_t i, bowgpu_out *out);
+
+int bowgpu_parquet_read_bool_column(bowgpu_parquet *handle, int32_t i, bowgpu_out *out) {
+    try { return parquet_read_bool_column_impl(handle, i, out); }
+    catch (const std::exception &e) { return fail(BOWGPU_ERR_ARG, "parquet: malformed file (%s)", e.what()); }
+    catch (...) { return fail(BOWGPU_ERR_ARG, "parquet: malformed file"); }
+}
 
 int bowgpu_parquet_read_column(bowgpu_parquet *handle, int32_t i, bowgpu_out *out) {
     try { return parquet_read_column_impl(handle, i, out); }
@@ -487,12 +574,17 @@ int bowgpu_parquet_read_column(bowgpu_parquet *handle, int32_t i, bowgpu_out *ou
     catch (...) { return fail(BOWGPU_ERR_ARG, "parquet: malformed file"); }
 }
 
-int bowgpu_parquet_column_check(const bowgpu_parquet *handle, int32_t i, uint32_t *value_encodings) {
+// the host-only twin of a read entry point: the same type gate and the same walk
+static int column_check(const bowgpu_parquet *handle, int32_t i, uint32_t *value_encodings, bool boolean) {
     const ParquetFile *pf = reinterpret_cast<const ParquetFile *>(handle);
     if (!pf) return fail(BOWGPU_ERR_ARG, "null argument");
     if (value_encodings) *value_encodings = 0;
     try {
-        BG_TRY(check_column_type(pf, i));
+        BG_TRY(check_column_type(pf, i, boolean));
+        // A file without rows: both read entry points hand over an empty column without walking (writers leave such a file's chunk
+        // offsets unset, which the walk would refuse).  The Boolean check answers what its read answers, which is its contract; the
+        // INT64 / DOUBLE check has always walked here although its read does not, and keeps doing so byte for byte.
+        if (boolean && pf->num_rows == 0) return 0;
         PqWalk walk;
         const int rc = walk_column(pf, i, &walk);
         if (value_encodings) *value_encodings = walk.encodings;   // (on an error: what the walk had seen, the declined encoding included)
@@ -500,6 +592,14 @@ int bowgpu_parquet_column_check(const bowgpu_parquet *handle, int32_t i, uint32_
     }
     catch (const std::exception &e) { return fail(BOWGPU_ERR_ARG, "parquet: malformed file (%s)", e.what()); }
     catch (...) { return fail(BOWGPU_ERR_ARG, "parquet: malformed file"); }
+}
+
+int bowgpu_parquet_column_check(const bowgpu_parquet *handle, int32_t i, uint32_t *value_encodings) {
+    return column_check(handle, i, value_encodings, false);
+}
+
+int bowgpu_parquet_bool_column_check(const bowgpu_parquet *handle, int32_t i, uint32_t *value_encodings) {
+    return column_check(handle, i, value_encodings, true);
 }
 
 static int parquet_read_column_impl(bowgpu_parquet *handle, int32_t i, bowgpu_out *out) {
@@ -518,43 +618,41 @@ static int parquet_read_column_impl(bowgpu_parquet *handle, int32_t i, bowgpu_ou
 
     PqWalk walk;
     BG_TRY(walk_column(pf, i, &walk));
-    const std::vector<PqSpan> &spans = walk.spans;
-    const std::vector<PqPage> &pages = walk.pages;
-    const int64_t raw_total = walk.raw_total, dev_total = walk.dev_total;
-    const bool any_comp = walk.any_comp;
 
     // ---- upload + decode
-    void *d_bytes, *d_pages, *d_raw = nullptr;
-    BG_TRY(ctx_pool(c, kPoolInterp + 0, (size_t)dev_total + 32, &d_bytes));
-    BG_TRY(ctx_pool(c, kPoolInterp + 1, pages.size() * sizeof(PqPage) + 32, &d_pages));
-    if (any_comp) BG_TRY(ctx_pool(c, kPoolInterp + 2, (size_t)raw_total + 32, &d_raw));
-    for (const PqSpan &sp : spans)
-        BG_TRY(copy_h2d(c, reinterpret_cast<char *>(d_bytes) + sp.dev_off, pf->map + sp.file_off, (size_t)sp.len));
-    BG_HIP(hipMemcpyAsync(d_pages, pages.data(), pages.size() * sizeof(PqPage), hipMemcpyHostToDevice, c->stream));
-    uint32_t *status;
-    unsigned long long *dcnt;
-    BG_TRY(scratch_at(c, kScrStatus, &status));
-    BG_TRY(scratch_at(c, kScrOneCount, &dcnt));
-    BG_HIP(hipMemsetAsync(status, 0, kStatusHeadBytes, c->stream));
-    BG_HIP(hipMemsetAsync(dcnt, 0, kScrOneCount.size, c->stream));
-    BG_HIP(hipMemsetAsync(dout.validity, 0, temp_bits_bytes((size_t)((n + 7) >> 3)), c->stream));
+    PqDevice d;
+    BG_TRY(upload_column(c, pf, walk, dout.validity, n, &d));
     void *d_idx = nullptr, *d_exp = nullptr;   // 4 B / 8 B per row of workspace, taken only when a page needs it (a chunk may mix encodings)
     // (behind the n index slots: one word per page, the count of indices its stream gave)
-    if (walk.kinds & 2u) BG_TRY(ctx_pool(c, kPoolInterp + 3, ((size_t)n + pages.size()) * 4 + 32, &d_idx));
+    if (walk.kinds & 2u) BG_TRY(ctx_pool(c, kPoolInterp + 3, ((size_t)n + walk.pages.size()) * 4 + 32, &d_idx));
     if (walk.kinds & (8u | 16u)) BG_TRY(ctx_pool(c, kPoolInterp + 4, (size_t)n * 8 + 32, &d_exp));
-    BG_TRY(launch_parquet_decode(c, reinterpret_cast<const uint8_t *>(d_bytes), reinterpret_cast<const PqPage *>(d_pages), (int64_t)pages.size(),
-                                 any_comp, reinterpret_cast<uint8_t *>(d_raw), optional, walk.kinds, reinterpret_cast<uint32_t *>(d_idx),
-                                 d_idx ? reinterpret_cast<uint32_t *>(d_idx) + n : nullptr, reinterpret_cast<uint64_t *>(d_exp),
-                                 reinterpret_cast<uint64_t *>(dout.values), reinterpret_cast<uint32_t *>(dout.validity), dcnt, status));
-    uint32_t hstat = 0;
-    uint64_t hcnt = 0;
-    BG_HIP(hipMemcpyAsync(&hstat, status, 4, hipMemcpyDeviceToHost, c->stream));
-    BG_HIP(hipMemcpyAsync(&hcnt, dcnt, 8, hipMemcpyDeviceToHost, c->stream));
-    BG_HIP(hipStreamSynchronize(c->stream));
-    if (hstat) return fail(BOWGPU_ERR_ARG, "parquet: malformed page data in column '%s' (status %u)", sc.name.c_str(), hstat);
-    BG_TRY(devout_finish(c, &dout, n, otype, n - (int64_t)hcnt));
-    BG_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    BG_TRY(launch_parquet_decode(c, d.bytes, d.pages, (int64_t)walk.pages.size(), walk.any_comp, d.raw, optional, walk.kinds,
+                                 reinterpret_cast<uint32_t *>(d_idx), d_idx ? reinterpret_cast<uint32_t *>(d_idx) + n : nullptr,
+                                 reinterpret_cast<uint64_t *>(d_exp), reinterpret_cast<uint64_t *>(dout.values),
+                                 reinterpret_cast<uint32_t *>(dout.validity), d.count, d.status));
+    return finish_column(c, d, sc, &dout, n, otype);
+}
+
+// BOOLEAN columns: the same walk, upload and hand-over around bool_pages_kernel; the output's values are bits like its validity
+static int parquet_read_bool_column_impl(bowgpu_parquet *handle, int32_t i, bowgpu_out *out) {
+    ParquetFile *pf = reinterpret_cast<ParquetFile *>(handle);
+    if (!pf || !out) return fail(BOWGPU_ERR_ARG, "null argument");
+    BG_TRY(check_column_type(pf, i, true));
+    const PqSchemaCol &sc = pf->cols[i];
+    const int64_t n = pf->num_rows;
+    PqWalk walk;
+    if (n > 0) BG_TRY(walk_column(pf, i, &walk));   // (every decline comes before a device is touched; n == 0: no walk, as bowgpu_parquet_read_column)
+    Ctx *c;
+    BG_TRY(ctx_get(&c));
+    DevOut dout;
+    BG_TRY(devout_prepare(c, out, n, &dout, 0, true));
+    if (n == 0) { BG_TRY(devout_finish(c, &dout, 0, BOWGPU_BOOLEAN, 0)); return 0; }
+    PqDevice d;
+    BG_TRY(upload_column(c, pf, walk, dout.validity, n, &d));
+    BG_HIP(hipMemsetAsync(dout.values, 0, temp_bits_bytes((size_t)((n + 7) >> 3)), c->stream));
+    BG_TRY(launch_parquet_bool_decode(c, d.bytes, d.pages, (int64_t)walk.pages.size(), walk.any_comp, d.raw, sc.repetition == 1 ? 1 : 0,
+                                      reinterpret_cast<uint32_t *>(dout.values), reinterpret_cast<uint32_t *>(dout.validity), d.count, d.status));
+    return finish_column(c, d, sc, &dout, n, BOWGPU_BOOLEAN);
 }
 
 }  // extern "C"

@@ -16,7 +16,12 @@
 //                         (RLE / bit-packed hybrid, bit width 1) -> Arrow validity bits; dense PLAIN / expanded values -> row slots
 //                         (null slots = 0, as bow.NewBuffer leaves them: bowbuffer.go:22-40).  Lane l owns rows 32k + l ... of the
 //                         page in words of 32: level word, popcount, wave scan = index of its first value.
+//   bool_pages_kernel     data page (v1 / v2) of a flat OPTIONAL / REQUIRED BOOLEAN column: the same level words -> validity bits; the
+//                         page's dense value bits (PLAIN: one bit each; RLE: 4-byte length + RLE / bit-packed hybrid, bit width 1)
+//                         -> Arrow value bits, deposited onto the set positions of the lane's validity word (null rows = 0).  No
+//                         expansion pass and no per-row workspace: a lane takes its bits [vi, vi + popcount) straight from the page.
 #include "agg_device.h"
+#include "wave_scan.h"
 
 namespace bowgpu {
 
@@ -28,7 +33,8 @@ struct PqPage {
     int32_t num_values;     // rows of the page (levels); non-null values = what the levels say
     int32_t compressed;     // 1: Snappy
     int32_t kind;           // 0: data page, PLAIN values; 1: data page, dictionary indices; 2: the chunk's dictionary page (PLAIN values);
-                            // 3: data page, DELTA_BINARY_PACKED; 4: data page, BYTE_STREAM_SPLIT
+                            // 3: data page, DELTA_BINARY_PACKED; 4: data page, BYTE_STREAM_SPLIT;
+                            // 5: data page of a BOOLEAN column, PLAIN bits; 6: data page of a BOOLEAN column, RLE (bool_pages_kernel)
     int32_t dict_count;     // kind 1: entries of the chunk's dictionary
     int64_t dict_off;       // kind 1: offset of the dictionary's values (same buffer as raw_off)
     int64_t idx_off;        // kind 1: first slot of this page in the expanded index array; kind 3 / 4: in the expanded value array
@@ -79,7 +85,11 @@ __device__ __forceinline__ int64_t values_offset(const uint8_t *src, const PqPag
     return 4 + (int64_t)lbytes;
 }
 
-// status bits of the expanded encodings (1 .. 16 belong to the kernels below)
+// status bits of the scatter kernels (page_scatter_kernel, bool_pages_kernel).  1 (a broken Snappy block), 8 (an index outside the
+// dictionary) and 16 (a broken index stream) stay literals of the one kernel each that raises them
+constexpr uint32_t kStLevelLength = 2u;   // a v1 page's level length prefix runs past the page
+constexpr uint32_t kStValuesEnd = 4u;     // a PLAIN values section ends before the values the levels count
+// status bits of the expanded encodings
 constexpr uint32_t kStPastPage = 32u;     // a position past the page's raw_size
 constexpr uint32_t kStWidth = 64u;        // DELTA_BINARY_PACKED: a miniblock's bit width above 64
 constexpr uint32_t kStBlockSize = 128u;   // DELTA_BINARY_PACKED: illegal block / miniblock size
@@ -103,6 +113,87 @@ __device__ __forceinline__ uint32_t delta_header(const uint8_t *src, int64_t *po
     *total = tot > (uint64_t)INT64_MAX ? INT64_MAX : (int64_t)tot;
     *first = unzigzag64(fv);
     return 0;
+}
+
+// A page's definition levels (RLE / bit-packed hybrid, bit width 1) arrive as runs; rows are handled 2048 at a time (64 lanes x one
+// 32-row word).  The walk's state between two trips of a wavefront:
+struct LevelWalk {
+    int64_t lpos = 0;        // read position in the level bytes
+    int run_left = 0;        // levels left in the current run
+    int run_kind = 0;        // 0: RLE, 1: bit-packed
+    int run_val = 0;         // RLE value
+    int64_t run_bits = 0;    // bit-packed: BIT position (from lv) of the run's next unread level
+};
+
+// The lane's validity word of one trip: rows [row + 32 * lane, + 32) of a page of nv rows, bit k = row k is not null.  A REQUIRED
+// column gets all ones up to the page's rows.  Every lane walks the same runs (uniform), keeping the bits of its own word.
+__device__ __forceinline__ uint32_t level_trip_word(int optional, const uint8_t *lv, int64_t lv_end, LevelWalk &W, int row, int nv, int lane,
+                                                    uint32_t *status) {
+    uint32_t word = 0;
+    const int my0 = row + 32 * lane;
+    if (!optional) {
+        const int cnt = nv - my0;
+        return cnt >= 32 ? 0xFFFFFFFFu : (cnt > 0 ? ((1u << cnt) - 1u) : 0u);
+    }
+    int pos = row;               // level index the walk has reached
+    const int stop = row + 2048 < nv ? row + 2048 : nv;
+    while (pos < stop) {
+        if (W.run_left == 0) {
+            if (W.lpos >= lv_end) { if (lane == 0) atomicOr(&status[0], kStLevelsEnd); break; }  // rows are left, levels are not
+            const uint32_t h = rd_varint(lv, &W.lpos, lv_end);
+            if (h & 1) { W.run_kind = 1; W.run_left = (int)(h >> 1) * 8; W.run_bits = W.lpos * 8; W.lpos += (h >> 1); }  // bit width 1: one byte per group of 8
+            else { W.run_kind = 0; W.run_left = (int)(h >> 1); W.run_val = W.lpos < lv_end ? (lv[W.lpos] & 1) : 0; W.lpos += 1; }
+            if (W.lpos > lv_end && lane == 0) atomicOr(&status[0], kStLevelsEnd);  // the run's own bytes lie past the levels
+            if (W.run_left == 0) continue;
+        }
+        const int take = W.run_left < stop - pos ? W.run_left : stop - pos;
+        // levels [pos, pos + take) come from this run; intersect with my word [my0, my0 + 32)
+        const int a = pos > my0 ? pos : my0, b = (pos + take) < (my0 + 32) ? (pos + take) : (my0 + 32);
+        if (a < b) {
+            if (W.run_kind == 0) {
+                if (W.run_val) word |= (b - a >= 32 ? 0xFFFFFFFFu : ((1u << (b - a)) - 1u)) << (a - my0);
+            } else {
+                for (int r = a; r < b; r++) {  // (at most 32 single-bit reads; LSB first, like Arrow validity)
+                    const int64_t bit = W.run_bits + (r - pos);
+                    const uint8_t byte = (bit >> 3) < lv_end ? lv[bit >> 3] : 0;
+                    word |= (uint32_t)((byte >> (bit & 7)) & 1u) << (r - my0);
+                }
+            }
+        }
+        pos += take;
+        W.run_left -= take;
+        if (W.run_kind == 1) W.run_bits += take;
+    }
+    if (my0 < nv) { const int cnt = nv - my0; if (cnt < 32) word &= (1u << cnt) - 1u; }
+    else word = 0;
+    return word;
+}
+
+// Up to 32 bits at BIT position `bit` from p (any byte alignment), LSB first, by aligned 8-byte loads and a funnel shift.  The
+// caller keeps byte bit / 8 inside the page; the loads reach at most 11 bytes past it (the buffers are padded by 16, as for PLAIN)
+// and, the address being aligned DOWN to 8, up to 7 bytes in front of it.  The latter is safe because a page lies inside the
+// uploaded chunk bytes or the Snappy scratch, both pool blocks of their own whose base is at least 8-byte aligned (an address is
+// never aligned down past the block's base); a caller that hands in a sub-allocated buffer must keep its base 8-byte aligned too.
+__device__ __forceinline__ uint32_t bits32_at(const uint8_t *p, int64_t bit) {
+    const uintptr_t addr = reinterpret_cast<uintptr_t>(p + (bit >> 3));
+    const uint64_t *al = reinterpret_cast<const uint64_t *>(addr & ~(uintptr_t)7);
+    const int shb = (int)(addr & 7) * 8 + (int)(bit & 7);
+    uint64_t v = al[0] >> shb;
+    if (shb > 32) v |= al[1] << (64 - shb);
+    return (uint32_t)v;
+}
+
+__device__ __forceinline__ uint32_t low_mask32(int k) { return k >= 32 ? 0xFFFFFFFFu : ((1u << k) - 1u); }
+
+// `bits`, dense from bit 0, onto the set positions of `mask`, ascending; zeros elsewhere (a 32-bit pdep)
+__device__ __forceinline__ uint32_t deposit32(uint32_t bits, uint32_t mask) {
+    if (mask == 0xFFFFFFFFu) return bits;
+    uint32_t r = 0;
+    for (uint32_t m = mask; m; m &= m - 1u) {
+        if (bits & 1u) r |= m & (0u - m);
+        bits >>= 1;
+    }
+    return r;
 }
 
 }  // namespace
@@ -247,7 +338,7 @@ __global__ __launch_bounds__(256) void delta_pages_kernel(const uint8_t *__restr
     const uint8_t *src = (P.compressed ? raw : chunk) + P.raw_off;
     const int64_t end = P.raw_size;
     int64_t pos = values_offset(src, P, optional);
-    if (pos < 0) { if (lane == 0) atomicOr(&status[0], 2u); return; }
+    if (pos < 0) { if (lane == 0) atomicOr(&status[0], kStLevelLength); return; }
     if (pos >= end) return;  // a page of nulls only may carry no values section
     int64_t V, mpb, total;
     uint64_t carry;
@@ -313,7 +404,7 @@ __global__ __launch_bounds__(256) void bss_pages_kernel(const uint8_t *__restric
     if (P.kind != 4) return;
     const uint8_t *src = (P.compressed ? raw : chunk) + P.raw_off;
     const int64_t vpos = values_offset(src, P, optional);
-    if (vpos < 0) { if (lane == 0) atomicOr(&status[0], 2u); return; }
+    if (vpos < 0) { if (lane == 0) atomicOr(&status[0], kStLevelLength); return; }
     const int64_t len = P.raw_size - vpos;
     if (len <= 0) return;
     const int64_t N = len >> 3;
@@ -351,7 +442,7 @@ __global__ __launch_bounds__(256) void page_scatter_kernel(const uint8_t *__rest
         lv_end = P.lv_len;
     } else if (optional) {
         const uint32_t lbytes = (uint32_t)src[0] | ((uint32_t)src[1] << 8) | ((uint32_t)src[2] << 16) | ((uint32_t)src[3] << 24);
-        if ((int64_t)lbytes + 4 > P.raw_size) { if (lane == 0) atomicOr(&status[0], 2u); return; }
+        if ((int64_t)lbytes + 4 > P.raw_size) { if (lane == 0) atomicOr(&status[0], kStLevelLength); return; }
         lv = src + 4;
         lv_end = lbytes;
         vpos = 4 + (int64_t)lbytes;
@@ -371,53 +462,11 @@ __global__ __launch_bounds__(256) void page_scatter_kernel(const uint8_t *__rest
     if (xcount > nv) xcount = nv;
     const int64_t icount = P.kind == 1 ? (int64_t)idx_counts[pg] : 0;  // kind 1: how many indices dict_indices_kernel gave
 
-    // the levels arrive as runs; rows are handled 2048 at a time (64 lanes x one 32-row word)
-    int64_t lpos = 0;        // read position in the level bytes
-    int run_left = 0;        // levels left in the current run
-    int run_kind = 0;        // 0: RLE, 1: bit-packed
-    int run_val = 0;         // RLE value
-    int64_t run_bits = 0;    // bit-packed: BIT position (from lv) of the run's next unread level
+    LevelWalk walk;          // the levels arrive as runs; rows are handled 2048 at a time (64 lanes x one 32-row word)
     int64_t vidx_base = 0;   // values consumed so far
     for (int row = 0; row < nv; row += 2048) {
-        uint32_t word = 0;
         const int my0 = row + 32 * lane;
-        if (!optional) {
-            const int cnt = nv - my0;
-            word = cnt >= 32 ? 0xFFFFFFFFu : (cnt > 0 ? ((1u << cnt) - 1u) : 0u);
-        } else {
-            // every lane walks the same runs (uniform), keeping the bits of its own word
-            int pos = row;               // level index the walk has reached
-            const int stop = row + 2048 < nv ? row + 2048 : nv;
-            while (pos < stop) {
-                if (run_left == 0) {
-                    if (lpos >= lv_end) { if (lane == 0) atomicOr(&status[0], kStLevelsEnd); break; }  // rows are left, levels are not
-                    const uint32_t h = rd_varint(lv, &lpos, lv_end);
-                    if (h & 1) { run_kind = 1; run_left = (int)(h >> 1) * 8; run_bits = lpos * 8; lpos += (h >> 1); }  // bit width 1: one byte per group of 8
-                    else { run_kind = 0; run_left = (int)(h >> 1); run_val = lpos < lv_end ? (lv[lpos] & 1) : 0; lpos += 1; }
-                    if (lpos > lv_end && lane == 0) atomicOr(&status[0], kStLevelsEnd);  // the run's own bytes lie past the levels
-                    if (run_left == 0) continue;
-                }
-                const int take = run_left < stop - pos ? run_left : stop - pos;
-                // levels [pos, pos + take) come from this run; intersect with my word [my0, my0 + 32)
-                const int a = pos > my0 ? pos : my0, b = (pos + take) < (my0 + 32) ? (pos + take) : (my0 + 32);
-                if (a < b) {
-                    if (run_kind == 0) {
-                        if (run_val) word |= (b - a >= 32 ? 0xFFFFFFFFu : ((1u << (b - a)) - 1u)) << (a - my0);
-                    } else {
-                        for (int r = a; r < b; r++) {  // (at most 32 single-bit reads; LSB first, like Arrow validity)
-                            const int64_t bit = run_bits + (r - pos);
-                            const uint8_t byte = (bit >> 3) < lv_end ? lv[bit >> 3] : 0;
-                            word |= (uint32_t)((byte >> (bit & 7)) & 1u) << (r - my0);
-                        }
-                    }
-                }
-                pos += take;
-                run_left -= take;
-                if (run_kind == 1) run_bits += take;
-            }
-            if (my0 < nv) { const int cnt = nv - my0; if (cnt < 32) word &= (1u << cnt) - 1u; }
-            else word = 0;
-        }
+        const uint32_t word = level_trip_word(optional, lv, lv_end, walk, row, nv, lane, status);
         // value index of my word's first value: scan of the popcounts
         const int pc = __popc(word);
         int inc = pc;
@@ -453,7 +502,7 @@ __global__ __launch_bounds__(256) void page_scatter_kernel(const uint8_t *__rest
                         const int shb = (int)(addr & 7) * 8;
                         v = shb ? ((al[0] >> shb) | (al[1] << (64 - shb))) : al[0];
                     } else {
-                        atomicOr(&status[0], 4u);
+                        atomicOr(&status[0], kStValuesEnd);
                     }
                     vi++;
                 }
@@ -471,6 +520,124 @@ __global__ __launch_bounds__(256) void page_scatter_kernel(const uint8_t *__rest
         page_valid += total;
     }
     if (lane == 0 && page_valid) atomicAdd(valid_count, page_valid);
+}
+
+// Data pages of a BOOLEAN column (kind 5: PLAIN, kind 6: RLE) -> Arrow value bits and validity bits; both bitmaps must be zeroed.
+// A trip covers 2048 rows, a lane one 32-row word of them: validity word from the levels, popcount + exclusive wave scan = index vi of
+// the lane's first value, the dense bits [vi, vi + popcount) of the values section, deposited onto the word's set positions.
+//   PLAIN  a bit-field at bit vi of the section.
+//   RLE    <4-byte length> <hybrid, bit width 1>: every lane walks the same value runs over the trip's value range (uniform, the run
+//          state carries across trips like the level walk's) and keeps the intersection with its own range: an RLE run is a mask
+//          fill, a bit-packed run a bit-field.  A bit-packed run is whole groups of 8: what its last group holds past the page's
+//          values is never reached, because a trip asks for exactly the values its levels count.
+// A page's first row lies anywhere inside an output word and pages of other wavefronts meet it there: a word the lane does not own
+// alone is combined with atomicOr, one it owns (row0 a multiple of 32, 32 rows) is stored whole.  A damaged page raises a status bit
+// and the wavefront leaves it; every read lies below raw_size (+ the padding bits32_at names), every write inside the page's rows.
+__global__ __launch_bounds__(256) void bool_pages_kernel(const uint8_t *__restrict__ raw, const uint8_t *__restrict__ chunk,
+                                                         const PqPage *__restrict__ pages, int64_t npages, int optional,
+                                                         uint32_t *out_bits, uint32_t *out_valid, unsigned long long *valid_count,
+                                                         uint32_t *status) {
+    const int lane = threadIdx.x & 63;
+    const int64_t pg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pg >= npages) return;
+    const PqPage P = pages[pg];
+    if (P.kind != 5 && P.kind != 6) return;
+    const uint8_t *src = (P.compressed ? raw : chunk) + P.raw_off;
+    const int nv = P.num_values;
+    const int64_t vpos = values_offset(src, P, optional);
+    if (vpos < 0) { if (lane == 0) atomicOr(&status[0], kStLevelLength); return; }
+    const uint8_t *lv = nullptr;
+    int64_t lv_end = 0;
+    if (optional && P.v2) { lv = chunk + P.lv_off; lv_end = P.lv_len; }   // (uncompressed in the chunk, without a length prefix)
+    else if (optional) { lv = src + 4; lv_end = vpos - 4; }
+    // the value bits: PLAIN [vpos, raw_size); RLE [vpos + 4, vpos + 4 + length).  A section too short for its length prefix is one
+    // without values (a page of nulls only may carry none)
+    int64_t vbeg = vpos, vend = P.raw_size;
+    if (P.kind == 6) {
+        if (vend - vpos >= 4) {
+            const uint32_t rl = (uint32_t)src[vpos] | ((uint32_t)src[vpos + 1] << 8) | ((uint32_t)src[vpos + 2] << 16) | ((uint32_t)src[vpos + 3] << 24);
+            if ((int64_t)rl + 4 > vend - vpos) { if (lane == 0) atomicOr(&status[0], kStPastPage); return; }
+            vbeg = vpos + 4;
+            vend = vbeg + (int64_t)rl;
+        } else {
+            vend = vbeg;
+        }
+    }
+    int64_t rpos = vbeg;     // RLE: read position in the page's bytes
+    int64_t vrun_left = 0;   //      values left in the current run
+    int vrun_kind = 0;       //      0: RLE, 1: bit-packed
+    int vrun_val = 0;        //      RLE value
+    int64_t vrun_bits = 0;   //      bit-packed: BIT position (from src) of the run's next unread value
+    LevelWalk walk;
+    int64_t vidx_base = 0;   // values consumed so far
+    unsigned long long page_valid = 0;
+    for (int row = 0; row < nv; row += 2048) {
+        const int my0 = row + 32 * lane;
+        const uint32_t word = level_trip_word(optional, lv, lv_end, walk, row, nv, lane, status);
+        const int pc = __popc(word);
+        const int inc = (int)wave_inclusive_scan((uint32_t)pc, lane);
+        const int total = __shfl(inc, 63);
+        const int64_t vi = vidx_base + inc - pc;
+        uint32_t dense = 0;
+        if (P.kind == 5) {
+            if (((vidx_base + total + 7) >> 3) > vend - vbeg) { if (lane == 0) atomicOr(&status[0], kStValuesEnd); return; }  // the section ends before the values do
+            if (pc) dense = bits32_at(src + vbeg, vi) & low_mask32(pc);
+        } else {
+            int64_t vp = vidx_base;
+            const int64_t vstop = vidx_base + total;
+            while (vp < vstop) {
+                if (vrun_left == 0) {
+                    if (rpos >= vend) { if (lane == 0) atomicOr(&status[0], kStLevels); return; }  // values are left, runs are not
+                    const uint32_t h = rd_varint(src, &rpos, vend);
+                    if (h & 1) { vrun_kind = 1; vrun_left = (int64_t)(h >> 1) * 8; vrun_bits = rpos * 8; rpos += (h >> 1); }
+                    else { vrun_kind = 0; vrun_left = (int64_t)(h >> 1); vrun_val = rpos < vend ? (src[rpos] & 1) : 0; rpos += 1; }
+                    if (rpos > vend) { if (lane == 0) atomicOr(&status[0], kStPastPage); return; }  // the run's own bytes lie past the section
+                    if (vrun_left == 0) continue;   // (a zero-length run: its header is consumed, so the walk moves on)
+                }
+                const int64_t take = vrun_left < vstop - vp ? vrun_left : vstop - vp;
+                // values [vp, vp + take) come from this run; intersect with mine [vi, vi + pc)
+                const int64_t a = vp > vi ? vp : vi, b = (vp + take) < (vi + pc) ? (vp + take) : (vi + pc);
+                if (a < b) {
+                    const uint32_t m = low_mask32((int)(b - a));
+                    if (vrun_kind == 0) { if (vrun_val) dense |= m << (a - vi); }
+                    else dense |= (bits32_at(src, vrun_bits + (a - vp)) & m) << (a - vi);   // (its bytes lie below rpos <= vend)
+                }
+                vp += take;
+                vrun_left -= take;
+                if (vrun_kind == 1) vrun_bits += take;
+            }
+        }
+        if (my0 < nv && word) {
+            const uint32_t bits = deposit32(dense, word);
+            const int64_t orow = P.row0 + my0;
+            const int sh = (int)(orow & 31);
+            const int64_t w = orow >> 5;
+            if (sh == 0 && nv - my0 >= 32) {
+                out_valid[w] = word;
+                out_bits[w] = bits;
+            } else {
+                atomicOr(&out_valid[w], word << sh);
+                if (bits << sh) atomicOr(&out_bits[w], bits << sh);
+                if (sh && (word >> (32 - sh))) atomicOr(&out_valid[w + 1], word >> (32 - sh));
+                if (sh && (bits >> (32 - sh))) atomicOr(&out_bits[w + 1], bits >> (32 - sh));
+            }
+        }
+        vidx_base += total;
+        page_valid += total;
+    }
+    if (lane == 0 && page_valid) atomicAdd(valid_count, page_valid);
+}
+
+// the pages of a BOOLEAN column (behind the same Snappy pass): out_bits and out_valid are zeroed by the caller
+int launch_parquet_bool_decode(Ctx *c, const uint8_t *chunk, const PqPage *pages, int64_t npages, bool any_compressed, uint8_t *raw,
+                               int optional, uint32_t *out_bits, uint32_t *out_valid, unsigned long long *valid_count, uint32_t *status) {
+    if (npages <= 0) return 0;
+    const unsigned grid = (unsigned)((npages + 3) / 4);
+    if (any_compressed) hipLaunchKernelGGL(snappy_pages_kernel, dim3(grid), dim3(256), 0, c->stream, chunk, pages, npages, raw, status);
+    hipLaunchKernelGGL(bool_pages_kernel, dim3(grid), dim3(256), 0, c->stream, raw, chunk, pages, npages, optional, out_bits, out_valid,
+                       valid_count, status);
+    BG_HIP(hipGetLastError());
+    return 0;
 }
 
 int launch_parquet_decode(Ctx *c, const uint8_t *chunk, const PqPage *pages, int64_t npages, bool any_compressed, uint8_t *raw,

@@ -433,9 +433,13 @@ inline std::pair<BowPtr, Error> Bow::FillLinear(int refColIndex, int toFillColIn
     return {out, Error()};
 }
 
-// NewBowFromParquet: bowparquet.go:44-153, with the columns decoded on the device (bowgpu_parquet_*).  This mirror holds
-// Int64 / Float64 columns; the reference's Boolean / String columns are outside the device path and are skipped.
-inline std::pair<BowPtr, Error> NewBowFromParquet(const std::string &path) {
+// NewBowFromParquet: bowparquet.go:44-153, with the columns decoded on the device (bowgpu_parquet_*): Int64 / Float64 columns
+// through bowgpu_parquet_read_column.  ParquetBooleans::Read sends a column whose reported type is BOWGPU_BOOLEAN to
+// bowgpu_parquet_read_bool_column, so a file with a flag column becomes a Bow with a Boolean series (bit-packed on arrival,
+// unpacked by OutStore::ToSeries); the default, ParquetBooleans::Skip, is what this mirror always did with such a column, and what
+// its callers that index the result's columns rely on.  The reference's String columns are outside the device path and are skipped.
+enum class ParquetBooleans { Skip, Read };
+inline std::pair<BowPtr, Error> NewBowFromParquet(const std::string &path, ParquetBooleans booleans = ParquetBooleans::Skip) {
     bowgpu_parquet *h = nullptr;
     int rc = bowgpu_parquet_open(path.c_str(), &h);
     if (rc) return {nullptr, Wrap("bow.NewBowFromParquet", detail::AbiError(rc))};
@@ -447,10 +451,11 @@ inline std::pair<BowPtr, Error> NewBowFromParquet(const std::string &path) {
         char name[256];
         int32_t type = -1, optional = 0;
         bowgpu_parquet_column(h, i, name, (int32_t)sizeof name, &type, &optional);
-        if (type != BOWGPU_INT64 && type != BOWGPU_FLOAT64) continue;
+        const bool flag = type == BOWGPU_BOOLEAN && booleans == ParquetBooleans::Read;
+        if (type != BOWGPU_INT64 && type != BOWGPU_FLOAT64 && !flag) continue;
         detail::OutStore st;
         bowgpu_out o = st.Make(rows);
-        rc = bowgpu_parquet_read_column(h, i, &o);
+        rc = flag ? bowgpu_parquet_read_bool_column(h, i, &o) : bowgpu_parquet_read_column(h, i, &o);
         if (!rc) series.push_back(st.ToSeries(name, o));
     }
     const Error err = rc ? Wrap("bow.NewBowFromParquet", detail::AbiError(rc)) : Error();

@@ -51,6 +51,9 @@ extern "C" {
  * version: two new entry points beside bowgpu_join_rows / bowgpu_join, no struct added or changed. */
 /* (still 14): bowgpu_equal (with the bowgpu_equal_info struct), bowgpu_valid_row and bowgpu_is_col_empty (Bow.Equal's rows, the Prev / Next
  * valid-row getters, IsColEmpty) added under the same version: three new entry points and one new struct, nothing existing changed. */
+/* (still 14): bowgpu_parquet_read_bool_column and bowgpu_parquet_bool_column_check (a Parquet BOOLEAN column decoded on the device into a
+ * bit-packed Boolean column) added under the same version: two new entry points beside bowgpu_parquet_read_column /
+ * bowgpu_parquet_column_check, which keep declining a BOOLEAN column as before; BOWGPU_PARQUET_ENC_RLE added to the encoding bits. */
 #define BOWGPU_ABI_VERSION 14
 
 /* bow.Type (reference bowtypes.go:17-32) */
@@ -1032,11 +1035,30 @@ int bowgpu_parquet_read_column(bowgpu_parquet *handle, int32_t i, bowgpu_out *ou
 enum {
     BOWGPU_PARQUET_ENC_PLAIN = 1,                  /* 1 << 0 */
     BOWGPU_PARQUET_ENC_PLAIN_DICTIONARY = 4,       /* 1 << 2 */
+    BOWGPU_PARQUET_ENC_RLE = 8,                    /* 1 << 3 (BOOLEAN columns: bowgpu_parquet_bool_column_check) */
     BOWGPU_PARQUET_ENC_DELTA_BINARY_PACKED = 32,   /* 1 << 5 */
     BOWGPU_PARQUET_ENC_RLE_DICTIONARY = 256,       /* 1 << 8 */
     BOWGPU_PARQUET_ENC_BYTE_STREAM_SPLIT = 512     /* 1 << 9 */
 };
 int bowgpu_parquet_column_check(const bowgpu_parquet *handle, int32_t i, uint32_t *value_encodings);
+
+/* Column i, of physical type BOOLEAN in a flat schema (OPTIONAL or REQUIRED; bowgpu_parquet_column reports BOWGPU_BOOLEAN), decoded on
+ * the device into a BOWGPU_BOOLEAN output in the layout bowgpu_convert and the Boolean reducers use: values bit-packed LSB first,
+ * ceil(num_rows / 8) bytes, validity ceil(num_rows / 8) bytes, null_count exact; the value bit of a null row is 0 (what
+ * bow.NewBuffer leaves, bowbuffer.go:22-40) and so is every bit at or past num_rows in the last byte of both buffers.  out: num_rows
+ * slots, any residency; its values buffer needs ceil(num_rows / 8) bytes.
+ * Read: value encodings PLAIN (one bit per non-null value, LSB first) and RLE (a 4-byte little-endian length, then the RLE /
+ * bit-packed hybrid at bit width 1), also mixed page by page inside a chunk; data pages v1 and v2; UNCOMPRESSED and SNAPPY; RLE
+ * definition levels; any number of row groups.
+ * BOWGPU_ERR_UNSUPPORTED, with the column named and before a device is touched: a column that is not BOOLEAN (INT64 / DOUBLE go
+ * through bowgpu_parquet_read_column), a nested schema, any other value encoding (dictionary pages included), codec or
+ * definition-level encoding.  BOWGPU_ERR_ARG and nothing handed to the caller: malformed page data - a PLAIN values section shorter
+ * than ceil(valid / 8) bytes, an RLE length prefix that runs past the page, a run stream that ends before the page's values do,
+ * levels that end before the rows do, implausible page sizes. */
+int bowgpu_parquet_read_bool_column(bowgpu_parquet *handle, int32_t i, bowgpu_out *out);
+/* The host-only twin of bowgpu_parquet_read_bool_column (no device is touched, none is needed): 0, or the code and text it would
+ * give about the column's structure.  value_encodings (may be NULL): BOWGPU_PARQUET_ENC_PLAIN and / or BOWGPU_PARQUET_ENC_RLE. */
+int bowgpu_parquet_bool_column_check(const bowgpu_parquet *handle, int32_t i, uint32_t *value_encodings);
 
 /* ---- device column -> Parquet file -------------------------------------------------- */
 
