@@ -1214,9 +1214,15 @@ def join_rows(left_key, right_key, kind, out_residency=HOST, capacity=None, coun
     rk = None if right_key is None else right_key.c()
     lp = None if lk is None else C.byref(lk)
     rp = None if rk is None else C.byref(rk)
+    return _join_rows_call(lambda *tail: lib().bowgpu_join_rows(lp, rp, kind, *tail), out_residency, capacity, count_only)
+
+
+def _join_rows_call(call, out_residency, capacity, count_only):
+    """what join_rows and join_keys_rows do with their entry point (call: it, up to `kind`): the count call where it is asked for or has
+    to size the index buffers, then the call that fills them - `capacity` slots each, -7 in a host slot nothing was written to"""
     rows, pairs = C.c_int64(0), C.c_int64(0)
     if count_only or capacity is None:
-        check(lib().bowgpu_join_rows(lp, rp, kind, None, None, C.c_int64(0), HOST, C.byref(rows), C.byref(pairs)))
+        check(call(None, None, C.c_int64(0), HOST, C.byref(rows), C.byref(pairs)))
         if count_only:
             return None, None, rows.value, pairs.value
         capacity = rows.value
@@ -1226,8 +1232,28 @@ def join_rows(left_key, right_key, kind, out_residency=HOST, capacity=None, coun
     else:
         bl, br = np.full(max(capacity, 1), -7, dtype=np.int64), np.full(max(capacity, 1), -7, dtype=np.int64)
         pl, pr = bl.ctypes.data_as(C.c_void_p), br.ctypes.data_as(C.c_void_p)
-    check(lib().bowgpu_join_rows(lp, rp, kind, pl, pr, C.c_int64(capacity), out_residency, C.byref(rows), C.byref(pairs)))
+    check(call(pl, pr, C.c_int64(capacity), out_residency, C.byref(rows), C.byref(pairs)))
     return bl, br, rows.value, pairs.value
+
+
+def _join_call(call, left, right, n_keys, kind, out_residency, outs, capacity, count):
+    """what join and join_keys do with their entry point (call: it, up to `kind`).  Where neither outs nor capacity is given the outputs
+    take the rows the count call states - count(); without a key they follow from the frames' lengths"""
+    if outs is None:
+        if capacity is None:
+            if n_keys == 0:
+                capacity = (left[0].length if left else 0) + (right[0].length if right else 0) if kind == JOIN_OUTER else 0
+            else:
+                capacity = count()
+        outs = [OutColumn(capacity, out_residency) for _ in range(max(len(left) + len(right) - n_keys, 0))]
+    oarr = (Out * max(len(outs), 1))()
+    for i, o in enumerate(outs):
+        oarr[i] = o.c()
+    rows = C.c_int64(0)
+    check(call(oarr, C.byref(rows)))
+    for i, o in enumerate(outs):
+        o.absorb(oarr[i])
+    return outs, rows.value
 
 
 def join(left, left_key, right, right_key, kind, out_residency=HOST, outs=None, capacity=None):
@@ -1235,26 +1261,13 @@ def join(left, left_key, right, right_key, kind, out_residency=HOST, outs=None, 
     (left_key == right_key == -1: no common column - all right columns).  outs / capacity: the output columns or their slots; by
     default the count call (join_rows) sizes them, and bowgpu_join then sorts the right key and probes a second time - a caller who
     knows a bound, or holds outputs from an earlier call, passes `capacity` or `outs` and pays for one pass"""
-    n_outs = len(left) + len(right) - (0 if left_key == -1 and right_key == -1 else 1)
-    if outs is None:
-        if capacity is None:
-            lk = left[left_key] if 0 <= left_key < len(left) else None
-            rk = right[right_key] if 0 <= right_key < len(right) else None
-            if lk is not None and rk is not None:
-                capacity = join_rows(lk, rk, kind, count_only=True)[2]
-            elif left_key == -1 and right_key == -1:
-                capacity = (left[0].length if left else 0) + (right[0].length if right else 0) if kind == JOIN_OUTER else 0
-            else:
-                capacity = 0      # a key index outside its frame: bowgpu_join says so
-        outs = [OutColumn(capacity, out_residency) for _ in range(max(n_outs, 0))]
-    oarr = (Out * max(len(outs), 1))()
-    for i, o in enumerate(outs):
-        oarr[i] = o.c()
-    rows = C.c_int64(0)
-    check(lib().bowgpu_join(_cols(left), len(left), left_key, _cols(right), len(right), right_key, kind, oarr, C.byref(rows)))
-    for i, o in enumerate(outs):
-        o.absorb(oarr[i])
-    return outs, rows.value
+    def count():
+        if 0 <= left_key < len(left) and 0 <= right_key < len(right):
+            return join_rows(left[left_key], right[right_key], kind, count_only=True)[2]
+        return 0      # a key index outside its frame: bowgpu_join says so
+
+    return _join_call(lambda *tail: lib().bowgpu_join(_cols(left), len(left), left_key, _cols(right), len(right), right_key, kind, *tail),
+                      left, right, 0 if left_key == -1 and right_key == -1 else 1, kind, out_residency, outs, capacity, count)
 
 
 def join_keys_rows(left_keys, right_keys, kind, out_residency=HOST, capacity=None, count_only=False):
@@ -1263,22 +1276,8 @@ def join_keys_rows(left_keys, right_keys, kind, out_residency=HOST, capacity=Non
     key pair is equal.  Indices, capacity and count_only as for join_rows"""
     if len(left_keys) != len(right_keys):
         raise ValueError("%d left keys, %d right keys" % (len(left_keys), len(right_keys)))
-    n_keys = len(left_keys)
     lp, rp = _cols(left_keys), _cols(right_keys)
-    rows, pairs = C.c_int64(0), C.c_int64(0)
-    if count_only or capacity is None:
-        check(lib().bowgpu_join_keys_rows(lp, rp, n_keys, kind, None, None, C.c_int64(0), HOST, C.byref(rows), C.byref(pairs)))
-        if count_only:
-            return None, None, rows.value, pairs.value
-        capacity = rows.value
-    if out_residency == DEVICE:
-        bl, br = DeviceBuffer(max(capacity, 1) * 8), DeviceBuffer(max(capacity, 1) * 8)
-        pl, pr = C.c_void_p(bl.ptr), C.c_void_p(br.ptr)
-    else:
-        bl, br = np.full(max(capacity, 1), -7, dtype=np.int64), np.full(max(capacity, 1), -7, dtype=np.int64)
-        pl, pr = bl.ctypes.data_as(C.c_void_p), br.ctypes.data_as(C.c_void_p)
-    check(lib().bowgpu_join_keys_rows(lp, rp, n_keys, kind, pl, pr, C.c_int64(capacity), out_residency, C.byref(rows), C.byref(pairs)))
-    return bl, br, rows.value, pairs.value
+    return _join_rows_call(lambda *tail: lib().bowgpu_join_keys_rows(lp, rp, len(left_keys), kind, *tail), out_residency, capacity, count_only)
 
 
 def join_keys(left, left_keys, right, right_keys, kind, out_residency=HOST, outs=None, capacity=None):
@@ -1288,26 +1287,15 @@ def join_keys(left, left_keys, right, right_keys, kind, out_residency=HOST, outs
     if len(left_keys) != len(right_keys):
         raise ValueError("%d left keys, %d right keys" % (len(left_keys), len(right_keys)))
     n_keys = len(left_keys)
-    n_outs = len(left) + len(right) - n_keys
-    if outs is None:
-        if capacity is None:
-            in_range = all(0 <= k < len(left) for k in left_keys) and all(0 <= k < len(right) for k in right_keys)
-            if n_keys == 0:
-                capacity = (left[0].length if left else 0) + (right[0].length if right else 0) if kind == JOIN_OUTER else 0
-            elif in_range:
-                capacity = join_keys_rows([left[k] for k in left_keys], [right[k] for k in right_keys], kind, count_only=True)[2]
-            else:
-                capacity = 0      # a key index outside its frame: bowgpu_join_keys says so
-        outs = [OutColumn(capacity, out_residency) for _ in range(max(n_outs, 0))]
-    oarr = (Out * max(len(outs), 1))()
-    for i, o in enumerate(outs):
-        oarr[i] = o.c()
-    rows = C.c_int64(0)
+
+    def count():
+        if all(0 <= k < len(left) for k in left_keys) and all(0 <= k < len(right) for k in right_keys):
+            return join_keys_rows([left[k] for k in left_keys], [right[k] for k in right_keys], kind, count_only=True)[2]
+        return 0      # a key index outside its frame: bowgpu_join_keys says so
+
     lk, rk = (C.c_int32 * max(n_keys, 1))(*left_keys), (C.c_int32 * max(n_keys, 1))(*right_keys)
-    check(lib().bowgpu_join_keys(_cols(left), len(left), lk, _cols(right), len(right), rk, n_keys, kind, oarr, C.byref(rows)))
-    for i, o in enumerate(outs):
-        o.absorb(oarr[i])
-    return outs, rows.value
+    return _join_call(lambda *tail: lib().bowgpu_join_keys(_cols(left), len(left), lk, _cols(right), len(right), rk, n_keys, kind, *tail),
+                      left, right, n_keys, kind, out_residency, outs, capacity, count)
 
 
 def out_as_column(out):

@@ -212,6 +212,12 @@ int outs_checks(const bowgpu_out *outs, int32_t ncols, int64_t slots);
 int aux_in(Ctx *c, const void *p, size_t bytes, int32_t residency, const char *what, const void **dptr, DevBuf *own);
 // a device buffer as the only column of a frame without nulls (what the scatter and the argsort take)
 bowgpu_col device_col(const void *values, int64_t n, int32_t type);
+// ... as a key: that column and its prepared form, the pair argsort_device and the join's count take
+struct DeviceKey {
+    bowgpu_col col;
+    DevCol dev;
+    DeviceKey(const void *values, int64_t n, int32_t type);
+};
 bool any_device_out(const bowgpu_out *outs, int32_t n);   // some output column is device-resident (the write epoch moves with the call)
 void out_empty(bowgpu_out *out, int32_t type);            // an output column of a result without rows
 template <class TypeOf> void outs_empty(bowgpu_out *outs, int32_t n, TypeOf type_of) {   // ... n of them, column i of type type_of(i)
@@ -756,6 +762,7 @@ struct SortWork {
     const uint32_t *perm() const { return idx[cur].as<const uint32_t>(); }
 };
 int argsort_device(Ctx *c, const bowgpu_col *key, const DevCol &dk, SortWork *w, int32_t *sorted);
+inline int argsort_device(Ctx *c, const DeviceKey &k, SortWork *w, int32_t *sorted) { return argsort_device(c, &k.col, k.dev, w, sorted); }
 // out[i] = idx[i] as 64 bits: idx32 (row numbers) zero-extended, else idx32s sign-extended (-1 stays -1)
 int launch_widen(Ctx *c, const uint32_t *idx32, const int32_t *idx32s, int64_t n, int64_t *out);
 // The index of a gather, exactly one of three: u32 (the library's own permutation: trusted), i64 (a caller's indices: range-checked,
@@ -953,7 +960,8 @@ struct ValidRowArgs {
 };
 int launch_valid_row(Ctx *c, const ValidRowArgs &a);   // presets *result, searches, hands the word to host_result
 
-// join.hip: Bow.InnerJoin / OuterJoin - the left-ordered lookup join on one key (host side: join_api.cpp)
+// join.hip: Bow.InnerJoin / OuterJoin - the left-ordered lookup join on one probe key per side: a call's one key pair, or the surrogates
+// of several (join_keys.hip, join_host.h).  Host side: join_api.cpp
 struct JoinStats {                       // one device block of a call, zeroed by the host
     unsigned long long pairs;            // length of the reference's commonRows
     unsigned long long matched_left;     // left rows with at least one match

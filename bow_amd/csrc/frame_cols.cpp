@@ -59,6 +59,12 @@ bowgpu_col device_col(const void *values, int64_t n, int32_t type) {
     return k;
 }
 
+DeviceKey::DeviceKey(const void *values, int64_t n, int32_t type) : col(device_col(values, n, type)) {
+    dev.values = values;
+    dev.length = n;
+    dev.type = type;
+}
+
 bool any_device_out(const bowgpu_out *outs, int32_t n) {
     bool device_out = false;
     for (int i = 0; i < n; i++) device_out |= outs[i].residency == BOWGPU_DEVICE;

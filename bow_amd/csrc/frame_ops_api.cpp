@@ -138,22 +138,15 @@ int distinct_device(Ctx *c, const bowgpu_col *col, bowgpu_out *out, int64_t *n_d
     MaskWork vw, tw;
     DevBuf cvals, cbits, gvals, gbits;
     BG_HIP(hipEventRecord(c->ev0, c->stream));
-    bowgpu_col key = *col;
-    DevCol ck;   // the key as the argsort sees it
-    const DevCol *pk = &dk;
     if (dk.vbits) {
         BG_TRY(synced(c, compact_valid_device(c, dk, &vw, &cvals, &cbits, &m)));
         if (m == 0) return 0;
         keys = cvals.as<const uint64_t>();
-        key = device_col(keys, m, col->type);
-        ck.values = keys;
-        ck.length = m;
-        ck.type = col->type;
-        pk = &ck;
     }
     SortWork sw;
     int32_t sorted = 0;
-    const int rc = synced(c, argsort_device(c, &key, *pk, &sw, &sorted));
+    // the key as the argsort sees it: the compacted values, else the column as it lies
+    const int rc = synced(c, dk.vbits ? argsort_device(c, DeviceKey(keys, m, col->type), &sw, &sorted) : argsort_device(c, col, dk, &sw, &sorted));
     if (rc == BOWGPU_ERR_UNSUPPORTED)
         return fail(BOWGPU_ERR_UNSUPPORTED, "column holds a NaN among its valid rows: every NaN is a key of its own in the reference's map and Less "
                                             "is no order there (the caller keeps the reference path)");

@@ -1,39 +1,20 @@
-// join_host.h — what the host files of the join hand each other: join_api.cpp (one key per side) owns the checks, the count and the
-// expand; join_keys_api.cpp (several keys per side) reduces its key tuples to one surrogate key per side and calls them as they stand.
+// join_host.h — the surrogate key of a tuple of keys: what join_api.cpp (the join's entry points and its one host path), join_surrogate.cpp
+// (the host side of the reduction) and join_keys.hip (its kernels) hand each other.
 #pragma once
 
 #include "common.h"
 
 namespace bowgpu {
 
-constexpr int64_t kJoinMaxRows = (int64_t)1 << 31;   // rows inside the kernels are 32 bits wide
-
-// everything a call keeps on the device between its count and its gather
-struct JoinWork {
-    DevCol rk;                 // the right key
-    StagedCols left;           // the left key, by left frame column (moved with its group)
-    const DevCol *lk = nullptr;
-    MaskWork vw, uw;           // the right key's validity; the right-only rows
-    SortWork sw;
-    DevBuf vrows, ckeys, index, simg, first, count, starts, sums, head, stats, ubits, urows, out_l, out_r;
-    int64_t n_left = 0, n_right = 0, rn = 0, rv = 0, rows_left = 0, tail = 0;
-    bool probed = false;       // false: no pair list (an empty side, no common column) - identity rows
+// one key pair's two columns on the device
+struct KeyPair {
+    const DevCol *l, *r;
 };
+// The surrogate keys of n_keys >= 2 key pairs of n_left / n_right rows: packed[0, n_left) the left rows', packed[n_left, n_left + n_right)
+// the right rows', Int64.  Equal exactly when the tuples are (a null equals a null per column), no nulls, no NaN.  Synchronises
+int surrogate_keys(Ctx *c, const KeyPair *keys, int32_t n_keys, int64_t n_left, int64_t n_right, DevBuf *packed);
 
-// the checks of the entry points, in the words every join entry point reports them with
-int join_side_limit(int64_t n, const char *side);
-int join_key_checks(const bowgpu_col *k, const char *side);
-int join_kind_check(int32_t kind);
-int join_types_check(const bowgpu_col *l, const bowgpu_col *r);   // bowjoin.go:135-139, up to the column name
-int join_rows_limit(int64_t rows);
-
-// the count: the right side, the probe, the right-only rows.  *rows / *pairs; nothing of the caller's is written.  Synchronises.
-// lkey_col: the left frame column the key is (the gather then finds it staged in w->left); -1: the key is no frame column
-int join_count_device(Ctx *c, const bowgpu_col *lkey, int32_t lkey_col, const bowgpu_col *rkey, int32_t kind, JoinWork *w, int64_t *rows, int64_t *pairs);
-// the index pairs of the `rows` output rows, as 32-bit rows in the workspace (no synchronise)
-int join_expand_device(Ctx *c, int32_t kind, JoinWork *w, int64_t rows);
-
-// join_keys.hip: the surrogate key of a tuple of keys (host side: join_keys_api.cpp)
+// join_keys.hip
 struct JoinKeysConcatArgs {
     const uint64_t *keys[2];     // left, right
     const uint32_t *vbits[2];    // nullptr: no nulls

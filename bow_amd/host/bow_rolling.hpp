@@ -760,7 +760,6 @@ inline std::pair<BowPtr, Error> Bow::join(const BowPtr &other, int32_t kind, boo
     const Bow &right = *other;
     if (kind == BOWGPU_JOIN_INNER && (NumCols() == 0 || right.NumCols() == 0))   // bowjoin.go:19-29
         return {NumCols() == 0 && right.NumCols() > 0 ? right.NewEmptySlice() : NewEmptySlice(), Error()};
-    int lk = -1, rk = -1, common = 0;
     std::vector<int32_t> lks, rks;   // every common column, in the left bow's order
     for (int i = 0; i < NumCols(); i++) {   // getCommonCols: bowjoin.go:128-155
         int found = -1, n = 0;
@@ -770,54 +769,37 @@ inline std::pair<BowPtr, Error> Bow::join(const BowPtr &other, int32_t kind, boo
         if (n > 1) return {nullptr, Errorf("too many columns have the same name: right:" + right.String() + " left:" + String())};
         if (right.cols[found].typ != cols[i].typ)
             return {nullptr, Errorf("left and right bow on join columns are of incompatible types: " + cols[i].Name)};
-        if (common++ == 0) { lk = i; rk = found; }
         lks.push_back(i);
         rks.push_back(found);
     }
+    const int32_t common = (int32_t)lks.size();
     if (common > 1 && !all_common)
         return {nullptr, Errorf("bow.Join: " + std::to_string(common) + " common columns, the device join takes one")};
-    std::vector<bowgpu_col> lc, rc;
+    if (common > BOWGPU_JOIN_MAX_KEYS)
+        return {nullptr, Errorf("bow.Join: " + std::to_string(common) + " common columns, the device join takes at most " +
+                                std::to_string(BOWGPU_JOIN_MAX_KEYS))};
+    // any number of common columns through the several-keys entry points: none and one are the one-key join there
+    std::vector<bowgpu_col> lc, rc, lkc, rkc;
     for (int i = 0; i < NumCols(); i++) lc.push_back(ArrowCol(i));
     for (int i = 0; i < right.NumCols(); i++) rc.push_back(right.ArrowCol(i));
-    if (common > 1) {   // several keys: the count call sizes the outputs, as below
-        if (common > BOWGPU_JOIN_MAX_KEYS)
-            return {nullptr, Errorf("bow.Join: " + std::to_string(common) + " common columns, the device join takes at most " +
-                                    std::to_string(BOWGPU_JOIN_MAX_KEYS))};
-        std::vector<bowgpu_col> lkc, rkc;
-        for (int k = 0; k < common; k++) {
-            lkc.push_back(lc[(size_t)lks[(size_t)k]]);
-            rkc.push_back(rc[(size_t)rks[(size_t)k]]);
-        }
-        int64_t rows = 0, pairs = 0;
+    for (int32_t k = 0; k < common; k++) {
+        lkc.push_back(lc[(size_t)lks[(size_t)k]]);
+        rkc.push_back(rc[(size_t)rks[(size_t)k]]);
+    }
+    // no input size bounds a join's rows: the count call sizes the outputs (without a common column it is not told the frames' lengths)
+    int64_t rows = kind == BOWGPU_JOIN_OUTER ? (int64_t)NumRows() + right.NumRows() : 0, pairs = 0;
+    if (common > 0)
         if (int rcode = bowgpu_join_keys_rows(lkc.data(), rkc.data(), common, kind, nullptr, nullptr, 0, BOWGPU_HOST, &rows, &pairs))
             return {nullptr, detail::AbiError(rcode)};
-        std::vector<std::string> names;
-        for (int i = 0; i < NumCols(); i++) names.push_back(cols[i].Name);
-        for (int i = 0; i < right.NumCols(); i++)
-            if (std::find(rks.begin(), rks.end(), i) == rks.end()) names.push_back(right.cols[i].Name);
-        std::vector<detail::OutStore> st(names.size());
-        std::vector<bowgpu_out> o(names.size() + 1);
-        for (size_t i = 0; i < names.size(); i++) o[i] = st[i].Make(rows);
-        int64_t got = 0;
-        const int rcode = bowgpu_join_keys(lc.data(), NumCols(), lks.data(), rc.data(), right.NumCols(), rks.data(), common, kind, o.data(), &got);
-        if (rcode) return {nullptr, detail::AbiError(rcode)};
-        auto out = std::make_shared<Bow>();
-        for (size_t i = 0; i < names.size(); i++) out->cols.push_back(st[i].ToSeries(names[i], o[i]));
-        return {out, Error()};
-    }
-    int64_t rows = 0, pairs = 0;   // no input size bounds a join's rows: the count call sizes the outputs
-    if (common == 0) rows = kind == BOWGPU_JOIN_OUTER ? (int64_t)NumRows() + right.NumRows() : 0;
-    else if (int rcode = bowgpu_join_rows(&lc[(size_t)lk], &rc[(size_t)rk], kind, nullptr, nullptr, 0, BOWGPU_HOST, &rows, &pairs))
-        return {nullptr, detail::AbiError(rcode)};
     std::vector<std::string> names;
     for (int i = 0; i < NumCols(); i++) names.push_back(cols[i].Name);
     for (int i = 0; i < right.NumCols(); i++)
-        if (i != rk) names.push_back(right.cols[i].Name);
+        if (std::find(rks.begin(), rks.end(), i) == rks.end()) names.push_back(right.cols[i].Name);
     std::vector<detail::OutStore> st(names.size());
     std::vector<bowgpu_out> o(names.size() + 1);
     for (size_t i = 0; i < names.size(); i++) o[i] = st[i].Make(rows);
     int64_t got = 0;
-    const int rcode = bowgpu_join(lc.data(), NumCols(), lk, rc.data(), right.NumCols(), rk, kind, o.data(), &got);
+    const int rcode = bowgpu_join_keys(lc.data(), NumCols(), lks.data(), rc.data(), right.NumCols(), rks.data(), common, kind, o.data(), &got);
     if (rcode) return {nullptr, detail::AbiError(rcode)};
     auto out = std::make_shared<Bow>();
     for (size_t i = 0; i < names.size(); i++) out->cols.push_back(st[i].ToSeries(names[i], o[i]));

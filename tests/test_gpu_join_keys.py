@@ -248,6 +248,39 @@ def test_key_counts_types_and_positions(n_keys):
         assert len(fewer[0]) != rows, drop
 
 
+@pytest.mark.parametrize("lks", [[10, 5], [0, 1]], ids=["keys-at-5-and-10", "keys-at-0-and-1"])
+def test_a_key_column_anywhere_within_its_piece_of_the_left_frame(lks):
+    """The left frame is gathered in pieces cut after every key column but the last.  11 columns, 4 to a launch.  Keys at 5 and 10: piece
+    0 is columns 0-5 with its key in the second group of four at slot 1, piece 1 is columns 6-10 with its key in the second group at slot
+    0 - and the pairs are listed [10, 5], not in frame order.  Keys at 0 and 1: a piece of one column, then a piece that starts with its
+    key.  A key column's right partner is read through the second index on right-only rows alone: an OuterJoin that has some, nulls in
+    both keys, one Int64 and one Float64 key, one left key host-resident and one device-resident"""
+    rng = np.random.default_rng(11)
+    nl, nr = 300, 200
+    rks = [2, 0]
+
+    def keys(n, span):
+        return icol(rng.integers(0, span, n), rng.random(n) < 0.9), fcol(rng.integers(0, span - 2, n) * 0.5, rng.random(n) < 0.9)
+
+    lkeys, rkeys = keys(nl, 6), keys(nr, 9)      # right tuples beyond the left's: right-only rows
+    fill = [c for seed in range(6) for c in values(nl, 20 + seed)]
+    left = [lkeys[lks.index(i)] if i in lks else fill[i] for i in range(11)]
+    right = [rkeys[1], values(nr, 30)[0], rkeys[0], values(nr, 31)[1]]
+    mix = [HOST, PINNED, DEVICE]
+
+    def res(side, i):
+        if side == 0 and i in lks:
+            return HOST if i == lks[0] else DEVICE
+        return mix[(side + i) % 3]
+
+    for kind in (INNER, OUTER):
+        outs, li, ri = run_keys(left, lks, right, rks, kind, res, DEVICE if kind == OUTER else HOST)
+    right_only = ri[li == -1]
+    assert len(right_only) > 0 and (li >= 0).sum() > nl      # right-only rows, and left rows with several partners
+    for k in range(2):      # ... some of them with a null in each key: the right partner's validity is read there too
+        assert not model.valid_of(right[rks[k]])[right_only].all() and model.valid_of(right[rks[k]])[right_only].any()
+
+
 # ------------------------------------------------------------------ nulls and NaN
 @pytest.mark.parametrize("which", ["none-null", "key0", "key1", "both", "all-null"])
 def test_nulls_in_every_subset_of_the_keys(which):
