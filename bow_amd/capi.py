@@ -179,6 +179,7 @@ SYMBOLS = [
     "bowgpu_convert",
     "bowgpu_parquet_write_codec", "bowgpu_parquet_read_bool_column", "bowgpu_parquet_bool_column_check",
     "bowgpu_equal", "bowgpu_valid_row", "bowgpu_is_col_empty",
+    "bowgpu_parquet_write_bool",
 ]
 
 _lib = None
@@ -1404,14 +1405,17 @@ class ParquetFile:
 PARQUET_CODEC_UNCOMPRESSED, PARQUET_CODEC_SNAPPY = 0, 1   # Parquet CompressionCodec values bowgpu_parquet_write_codec takes
 
 
-def write_parquet(path, cols, names, page_rows=0, row_group_rows=0, encodings=None, statistics=True, metadata=None, reserved=0, codec=0):
+def write_parquet(path, cols, names, page_rows=0, row_group_rows=0, encodings=None, statistics=True, metadata=None, reserved=0, codec=0,
+                  booleans=False):
     """bowgpu_parquet_write: the frame `cols` (Int64 / Float64 Columns of any residency) as the Parquet file `path`, encoded on the
     device.  encodings: None (PLAIN everywhere) or one Parquet Encoding per column (PARQUET_PLAIN / PARQUET_DELTA_BINARY_PACKED /
     PARQUET_RLE_DICTIONARY: per column chunk a dictionary of its distinct 64-bit patterns, built on the device, and bit-packed
     indices; a chunk with more than PARQUET_DICT_MAX patterns or without a valid row comes out PLAIN - ParquetFile.check_column on
     the written file tells);
     metadata: a dict (or a list of pairs) for the footer's key_value_metadata; codec: 0, or another Parquet CompressionCodec
-    (PARQUET_CODEC_SNAPPY: pages compressed on the device) through bowgpu_parquet_write_codec.  Returns the ParquetWriteInfo."""
+    (PARQUET_CODEC_SNAPPY: pages compressed on the device) through bowgpu_parquet_write_codec; booleans: True goes through
+    bowgpu_parquet_write_bool, which admits bit-packed Boolean Columns (written as Parquet BOOLEAN columns, PLAIN) next to the
+    others - without it a Boolean column is declined as ever.  Returns the ParquetWriteInfo."""
     o = ParquetWriteOptions()
     o.row_group_rows, o.page_rows, o.statistics, o.reserved = row_group_rows, page_rows, 1 if statistics else 0, reserved
     if encodings is not None:
@@ -1424,7 +1428,9 @@ def write_parquet(path, cols, names, page_rows=0, row_group_rows=0, encodings=No
         o.meta_keys, o.meta_values, o.n_meta = C.cast(keys, C.POINTER(C.c_char_p)), C.cast(vals, C.POINTER(C.c_char_p)), len(pairs)
     cnames = (C.c_char_p * max(len(names), 1))(*[None if nm is None else nm.encode() for nm in names])
     info = ParquetWriteInfo()
-    if codec == 0:
+    if booleans:
+        check(lib().bowgpu_parquet_write_bool(os.fsencode(path), _cols(cols), cnames, len(cols), C.byref(o), C.c_int32(codec), C.byref(info)))
+    elif codec == 0:
         check(lib().bowgpu_parquet_write(os.fsencode(path), _cols(cols), cnames, len(cols), C.byref(o), C.byref(info)))
     else:
         check(lib().bowgpu_parquet_write_codec(os.fsencode(path), _cols(cols), cnames, len(cols), C.byref(o), C.c_int32(codec), C.byref(info)))

@@ -1,11 +1,12 @@
 // parquet_write.cpp — host side of the device -> Parquet writer (the reference's Bow.WriteParquet, bowparquet.go:157-253, minus
 // its codec): a Thrift compact WRITER for the page headers and the footer (restated from the Parquet format specification), the
-// assembly of the file from the page tables and the level / value images that parquet_encode.hip leaves in host memory, and the
-// entry point bowgpu_parquet_write.  The assembly (PqWriter) is plain C++ over host buffers and touches no device and nothing
-// else of the library; with BOWGPU_PARQUET_ASSEMBLE_ONLY defined this file is that alone (tests/cpp/test_parquet_assemble.cpp).
+// assembly of the file from the page tables and the level / value images that parquet_encode.hip (Boolean columns:
+// parquet_bool_encode.hip) leaves in host memory, and the entry points bowgpu_parquet_write / _codec / _bool.  The assembly
+// (PqWriter) is plain C++ over host buffers and touches no device and nothing else of the library; with
+// BOWGPU_PARQUET_ASSEMBLE_ONLY defined this file is that alone (tests/cpp/test_parquet_assemble.cpp).
 //
-// The file: format version 1, root `Schema`, every column OPTIONAL (bowparquet.go:190), INT64 / DOUBLE, UNCOMPRESSED, data page
-// v1, definition levels as RLE / bit-packed hybrid of bit width 1, PLAIN, DELTA_BINARY_PACKED or RLE_DICTIONARY values (the last
+// The file: format version 1, root `Schema`, every column OPTIONAL (bowparquet.go:190), INT64 / DOUBLE / BOOLEAN, UNCOMPRESSED,
+// data page v1, definition levels as RLE / bit-packed hybrid of bit width 1, PLAIN, DELTA_BINARY_PACKED or RLE_DICTIONARY values (the last
 // behind the chunk's dictionary page, whose entries parquet_dict.hip finds and the host orders).  With codec SNAPPY
 // (bowgpu_parquet_write_codec; the reference's codec, bowparquet.go:326-338) a page's section is one raw Snappy stream of
 // [4-byte levels length | levels | values]: the preamble and the levels literal are written here, the values' elements come from
@@ -298,8 +299,9 @@ int PqWriter::finish(PqwTotals *totals) {
             w.open_struct(12);            //   Statistics
             w.i64(3, ch.stats.null_count);
             if (stats_ && ch.stats.has_minmax) {
-                w.binary(5, &ch.stats.max, 8);   // max_value / min_value: PLAIN little-endian, TYPE_DEFINED_ORDER
-                w.binary(6, &ch.stats.min, 8);
+                const size_t sb = types_[i] == kPqBoolean ? 1 : 8;   // (the low byte of the payload comes first)
+                w.binary(5, &ch.stats.max, sb);   // max_value / min_value: PLAIN little-endian, TYPE_DEFINED_ORDER
+                w.binary(6, &ch.stats.min, sb);
             }
             w.close_struct();
             w.close_struct();
@@ -354,6 +356,8 @@ namespace bowgpu {
 // parquet_encode.hip: rows [a, b) of one column as the pages of one column chunk, encoded on the device and brought back once
 // (codec kPqSnappy: the values sections stay on the device and their Snappy streams come back instead, snappy_encode.hip)
 int pq_encode_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, int32_t page_rows, int32_t encoding, int32_t codec, bool minmax, PqEncChunk *out);
+// parquet_bool_encode.hip: the same for a Boolean column, whose pages hold the value bits of their valid rows (PLAIN)
+int pq_encode_bool_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, int32_t page_rows, int32_t codec, bool minmax, PqEncChunk *out);
 }
 
 using namespace bowgpu;
@@ -364,8 +368,10 @@ constexpr int64_t kWriteMaxRows = ((int64_t)1 << 31) - 1;
 
 struct WritePlan { int64_t n, rg_rows; int32_t page_rows; bool statistics; std::vector<int32_t> enc, types; };
 
-// everything that can be said about the call without a device or the file system
-int write_checks(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols, const bowgpu_parquet_write_options *o, WritePlan *p) {
+// everything that can be said about the call without a device or the file system; booleans: Boolean columns are admitted
+// (bowgpu_parquet_write_bool) - the older entry points decline them with the text they always had
+int write_checks(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols, const bowgpu_parquet_write_options *o, bool booleans,
+                 WritePlan *p) {
     if (!path || !path[0] || !cols || !names) return fail(BOWGPU_ERR_ARG, "null argument");
     if (ncols < 1) return fail(BOWGPU_ERR_ARG, "parquet: a file needs at least one column (ncols = %d)", ncols);
     if (o && o->reserved != 0) return fail(BOWGPU_ERR_ARG, "parquet: bowgpu_parquet_write_options.reserved must be 0");
@@ -382,7 +388,10 @@ int write_checks(const char *path, const bowgpu_col *cols, const char *const *na
     std::set<std::string> seen;
     for (int i = 0; i < ncols; i++) {
         const bowgpu_col &col = cols[i];
-        if (!movable_type(col.type)) return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: column %d is of unsupported type (Int64 / Float64 are written)", i);
+        const bool is_bool = booleans && col.type == BOWGPU_BOOLEAN;
+        if (!movable_type(col.type) && !is_bool)
+            return fail(BOWGPU_ERR_UNSUPPORTED, booleans ? "parquet: column %d is of unsupported type (Int64 / Float64 / Boolean are written)"
+                                                         : "parquet: column %d is of unsupported type (Int64 / Float64 are written)", i);
         if (col.length < 0 || col.offset < 0) return fail(BOWGPU_ERR_ARG, "negative column length/offset");
         if (col.length != p->n) return fail(BOWGPU_ERR_ARG, "columns differ in length");
         if (!residency_ok(col.residency)) return fail(BOWGPU_ERR_ARG, "unknown residency %d", col.residency);
@@ -390,20 +399,22 @@ int write_checks(const char *path, const bowgpu_col *cols, const char *const *na
         if (!names[i] || !names[i][0]) return fail(BOWGPU_ERR_ARG, "parquet: column %d has no name", i);
         if (!seen.insert(names[i]).second) return fail(BOWGPU_ERR_ARG, "parquet: two columns are named '%s'", names[i]);
         const int32_t e = o && o->encodings ? o->encodings[i] : kPqEncPlain;
+        if (is_bool && e != kPqEncPlain)
+            return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: value encoding %d for the Boolean column '%s' (PLAIN = 0 is written; RLE value runs are not)", e, names[i]);
         if (e != kPqEncPlain && e != kPqEncDelta && e != kPqEncRleDict)
             return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: value encoding %d for column '%s' (PLAIN = 0, DELTA_BINARY_PACKED = 5 and RLE_DICTIONARY = 8 are written)", e, names[i]);
         if (e == kPqEncDelta && col.type != BOWGPU_INT64) return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: DELTA_BINARY_PACKED on the Float64 column '%s' (it is written for Int64 columns)", names[i]);
         p->enc.push_back(e);
-        p->types.push_back(col.type == BOWGPU_INT64 ? kPqInt64 : kPqDouble);
+        p->types.push_back(is_bool ? kPqBoolean : col.type == BOWGPU_INT64 ? kPqInt64 : kPqDouble);
     }
     if (p->n > kWriteMaxRows) return fail(BOWGPU_ERR_UNSUPPORTED, "the frame has %lld rows: the writer serves up to 2^31 - 1 = 2147483647 rows", (long long)p->n);
     return 0;
 }
 
 int write_impl(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols, const bowgpu_parquet_write_options *o, int32_t codec,
-               bowgpu_parquet_write_info *info) {
+               bool booleans, bowgpu_parquet_write_info *info) {
     WritePlan plan;
-    BG_TRY(write_checks(path, cols, names, ncols, o, &plan));
+    BG_TRY(write_checks(path, cols, names, ncols, o, booleans, &plan));
     if (codec != kPqUncompressed && codec != kPqSnappy)
         return fail(BOWGPU_ERR_UNSUPPORTED, "parquet: compression codec %d (UNCOMPRESSED = 0 and SNAPPY = 1 are written)", codec);
     Ctx *c;
@@ -416,7 +427,8 @@ int write_impl(const char *path, const bowgpu_col *cols, const char *const *name
         const int64_t b = a + plan.rg_rows < plan.n ? a + plan.rg_rows : plan.n;
         if (w.begin_row_group(b - a) != 0) return fail(BOWGPU_ERR_ARG, "%s", w.error().c_str());
         for (int i = 0; i < ncols; i++) {
-            BG_TRY(synced(c, pq_encode_chunk(c, cols[i], a, b, plan.page_rows, plan.enc[(size_t)i], codec, plan.statistics, &ch)));
+            if (plan.types[(size_t)i] == kPqBoolean) BG_TRY(synced(c, pq_encode_bool_chunk(c, cols[i], a, b, plan.page_rows, codec, plan.statistics, &ch)));
+            else BG_TRY(synced(c, pq_encode_chunk(c, cols[i], a, b, plan.page_rows, plan.enc[(size_t)i], codec, plan.statistics, &ch)));
             // (ch.encoding: PLAIN where a dictionary was asked for and the chunk fell back)
             if (w.add_chunk(ch.encoding, ch.pages.data(), (int64_t)ch.pages.size(), ch.stats, codec, ch.dict.empty() ? nullptr : ch.dict.data(), (int64_t)ch.dict.size()) != 0)
                 return fail(BOWGPU_ERR_ARG, "%s", w.error().c_str());
@@ -441,14 +453,21 @@ int write_impl(const char *path, const bowgpu_col *cols, const char *const *name
 extern "C" int bowgpu_parquet_write(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols,
                                     const bowgpu_parquet_write_options *opts, bowgpu_parquet_write_info *info) {
     // (no C++ exception may cross the C ABI; the writer's destructor has removed the temporary by the time one is caught)
-    try { return write_impl(path, cols, names, ncols, opts, kPqUncompressed, info); }
+    try { return write_impl(path, cols, names, ncols, opts, kPqUncompressed, false, info); }
     catch (const std::bad_alloc &) { return fail(BOWGPU_ERR_OOM, "parquet: out of host memory while writing '%s'", path); }
     catch (const std::exception &e) { return fail(BOWGPU_ERR_ARG, "parquet: writing '%s' failed (%s)", path, e.what()); }
 }
 
 extern "C" int bowgpu_parquet_write_codec(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols,
                                           const bowgpu_parquet_write_options *opts, int32_t codec, bowgpu_parquet_write_info *info) {
-    try { return write_impl(path, cols, names, ncols, opts, codec, info); }
+    try { return write_impl(path, cols, names, ncols, opts, codec, false, info); }
+    catch (const std::bad_alloc &) { return fail(BOWGPU_ERR_OOM, "parquet: out of host memory while writing '%s'", path); }
+    catch (const std::exception &e) { return fail(BOWGPU_ERR_ARG, "parquet: writing '%s' failed (%s)", path, e.what()); }
+}
+
+extern "C" int bowgpu_parquet_write_bool(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols,
+                                         const bowgpu_parquet_write_options *opts, int32_t codec, bowgpu_parquet_write_info *info) {
+    try { return write_impl(path, cols, names, ncols, opts, codec, true, info); }
     catch (const std::bad_alloc &) { return fail(BOWGPU_ERR_OOM, "parquet: out of host memory while writing '%s'", path); }
     catch (const std::exception &e) { return fail(BOWGPU_ERR_ARG, "parquet: writing '%s' failed (%s)", path, e.what()); }
 }

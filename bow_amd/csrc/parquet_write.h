@@ -1,6 +1,7 @@
 // What parquet_write.cpp (the file assembly: plain C++ over host buffers, no device, no other translation unit of the library)
-// and parquet_encode.hip (the encoding of one column chunk on the device) hand each other.  Included by the stand-alone
-// assembly test as well (tests/cpp/test_parquet_assemble.cpp), so nothing here needs HIP.
+// and parquet_encode.hip / parquet_bool_encode.hip (the encoding of one column chunk on the device) hand each other.  Included by
+// the stand-alone assembly tests as well (tests/cpp/test_parquet_assemble.cpp, test_parquet_bool_assemble.cpp), so nothing here
+// needs HIP.
 #pragma once
 
 #include <stdint.h>
@@ -12,7 +13,7 @@
 namespace bowgpu {
 
 constexpr int32_t kPqEncPlain = 0, kPqEncDelta = 5, kPqEncRleDict = 8;   // Parquet Encoding values the writer produces
-constexpr int32_t kPqInt64 = 2, kPqDouble = 5;        // Parquet physical types
+constexpr int32_t kPqBoolean = 0, kPqInt64 = 2, kPqDouble = 5;   // Parquet physical types
 constexpr int32_t kPqUncompressed = 0, kPqSnappy = 1; // Parquet CompressionCodec values the writer produces
 
 // One data page as the assembly takes it: its level BIT bytes (ceil(rows / 8), bit k = row k of the page is valid; read only when
@@ -26,7 +27,7 @@ struct PqwPage {
     const uint8_t *comp = nullptr;
     int64_t comp_bytes = 0;
 };
-// Statistics of one column chunk: min / max are the raw 8-byte payloads of the column's type
+// Statistics of one column chunk: min / max are the raw 8-byte payloads of the column's type (kPqBoolean: 0 / 1, written as one byte)
 struct PqwStats {
     bool has_minmax = false;
     uint64_t min = 0, max = 0;
@@ -62,7 +63,7 @@ public:
     PqWriter(const PqWriter &) = delete;
     PqWriter &operator=(const PqWriter &) = delete;
     ~PqWriter();
-    // types: kPqInt64 / kPqDouble per column; statistics: min / max in the chunk metadata and column_orders in the footer
+    // types: kPqInt64 / kPqDouble / kPqBoolean per column; statistics: min / max in the chunk metadata and column_orders in the footer
     int open(const char *path, const char *const *names, const int32_t *types, int32_t ncols, bool statistics, const char *const *meta_keys,
              const char *const *meta_values, int32_t n_meta);
     int begin_row_group(int64_t rows);

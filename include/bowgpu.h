@@ -54,6 +54,9 @@ extern "C" {
 /* (still 14): bowgpu_parquet_read_bool_column and bowgpu_parquet_bool_column_check (a Parquet BOOLEAN column decoded on the device into a
  * bit-packed Boolean column) added under the same version: two new entry points beside bowgpu_parquet_read_column /
  * bowgpu_parquet_column_check, which keep declining a BOOLEAN column as before; BOWGPU_PARQUET_ENC_RLE added to the encoding bits. */
+/* (still 14): bowgpu_parquet_write_bool (the writer with BOWGPU_BOOLEAN columns admitted, written as Parquet BOOLEAN columns) added under
+ * the same version: a new entry point beside bowgpu_parquet_write / bowgpu_parquet_write_codec, which keep declining a Boolean column as
+ * before; no struct added or changed. */
 #define BOWGPU_ABI_VERSION 14
 
 /* bow.Type (reference bowtypes.go:17-32) */
@@ -63,8 +66,9 @@ enum {
     BOWGPU_INT64 = 2,
     BOWGPU_BOOLEAN = 3,            /* Arrow bit-packed values.  Accepted as a VALUE column of bowgpu_rolling_aggregate and
                                       bowgpu_rolling_aggregate_planned (see there), as source or target of bowgpu_convert and as a
-                                      column of bowgpu_equal (bowgpu_valid_row / bowgpu_is_col_empty read bitmaps alone); every other
-                                      entry point declines it */
+                                      column of bowgpu_equal (bowgpu_valid_row / bowgpu_is_col_empty read bitmaps alone) and of
+                                      bowgpu_parquet_write_bool; what bowgpu_parquet_read_bool_column gives; every other entry point
+                                      declines it */
     BOWGPU_STRING = 4,             /* not accepted by the device path */
     BOWGPU_INPUT_DEPENDENT = 5,
     BOWGPU_ITERATOR_DEPENDENT = 6
@@ -1143,6 +1147,31 @@ int bowgpu_parquet_write(const char *path, const bowgpu_col *cols, const char *c
 int bowgpu_parquet_write_codec(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols,
                                const bowgpu_parquet_write_options *opts /* NULL: defaults */, int32_t codec,
                                bowgpu_parquet_write_info *info /* nullable */);
+
+/* bowgpu_parquet_write_codec with BOWGPU_BOOLEAN columns admitted next to Int64 / Float64: a Boolean column leaves as the Parquet BOOLEAN
+ * column bowgpu_parquet_read_bool_column reads (the reference maps Type_BOOLEAN to Boolean, bowparquet.go:21,28).  A call without a
+ * Boolean column writes, byte for byte, the file bowgpu_parquet_write_codec writes for the same arguments.
+ *   A Boolean column in the file: SchemaElement of physical type BOOLEAN (0), OPTIONAL; data page v1, value encoding PLAIN (0);
+ *   definition levels in the forms of bowgpu_parquet_write.  A page's values section holds the value bits of its k valid rows in row
+ *   order, one bit each, LSB first, ceil(k / 8) bytes, the padding bits of the last byte 0; k = 0: an empty section.  The bits are taken
+ *   out from between the null rows and packed on the device, one pass over the column's two bit ranges per row group; every byte is a
+ *   function of the input alone.
+ *   Input: bowgpu_col.type == BOWGPU_BOOLEAN, values and validity Arrow bit-packed (bit offset + i is row i), any byte address, any
+ *   offset (no multiple of 8 included), the three residencies; validity NULL or null_count 0: every row is valid.  Value bits of null
+ *   rows and bits outside the slice may hold anything: none reaches the file.
+ *   options.encodings[i] of a Boolean column must be 0: 3 (RLE), 5, 8 and every other value are BOWGPU_ERR_UNSUPPORTED with the column
+ *   named.  A String column stays BOWGPU_ERR_UNSUPPORTED.  Every decline and every BOWGPU_ERR_ARG rule of bowgpu_parquet_write applies
+ *   unchanged, before a device or the file system is touched.
+ *   Statistics of a Boolean column chunk: null_count always; with options.statistics min_value / max_value of ONE byte each (0x00 / 0x01,
+ *   false < true): the minimum is false iff some valid row is false, the maximum true iff some valid row is true; both are left out when
+ *   the chunk has no valid row.
+ *   codec: 0 and 1 (SNAPPY) as for bowgpu_parquet_write_codec; under SNAPPY a Boolean page's values section is compressed on the device
+ *   like any other.
+ *   info: value_bytes counts ceil(k / 8) per Boolean page, level_bytes as before.
+ * Not written: RLE value runs, data page v2. */
+int bowgpu_parquet_write_bool(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols,
+                              const bowgpu_parquet_write_options *opts /* NULL: defaults */, int32_t codec,
+                              bowgpu_parquet_write_info *info /* nullable */);
 
 /* ---- row-range sharded Rolling.Aggregate across GPUs: the records the ranks exchange ------------------ */
 
