@@ -1,6 +1,6 @@
 // parquet_bool_encode.hip — the device side of bowgpu_parquet_write_bool for a Boolean column: rows [a, b) of one bit-packed
 // column (one column chunk of one row group) turned into what the pages of a Parquet BOOLEAN column hold.  Hand-written for gfx950
-// (wave64); the file assembly is parquet_write.cpp, the Int64 / Float64 twin parquet_encode.hip.  This is the inverse of the
+// (wave64); the Int64 / Float64 twin is parquet_encode.hip, whose pq_finish_chunk takes this driver's sections over.  This is the inverse of the
 // loader's deposit32 (parquet_decode.hip): there the dense value bits are spread to the valid rows, here they are taken out from
 // between the null rows.
 //
@@ -24,9 +24,8 @@
 // input alone (an OR does not depend on who arrives first).
 #include <string.h>
 
-#include "common.h"
 #include "bitmap_word.h"
-#include "parquet_write.h"
+#include "parquet_encode.h"
 #include "wave_scan.h"
 
 namespace bowgpu {
@@ -129,13 +128,10 @@ __global__ __launch_bounds__(kThreads) void pq_bool_pages_kernel(const uint32_t 
 
 }  // namespace
 
-// snappy_encode.hip
-int pq_snappy_chunk(Ctx *c, const uint8_t *image, const std::vector<int64_t> &off, const std::vector<int64_t> &len, PqHostBytes *out,
-                    std::vector<int64_t> *coff, std::vector<int64_t> *clen);
-
 int pq_encode_bool_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, int32_t page_rows, int32_t codec, bool minmax, PqEncChunk *out) {
-    const int64_t n = b - a, npages = (n + page_rows - 1) / page_rows;
-    const size_t page_bytes = (size_t)page_rows >> 3;   // of a page's levels words, and of its region in the values image: a multiple of 8
+    const PqGrid g(b - a, page_rows);
+    const int64_t n = g.n, npages = g.npages;
+    const size_t page_bytes = g.level_bytes();   // of a page's levels words, and of its region in the values image: a multiple of 8
     out->stats = PqwStats();
     out->encoding = kPqEncPlain;
     out->dict.clear();
@@ -149,34 +145,32 @@ int pq_encode_bool_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, in
     BG_TRY(devboolcol_prepare(c, &view, &dc));
 
     // ---- one pass: levels, sections, counts
-    DevBuf d_levels, d_image, d_counts;
+    DevBuf d_levels;
+    PqSections s;
+    DevBuf d_counts;
     if (dc.v.words) BG_TRY(d_levels.alloc((size_t)npages * page_bytes));
-    BG_TRY(d_image.alloc((size_t)npages * page_bytes));
+    BG_TRY(s.own.alloc((size_t)npages * page_bytes));
     BG_TRY(d_counts.alloc((size_t)npages * 8));
     hipLaunchKernelGGL(pq_bool_pages_kernel, dim3((unsigned)npages), dim3(kThreads), 0, c->stream, dc.t.words, dc.t.bit0, dc.t.nwords, dc.v.words, dc.v.bit0,
-                       dc.v.nwords, n, page_rows, d_levels.as<unsigned long long>(), d_image.as<unsigned long long>(), d_counts.as<uint32_t>());
+                       dc.v.nwords, n, page_rows, d_levels.as<unsigned long long>(), s.own.as<unsigned long long>(), d_counts.as<uint32_t>());
     BG_HIP(hipGetLastError());
-    std::vector<uint32_t> counts((size_t)npages * 2);
+    std::vector<uint32_t> counts((size_t)npages * 2), valid((size_t)npages);
     BG_TRY(copy_d2h(c, counts.data(), d_counts.p, counts.size() * 4));
     BG_HIP(hipStreamSynchronize(c->stream));
+    // ---- the values sections: ceil(k / 8) bytes at the start of each page's region, which begins 8-byte aligned
     int64_t m = 0, trues = 0;
-    bool mixed = false;
-    std::vector<int64_t> voff((size_t)npages), vlen((size_t)npages);
-    size_t used = 0;   // of the image: up to the end of the last section that holds a byte
+    s.image = s.own.as<const uint8_t>();
+    s.off.resize((size_t)npages);
+    s.len.resize((size_t)npages);
     for (int64_t p = 0; p < npages; p++) {
-        const int64_t rows = p + 1 < npages ? page_rows : n - p * page_rows, k = counts[2 * (size_t)p];
+        const int64_t rows = g.rows(p), k = counts[2 * (size_t)p];
         if (k > rows || counts[2 * (size_t)p + 1] > k) return fail(BOWGPU_ERR_HIP, "parquet: page %lld of a Boolean chunk counts %lld valid rows of %lld", (long long)p, (long long)k, (long long)rows);
+        valid[(size_t)p] = (uint32_t)k;
         m += k;
         trues += counts[2 * (size_t)p + 1];
-        mixed |= k != 0 && k != rows;
-        voff[(size_t)p] = (int64_t)((size_t)p * page_bytes);
-        vlen[(size_t)p] = (k + 7) >> 3;
-        if (k > 0) used = (size_t)(voff[(size_t)p] + vlen[(size_t)p]);
-    }
-    const uint8_t *h_levels = nullptr;
-    if (mixed) {
-        h_levels = out->levels.take((size_t)npages * page_bytes);
-        BG_TRY(copy_d2h(c, out->levels.take(0), d_levels.p, (size_t)npages * page_bytes));
+        s.off[(size_t)p] = (int64_t)((size_t)p * page_bytes);
+        s.len[(size_t)p] = (k + 7) >> 3;
+        if (k > 0) s.used = (size_t)(s.off[(size_t)p] + s.len[(size_t)p]);
     }
 
     // ---- statistics: false < true
@@ -186,30 +180,7 @@ int pq_encode_bool_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, in
         out->stats.min = trues < m ? 0 : 1;
         out->stats.max = trues > 0 ? 1 : 0;
     }
-
-    // ---- the values sections: the image brought back in one copy as it lies (at most 1/8 byte a row; the file takes ceil(k / 8)
-    // bytes of each page's region), or (kPqSnappy) left on the device for the codec, whose sections want 8-byte-aligned offsets
-    const bool snappy = codec == kPqSnappy;
-    std::vector<int64_t> coff, clen;
-    if (snappy) {
-        BG_TRY(pq_snappy_chunk(c, d_image.as<const uint8_t>(), voff, vlen, &out->comp, &coff, &clen));   // (returns with the stream drained)
-    } else {
-        BG_TRY(copy_d2h(c, out->values.take(used), d_image.p, used));
-        BG_HIP(hipStreamSynchronize(c->stream));
-    }
-
-    out->pages.resize((size_t)npages);
-    for (int64_t p = 0; p < npages; p++) {
-        PqwPage &pg = out->pages[(size_t)p];
-        pg.rows = (int32_t)(p + 1 < npages ? page_rows : n - p * page_rows);
-        pg.valid = (int32_t)counts[2 * (size_t)p];
-        pg.level_bits = mixed ? h_levels + (size_t)p * page_bytes : nullptr;
-        pg.values = snappy ? nullptr : out->values.take(0) + voff[(size_t)p];
-        pg.value_bytes = vlen[(size_t)p];
-        pg.comp = snappy ? out->comp.take(0) + coff[(size_t)p] : nullptr;
-        pg.comp_bytes = snappy ? clen[(size_t)p] : 0;
-    }
-    return 0;
+    return pq_finish_chunk(c, g, valid, d_levels.p, s, codec, out);
 }
 
 }  // namespace bowgpu

@@ -1,6 +1,6 @@
 // parquet_dict.hip — RLE_DICTIONARY for bowgpu_parquet_write: the dictionary of one column chunk built on the device, and the
 // chunk's values sections (bit width, one bit-packed run of dictionary indices per page).  Hand-written for gfx950 (wave64); called
-// by pq_encode_chunk (parquet_encode.hip) with the chunk's dense values and page counts, the file assembly is parquet_write.cpp.
+// by pq_encode_chunk (parquet_encode.hip) with the chunk's dense values and page counts - pq_dict_chunk, declared in parquet_encode.h.
 //
 //   pq_dict_insert_kernel   the distinct 64-bit patterns of the dense values, capped.  A workgroup keeps the patterns it has met in a
 //                           small LDS set, so that a value goes to global memory once per workgroup at the most while the set has
@@ -25,8 +25,7 @@
 #include <algorithm>
 #include <numeric>
 
-#include "common.h"
-#include "parquet_write.h"
+#include "parquet_encode.h"
 
 namespace bowgpu {
 
@@ -193,12 +192,7 @@ __global__ __launch_bounds__(kThreads) void pq_dict_pack_kernel(const uint64_t *
 
 }  // namespace
 
-// The dictionary of the chunk's dense values (m > 0 of them, page p holds counts[p]) and its values sections.  *fallback: more than
-// BOWGPU_PARQUET_DICT_MAX distinct patterns, nothing else is set.  Else dict holds the entries in the contract's order, image the
-// sections - page p's at off[p], a multiple of 8, len[p] bytes, the image readable up to the next multiple of 8 - and the stream
-// has drained.
-int pq_dict_chunk(Ctx *c, const uint64_t *dense, int64_t m, const std::vector<uint32_t> &counts, std::vector<uint64_t> *dict, DevBuf *image,
-                  std::vector<int64_t> *off, std::vector<int64_t> *len, bool *fallback) {
+int pq_dict_chunk(Ctx *c, const uint64_t *dense, int64_t m, const std::vector<uint32_t> &counts, std::vector<uint64_t> *dict, PqSections *s, bool *fallback) {
     const int64_t npages = (int64_t)counts.size();
     DevBuf d_table, d_ctl, d_entries, d_eslot, d_rank, d_slot_rank, d_pages;
     BG_TRY(d_table.alloc(((size_t)kTableSlots + 1) * 8));
@@ -243,8 +237,8 @@ int pq_dict_chunk(Ctx *c, const uint64_t *dense, int64_t m, const std::vector<ui
     uint32_t width = 1;
     while (width < 16 && (1u << width) < entries) width++;
     std::vector<PqDictPage> pages((size_t)npages + 1);
-    off->resize((size_t)npages);
-    len->resize((size_t)npages);
+    s->off.resize((size_t)npages);
+    s->len.resize((size_t)npages);
     int64_t v0 = 0, groups = 0;
     uint64_t at = 0;
     for (int64_t p = 0; p <= npages; p++) {
@@ -252,19 +246,21 @@ int pq_dict_chunk(Ctx *c, const uint64_t *dense, int64_t m, const std::vector<ui
         pages[(size_t)p] = PqDictPage{v0, at, (int32_t)cnt, (uint32_t)groups};
         if (p == npages) break;
         const uint64_t bytes = dict_lead_bytes(cnt) + (uint64_t)((cnt + 7) >> 3) * width;
-        (*off)[(size_t)p] = (int64_t)at;
-        (*len)[(size_t)p] = (int64_t)bytes;
+        s->off[(size_t)p] = (int64_t)at;
+        s->len[(size_t)p] = (int64_t)bytes;
+        s->used = (size_t)(at + bytes);   // (every section holds its width byte)
         at += (bytes + 7) & ~(uint64_t)7;
         v0 += cnt;
         groups += cnt > 0 ? (cnt + kPackValues - 1) / kPackValues : 1;
     }
     if (v0 != m) return fail(BOWGPU_ERR_HIP, "parquet: the page counts (%lld) and the dense values (%lld) disagree", (long long)v0, (long long)m);
-    BG_TRY(image->alloc((size_t)at));
+    BG_TRY(s->own.alloc((size_t)at));
+    s->image = s->own.as<const uint8_t>();
     BG_TRY(d_pages.alloc(pages.size() * sizeof(PqDictPage)));
     BG_TRY(copy_h2d(c, d_pages.p, pages.data(), pages.size() * sizeof(PqDictPage)));
     hipLaunchKernelGGL(pq_dict_pack_kernel, dim3((unsigned)groups), dim3(kThreads), 0, c->stream, dense, d_pages.as<const PqDictPage>(), npages,
                        d_table.as<const unsigned long long>(), d_slot_rank.as<const uint16_t>(), width, ctl.has_empty, d_ctl.as<PqDictCtl>(),
-                       image->as<uint8_t>());
+                       s->own.as<uint8_t>());
     BG_HIP(hipGetLastError());
     BG_TRY(copy_d2h(c, &ctl, d_ctl.p, sizeof ctl));
     BG_HIP(hipStreamSynchronize(c->stream));

@@ -12,16 +12,17 @@
 //   pq_delta_pack_kernel    one wavefront per block: the block's bytes assembled in LDS - one lane per 32-bit word of a miniblock,
 //                           built from the remainders that overlap it - and stored with aligned 8-byte stores, bytes at the edges
 //   (RLE_DICTIONARY: parquet_dict.hip finds the chunk's dictionary and packs the indices - pq_dict_chunk; a chunk without a value
-//    or with more distinct patterns than the cap takes the PLAIN branch here, and PqEncChunk::encoding says which it was)
+//    or with more distinct patterns than the cap is written PLAIN here, and PqEncChunk::encoding says which it was)
 //   (codec SNAPPY: the values sections stay on the device and snappy_encode.hip compresses them there - pq_snappy_chunk)
+// The host side: pq_encode_chunk, a list of named steps, and pq_finish_chunk, the hand-over to parquet_write.cpp that it shares with
+// pq_encode_bool_chunk (parquet_bool_encode.hip).  What crosses files is declared once, in parquet_encode.h.
 //
 // No atomics, no workgroup waits on another, every byte of the output is a function of the input alone.  Nothing reads or
 // writes global memory unaligned: a block body starts at an arbitrary byte of the image, so its LDS copy is laid out at the same
 // offset inside an 8-byte word as its destination.
 #include <string.h>
 
-#include "common.h"
-#include "parquet_write.h"
+#include "parquet_encode.h"
 
 namespace bowgpu {
 
@@ -282,14 +283,45 @@ int checked_launch() {
     return 0;
 }
 
-// the row group's non-null values in row order (what frame_ops_api.cpp does for Bow.Distinct's key)
-int compact_valid(Ctx *c, const DevCol &dk, MaskWork *w, DevBuf *vals, DevBuf *bits, int64_t *m) {
+// ---------------------------------------------------------------- the steps of pq_encode_chunk
+// rows [a, b) on the device, from an 8-row boundary: one bit offset serves values and bits
+int stage_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, DevBuf *svals, DevBuf *sbits, DevCol *dk) {
+    bowgpu_col piece;
+    BG_TRY(stage_rows(c, c->device, c->device, col, a, b, svals, sbits, &piece));
+    piece = uncounted(piece);
+    return devcol_prepare(c, &piece, dk, true, true);
+}
+
+// counts[p]: page p's valid rows, *m: the chunk's; d_levels: the levels image, where the column has a bitmap to read
+int page_levels(Ctx *c, const DevCol &dk, const PqGrid &g, DevBuf *d_levels, DevBuf *d_counts, std::vector<uint32_t> *counts, int64_t *m) {
+    counts->resize((size_t)g.npages);
+    if (dk.vbits) {
+        BG_TRY(d_levels->alloc((size_t)g.npages * g.level_bytes()));
+        BG_TRY(d_counts->alloc((size_t)g.npages * 4));
+        hipLaunchKernelGGL(pq_page_levels_kernel, dim3((unsigned)g.npages), dim3(kThreads), 0, c->stream, dk.vbits, dk.vbit0, dk.vwords, g.n, g.page_rows,
+                           d_levels->as<unsigned long long>(), d_counts->as<uint32_t>());
+        BG_TRY(checked_launch());
+        BG_TRY(copy_d2h(c, counts->data(), d_counts->p, (size_t)g.npages * 4));
+        BG_HIP(hipStreamSynchronize(c->stream));
+    }
+    *m = 0;
+    for (int64_t p = 0; p < g.npages; p++) {
+        if (!dk.vbits) (*counts)[(size_t)p] = (uint32_t)g.rows(p);
+        *m += (*counts)[(size_t)p];
+    }
+    return 0;
+}
+
+// *dense: the chunk's m non-null values in row order (what frame_ops_api.cpp does for Bow.Distinct's key); a chunk without nulls
+// is its own dense array
+int compact_valid(Ctx *c, const DevCol &dk, int64_t m, MaskWork *w, DevBuf *vals, DevBuf *bits, const uint64_t **dense) {
+    *dense = reinterpret_cast<const uint64_t *>(dk.values);
+    if (m == 0 || m == dk.length) return 0;
     TileRecords t;
     BG_TRY(valid_rows_scanned(c, dk, w, &t));
-    *m = w->selected;
-    if (*m == 0) return 0;
-    BG_TRY(vals->alloc(temp_values_bytes(*m)));
-    BG_TRY(bits->alloc((size_t)((*m + 63) >> 6) * 8));
+    if (w->selected != m) return fail(BOWGPU_ERR_HIP, "parquet: the page counts (%lld) and the compaction (%lld) disagree", (long long)m, (long long)w->selected);
+    BG_TRY(vals->alloc(temp_values_bytes(m)));
+    BG_TRY(bits->alloc((size_t)((m + 63) >> 6) * 8));
     FilterScatterArgs s;
     memset(&s, 0, sizeof s);
     s.cols.ncols = 1;
@@ -300,206 +332,179 @@ int compact_valid(Ctx *c, const DevCol &dk, MaskWork *w, DevBuf *vals, DevBuf *b
     s.mask = t.mask;
     s.tile_base = t.tile_counts;
     BG_HIP(hipMemsetAsync(bits->p, 0, bits->bytes, c->stream));
+    *dense = vals->as<const uint64_t>();
     return launch_filter_scatter(c, s);
+}
+
+// the (min, max, any) records of the m > 0 dense values on their way into rec: read them behind a synchronise (fold_minmax)
+int launch_minmax(Ctx *c, bool is_float, const uint64_t *dense, int64_t m, DevBuf *d_rec, std::vector<uint64_t> *rec) {
+    const int64_t grid = stream_grid(m, kThreads);
+    rec->resize((size_t)grid * 3);
+    BG_TRY(d_rec->alloc(rec->size() * 8));
+    if (is_float) hipLaunchKernelGGL(pq_minmax_kernel<true>, dim3((unsigned)grid), dim3(kThreads), 0, c->stream, dense, m, d_rec->as<uint64_t>());
+    else hipLaunchKernelGGL(pq_minmax_kernel<false>, dim3((unsigned)grid), dim3(kThreads), 0, c->stream, dense, m, d_rec->as<uint64_t>());
+    BG_TRY(checked_launch());
+    return copy_d2h(c, rec->data(), d_rec->p, rec->size() * 8);
+}
+
+void fold_minmax(const std::vector<uint64_t> &rec, bool is_float, PqwStats *st) {
+    bool any = false;
+    uint64_t mn = 0, mx = 0;
+    auto less = [&](uint64_t x, uint64_t y) {
+        if (!is_float) return (int64_t)x < (int64_t)y;
+        double dx, dy;
+        memcpy(&dx, &x, 8);
+        memcpy(&dy, &y, 8);
+        return dx < dy;
+    };
+    for (size_t k = 0; k + 2 < rec.size(); k += 3) {
+        if (!rec[k + 2]) continue;
+        if (!any || less(rec[k], mn)) mn = rec[k];
+        if (!any || less(mx, rec[k + 1])) mx = rec[k + 1];
+        any = true;
+    }
+    if (any && is_float) {   // TYPE_DEFINED_ORDER: a zero minimum is written as -0.0, a zero maximum as +0.0
+        if ((mn << 1) == 0) mn = 0x8000000000000000ull;
+        if ((mx << 1) == 0) mx = 0;
+    }
+    st->has_minmax = any;
+    st->min = mn;
+    st->max = mx;
+}
+
+// PLAIN: the sections lie in the dense values as they are
+void plain_sections(const uint64_t *dense, const std::vector<uint32_t> &counts, PqSections *s) {
+    s->image = reinterpret_cast<const uint8_t *>(dense);
+    s->off.clear();
+    s->len.clear();
+    int64_t v0 = 0;
+    for (const uint32_t cnt : counts) {
+        s->off.push_back(8 * v0);
+        s->len.push_back(8 * (int64_t)cnt);
+        v0 += cnt;
+    }
+    s->used = (size_t)v0 * 8;
+}
+
+// DELTA_BINARY_PACKED: sizes, their scan, the page headers, the pack pass; the stream has drained when this returns
+int delta_sections(Ctx *c, const uint64_t *dense, const std::vector<uint32_t> &counts, PqSections *s) {
+    const int64_t npages = (int64_t)counts.size();
+    DevBuf d_pages, d_min, d_widths, d_bytes, d_sums, d_info;
+    std::vector<PqDevPage> pages((size_t)npages + 1);
+    int64_t v0 = 0, nblocks = 0;
+    for (int64_t p = 0; p <= npages; p++) {
+        const int64_t cnt = p < npages ? counts[(size_t)p] : 0;
+        pages[(size_t)p] = PqDevPage{v0, (int32_t)cnt, (uint32_t)nblocks};
+        v0 += cnt;
+        nblocks += cnt > 1 ? (cnt - 1 + kDeltaBlock - 1) / kDeltaBlock : 0;
+    }
+    BG_TRY(d_pages.alloc(pages.size() * sizeof(PqDevPage)));
+    BG_TRY(copy_h2d(c, d_pages.p, pages.data(), pages.size() * sizeof(PqDevPage)));
+    BG_TRY(d_min.alloc((size_t)(nblocks + 1) * 8));
+    BG_TRY(d_widths.alloc((size_t)(nblocks + 1) * 4));
+    BG_TRY(d_bytes.alloc((size_t)(nblocks + 1) * 4));
+    BG_TRY(d_sums.alloc((size_t)((nblocks + 1 + 4095) / 4096) * 4));
+    BG_TRY(d_info.alloc((size_t)npages * sizeof(PqDevInfo)));
+    const unsigned wgrid = (unsigned)((nblocks + kWaves - 1) / kWaves);
+    BG_HIP(hipMemsetAsync(d_bytes.as<uint32_t>() + nblocks, 0, 4, c->stream));
+    if (nblocks > 0) {
+        hipLaunchKernelGGL(pq_delta_sizes_kernel, dim3(wgrid), dim3(kThreads), 0, c->stream, dense, d_pages.as<const PqDevPage>(), npages, (uint32_t)nblocks,
+                           d_min.as<int64_t>(), d_widths.as<uint32_t>(), d_bytes.as<uint32_t>());
+        BG_TRY(checked_launch());
+    }
+    BG_TRY(launch_scan_u32(c, d_bytes.as<uint32_t>(), nblocks + 1, d_sums.as<uint32_t>()));
+    uint32_t total = 0;   // a row group of at most 2^27 rows stays below 2^32 bytes (at most 1038 per 128 values)
+    BG_HIP(hipMemcpyAsync(&total, d_bytes.as<uint32_t>() + nblocks, 4, hipMemcpyDeviceToHost, c->stream));
+    BG_HIP(hipStreamSynchronize(c->stream));
+    const size_t image_bytes = (((size_t)total + 7) & ~(size_t)7) + (size_t)kPageSlack * (size_t)(npages + 1);
+    BG_TRY(s->own.alloc(image_bytes));
+    hipLaunchKernelGGL(pq_delta_pages_kernel, dim3((unsigned)((npages + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, dense,
+                       d_pages.as<const PqDevPage>(), npages, d_bytes.as<const uint32_t>(), s->own.as<uint8_t>(), d_info.as<PqDevInfo>());
+    BG_TRY(checked_launch());
+    if (nblocks > 0) {
+        hipLaunchKernelGGL(pq_delta_pack_kernel, dim3(wgrid), dim3(kThreads), 0, c->stream, dense, d_pages.as<const PqDevPage>(), npages, (uint32_t)nblocks,
+                           d_min.as<const int64_t>(), d_widths.as<const uint32_t>(), d_bytes.as<const uint32_t>(), d_info.as<const PqDevInfo>(),
+                           s->own.as<uint8_t>());
+        BG_TRY(checked_launch());
+    }
+    std::vector<PqDevInfo> info((size_t)npages);
+    BG_TRY(copy_d2h(c, info.data(), d_info.p, info.size() * sizeof(PqDevInfo)));
+    BG_HIP(hipStreamSynchronize(c->stream));
+    s->image = s->own.as<const uint8_t>();
+    s->off.resize((size_t)npages);
+    s->len.resize((size_t)npages);
+    s->used = 0;
+    for (int64_t p = 0; p < npages; p++) {
+        s->off[(size_t)p] = (int64_t)info[(size_t)p].off;
+        s->len[(size_t)p] = info[(size_t)p].bytes;
+        if ((size_t)(s->off[(size_t)p] + s->len[(size_t)p]) > s->used) s->used = (size_t)(s->off[(size_t)p] + s->len[(size_t)p]);
+    }
+    if (s->used > image_bytes) return fail(BOWGPU_ERR_HIP, "parquet: a page's values section lies outside the image");
+    return 0;
 }
 
 }  // namespace
 
-// snappy_encode.hip
-int pq_snappy_chunk(Ctx *c, const uint8_t *image, const std::vector<int64_t> &off, const std::vector<int64_t> &len, PqHostBytes *out,
-                    std::vector<int64_t> *coff, std::vector<int64_t> *clen);
-// parquet_dict.hip
-int pq_dict_chunk(Ctx *c, const uint64_t *dense, int64_t m, const std::vector<uint32_t> &counts, std::vector<uint64_t> *dict, DevBuf *image,
-                  std::vector<int64_t> *off, std::vector<int64_t> *len, bool *fallback);
-
-int pq_encode_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, int32_t page_rows, int32_t encoding, int32_t codec, bool minmax, PqEncChunk *out) {
-    const int64_t n = b - a, npages = (n + page_rows - 1) / page_rows;
-    const size_t page_level_bytes = (size_t)page_rows >> 3;
-    const bool is_float = col.type == BOWGPU_FLOAT64;
-    // ---- the rows on the device, from an 8-row boundary: one bit offset serves values and bits
-    DevBuf svals, sbits;
-    bowgpu_col piece;
-    BG_TRY(stage_rows(c, c->device, c->device, col, a, b, &svals, &sbits, &piece));
-    piece = uncounted(piece);
-    DevCol dk;
-    BG_TRY(devcol_prepare(c, &piece, &dk, true, true));
-
-    // ---- page counts and the levels image
-    std::vector<uint32_t> counts((size_t)npages);
-    DevBuf d_levels, d_counts;
-    int64_t m = 0;
-    bool mixed = false;
-    if (dk.vbits) {
-        BG_TRY(d_levels.alloc((size_t)npages * page_level_bytes));
-        BG_TRY(d_counts.alloc((size_t)npages * 4));
-        hipLaunchKernelGGL(pq_page_levels_kernel, dim3((unsigned)npages), dim3(kThreads), 0, c->stream, dk.vbits, dk.vbit0, dk.vwords, n, page_rows,
-                           d_levels.as<unsigned long long>(), d_counts.as<uint32_t>());
-        BG_TRY(checked_launch());
-        BG_TRY(copy_d2h(c, counts.data(), d_counts.p, (size_t)npages * 4));
-        BG_HIP(hipStreamSynchronize(c->stream));
-    }
-    for (int64_t p = 0; p < npages; p++) {
-        const int64_t rows = p + 1 < npages ? page_rows : n - p * page_rows;
-        if (!dk.vbits) counts[(size_t)p] = (uint32_t)rows;
-        m += counts[(size_t)p];
-        mixed |= counts[(size_t)p] != 0 && counts[(size_t)p] != (uint32_t)rows;
-    }
-    const uint8_t *h_levels = nullptr;
-    if (mixed) {
-        h_levels = out->levels.take((size_t)npages * page_level_bytes);
-        BG_TRY(copy_d2h(c, out->levels.take(0), d_levels.p, (size_t)npages * page_level_bytes));
-    }
-
-    // ---- the dense values
-    MaskWork mw;
-    DevBuf dvals, dbits;
-    const uint64_t *dense = reinterpret_cast<const uint64_t *>(dk.values);   // a chunk without nulls is its own dense array
-    if (m > 0 && m < n) {
-        int64_t kept = 0;
-        BG_TRY(compact_valid(c, dk, &mw, &dvals, &dbits, &kept));
-        if (kept != m) return fail(BOWGPU_ERR_HIP, "parquet: the page counts (%lld) and the compaction (%lld) disagree", (long long)m, (long long)kept);
-        dense = dvals.as<const uint64_t>();
-    }
-
-    // ---- statistics
-    out->stats = PqwStats();
-    out->stats.null_count = n - m;
-    DevBuf d_rec;
-    std::vector<uint64_t> rec;
-    if (minmax && m > 0) {
-        const int64_t grid = stream_grid(m, kThreads);
-        rec.resize((size_t)grid * 3);
-        BG_TRY(d_rec.alloc(rec.size() * 8));
-        if (is_float) hipLaunchKernelGGL(pq_minmax_kernel<true>, dim3((unsigned)grid), dim3(kThreads), 0, c->stream, dense, m, d_rec.as<uint64_t>());
-        else hipLaunchKernelGGL(pq_minmax_kernel<false>, dim3((unsigned)grid), dim3(kThreads), 0, c->stream, dense, m, d_rec.as<uint64_t>());
-        BG_TRY(checked_launch());
-        BG_TRY(copy_d2h(c, rec.data(), d_rec.p, rec.size() * 8));
-    }
-
-    // ---- the values sections: brought back as they are, or (kPqSnappy) left on the device for the codec
+int pq_finish_chunk(Ctx *c, const PqGrid &g, const std::vector<uint32_t> &valid, const void *d_levels, const PqSections &s, int32_t codec, PqEncChunk *out) {
     const bool snappy = codec == kPqSnappy;
-    const uint8_t *d_sections = reinterpret_cast<const uint8_t *>(dense);
-    std::vector<int64_t> voff((size_t)npages), vlen((size_t)npages);
-    DevBuf d_pages, d_min, d_widths, d_bytes, d_sums, d_info, d_image;
-    out->dict.clear();
-    if (encoding == kPqEncRleDict) {   // a chunk without a value, or with more distinct patterns than the cap: the PLAIN branch below
-        bool fallback = m == 0;
-        if (!fallback) BG_TRY(pq_dict_chunk(c, dense, m, counts, &out->dict, &d_image, &voff, &vlen, &fallback));
-        if (fallback) {
-            encoding = kPqEncPlain;
-        } else {
-            if (!snappy) {
-                BG_TRY(copy_d2h(c, out->values.take(d_image.bytes), d_image.p, d_image.bytes));
-                BG_HIP(hipStreamSynchronize(c->stream));
-            }
-            d_sections = d_image.as<const uint8_t>();
-        }
-    }
-    out->encoding = encoding;
-    if (encoding == kPqEncPlain) {
-        if (!snappy) {
-            BG_TRY(copy_d2h(c, out->values.take((size_t)m * 8), dense, (size_t)m * 8));
-            BG_HIP(hipStreamSynchronize(c->stream));
-        }
-        int64_t v0 = 0;
-        for (int64_t p = 0; p < npages; p++) {
-            voff[(size_t)p] = 8 * v0;
-            vlen[(size_t)p] = 8 * (int64_t)counts[(size_t)p];
-            v0 += counts[(size_t)p];
-        }
-    } else if (encoding == kPqEncDelta) {
-        std::vector<PqDevPage> pages((size_t)npages + 1);
-        int64_t v0 = 0, nblocks = 0;
-        for (int64_t p = 0; p <= npages; p++) {
-            const int64_t cnt = p < npages ? counts[(size_t)p] : 0;
-            pages[(size_t)p] = PqDevPage{v0, (int32_t)cnt, (uint32_t)nblocks};
-            v0 += cnt;
-            nblocks += cnt > 1 ? (cnt - 1 + kDeltaBlock - 1) / kDeltaBlock : 0;
-        }
-        BG_TRY(d_pages.alloc(pages.size() * sizeof(PqDevPage)));
-        BG_TRY(copy_h2d(c, d_pages.p, pages.data(), pages.size() * sizeof(PqDevPage)));
-        BG_TRY(d_min.alloc((size_t)(nblocks + 1) * 8));
-        BG_TRY(d_widths.alloc((size_t)(nblocks + 1) * 4));
-        BG_TRY(d_bytes.alloc((size_t)(nblocks + 1) * 4));
-        BG_TRY(d_sums.alloc((size_t)((nblocks + 1 + 4095) / 4096) * 4));
-        BG_TRY(d_info.alloc((size_t)npages * sizeof(PqDevInfo)));
-        const unsigned wgrid = (unsigned)((nblocks + kWaves - 1) / kWaves);
-        BG_HIP(hipMemsetAsync(d_bytes.as<uint32_t>() + nblocks, 0, 4, c->stream));
-        if (nblocks > 0) {
-            hipLaunchKernelGGL(pq_delta_sizes_kernel, dim3(wgrid), dim3(kThreads), 0, c->stream, dense, d_pages.as<const PqDevPage>(), npages, (uint32_t)nblocks,
-                               d_min.as<int64_t>(), d_widths.as<uint32_t>(), d_bytes.as<uint32_t>());
-            BG_TRY(checked_launch());
-        }
-        BG_TRY(launch_scan_u32(c, d_bytes.as<uint32_t>(), nblocks + 1, d_sums.as<uint32_t>()));
-        uint32_t total = 0;   // a row group of at most 2^27 rows stays below 2^32 bytes (at most 1038 per 128 values)
-        BG_HIP(hipMemcpyAsync(&total, d_bytes.as<uint32_t>() + nblocks, 4, hipMemcpyDeviceToHost, c->stream));
-        BG_HIP(hipStreamSynchronize(c->stream));
-        const size_t image_bytes = (((size_t)total + 7) & ~(size_t)7) + (size_t)kPageSlack * (size_t)(npages + 1);
-        BG_TRY(d_image.alloc(image_bytes));
-        hipLaunchKernelGGL(pq_delta_pages_kernel, dim3((unsigned)((npages + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, dense,
-                           d_pages.as<const PqDevPage>(), npages, d_bytes.as<const uint32_t>(), d_image.as<uint8_t>(), d_info.as<PqDevInfo>());
-        BG_TRY(checked_launch());
-        if (nblocks > 0) {
-            hipLaunchKernelGGL(pq_delta_pack_kernel, dim3(wgrid), dim3(kThreads), 0, c->stream, dense, d_pages.as<const PqDevPage>(), npages, (uint32_t)nblocks,
-                               d_min.as<const int64_t>(), d_widths.as<const uint32_t>(), d_bytes.as<const uint32_t>(), d_info.as<const PqDevInfo>(),
-                               d_image.as<uint8_t>());
-            BG_TRY(checked_launch());
-        }
-        std::vector<PqDevInfo> info((size_t)npages);
-        BG_TRY(copy_d2h(c, info.data(), d_info.p, info.size() * sizeof(PqDevInfo)));
-        BG_HIP(hipStreamSynchronize(c->stream));
-        size_t used = 0;
-        for (int64_t p = 0; p < npages; p++) {
-            voff[(size_t)p] = (int64_t)info[(size_t)p].off;
-            vlen[(size_t)p] = info[(size_t)p].bytes;
-            if ((size_t)(voff[(size_t)p] + vlen[(size_t)p]) > used) used = (size_t)(voff[(size_t)p] + vlen[(size_t)p]);
-        }
-        if (used > image_bytes) return fail(BOWGPU_ERR_HIP, "parquet: a page's values section lies outside the image");
-        if (!snappy) {
-            BG_TRY(copy_d2h(c, out->values.take(used), d_image.p, used));
-            BG_HIP(hipStreamSynchronize(c->stream));
-        }
-        d_sections = d_image.as<const uint8_t>();
-    }
+    bool mixed = false;
+    for (int64_t p = 0; p < g.npages; p++) mixed |= valid[(size_t)p] != 0 && valid[(size_t)p] != (uint32_t)g.rows(p);
+    const size_t level_bytes = (size_t)g.npages * g.level_bytes();
+    uint8_t *h_levels = mixed ? out->levels.take(level_bytes) : nullptr;
+    if (mixed) BG_TRY(copy_d2h(c, h_levels, d_levels, level_bytes));
     std::vector<int64_t> coff, clen;
-    if (snappy) BG_TRY(pq_snappy_chunk(c, d_sections, voff, vlen, &out->comp, &coff, &clen));   // (returns with the stream drained)
-
-    if (!rec.empty()) {   // (behind a synchronise in both branches)
-        bool any = false;
-        uint64_t mn = 0, mx = 0;
-        auto less = [&](uint64_t x, uint64_t y) {
-            if (!is_float) return (int64_t)x < (int64_t)y;
-            double dx, dy;
-            memcpy(&dx, &x, 8);
-            memcpy(&dy, &y, 8);
-            return dx < dy;
-        };
-        for (size_t k = 0; k + 2 < rec.size(); k += 3) {
-            if (!rec[k + 2]) continue;
-            if (!any || less(rec[k], mn)) mn = rec[k];
-            if (!any || less(mx, rec[k + 1])) mx = rec[k + 1];
-            any = true;
-        }
-        if (any && is_float) {   // TYPE_DEFINED_ORDER: a zero minimum is written as -0.0, a zero maximum as +0.0
-            if ((mn << 1) == 0) mn = 0x8000000000000000ull;
-            if ((mx << 1) == 0) mx = 0;
-        }
-        out->stats.has_minmax = any;
-        out->stats.min = mn;
-        out->stats.max = mx;
+    if (snappy) {
+        BG_TRY(pq_snappy_chunk(c, s, &out->comp, &coff, &clen));
+    } else {
+        BG_TRY(copy_d2h(c, out->values.take(s.used), s.image, s.used));
+        BG_HIP(hipStreamSynchronize(c->stream));
     }
-
-    out->pages.resize((size_t)npages);
-    for (int64_t p = 0; p < npages; p++) {
+    out->pages.resize((size_t)g.npages);
+    for (int64_t p = 0; p < g.npages; p++) {
         PqwPage &pg = out->pages[(size_t)p];
-        pg.rows = (int32_t)(p + 1 < npages ? page_rows : n - p * page_rows);
-        pg.valid = (int32_t)counts[(size_t)p];
-        pg.level_bits = mixed ? h_levels + (size_t)p * page_level_bytes : nullptr;
-        pg.values = snappy ? nullptr : out->values.take(0) + voff[(size_t)p];
-        pg.value_bytes = vlen[(size_t)p];
+        pg.rows = (int32_t)g.rows(p);
+        pg.valid = (int32_t)valid[(size_t)p];
+        pg.level_bits = mixed ? h_levels + (size_t)p * g.level_bytes() : nullptr;
+        pg.values = snappy ? nullptr : out->values.take(0) + s.off[(size_t)p];
+        pg.value_bytes = s.len[(size_t)p];
         pg.comp = snappy ? out->comp.take(0) + coff[(size_t)p] : nullptr;
         pg.comp_bytes = snappy ? clen[(size_t)p] : 0;
     }
+    return 0;
+}
+
+int pq_encode_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, int32_t page_rows, int32_t encoding, int32_t codec, bool minmax, PqEncChunk *out) {
+    const PqGrid g(b - a, page_rows);
+    const bool is_float = col.type == BOWGPU_FLOAT64;
+    // (each step's device buffers live until the hand-over has drained the stream; they go back to the block cache in this order)
+    DevBuf svals, sbits;
+    DevCol dk;
+    BG_TRY(stage_chunk(c, col, a, b, &svals, &sbits, &dk));
+    DevBuf d_levels, d_counts;
+    std::vector<uint32_t> counts;
+    int64_t m = 0;
+    BG_TRY(page_levels(c, dk, g, &d_levels, &d_counts, &counts, &m));
+    MaskWork mw;
+    DevBuf dvals, dbits;
+    const uint64_t *dense = nullptr;
+    BG_TRY(compact_valid(c, dk, m, &mw, &dvals, &dbits, &dense));
+    DevBuf d_rec;
+    std::vector<uint64_t> rec;
+    if (minmax && m > 0) BG_TRY(launch_minmax(c, is_float, dense, m, &d_rec, &rec));
+    PqSections s;
+    out->dict.clear();
+    if (encoding == kPqEncRleDict) {   // a chunk without a value, or with more distinct patterns than the cap, is written PLAIN
+        bool fallback = m == 0;
+        if (!fallback) BG_TRY(pq_dict_chunk(c, dense, m, counts, &out->dict, &s, &fallback));
+        if (fallback) encoding = kPqEncPlain;
+    }
+    out->encoding = encoding;
+    if (encoding == kPqEncPlain) plain_sections(dense, counts, &s);
+    else if (encoding == kPqEncDelta) BG_TRY(delta_sections(c, dense, counts, &s));
+    BG_TRY(pq_finish_chunk(c, g, counts, d_levels.p, s, codec, out));
+    out->stats = PqwStats();
+    out->stats.null_count = g.n - m;
+    if (!rec.empty()) fold_minmax(rec, is_float, &out->stats);   // the hand-over has drained the stream: the records have landed
     return 0;
 }
 

@@ -1,7 +1,7 @@
 // parquet_write.cpp — host side of the device -> Parquet writer (the reference's Bow.WriteParquet, bowparquet.go:157-253, minus
 // its codec): a Thrift compact WRITER for the page headers and the footer (restated from the Parquet format specification), the
-// assembly of the file from the page tables and the level / value images that parquet_encode.hip (Boolean columns:
-// parquet_bool_encode.hip) leaves in host memory, and the entry points bowgpu_parquet_write / _codec / _bool.  The assembly
+// assembly of the file from the page tables and the level / value images that pq_finish_chunk (parquet_encode.hip; declared, like
+// the two chunk drivers called here, in parquet_encode.h) leaves in host memory, and the entry points bowgpu_parquet_write / _codec / _bool.  The assembly
 // (PqWriter) is plain C++ over host buffers and touches no device and nothing else of the library; with
 // BOWGPU_PARQUET_ASSEMBLE_ONLY defined this file is that alone (tests/cpp/test_parquet_assemble.cpp).
 //
@@ -79,6 +79,30 @@ void put_levels(std::vector<uint8_t> *out, const PqwPage &pg) {
     const uint32_t len = (uint32_t)w.b.size();
     for (int k = 0; k < 4; k++) out->push_back((uint8_t)(len >> (8 * k)));
     out->insert(out->end(), w.b.begin(), w.b.end());
+}
+
+// the tag of a Snappy literal element of n bytes, 1 <= n <= 2^24: the length in the tag itself, or in the 1 to 3 bytes behind it
+void put_literal_tag(TWriter *s, size_t n) {
+    if (n <= 60) { s->byte((uint8_t)((n - 1) << 2)); return; }
+    const int k = n <= 256 ? 1 : n <= 65536 ? 2 : 3;
+    s->byte((uint8_t)((59 + k) << 2));
+    for (int j = 0; j < k; j++) s->byte((uint8_t)((n - 1) >> (8 * j)));
+}
+
+// a page's Thrift header; type 2: the DICTIONARY_PAGE of num_values entries, type 0: the v1 DATA_PAGE of num_values rows
+std::vector<uint8_t> page_header(int32_t type, int64_t raw, int64_t comp, int32_t num_values, int32_t encoding) {
+    TWriter w;
+    w.open_struct();
+    w.i32(1, type);
+    w.i32(2, (int32_t)raw);       // uncompressed_page_size
+    w.i32(3, (int32_t)comp);      // compressed_page_size
+    w.open_struct(type == 2 ? 7 : 5);   // DictionaryPageHeader / DataPageHeader
+    w.i32(1, num_values);         //   of a data page: rows, nulls included
+    w.i32(2, encoding);
+    if (type == 0) { w.i32(3, 3); w.i32(4, 3); }   //   definition levels: RLE; repetition levels: RLE (there are none)
+    w.close_struct();
+    w.close_struct();
+    return w.b;
 }
 
 constexpr size_t kBufBytes = 1u << 20;   // what put() gathers before it writes; longer pieces go out as they lie
@@ -170,29 +194,15 @@ int PqWriter::add_chunk(int32_t encoding, const PqwPage *pages, int64_t npages, 
             s.varint((uint64_t)raw);
             for (int64_t at = 0; at < raw; at += 65536) {
                 const size_t n = (size_t)(raw - at < 65536 ? raw - at : 65536);   // a multiple of 8
-                if (n <= 60) s.byte((uint8_t)((n - 1) << 2));
-                else {
-                    const int k = n <= 256 ? 1 : 2;
-                    s.byte((uint8_t)((59 + k) << 2));
-                    for (int j = 0; j < k; j++) s.byte((uint8_t)((n - 1) >> (8 * j)));
-                }
+                put_literal_tag(&s, n);
                 s.b.insert(s.b.end(), body + at, body + at + n);
             }
         }
         const int64_t comp = codec == kPqSnappy ? (int64_t)s.b.size() : raw;
-        TWriter w;
-        w.open_struct();
-        w.i32(1, 2);                  // DICTIONARY_PAGE
-        w.i32(2, (int32_t)raw);       // uncompressed_page_size
-        w.i32(3, (int32_t)comp);      // compressed_page_size
-        w.open_struct(7);             // DictionaryPageHeader
-        w.i32(1, (int32_t)ndict);     //   num_values
-        w.i32(2, kPqEncPlain);
-        w.close_struct();
-        w.close_struct();
-        if (put(w.b.data(), w.b.size()) != 0) return -1;
+        head = page_header(2, raw, comp, (int32_t)ndict, kPqEncPlain);
+        if (put(head.data(), head.size()) != 0) return -1;
         if (codec == kPqSnappy ? put(s.b.data(), s.b.size()) != 0 : put(body, (size_t)raw) != 0) return -1;
-        ch.raw += (int64_t)w.b.size() + raw;
+        ch.raw += (int64_t)head.size() + raw;
         ch.data_offset = pos_;
         tot_.value_bytes += raw;
     }
@@ -208,30 +218,13 @@ int PqWriter::add_chunk(int32_t encoding, const PqwPage *pages, int64_t npages, 
             s.varint((uint64_t)body);
             const size_t n = lv.size();   // 4 + a run header + at most 128 KiB of bits: the 3-byte length form at the most
             if (n - 1 >= (1u << 24)) { err_ = "parquet: a page's levels section of " + std::to_string(n) + " bytes does not fit a literal"; drop(); return -1; }
-            if (n <= 60) s.byte((uint8_t)((n - 1) << 2));
-            else {
-                const int k = n <= 256 ? 1 : n <= 65536 ? 2 : 3;
-                s.byte((uint8_t)((59 + k) << 2));
-                for (int j = 0; j < k; j++) s.byte((uint8_t)((n - 1) >> (8 * j)));
-            }
+            put_literal_tag(&s, n);
             s.b.insert(s.b.end(), lv.begin(), lv.end());
             lv.swap(s.b);
             values = pg.comp;
             value_bytes = pg.comp_bytes;
         }
-        TWriter w;
-        w.open_struct();
-        w.i32(1, 0);                  // DATA_PAGE
-        w.i32(2, (int32_t)body);      // uncompressed_page_size
-        w.i32(3, (int32_t)((int64_t)lv.size() + value_bytes));   // compressed_page_size
-        w.open_struct(5);             // DataPageHeader
-        w.i32(1, pg.rows);            //   num_values: rows, nulls included
-        w.i32(2, encoding);
-        w.i32(3, 3);                  //   definition levels: RLE
-        w.i32(4, 3);                  //   repetition levels: RLE (there are none)
-        w.close_struct();
-        w.close_struct();
-        head = w.b;
+        head = page_header(0, body, (int64_t)lv.size() + value_bytes, pg.rows, encoding);
         ch.raw += (int64_t)head.size() + body;
         head.insert(head.end(), lv.begin(), lv.end());
         if (put(head.data(), head.size()) != 0) return -1;
@@ -350,15 +343,7 @@ int PqWriter::finish(PqwTotals *totals) {
 
 #ifndef BOWGPU_PARQUET_ASSEMBLE_ONLY
 // ---------------------------------------------------------------- bowgpu_parquet_write
-#include "common.h"
-
-namespace bowgpu {
-// parquet_encode.hip: rows [a, b) of one column as the pages of one column chunk, encoded on the device and brought back once
-// (codec kPqSnappy: the values sections stay on the device and their Snappy streams come back instead, snappy_encode.hip)
-int pq_encode_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, int32_t page_rows, int32_t encoding, int32_t codec, bool minmax, PqEncChunk *out);
-// parquet_bool_encode.hip: the same for a Boolean column, whose pages hold the value bits of their valid rows (PLAIN)
-int pq_encode_bool_chunk(Ctx *c, const bowgpu_col &col, int64_t a, int64_t b, int32_t page_rows, int32_t codec, bool minmax, PqEncChunk *out);
-}
+#include "parquet_encode.h"
 
 using namespace bowgpu;
 
@@ -411,6 +396,8 @@ int write_checks(const char *path, const bowgpu_col *cols, const char *const *na
     return 0;
 }
 
+int writer_fail(const PqWriter &w) { return fail(BOWGPU_ERR_ARG, "%s", w.error().c_str()); }
+
 int write_impl(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols, const bowgpu_parquet_write_options *o, int32_t codec,
                bool booleans, bowgpu_parquet_write_info *info) {
     WritePlan plan;
@@ -421,22 +408,22 @@ int write_impl(const char *path, const bowgpu_col *cols, const char *const *name
     BG_TRY(ctx_get(&c));
     PqWriter w;
     if (w.open(path, names, plan.types.data(), ncols, plan.statistics, o ? o->meta_keys : nullptr, o ? o->meta_values : nullptr, o ? o->n_meta : 0) != 0)
-        return fail(BOWGPU_ERR_ARG, "%s", w.error().c_str());
+        return writer_fail(w);
     PqEncChunk ch;   // (one chunk's images at a time, in host buffers that are taken once)
     for (int64_t a = 0; a < plan.n; a += plan.rg_rows) {
         const int64_t b = a + plan.rg_rows < plan.n ? a + plan.rg_rows : plan.n;
-        if (w.begin_row_group(b - a) != 0) return fail(BOWGPU_ERR_ARG, "%s", w.error().c_str());
+        if (w.begin_row_group(b - a) != 0) return writer_fail(w);
         for (int i = 0; i < ncols; i++) {
             if (plan.types[(size_t)i] == kPqBoolean) BG_TRY(synced(c, pq_encode_bool_chunk(c, cols[i], a, b, plan.page_rows, codec, plan.statistics, &ch)));
             else BG_TRY(synced(c, pq_encode_chunk(c, cols[i], a, b, plan.page_rows, plan.enc[(size_t)i], codec, plan.statistics, &ch)));
             // (ch.encoding: PLAIN where a dictionary was asked for and the chunk fell back)
             if (w.add_chunk(ch.encoding, ch.pages.data(), (int64_t)ch.pages.size(), ch.stats, codec, ch.dict.empty() ? nullptr : ch.dict.data(), (int64_t)ch.dict.size()) != 0)
-                return fail(BOWGPU_ERR_ARG, "%s", w.error().c_str());
+                return writer_fail(w);
         }
-        if (w.end_row_group() != 0) return fail(BOWGPU_ERR_ARG, "%s", w.error().c_str());
+        if (w.end_row_group() != 0) return writer_fail(w);
     }
     PqwTotals t;
-    if (w.finish(&t) != 0) return fail(BOWGPU_ERR_ARG, "%s", w.error().c_str());
+    if (w.finish(&t) != 0) return writer_fail(w);
     if (info) {
         info->file_bytes = t.file_bytes;
         info->rows = t.rows;
@@ -448,27 +435,28 @@ int write_impl(const char *path, const bowgpu_col *cols, const char *const *name
     return 0;
 }
 
+// no C++ exception may cross the C ABI; the writer's destructor has removed the temporary by the time one is caught
+int write_guarded(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols, const bowgpu_parquet_write_options *o, int32_t codec,
+                  bool booleans, bowgpu_parquet_write_info *info) {
+    try { return write_impl(path, cols, names, ncols, o, codec, booleans, info); }
+    catch (const std::bad_alloc &) { return fail(BOWGPU_ERR_OOM, "parquet: out of host memory while writing '%s'", path); }
+    catch (const std::exception &e) { return fail(BOWGPU_ERR_ARG, "parquet: writing '%s' failed (%s)", path, e.what()); }
+}
+
 }  // namespace
 
 extern "C" int bowgpu_parquet_write(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols,
                                     const bowgpu_parquet_write_options *opts, bowgpu_parquet_write_info *info) {
-    // (no C++ exception may cross the C ABI; the writer's destructor has removed the temporary by the time one is caught)
-    try { return write_impl(path, cols, names, ncols, opts, kPqUncompressed, false, info); }
-    catch (const std::bad_alloc &) { return fail(BOWGPU_ERR_OOM, "parquet: out of host memory while writing '%s'", path); }
-    catch (const std::exception &e) { return fail(BOWGPU_ERR_ARG, "parquet: writing '%s' failed (%s)", path, e.what()); }
+    return write_guarded(path, cols, names, ncols, opts, kPqUncompressed, false, info);
 }
 
 extern "C" int bowgpu_parquet_write_codec(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols,
                                           const bowgpu_parquet_write_options *opts, int32_t codec, bowgpu_parquet_write_info *info) {
-    try { return write_impl(path, cols, names, ncols, opts, codec, false, info); }
-    catch (const std::bad_alloc &) { return fail(BOWGPU_ERR_OOM, "parquet: out of host memory while writing '%s'", path); }
-    catch (const std::exception &e) { return fail(BOWGPU_ERR_ARG, "parquet: writing '%s' failed (%s)", path, e.what()); }
+    return write_guarded(path, cols, names, ncols, opts, codec, false, info);
 }
 
 extern "C" int bowgpu_parquet_write_bool(const char *path, const bowgpu_col *cols, const char *const *names, int32_t ncols,
                                          const bowgpu_parquet_write_options *opts, int32_t codec, bowgpu_parquet_write_info *info) {
-    try { return write_impl(path, cols, names, ncols, opts, codec, true, info); }
-    catch (const std::bad_alloc &) { return fail(BOWGPU_ERR_OOM, "parquet: out of host memory while writing '%s'", path); }
-    catch (const std::exception &e) { return fail(BOWGPU_ERR_ARG, "parquet: writing '%s' failed (%s)", path, e.what()); }
+    return write_guarded(path, cols, names, ncols, opts, codec, true, info);
 }
 #endif  // BOWGPU_PARQUET_ASSEMBLE_ONLY

@@ -1,5 +1,6 @@
 // What parquet_write.cpp (the file assembly: plain C++ over host buffers, no device, no other translation unit of the library)
-// and parquet_encode.hip / parquet_bool_encode.hip (the encoding of one column chunk on the device) hand each other.  Included by
+// and parquet_encode.hip / parquet_bool_encode.hip (the encoding of one column chunk on the device; what those files share among
+// themselves is parquet_encode.h) hand each other.  Included by
 // the stand-alone assembly tests as well (tests/cpp/test_parquet_assemble.cpp, test_parquet_bool_assemble.cpp), so nothing here
 // needs HIP.
 #pragma once

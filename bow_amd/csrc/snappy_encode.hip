@@ -1,6 +1,6 @@
 // snappy_encode.hip — the values sections of one column chunk compressed to raw Snappy streams on the device (the SNAPPY codec of
-// bowgpu_parquet_write_codec).  Hand-written for gfx950 (wave64); called by pq_encode_chunk (parquet_encode.hip) on the values image
-// as it lies on the device; the page's preamble and its levels literal are the host's (parquet_write.cpp).
+// bowgpu_parquet_write_codec).  Hand-written for gfx950 (wave64); called by pq_finish_chunk (parquet_encode.hip) on the values sections
+// as they lie on the device (declared in parquet_encode.h); the page's preamble and its levels literal are the host's (parquet_write.cpp).
 //
 //   snenc_compress_kernel   one wavefront (one workgroup of 64) per fragment of kSnFrag bytes of a page's values section: the
 //                           fragment in LDS, a hash table of 4-byte keys in LDS, the element stream built in LDS and stored with
@@ -17,8 +17,7 @@
 
 #include <vector>
 
-#include "common.h"
-#include "parquet_write.h"
+#include "parquet_encode.h"
 
 namespace bowgpu {
 
@@ -195,11 +194,8 @@ __global__ __launch_bounds__(kSnThreads) void snenc_pack_kernel(const uint8_t *s
 
 }  // namespace
 
-// The values sections [off[p], off[p] + len[p]) of `image` (device memory, every off a multiple of 8, readable up to the next
-// multiple of 8 behind each section) as one raw Snappy stream per page: the streams end to end in out (host), page p's at coff[p]
-// with clen[p] bytes (0 for a section without bytes).  The stream has drained when this returns.
-int pq_snappy_chunk(Ctx *c, const uint8_t *image, const std::vector<int64_t> &off, const std::vector<int64_t> &len, PqHostBytes *out,
-                    std::vector<int64_t> *coff, std::vector<int64_t> *clen) {
+int pq_snappy_chunk(Ctx *c, const PqSections &s, PqHostBytes *out, std::vector<int64_t> *coff, std::vector<int64_t> *clen) {
+    const std::vector<int64_t> &off = s.off, &len = s.len;
     const int64_t npages = (int64_t)off.size();
     coff->assign((size_t)npages, 0);
     clen->assign((size_t)npages, 0);
@@ -224,7 +220,7 @@ int pq_snappy_chunk(Ctx *c, const uint8_t *image, const std::vector<int64_t> &of
     BG_TRY(d_tab.alloc((size_t)npages * sizeof(SnPageOut)));
     BG_HIP(hipMemsetAsync(d_bytes.as<uint32_t>() + nfrags, 0, 4, c->stream));
     BG_HIP(hipMemsetAsync(d_slots.as<uint8_t>() + (size_t)nfrags * kSnSlot, 0, 8, c->stream));
-    hipLaunchKernelGGL(snenc_compress_kernel, dim3((unsigned)nfrags), dim3(64), 0, c->stream, image, d_pages.as<const SnPage>(), npages, d_slots.as<uint8_t>(),
+    hipLaunchKernelGGL(snenc_compress_kernel, dim3((unsigned)nfrags), dim3(64), 0, c->stream, s.image, d_pages.as<const SnPage>(), npages, d_slots.as<uint8_t>(),
                        d_bytes.as<uint32_t>());
     BG_HIP(hipGetLastError());
     BG_TRY(launch_scan_u32(c, d_bytes.as<uint32_t>(), nfrags + 1, d_sums.as<uint32_t>()));

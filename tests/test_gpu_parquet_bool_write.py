@@ -323,6 +323,27 @@ def test_frame_without_a_boolean_column_is_the_codec_entry_points_file(tmp_path)
         verify(a, fr.data, fr.names, 128, 512, encodings=enc, info=ia, codec=codec)
 
 
+@pytest.mark.parametrize("codec", [0, 1])
+@pytest.mark.parametrize("kind", ["none", "allnull", "p30"])
+def test_every_route_through_one_hand_over_at_its_edges(tmp_path, kind, codec):
+    """DELTA, RLE_DICTIONARY, PLAIN and Boolean chunks in one call; the second row group is one page of 2 rows.  allnull: no
+    values image on any route, no Snappy fragment, and the dictionary request comes out PLAIN; none: no levels image comes back."""
+    rng = np.random.default_rng(650)
+    n, page, rg = 130, 64, 128
+    fr = Frame(codec)
+    columns = (delta_shapes(n, rng)["timestamps"], np.round(rng.standard_normal(n), 1), int_values(n, rng), rng.random(n) < 0.5)
+    for name, values, offset in zip(("delta", "dict", "plain", "flag"), columns, (0, 3, 9, 1)):
+        fr.add(name, values, validity(kind, n, page, rng), offset=offset, res=capi.DEVICE)
+    enc = [DELTA, DICT, PLAIN, PLAIN]
+    path = str(tmp_path / "routes.parquet")
+    info = write(path, fr, page_rows=page, row_group_rows=rg, encodings=enc, codec=codec)
+    # (a dictionary chunk without a value is a PLAIN chunk: verify walks its pages too)
+    md = verify(path, fr.data, fr.names, page, rg, encodings=[DELTA, PLAIN, PLAIN, PLAIN] if kind == "allnull" else enc, info=info, codec=codec)
+    assert md.num_row_groups == 2 and md.row_group(1).num_rows == 2
+    has_value = [bool(fr.data[1][1][a:a + rg].any()) for a in (0, rg)]   # a chunk has a dictionary exactly when it has a value
+    assert [("RLE_DICTIONARY" in md.row_group(g).column(1).encodings) for g in range(2)] == has_value
+
+
 # ------------------------------------------------------------------ 6. parquet -> Boolean reducer -> parquet, in HBM throughout
 def test_flag_column_in_reduced_and_out_again_without_leaving_the_device(tmp_path):
     from oracle import pyoracle as orc
